@@ -22,6 +22,11 @@ arrays": every rank buckets ITS slice of a Zipf stream over ALL 65 536 names, lh
 the per-row merged windows so that rank r ends with the rows of the names it owns, which it extracts) runs on the
 same ranks afterwards and is reported under secondary.c4 with its own one-rank reference.
 
+A plain run only sets up, warms up, times the K steps and prints the line (value, ms_per_step, the K1 roofline from the
+timed launches' HIP events).  Everything else -- the full-stream oracle parity, cpu_baseline, the secondary legs, the
+extract latency flips, the serial pass and the read ceiling -- runs with --full.  --dump-outputs DIR writes the arrays
+the last timed step returned (rank 0's extract results) as DIR/<name>.npy, so that two builds can be compared.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -120,7 +125,27 @@ def parse():
                          "reduce-scatter merge as the top-level line")
     ap.add_argument("--names", type=int, default=0, help="histogram names (default 1024 for c3, 65536 for c4)")
     ap.add_argument("--c4-slice", type=float, default=1.25e8, help="pairs per rank per step of the C4 stream")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle parity, cpu_baseline, secondary legs, extract latency, the "
+                         "serial pass and the read ceiling (the --no-* options and --latency-flips act only with --full); "
+                         "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_parity = args.no_cpu_baseline = args.no_secondary = True
+        args.latency_flips = 0
+    return args
+
+
+def dump_outputs(outputs: dict, out_dir: str):
+    """The arrays of the last timed step as <out_dir>/<name>.npy, float64 (every field is an integer below 2^53 or a
+    float64 already, so the conversion is exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(outputs.items()):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def make_samples(n: int, kind: str, seed: int) -> torch.Tensor:
@@ -429,20 +454,25 @@ def run_c2(args, la, stream, rank, world=1, dist=None, comm=0, frontend="none", 
         dt = float(tt.item())
     assert int(out["count"].sum()) == n * world, (int(out["count"].sum()), n, world)
     k1_ms = sum(a.elapsed_time(b) for a, b in events) / len(events)
-    # The same K steps once more, SERIAL: every step drained (ingest, flip, reduce, results on the host) before the next
-    # one is enqueued -- what a caller gets that does not overlap reduction with the next interval's ingest (ADVICE r4:
-    # the pipelined figure alone is not comparable with rounds 1 - 3).  Reported beside the headline, never as `value`.
-    def serial_step(timed):
-        eng.submit_device(0, data, n, stream=stream)
-        return finish(eng.flip(), False)
+    full = getattr(args, "full", True)
+    dt_serial = ceil_avg = ceil_best = None
+    if full:
+        # The same K steps once more, SERIAL: every step drained (ingest, flip, reduce, results on the host) before the
+        # next one is enqueued -- what a caller gets that does not overlap reduction with the next interval's ingest
+        # (the pipelined figure alone is not comparable with rounds 1 - 3).  Reported beside the headline,
+        # never as `value`.
+        def serial_step(timed):
+            eng.submit_device(0, data, n, stream=stream)
+            return finish(eng.flip(), False)
 
-    dt_serial, _ = timed_steps(serial_step, args.steps, 1, fence)
-    if dist is not None:
-        tt = torch.tensor([dt_serial], dtype=torch.float64, device="cuda")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt_serial = float(tt.item())
-    # what a kernel that only reads gets from this box, now, on the same block of memory (K1's loop without the buckets)
-    ceil_avg, ceil_best = buf.read_ceiling_gbs(reps=10, stream=stream)
+        dt_serial, _ = timed_steps(serial_step, args.steps, 1, fence)
+        if dist is not None:
+            tt = torch.tensor([dt_serial], dtype=torch.float64, device="cuda")
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt_serial = float(tt.item())
+        # what a kernel that only reads gets from this box, now, on the same block of memory (K1's loop without the
+        # buckets)
+        ceil_avg, ceil_best = buf.read_ceiling_gbs(reps=10, stream=stream)
 
     # p99 extract latency: flip -> stats on host (BASELINE.json metric, part 2); one rank's own interval
     lat = []
@@ -475,9 +505,14 @@ def run_c2(args, la, stream, rank, world=1, dist=None, comm=0, frontend="none", 
                                      "sources, not measured in this run)"
         except Exception:
             traffic = None
+    ceiling = {}
+    if full:
+        ceiling = dict(read_ceiling_same_box=ceil_avg, read_ceiling_same_box_best_launch=ceil_best,
+                       frac_of_read_ceiling=n * BYTES_SINGLE / (k1_ms * 1e-3) / 1e9 / ceil_avg,
+                       read_ceiling_source="lh_tool_read_ceiling: 10 launches of K1's loop without the bucket work over "
+                                           "the step's input block, in this process, right after the timed steps")
     res = {
         "value": world * n * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
-        "ms_per_step_serial": dt_serial / args.steps * 1e3, "value_serial": world * n * args.steps / dt_serial,
         "config": {"workload": "C2 single-metric float64 stream, one ingest kernel + one percentile scan per step"
                                + ("" if world == 1 else "; every rank buckets its own slice, the row's merged window is "
                                   "all-reduced at the flip (lh_snapshot_merge, LH_MERGE_ALLREDUCE), every rank extracts"),
@@ -489,13 +524,14 @@ def run_c2(args, la, stream, rank, world=1, dist=None, comm=0, frontend="none", 
                             "waits for step i's results (as the reference's reaper overlaps reduction with ingest)"},
         "roofline": roofline(n * BYTES_SINGLE, k1_ms, "k_ingest_single", traffic=traffic,
                              traffic_source=traffic_source, frac_of_measured_copy_ceiling_6290=n * BYTES_SINGLE / (k1_ms * 1e-3) / 1e9 / 6290.0,
-                             read_ceiling_same_box=ceil_avg, read_ceiling_same_box_best_launch=ceil_best,
-                             frac_of_read_ceiling=n * BYTES_SINGLE / (k1_ms * 1e-3) / 1e9 / ceil_avg,
-                             read_ceiling_source="lh_tool_read_ceiling: 10 launches of K1's loop without the bucket work over "
-                                                 "the step's input block, in this process, right after the timed steps"),
-        "extract_latency_us": {"p50": float(np.percentile(lat_us, 50)), "p99": float(np.percentile(lat_us, 99)),
-                               "flips": len(lat), "names": 1},
+                             **ceiling),
+        "_outputs": out,
     }
+    if full:
+        res["ms_per_step_serial"] = dt_serial / args.steps * 1e3
+        res["value_serial"] = world * n * args.steps / dt_serial
+        res["extract_latency_us"] = {"p50": float(np.percentile(lat_us, 50)), "p99": float(np.percentile(lat_us, 99)),
+                                     "flips": len(lat), "names": 1}
     if world > 1:
         res["value_per_gpu"] = res["value"] / world
         res["merge"] = {"device_ms": {k: minfo.get(k) for k in ("ranges_ms", "plan_ms", "pack_ms", "collective_ms",
@@ -618,7 +654,8 @@ def run_c3(args, la, stream, rank, steps, warmup, latency_flips=0):
            "roofline": roofline(n * BYTES_PAIR, ing_ms,
                                 "k_survey_* + k_scatter3 + k_plan_* + k_part_hist2 (all launches of one lh_submit_pairs_device)",
                                 **c3_traffic(n, M)),
-           "scratch_bytes": c["scratch_bytes"], "sublaunches_per_step": c["sublaunches"] // max(1, steps + warmup)}
+           "scratch_bytes": c["scratch_bytes"], "sublaunches_per_step": c["sublaunches"] // max(1, steps + warmup),
+           "_outputs": out}
     if latency_flips:
         lat = []
         sl_i, sl_v = ids[: 1 << 22], data[: 1 << 22]
@@ -920,6 +957,7 @@ def run_c4(args, la, stream, rank, world, dist, steps, warmup, comm_override=Non
                           "round trip for the plan totals); host_call_ms: wall time of lh_snapshot_merge returning; "
                           "wall_ms: until its last kernel has finished (extract_owned_ms starts there)"},
         "extract_owned_ms": sum(t_ext) / len(t_ext), "parity": parity, "scratch_bytes": c["scratch_bytes"],
+        "_outputs": out_p,
     }
     if info.get("packed_cells") and t_k2:
         # K2's roofline: every cell of every owned row's window read once (8 B x row_len per metric);
@@ -1213,6 +1251,9 @@ def main():
 
     res, clean = run_job(args, la, stream, rank, world, dist, comm, frontend, why, workload,
                          on_headline=(lambda r: _Watchdog(r, emit)) if (world > 1 and rank == 0) else None)
+    outputs = res.pop("_outputs", None)
+    if args.dump_outputs and rank == 0 and outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     if not clean:
         # a secondary leg failed on this rank while the others may still sit in one of its collectives: no barrier, no
         # communicator teardown (either could hang) -- the headline is complete, print it and leave
@@ -1283,6 +1324,7 @@ def run_job(args, la, stream, rank, world, dist, comm, frontend, why, workload="
 
     if workload == "c2":
         res = run_c2(args, la, stream, rank, world, dist, comm, frontend, why)
+        outputs = res.pop("_outputs", None)          # kept off the headline while the secondary legs run (_Watchdog)
         if not args.no_secondary:
             sec = {}
             if world == 1:
@@ -1300,6 +1342,7 @@ def run_job(args, la, stream, rank, world, dist, comm, frontend, why, workload="
             for name, fn in legs:
                 try:
                     sec[name] = fn()
+                    sec[name].pop("_outputs", None)
                 except Exception as exc:  # noqa: BLE001 -- a secondary leg must not take the headline down
                     sec[name] = {"failed": repr(exc)[:300]}
                     if world > 1:
@@ -1324,6 +1367,7 @@ def run_job(args, la, stream, rank, world, dist, comm, frontend, why, workload="
                            value_c4=c4["value"], value_c4_per_gpu=c4["value"] / world, ms_per_step_c4=c4["ms_per_step"],
                            ms_per_step_c4_serial=c4.get("serial_ms_per_step"),
                            c4_efficiency_vs_one_rank=c4.get("efficiency_vs_one_rank"))
+        res["_outputs"] = outputs
     elif workload == "c3":
         res = run_c3(args, la, stream, rank, args.steps, args.warmup, latency_flips=min(args.latency_flips, 200))
     elif world > 1:

@@ -6,12 +6,12 @@
 # cold-clock draw).
 # Every PMC summary records the hashes of the kernel sources it was measured on (bench.source_hashes): bench.py refuses a
 # summary whose hashes differ from the tree's (traffic_source: "stale ...").
-#   bench.json              python bench.py (default flags: headline C2 + secondary C3 / C4 / host-fed / C5)
+#   bench.json              python bench.py --full (headline C2 + secondary C3 / C4 / host-fed / C5)
 #   kernel_trace.txt        rocprofv3 --kernel-trace of the C2 bench command (no cpu baseline), summarised
 #   k1_pmc.json             FETCH_SIZE / WRITE_SIZE passes for k_ingest_single, corrected per MI355X_MICROARCH.md
 #   c3_kernel_trace.txt     rocprofv3 --kernel-trace of bench.py --workload c3
 #   c3_pmc.json             FETCH_SIZE / WRITE_SIZE passes of the same command, every kernel of the call summed
-#   c4_bench.json           bench.py --workload c4 (one rank)
+#   c4_bench.json           bench.py --full --workload c4 (one rank)
 #   c4_kernel_trace.txt / c4_pmc.json   the same for bench.py --workload c4 (65 536 names, one rank's 1.25e8-pair slice)
 #   first_calls.txt         tools/first_call.py: calls 0 .. 3 of fresh engines on wide, sorted and run-clustered streams
 # PMC passes are separate runs with no tracing domain mixed in.
@@ -19,7 +19,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/round; mkdir -p $OUT; cd $R
 STAMP=$(python -c "import bench; print(bench.tree_stamp())")
 { echo "{\"tree_stamp\": \"$STAMP\"}"; loghisto_amd/build/read_ceiling --reps 20 2>&1; } > $OUT/read_ceiling.jsonl
 cd /tmp; export TMPDIR=/tmp
-CMD="python $R/bench.py --workload c2 --no-secondary --steps 30 --warmup 5 --no-cpu-baseline --no-parity --latency-flips 0"
+CMD="python $R/bench.py --full --workload c2 --no-secondary --steps 30 --warmup 5 --no-cpu-baseline --no-parity --latency-flips 0"
 rm -rf /tmp/pr_trace; rocprofv3 --kernel-trace -d /tmp/pr_trace -o t -- $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_under_trace.json
 $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_unprofiled_after.json
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD"
@@ -27,17 +27,17 @@ $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_unprofiled_after.json
   python $R/profiles/summarize_rocpd.py list /tmp/pr_trace/t_results.db k_ingest_single --min-ns 500000 --skip 30
   for f in bench_under_trace bench_unprofiled_after; do python -c "
 import json; j=json.loads(open('$OUT/$f.json').read()); r=j['roofline']; print('HIP events, $f run: avg_launch_ms %.4f frac %.4f ms_per_step %.4f' % (r['avg_launch_ms'], r['frac'], j['ms_per_step']))"; done; } > $OUT/kernel_trace.txt
-CMD2="python $R/bench.py --workload c2 --no-secondary --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
+CMD2="python $R/bench.py --full --workload c2 --no-secondary --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
 rm -rf /tmp/pr_fetch /tmp/pr_write
 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_fetch -o t -- $CMD2 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_write -o t -- $CMD2 > /dev/null 2>&1
-CMD3="python $R/bench.py --workload c3 --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
+CMD3="python $R/bench.py --full --workload c3 --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
 rm -rf /tmp/pr_c3t /tmp/pr_c3f /tmp/pr_c3w
 rocprofv3 --kernel-trace -d /tmp/pr_c3t -o t -- $CMD3 > $OUT/c3_under_trace.json 2>/dev/null
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD3"; python $R/profiles/summarize_rocpd.py stats /tmp/pr_c3t/t_results.db | grep -E "^#|^kernel|lh::" | cut -c1-170; } > $OUT/c3_kernel_trace.txt
 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_c3f -o t -- $CMD3 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_c3w -o t -- $CMD3 > /dev/null 2>&1
-CMD4="python $R/bench.py --workload c4 --steps 3 --warmup 1 --no-parity --latency-flips 0"
+CMD4="python $R/bench.py --full --workload c4 --steps 3 --warmup 1 --no-parity --latency-flips 0"
 rm -rf /tmp/pr_c4t /tmp/pr_c4f /tmp/pr_c4w
 rocprofv3 --kernel-trace -d /tmp/pr_c4t -o t -- $CMD4 > $OUT/c4_under_trace.json 2>/dev/null
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD4"; python $R/profiles/summarize_rocpd.py stats /tmp/pr_c4t/t_results.db | grep -E "^#|^kernel|lh::" | cut -c1-170
@@ -141,9 +141,9 @@ PY
 # summaries measured on other kernel sources -- the ones just written are this tree's.
 cd $R
 for f in k1_pmc c3_pmc c4_pmc c4_names_1e9_pmc; do cp $OUT/$f.json $R/profiles/r06_$f.json; done
-python bench.py 2> $OUT/bench.err | grep "^{" | tail -1 > $OUT/bench.json
+python bench.py --full 2> $OUT/bench.err | grep "^{" | tail -1 > $OUT/bench.json
 python bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/bench20.err | grep "^{" | tail -1 > $OUT/bench_steps20_warmup5.json
-python bench.py --workload c4 2> $OUT/c4_bench.err | grep "^{" | tail -1 > $OUT/c4_bench.json
+python bench.py --full --workload c4 2> $OUT/c4_bench.err | grep "^{" | tail -1 > $OUT/c4_bench.json
 # first calls of fresh engines and clustered streams (sweeps drop their first calls): per-call times of four calls each
 cd $R
 { echo "# tree_stamp: $STAMP"; echo "# tools/first_call.py <dists> <ids> 1e9 (NAMES=..., ONLY0=1): ms per call, calls 0 .. 3 of a fresh engine"

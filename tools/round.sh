@@ -159,7 +159,7 @@ extract)
     # K2 at 65 536 names: the tests that hold k_extract_wave against the oracle and against k_extract, then config 4 on one
     # rank (extract_roofline: kernel and copy apart; extract latency over 300 flips) and the kernel under the tracer
     suite tests/test_gpu_extract_thresholds.py tests/test_gpu_options.py tests/test_gpu_part3.py tests/test_gpu_parity.py tests/test_gpu_fuzz.py tests/test_gpu_merge.py
-    python bench.py --workload c4 --steps 5 --warmup 2 --no-parity --latency-flips 300 2> $OUT/c4.err | grep "^{" | tail -1 > $OUT/c4_bench.json
+    python bench.py --full --workload c4 --steps 5 --warmup 2 --no-parity --latency-flips 300 2> $OUT/c4.err | grep "^{" | tail -1 > $OUT/c4_bench.json
     python - <<PY | tee $OUT/extract.txt
 import json
 j = json.load(open("$OUT/c4_bench.json"))
@@ -168,7 +168,7 @@ print("k_extract_wave kernel_ms %.4f copy_ms %.4f kernel_frac %.3f  extract_owne
     x["kernel_ms"], x["copy_ms"], x["kernel_frac"], j.get("extract_owned_ms", -1), j.get("extract_latency_us")))
 PY
     (cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/pk
-     timeout 300 rocprofv3 --kernel-trace -d /tmp/pk -o t -- python $R/bench.py --workload c4 --steps 3 --warmup 1 --no-parity --latency-flips 0 > /dev/null 2>&1
+     timeout 300 rocprofv3 --kernel-trace -d /tmp/pk -o t -- python $R/bench.py --full --workload c4 --steps 3 --warmup 1 --no-parity --latency-flips 0 > /dev/null 2>&1
      python $R/profiles/summarize_rocpd.py stats /tmp/pk/t_results.db | grep -E "^kernel|k_extract|k_clear|k_pack|k_unpack|k_merge" | cut -c1-170) | tee $OUT/trace.txt
     ;;
 order)
