@@ -266,6 +266,41 @@ int lh_snapshot_cells(lh_snapshot *s, void **d_cells, uint32_t *nrows, uint32_t 
 int lh_cell_bytes(lh_engine *e);
 int lh_snapshot_ranges(lh_snapshot *s, void **d_ranges /* uint32[nrows][2] lo,hi bins */);
 int lh_snapshot_mark_dirty(lh_snapshot *s, uint32_t first_row, uint32_t nrows, uint32_t lo_bin, uint32_t hi_bin);
+/* Cells back IN: the inverse of lh_buckets / lh_buckets_all.  An interval that already exists in bucket form -- another
+ * process's RawMetricSet.Histograms, name -> {int16 key -> count} (/root/reference/metrics.go:54-60), an older interval
+ * of this engine (1 s -> 10 s / 60 s roll-ups), a checkpoint -- is added to the snapshot per CELL, not per sample: cells
+ * are a commutative integer sum (atomic.AddUint64, /root/reference/metrics.go:278, 292), so the percentile scan, the
+ * lifetime stores and lh_serialize then work on the merged interval unchanged.  No communicator, no peer engine.
+ *   lh_snapshot_add_buckets             snapshot[ids[i]][keys[i]] += counts[i] for i < n.  Host arrays, copied before
+ *                                       the call returns.
+ *   lh_snapshot_add_buckets_csr         metric first + i gets keys / counts[offsets[i] .. offsets[i + 1]), i < nmetrics:
+ *                                       exactly what lh_buckets_all hands out.  Host arrays, copied likewise.
+ *   lh_snapshot_add_buckets_device,     the same two with device arrays, enqueued on the snapshot's stream
+ *   lh_snapshot_add_buckets_csr_device  (lh_snapshot_stream): the producer of the arrays runs on that stream or is
+ *                                       complete; the arrays stay valid until the stream passes this point.
+ * Entries come in any order, keys unsorted, duplicates allowed (several entries of one cell add up); a cell wraps mod
+ * 2^64 as the reference's does.  Entries with count == 0 are skipped entirely: they touch neither a cell nor a row's
+ * dirty span, so nbuckets and `present` do not see them.  Every int16 is a valid key (bin = (uint16)key ^ 0x8000).
+ * ALL OR NOTHING: an id >= max_metrics or first + nmetrics > max_metrics -> LH_ERANGE, offsets that are not
+ * non-decreasing from offsets[0] -> LH_EINVAL, and no cell has been added.  The host forms check while they read; the
+ * device forms run a pre-pass over ids / offsets / counts and read one small result back (one stream wait per call)
+ * before the add is enqueued.  n == 0, an all-empty CSR or nothing but zero counts: LH_OK, nothing touched.  NULL or
+ * misaligned arrays (counts and offsets 8, ids 4, keys 2 bytes) -> LH_EINVAL without touching a device.
+ * The adds run on the uint64 rows of lh_snapshot_rows: a snapshot of 32-bit cells moves to its wide store first
+ * (allocated then, kept; LH_ENOMEM if it cannot be had, nothing added), so any count is exact, a single cell >= 2^32
+ * included.  Every touched row's [lo, hi] in lh_snapshot_ranges ends as the TIGHT union of what it was and the bins
+ * added -- extract and clear cover the new cells and nothing more -- and the buffer's cell sizes count as unknown to a
+ * later lh_snapshot_merge (lh_snapshot_mark_dirty, on one added cell).
+ * One thread per snapshot, as for lh_snapshot_merge.  Import BEFORE lh_snapshot_accumulate if the lifetime stores are
+ * to include the imported cells (it applies once per snapshot); every later lh_extract* / lh_buckets* / lh_serialize
+ * sees them.  Names need to be interned only for what requires it anyway (lh_serialize). */
+int lh_snapshot_add_buckets(lh_snapshot *s, const uint32_t *ids, const int16_t *keys, const uint64_t *counts, size_t n);
+int lh_snapshot_add_buckets_csr(lh_snapshot *s, uint32_t first, size_t nmetrics, const uint64_t *offsets,
+                                const int16_t *keys, const uint64_t *counts);
+int lh_snapshot_add_buckets_device(lh_snapshot *s, const uint32_t *d_ids, const int16_t *d_keys,
+                                   const uint64_t *d_counts, size_t n);
+int lh_snapshot_add_buckets_csr_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const uint64_t *d_offsets,
+                                       const int16_t *d_keys, const uint64_t *d_counts);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

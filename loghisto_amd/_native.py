@@ -181,6 +181,10 @@ SIGNATURES = {
     "lh_cell_bytes": (C.c_int, [_vp]),
     "lh_snapshot_ranges": (C.c_int, [_vp, C.POINTER(_vp)]),
     "lh_snapshot_mark_dirty": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "lh_snapshot_add_buckets": (C.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "lh_snapshot_add_buckets_csr": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _vp, _vp]),
+    "lh_snapshot_add_buckets_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "lh_snapshot_add_buckets_csr_device": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

@@ -253,6 +253,71 @@ class Snapshot:
     def mark_dirty(self, first_row: int, nrows: int, lo_bin: int = 0, hi_bin: int = N.NKEYS - 1):
         N.check(N.lib().lh_snapshot_mark_dirty(self._h, first_row, nrows, lo_bin, hi_bin), "lh_snapshot_mark_dirty")
 
+    # -- cells back in (RawMetricSet.Histograms, metrics.go:54-60; cells are an integer sum, metrics.go:278, 292) --------
+    def add_buckets(self, ids, keys, counts):
+        """snapshot[ids[i]][keys[i]] += counts[i] (lh_snapshot_add_buckets*): any order, duplicates add up, count 0 is
+        skipped, all or nothing.  numpy arrays / sequences take the host form (copied before the call returns); torch
+        device tensors (ids 4-byte, keys torch.int16, counts 8-byte) the device form, enqueued on the snapshot's stream."""
+        L = N.lib()
+        if hasattr(counts, "data_ptr"):
+            if ids.element_size() != 4 or keys.element_size() != 2 or counts.element_size() != 8:
+                raise TypeError("device form: ids are 4-byte, keys 2-byte and counts 8-byte tensors")
+            n = int(counts.numel())
+            if int(ids.numel()) != n or int(keys.numel()) != n:
+                raise ValueError("ids, keys and counts differ in length")
+            if not (ids.is_contiguous() and keys.is_contiguous() and counts.is_contiguous()):
+                raise ValueError("device form: the tensors must be contiguous")
+            N.check(L.lh_snapshot_add_buckets_device(self._h, _ptr(ids), _ptr(keys), _ptr(counts), n),
+                    "lh_snapshot_add_buckets_device")
+            return
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        k = np.ascontiguousarray(keys, dtype=np.int16)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if not (i.size == k.size == c.size):
+            raise ValueError("ids, keys and counts differ in length")
+        N.check(L.lh_snapshot_add_buckets(self._h, i.ctypes.data, k.ctypes.data, c.ctypes.data, c.size),
+                "lh_snapshot_add_buckets")
+
+    def add_buckets_csr(self, offsets, keys, counts, first: int = 0):
+        """The inverse of buckets_all(): metric first + i gets keys / counts[offsets[i] .. offsets[i + 1])
+        (lh_snapshot_add_buckets_csr*).  Accepts exactly what buckets_all() returns; torch device tensors (offsets and
+        counts 8-byte, keys torch.int16) take the device form."""
+        L = N.lib()
+        if hasattr(counts, "data_ptr"):
+            if offsets.element_size() != 8 or keys.element_size() != 2 or counts.element_size() != 8:
+                raise TypeError("device form: offsets and counts are 8-byte tensors, keys 2-byte")
+            if int(offsets.numel()) < 1 or int(keys.numel()) != int(counts.numel()):
+                raise ValueError("offsets holds nmetrics + 1 entries; keys and counts are equally long")
+            if not (offsets.is_contiguous() and keys.is_contiguous() and counts.is_contiguous()):
+                raise ValueError("device form: the tensors must be contiguous")
+            N.check(L.lh_snapshot_add_buckets_csr_device(self._h, first, int(offsets.numel()) - 1, _ptr(offsets), _ptr(keys),
+                                                         _ptr(counts)), "lh_snapshot_add_buckets_csr_device")
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        k = np.ascontiguousarray(keys, dtype=np.int16)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if o.size < 1 or k.size != c.size:
+            raise ValueError("offsets holds nmetrics + 1 entries; keys and counts are equally long")
+        if o.size > 1 and int(o.max()) > c.size:
+            raise ValueError("offsets point past the end of keys / counts")
+        N.check(L.lh_snapshot_add_buckets_csr(self._h, first, o.size - 1, o.ctypes.data, k.ctypes.data, c.ctypes.data),
+                "lh_snapshot_add_buckets_csr")
+
+    def add_raw(self, raw):
+        """A RawMetricSet.Histograms-shaped mapping, name -> (keys, counts): interns the names on the engine and adds
+        the cells (add_buckets)."""
+        ids, keys, counts = [], [], []
+        for name, (k, c) in raw.items():
+            k = np.ascontiguousarray(k, dtype=np.int16).ravel()
+            c = np.ascontiguousarray(c, dtype=np.uint64).ravel()
+            if k.size != c.size:
+                raise ValueError(f"{name}: keys and counts differ in length")
+            ids.append(np.full(k.size, self.engine.intern(name), dtype=np.uint32))
+            keys.append(k)
+            counts.append(c)
+        if ids:
+            self.add_buckets(np.concatenate(ids), np.concatenate(keys), np.concatenate(counts))
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
