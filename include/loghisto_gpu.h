@@ -301,6 +301,44 @@ int lh_snapshot_add_buckets_device(lh_snapshot *s, const uint32_t *d_ids, const 
                                    const uint64_t *d_counts, size_t n);
 int lh_snapshot_add_buckets_csr_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const uint64_t *d_offsets,
                                        const int16_t *d_keys, const uint64_t *d_counts);
+/* Counts at or below given values: the read-side counterpart of the import above, and the one query whose answers can be
+ * SUMMED across intervals, ranks and processes ("how many requests finished within 250 ms", an SLO / Apdex ratio, the
+ * fixed-boundary cumulative `le` buckets of a scraper).  It is the running count of percentile()'s bucket walk
+ * (/root/reference/metrics.go:389-418: `sofar += *count` over the cells in ascending key order) read at a VALUE instead of
+ * searched for a fraction, over the interval's cells (RawMetricSet.Histograms, metrics.go:54-60; filled by
+ * atomic.AddUint64, metrics.go:278):
+ *   cum[m * nb + j] = number of samples of metric first + m, in this snapshot, whose bucket key is <= the key of bounds[j]
+ *   total[m]        = all of its samples (the +Inf bucket; lh_stats.count)
+ * RESOLUTION IS THE BUCKET.  A bound b is mapped to the key compress(b) (metrics.go:316-322) by the arithmetic the ingest's
+ * threshold table is generated with; every sample v <= b is counted (compress is monotone), and so are the samples > b that
+ * share b's bucket (within 1 % of 1 + |v|, the histogram's own precision).  For b = decompress(k) the count is exactly the
+ * cells with key <= k.
+ *   bounds   a HOST array in both forms: nb doubles shared by all names, or, with LH_LE_PER_METRIC, nmetrics * nb doubles,
+ *            row m for metric first + m (SLO thresholds differ per endpoint).  Each row non-decreasing (equal neighbours
+ *            allowed); -0.0 == 0.0.  +Inf takes in everything (cum == total), -Inf nothing (0) -- an infinite SAMPLE lies
+ *            in bucket 0, where the ingest puts it.  A finite bound whose extended key floor(100 Log(1 + |b|) + 0.5) exceeds
+ *            32 767 (|b| >~ 1.9e142, where the reference's int16 keys wrap) saturates the same way: everything for b > 0,
+ *            nothing for b < 0.
+ *   LH_EINVAL, checked on the host before the snapshot or a device is touched: NULL s; nb == 0 or nb > LH_MAX_BOUNDS; NULL
+ *            bounds; both outputs NULL (either one may be); a NaN bound; a decreasing row; unknown flag bits; arrays not
+ *            8-byte aligned.  first + nmetrics > max_metrics -> LH_ERANGE.  nmetrics == 0 -> LH_OK, nothing written.  The rows of
+ *            per-metric bounds are checked before the snapshot is looked at: bounds holds nmetrics * nb doubles whatever
+ *            the call returns (an nmetrics no engine can have, above 2^32 - 1, is LH_ERANGE before a bound is read).
+ * READ-ONLY: no cell, span or cell width of the snapshot changes (the kernels read lh_snapshot_cells as they are: a snapshot
+ * of 32-bit cells stays one).  Works on whatever the snapshot holds: ingested, imported, merged, widened.
+ * Ordering and threading as for lh_snapshot_add_buckets*: enqueued on lh_snapshot_stream(s), one thread per snapshot.
+ * lh_count_le returns when the results are in the caller's arrays (host arrays that are pinned -- hipHostMalloc'ed or
+ * registered -- receive them by one copy, others through a pinned block of the library's).  lh_count_le_device returns
+ * after enqueueing; d_cum / d_total are device arrays that stay valid until the stream passes that point.  Per-metric
+ * bounds are copied before either call returns (a device-form call may first wait for the previous per-metric call's
+ * kernel, which reads that copy).  The unit's staging blocks are one set per DEVICE: calls on snapshots of different
+ * engines on one device are safe from any threads but take turns, a host-form call for its whole round trip.  Counts are exact uint64 sums; a total past 2^64 wraps as the reference's would. */
+#define LH_MAX_BOUNDS 64
+enum { LH_LE_PER_METRIC = 1 };
+int lh_count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags,
+                uint64_t *cum, uint64_t *total);
+int lh_count_le_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags,
+                       uint64_t *d_cum, uint64_t *d_total);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

@@ -133,6 +133,10 @@ int lh_tool_read_ceiling(const void *d_ptr, size_t bytes, int reps, void *stream
  * from ~240 names on), HIP events on the snapshot stream: the K2 kernel(s) alone, and the device-to-host copy of the
  * results behind them.  LH_ESTATE when the engine has not run such an extract. */
 int lh_tool_last_extract_ms(lh_engine *e, float *kernel_ms, float *copy_ms);
+/* lh_count_le* gives a row one wave when a call covers at least this many rows, one workgroup of 16 waves below it
+ * (default 1 024; profiles/count_le.txt has both shapes either side).  Process-wide; 0 restores the default; *previous
+ * (may be NULL) receives the value in force before.  Both shapes are exact: this moves time only. */
+int lh_tool_count_le_switch(uint32_t wave_from_rows, uint32_t *previous);
 
 #ifdef __cplusplus
 }

@@ -318,6 +318,43 @@ class Snapshot:
         if ids:
             self.add_buckets(np.concatenate(ids), np.concatenate(keys), np.concatenate(counts))
 
+    # -- counts at or below given values (the running count of percentile()'s bucket walk, metrics.go:389-418) -----------
+    def count_le(self, bounds, nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """dict(cum=uint64[nmetrics, nb], total=uint64[nmetrics]) for metrics [first, first+nmetrics) (lh_count_le*):
+        cum[m, j] = samples of metric first + m whose bucket key is <= the key of bound j (bucket resolution), total[m] =
+        all of them.  A 1-D `bounds` is shared by all names, a 2-D [nmetrics, nb] one holds a row per metric; every row is
+        non-decreasing.  out=(cum, total) of contiguous 8-byte torch device tensors (either may be None) takes the device
+        form: enqueued on the snapshot's stream, the tensors are returned as they are.  The host form's arrays are pinned
+        host memory, so that the results arrive by one copy."""
+        L = N.lib()
+        b = np.ascontiguousarray(bounds, dtype=np.float64)
+        if b.ndim == 2:
+            flags, nb = N.LE_PER_METRIC, int(b.shape[1])
+            if nmetrics is None:
+                nmetrics = int(b.shape[0])
+            if int(b.shape[0]) != nmetrics:
+                raise ValueError("per-metric bounds hold one row per metric")
+        elif b.ndim == 1:
+            flags, nb = 0, int(b.size)
+            if nmetrics is None:
+                nmetrics = self.engine.num_metrics() - first
+        else:
+            raise ValueError("bounds are 1-D (shared) or 2-D [nmetrics, nb]")
+        if out is not None:
+            cum, total = out
+            for t, n in ((cum, nmetrics * nb), (total, nmetrics)):
+                if t is not None and (t.element_size() != 8 or int(t.numel()) != n or not t.is_contiguous()):
+                    raise ValueError("device form: cum holds nmetrics * nb and total nmetrics contiguous 8-byte elements")
+            N.check(L.lh_count_le_device(self._h, first, nmetrics, b.ctypes.data, nb, flags, _ptr(cum), _ptr(total)),
+                    "lh_count_le_device")
+            return dict(cum=cum, total=total)
+        import torch
+        cum = torch.empty((nmetrics, nb), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)
+        total = torch.empty((nmetrics,), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)
+        N.check(L.lh_count_le(self._h, first, nmetrics, b.ctypes.data, nb, flags, cum.ctypes.data, total.ctypes.data),
+                "lh_count_le")
+        return dict(cum=cum, total=total)
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
