@@ -120,8 +120,20 @@ def test_percentile_thresholds_against_the_per_bucket_loop(native_lib, torch_cud
         if a.dtype.kind == "f":
             a, b = a.view(np.uint64), b.view(np.uint64)
         assert np.array_equal(a, b), k                              # the two kernels agree bit for bit
+    D = oracle.decompress_table()
     for m in range(M):
         ref = oracle.process_dense(dense[m], P)
+        # _sum against the oracle's (the kernels share their order of summation: agreeing with each other is not enough),
+        # and what processHistograms derives from it (metrics.go:356, 374)
+        s, n = np.float64(got["sum"][m]), int(got["count"][m])
+        terms = float(np.sum(np.abs(D) * dense[m].astype(np.float64)))
+        assert abs(float(s) - ref["sum"]) <= 1e-12 * terms, (m, float(s), ref["sum"])
+        if n:
+            assert np.array([s / np.float64(n)]).view(np.uint64)[0] == np.array([got["avg"][m]]).view(np.uint64)[0], m
+        else:
+            assert np.isnan(got["avg"][m]), m
+        assert int(got["agg_sum_add"][m]) == oracle.f64_to_u64_amd64(float(s)), (m, float(s))
+        assert int(got["present"][m]) == (1 if n else 0), m
         assert int(got["count"][m]) == ref["count"] and int(got["nbuckets"][m]) == ref["nbuckets"], m
         assert np.array_equal(got["pvalid"][m], ref["pvalid"]), (m, rows[m] if len(rows[m]) < 8 else len(rows[m]))
         assert np.array_equal(got["pkeys"][m], ref["pkeys"]), (m, got["pkeys"][m], ref["pkeys"])
