@@ -339,6 +339,44 @@ int lh_count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *b
                 uint64_t *cum, uint64_t *total);
 int lh_count_le_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags,
                        uint64_t *d_cum, uint64_t *d_total);
+/* Spread and percentile-trimmed sums per name: what statsd emits as std / mean_90 / sum_90 / count_90 / upper_90, a
+ * Coda-Hale-style registry as stddev, and the "tail mean" of the slowest few per cent.  One more weighted walk of the kind
+ * processHistograms does (/root/reference/metrics.go:342-346: `sum += value * float64(*count)` over the buckets), cut at the
+ * bucket percentile() selects (metrics.go:406-418).  With c[b] the cells of metric first + m (RawMetricSet.Histograms,
+ * metrics.go:54-60) and D[b] = decompress(key of bin b) (metrics.go:326-332), bit for bit the D[] of lh_codec_tables:
+ *   count[m] = sum of c[b]                          (uint64; wraps past 2^64 as the reference's would; lh_stats.count)
+ *   sum[m]   = sum of D[b] * float64(c[b])          (metrics.go:344)
+ *   m2[m]    = sum of float64(c[b]) * (D[b] - mean)^2, mean = sum / float64(count): the CENTRED second moment, taken in a
+ *              second walk of the row -- not a difference of raw power sums, so a name whose samples share one bucket has
+ *              a spread of (numerically) zero rather than rounding noise.  count == 0: sum and m2 are 0.
+ * and for each p[i], at the bucket percentile() selects -- the first bin whose inclusive prefix count reaches
+ * T = min{s in [1, total] : float64(s) / float64(total) >= p} (metrics.go:413):
+ *   pkeys[m * np + i], pvalid[m * np + i]   what lh_extract_rows returns for the same snapshot and p (p unsorted, repeated,
+ *                                           0, 1, > 1 or NaN included: the last two have no bucket, pvalid 0)
+ *   count_le[m * np + i]                    the inclusive prefix count at that bin
+ *   sum_le[m * np + i]                      sum of D[b] * float64(c[b]) over the bins up to and including it
+ * Where pvalid is 0 the key, count_le and sum_le are 0.  RESOLUTION IS THE BUCKET, as for lh_count_le: every sample of the
+ * selected bucket is taken in, so count_le / count may exceed p by that bucket's share.
+ * What a caller derives (Snapshot.spread in the Python binding does):
+ *   std = sqrt(m2 / count)      mean_p = sum_le / count_le      upper_p = D[pkey]
+ *   tail mean = (sum - sum_le) / (count - count_le)             (the samples above the percentile's bucket)
+ * Floating-point sums are taken in a fixed order: a result does not depend on timing (it may differ in the last bits
+ * between calls that cover different numbers of rows, which use differently shaped kernels, and from lh_stats.sum).
+ *   np <= LH_MAX_PERCENTILES; np == 0 is allowed: moments only, the four per-percentile outputs are ignored.
+ *   Any output may be NULL, but not all of them.
+ *   LH_EINVAL, checked on the host before the snapshot or a device is touched: NULL s; np too large; np > 0 with NULL p;
+ *            all outputs NULL; arrays not aligned to their element size.  first + nmetrics > max_metrics -> LH_ERANGE.
+ *            nmetrics == 0 -> LH_OK, nothing written.
+ * READ-ONLY, ordering, threading and staging as for lh_count_le*: enqueued on lh_snapshot_stream(s); lh_spread returns when
+ * the results are in the caller's arrays (pinned arrays receive them by one copy each, others go through a pinned block of
+ * the library's); lh_spread_device takes device arrays and returns after enqueueing (the first call on a device also
+ * generates the unit's copy of D[] and waits for it once).  p is a HOST array in both forms and travels by value.  One set
+ * of staging blocks per DEVICE behind a mutex: calls on snapshots of different engines take turns. */
+int lh_spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, uint64_t *count, double *sum,
+              double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le);
+int lh_spread_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, uint64_t *d_count,
+                     double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
+                     double *d_sum_le);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

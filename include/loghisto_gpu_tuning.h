@@ -137,6 +137,9 @@ int lh_tool_last_extract_ms(lh_engine *e, float *kernel_ms, float *copy_ms);
  * (default 1 024; profiles/count_le.txt has both shapes either side).  Process-wide; 0 restores the default; *previous
  * (may be NULL) receives the value in force before.  Both shapes are exact: this moves time only. */
 int lh_tool_count_le_switch(uint32_t wave_from_rows, uint32_t *previous);
+/* The same switch of lh_spread* (default 1 024; profiles/spread.txt has both shapes either side).  The two shapes agree
+ * exactly in every integer output and to rounding in the sums, which they associate differently. */
+int lh_tool_spread_switch(uint32_t wave_from_rows, uint32_t *previous);
 
 #ifdef __cplusplus
 }

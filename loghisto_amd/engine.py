@@ -355,6 +355,77 @@ class Snapshot:
                 "lh_count_le")
         return dict(cum=cum, total=total)
 
+    # -- spread and percentile-trimmed sums (the weighted walk of metrics.go:342-346, cut where percentile() cuts) --------
+    _SPREAD_OUT = (("count", 8, 0), ("sum", 8, 0), ("m2", 8, 0), ("pkeys", 2, 1), ("pvalid", 1, 1), ("count_le", 8, 1),
+                   ("sum_le", 8, 1))
+
+    def spread(self, percentiles, nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """dict(count, sum, m2, std, pkeys, pvalid, count_le, sum_le, mean_le, upper) for metrics [first, first+nmetrics)
+        (lh_spread*): count / sum as extract() has them, m2 = sum of count * (value - mean)^2 over the buckets, std =
+        sqrt(m2 / count); per percentile the key lh_extract_rows selects, the samples (count_le) and their sum (sum_le) up to
+        and including that bucket, mean_le = sum_le / count_le (statsd's mean_90) and upper = decompress(key) (upper_90).
+        Bucket resolution, like count_le.  The mean of the tail above a percentile is (sum - sum_le) / (count - count_le).
+        std, mean_le and upper are NaN where there is nothing to divide (an empty name, a percentile without a bucket).
+        `percentiles` may be empty: moments only.
+        out = a dict with any of count, sum, m2, pkeys, pvalid, count_le, sum_le -> contiguous arrays of nmetrics
+        (the first three) or nmetrics * np elements of 8, 8, 8, 2, 1, 8, 8 bytes; outputs left out are not computed.
+        torch device tensors take the device form: enqueued on the snapshot's stream, the tensors are returned as they are
+        and nothing is derived.  numpy arrays (pinned ones receive their results by one copy) take the host form."""
+        L = N.lib()
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        np_ = int(p.size)
+        if out is not None:
+            if not out or set(out) - {k for k, _, _ in self._SPREAD_OUT}:
+                raise ValueError("out holds some of count, sum, m2, pkeys, pvalid, count_le, sum_le")
+            device = [hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()]
+            if any(device) != all(device):
+                raise ValueError("out holds device tensors or host arrays, not both")
+            args = []
+            for k, width, per_p in self._SPREAD_OUT:
+                t = out.get(k)
+                if t is not None and not (per_p and np_ == 0):
+                    n = nmetrics * np_ if per_p else nmetrics
+                    if hasattr(t, "data_ptr"):
+                        ok = t.element_size() == width and int(t.numel()) == n and t.is_contiguous()
+                    else:
+                        ok = isinstance(t, np.ndarray) and t.itemsize == width and t.size == n and t.flags.c_contiguous
+                    if not ok:
+                        raise ValueError(f"out[{k!r}] holds {n} contiguous elements of {width} bytes")
+                args.append(_ptr(t))
+            if all(device):
+                N.check(L.lh_spread_device(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread_device")
+                return dict(out)
+            N.check(L.lh_spread(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread")
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
+                   if v is not None and (np_ or k in ("count", "sum", "m2"))}
+        else:
+            import torch
+            kinds = dict(count=(torch.int64, np.uint64), sum=(torch.float64, np.float64), m2=(torch.float64, np.float64),
+                         pkeys=(torch.int16, np.int16), pvalid=(torch.uint8, np.uint8), count_le=(torch.int64, np.uint64),
+                         sum_le=(torch.float64, np.float64))
+            res = {}
+            for k, _, per_p in self._SPREAD_OUT:       # (a row more than an empty call needs: the arrays have addresses)
+                shape = (max(nmetrics, 1), np_) if per_p else (max(nmetrics, 1),)
+                res[k] = torch.zeros(shape, dtype=kinds[k][0], pin_memory=True).numpy().view(kinds[k][1])
+            N.check(L.lh_spread(self._h, first, nmetrics, p.ctypes.data, np_,
+                                *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in self._SPREAD_OUT]), "lh_spread")
+            res = {k: v[:nmetrics] for k, v in res.items()}
+        res = {k: (v.reshape(nmetrics, np_) if dict((a, c) for a, _, c in self._SPREAD_OUT)[k] else v.reshape(nmetrics))
+               for k, v in res.items()}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if "m2" in res and "count" in res:
+                res["std"] = np.sqrt(res["m2"] / res["count"].view(np.uint64).astype(np.float64))
+            if "sum_le" in res and "count_le" in res:
+                res["mean_le"] = res["sum_le"] / res["count_le"].view(np.uint64).astype(np.float64)
+        if "pkeys" in res and "pvalid" in res:
+            if getattr(self.engine, "_decompress_table", None) is None:
+                self.engine._decompress_table = self.engine.codec_tables()[1]
+            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
+            res["upper"] = np.where(res["pvalid"] != 0, self.engine._decompress_table[bins], np.nan)
+        return res
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
