@@ -1,0 +1,171 @@
+// lh_beside.h -- host-only plumbing of the units built BESIDE the engine (lh_import.hip, lh_count.hip, lh_spread.hip; a
+// new reader of a snapshot starts here and in lh_wave.h).  Such a unit sees the engine through its public C ABI only
+// (include/loghisto_gpu.h: it cannot see struct lh_engine / lh_snapshot):
+//   lh_snapshot_cells    the cells AS THEY ARE, 4 or 8 bytes wide (nothing moves: a narrow snapshot stays narrow), and the
+//                        number of rows
+//   lh_snapshot_ranges   the rows' dirty spans [lo, hi] -- cells outside are zero; their address also names the device
+//   lh_snapshot_stream   the stream the snapshot's extract / clear work is ordered on: the unit's kernels go there
+//   lh_row_stride        >= LH_NKEYS + 4, so that whole 4-bin groups are readable up to bin 65 535
+// A reader is read-only: no store goes to a cell, a span or the engine.  (lh_import.hip writes, and says how.)
+//
+// What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
+// way a host form's results travel back, and the measurement switch's exchange.
+#pragma once
+
+#include "../../include/loghisto_gpu.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstring>
+
+namespace lh {
+namespace beside {
+
+// clears the sticky error; for functions that return an lh status
+#define LH_BESIDE_CHK(expr)                                                                    \
+    do {                                                                                       \
+        const hipError_t _e = (expr);                                                          \
+        if (_e != hipSuccess) {                                                                \
+            (void)hipGetLastError();                                                           \
+            return _e == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;                         \
+        }                                                                                      \
+    } while (0)
+
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+// pinned host memory the copy engine can write directly (hipHostMalloc'ed or registered by the caller)
+inline bool is_pinned(const void *p)
+{
+    if (!p) return true;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return attr.type == hipMemoryTypeHost;
+}
+
+// Per-device state of a unit, allocated on first use and kept for the life of the process (the engine's own pinned
+// blocks are not reachable through the ABI).  One array per context TYPE: each unit has its own slots, and its own
+// mutex in them -- units never wait for each other.  nullptr: no such slot.
+constexpr int MAX_DEVICES = 64;
+template <class Ctx> Ctx *device_ctx(int device)
+{
+    static Ctx slots[MAX_DEVICES];
+    return device < 0 || device >= MAX_DEVICES ? nullptr : &slots[device];
+}
+
+struct Opened {
+    uint32_t *ranges = nullptr;
+    int device = -1;
+    hipStream_t stream = nullptr;
+    size_t stride = 0;
+};
+
+// spans, device (made current), the unit's context there, stream, stride.  Moves nothing.
+template <class Ctx> int open_snapshot(lh_snapshot *s, Opened &o, Ctx *&cx)
+{
+    void *p = nullptr;
+    int rc = lh_snapshot_ranges(s, &p);
+    if (rc) return rc;
+    o.ranges = static_cast<uint32_t *>(p);
+    hipPointerAttribute_t attr;
+    LH_BESIDE_CHK(hipPointerGetAttributes(&attr, p));
+    cx = device_ctx<Ctx>(attr.device);
+    if (!cx) return LH_EDEVICE;
+    o.device = attr.device;
+    LH_BESIDE_CHK(hipSetDevice(attr.device));
+    rc = lh_snapshot_stream(s, &p);
+    if (rc) return rc;
+    o.stream = static_cast<hipStream_t>(p);
+    o.stride = lh_row_stride();
+    return LH_OK;
+}
+
+// A block that only grows: below `need` elements it is freed and allocated again at `floor` doubled until it fits.
+// After a failure the pointer is null and the capacity 0.
+inline size_t grown(size_t need, size_t floor)
+{
+    while (floor < need) floor <<= 1;
+    return floor;
+}
+template <class T> int grow_device(T *&ptr, size_t &cap, size_t need, size_t floor, size_t elem_bytes = sizeof(T))
+{
+    if (cap >= need) return LH_OK;
+    if (ptr) LH_BESIDE_CHK(hipFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    const size_t n = grown(need, floor);
+    LH_BESIDE_CHK(hipMalloc((void **)&ptr, n * elem_bytes));
+    cap = n;
+    return LH_OK;
+}
+template <class T> int grow_pinned(T *&ptr, size_t &cap, size_t need, size_t floor, size_t elem_bytes = sizeof(T))
+{
+    if (cap >= need) return LH_OK;
+    if (ptr) LH_BESIDE_CHK(hipHostFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    const size_t n = grown(need, floor);
+    LH_BESIDE_CHK(hipHostMalloc((void **)&ptr, n * elem_bytes, hipHostMallocDefault));
+    cap = n;
+    return LH_OK;
+}
+
+// The host form's results: the kernel's output in HBM / its pinned landing block (in bytes; part of the unit's context)
+struct ResultBlocks {
+    unsigned char *d_res = nullptr, *h_res = nullptr;
+    size_t d_cap = 0, h_cap = 0;
+};
+constexpr size_t RESULT_FLOOR = 32768;
+struct HostOut {
+    void *host; // the caller's array, or null: not asked for
+    size_t bytes;
+};
+
+// (the context's mutex held)  Lays the arrays that were asked for out in the device block, each at a multiple of 8 bytes,
+// has `enqueue(dev)` put the work that fills them on `st` (dev[k]: where array k goes, null with out[k].host), then
+// brings them back -- one copy per array straight into the caller's arrays when all of those are pinned, one copy through
+// the pinned block otherwise -- and waits for `st`.
+template <size_t N, class Enqueue> int host_results(ResultBlocks &rb, hipStream_t st, const HostOut (&out)[N], Enqueue enqueue)
+{
+    size_t at[N], need = 0;
+    bool direct = true;
+    for (size_t k = 0; k < N; k++) {
+        at[k] = need;
+        need += ((out[k].host ? out[k].bytes : 0) + 7) & ~(size_t)7;
+    }
+    int rc = grow_device(rb.d_res, rb.d_cap, need, RESULT_FLOOR);
+    if (rc) return rc;
+    for (size_t k = 0; k < N; k++) direct = direct && is_pinned(out[k].host);
+    if (!direct) {
+        rc = grow_pinned(rb.h_res, rb.h_cap, need, RESULT_FLOOR);
+        if (rc) return rc;
+    }
+    unsigned char *dev[N];
+    for (size_t k = 0; k < N; k++) dev[k] = out[k].host ? rb.d_res + at[k] : nullptr;
+    rc = enqueue(dev);
+    if (rc) return rc;
+    if (direct) {
+        for (size_t k = 0; k < N; k++)
+            if (out[k].host) LH_BESIDE_CHK(hipMemcpyAsync(out[k].host, dev[k], out[k].bytes, hipMemcpyDeviceToHost, st));
+        LH_BESIDE_CHK(hipStreamSynchronize(st));
+    } else {
+        LH_BESIDE_CHK(hipMemcpyAsync(rb.h_res, rb.d_res, need, hipMemcpyDeviceToHost, st));
+        LH_BESIDE_CHK(hipStreamSynchronize(st));
+        for (size_t k = 0; k < N; k++)
+            if (out[k].host) std::memcpy(out[k].host, rb.h_res + at[k], out[k].bytes);
+    }
+    return LH_OK;
+}
+
+// lh_tool_*_switch: the rows from which a call takes its wave form; 0 restores the default
+inline void switch_exchange(std::atomic<uint32_t> &v, uint32_t value, uint32_t dflt, uint32_t *previous)
+{
+    const uint32_t old = v.exchange(value ? value : dflt, std::memory_order_relaxed);
+    if (previous) *previous = old;
+}
+
+} // namespace beside
+} // namespace lh

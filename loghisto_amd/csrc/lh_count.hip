@@ -4,12 +4,7 @@
 // <= compress(bounds[j]) (metrics.go:316-322), total[m] = all of them.  Counts, unlike percentiles, add up across
 // intervals, ranks and processes.
 //
-// Built BESIDE the engine, on its public C ABI only, as lh_import.hip is (this unit cannot see struct lh_snapshot):
-//   lh_snapshot_cells    the cells AS THEY ARE, 4 or 8 bytes wide (nothing moves: a narrow snapshot stays narrow)
-//   lh_snapshot_ranges   the rows' dirty spans [lo, hi] -- cells outside are zero; their address also names the device
-//   lh_snapshot_stream   the stream the snapshot's extract / clear work is ordered on: the count goes there
-//   lh_row_stride        >= LH_NKEYS + 4, so that whole 4-bin groups are readable up to bin 65 535
-// Read-only: no store goes to a cell, a span or the engine.
+// Built BESIDE the engine, on its public C ABI only: lh_beside.h says what that gives a reader.  Read-only.
 //
 // A bound becomes E = the number of leading bins it takes in (0 .. 65 536): bin(compress(b)) + 1, by the same
 // arithmetic the threshold table of the ingest is generated with (lh::d_kext_golog of 1 + |b|); 0 for -Inf and for
@@ -28,7 +23,9 @@
 //                     512 KiB) as 256 dependent steps; this form takes two barriers.
 #include "../../include/loghisto_gpu.h"
 #include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
 #include "lh_codec.h"
+#include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,6 +34,12 @@
 #include <mutex>
 
 namespace {
+
+using namespace lh::beside;
+using lh::load4_cells;
+using lh::readlane_u64;
+using lh::shfl_u64;
+using lh::wave_scan_incl_u64;
 
 typedef unsigned long long u64;
 
@@ -49,61 +52,10 @@ constexpr uint32_t CL_TAKE_ALL = LH_NKEYS;
 // windows of a few hundred bins the wave form is ahead from 1 024 rows on and the two are level at 256; over one
 // full-span row the workgroup is several times faster -- so few rows, which may be wide, get workgroups.
 constexpr uint32_t CL_WAVE_FROM_DEFAULT = 1024;
-constexpr int CL_MAX_DEVICES = 64;
 static_assert(CL_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
 
 // shared bounds travel in the kernel arguments (512 bytes); per-metric ones are read from `pb`
 struct LeBounds { double b[LH_MAX_BOUNDS]; };
-
-// 16 bytes at a 4- / 8-byte-aligned address as ONE load (unaligned vector access is on for HSA)
-struct __attribute__((packed, aligned(4))) u32x4_a4 { uint32_t a, b, c, d; };
-struct __attribute__((packed, aligned(8))) u64x2_a8 { u64 a, b; };
-
-// bins b0 .. b0 + 3 of a row; a lane whose group starts beyond hi asks for nothing.  hi <= 65 535 and the rows are
-// at least LH_NKEYS + 4 cells apart (checked at launch), so the group ends inside the row's own stride.
-template <typename CELL> __device__ __forceinline__ void load4(const CELL *__restrict__ row, uint32_t b0, uint32_t hi, u64 (&c)[4])
-{
-    c[0] = c[1] = c[2] = c[3] = 0;
-    if (b0 <= hi) {
-        if constexpr (sizeof(CELL) == 4) {
-            const u32x4_a4 q = *reinterpret_cast<const u32x4_a4 *>(row + b0);
-            c[0] = q.a; c[1] = q.b; c[2] = q.c; c[3] = q.d;
-        } else {
-            const u64x2_a8 *rp = reinterpret_cast<const u64x2_a8 *>(row + b0);
-            const u64x2_a8 c01 = rp[0], c23 = rp[1];
-            c[0] = c01.a; c[1] = c01.b; c[2] = c23.a; c[3] = c23.b;
-        }
-    }
-}
-
-#define CL_DPP32(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), (rows), 0xf, false))
-template <int CTRL, int ROWS> __device__ __forceinline__ u64 dpp_u64(u64 x)
-{
-    const uint32_t lo = CL_DPP32((uint32_t)x, CTRL, ROWS), hi = CL_DPP32((uint32_t)(x >> 32), CTRL, ROWS);
-    return ((u64)hi << 32) | lo; // lanes without a source (or outside ROWS) get 0
-}
-// inclusive prefix sum over the 64 lanes: row_shr:1/2/4/8 inside the rows of 16 lanes, then row_bcast:15 and :31
-__device__ __forceinline__ u64 wave_scan_incl(u64 x)
-{
-    x += dpp_u64<0x111, 0xf>(x);
-    x += dpp_u64<0x112, 0xf>(x);
-    x += dpp_u64<0x114, 0xf>(x);
-    x += dpp_u64<0x118, 0xf>(x);
-    x += dpp_u64<0x142, 0xa>(x);
-    x += dpp_u64<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ u64 readlane_u64(u64 x, uint32_t src) // src wave-uniform
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)src);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 shfl_u64(u64 x, uint32_t src) // src per lane
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, (int)src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), (int)src, 64);
-    return ((u64)hi << 32) | lo;
-}
 
 // How many leading bins bound b takes in: bin(compress(b)) + 1 (metrics.go:316-322 with the extended key before its
 // int16 truncation; -0.0 and 0.0 both give key 0).  The host refused NaN.
@@ -130,14 +82,14 @@ __global__ __launch_bounds__(CL_BLOCK) void k_count_le_wave(const CELL *__restri
         const CELL *__restrict__ row = cells + (size_t)m * stride;
         const uint32_t base0 = lo & ~3u; // (cells below lo are zero) whole groups: every load is 16-byte aligned
         u64 c[4], nx[4];
-        load4(row, base0 + 4 * lane, hi, c);
+        load4_cells(row, base0 + 4 * lane, hi, c);
         uint32_t E = 0;
         if (lane < nb) E = le_take(pb ? pb[(size_t)m * nb + lane] : sb.b[lane]);
         bool pend = lane < nb && E > base0; // a bound at or below the span's first bin: 0
         for (uint32_t base = base0; base <= hi; base += CL_STEP) {
-            load4(row, base + CL_STEP + 4 * lane, hi, nx); // the next step's cells: in flight under this step's scan
+            load4_cells(row, base + CL_STEP + 4 * lane, hi, nx); // the next step's cells: in flight under this step's scan
             const u64 t = (c[0] + c[1]) + (c[2] + c[3]);
-            const u64 inc = wave_scan_incl(t);
+            const u64 inc = wave_scan_incl_u64(t);
             // (every pending E is > base: an earlier step would have taken it otherwise)
             const bool in = pend && E <= base + CL_STEP;
             if (__builtin_amdgcn_ballot_w64(in)) { // wave-uniform
@@ -183,12 +135,12 @@ __global__ __launch_bounds__(CL_WG) void k_count_le_block(const CELL *__restrict
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) { // (a chunk beyond the span starts beyond hi: nothing is read)
             u64 c[4];
-            load4(row, base0 + (c0 + u * CL_WG_WAVES) * CL_STEP + 4 * lane, hi, c);
+            load4_cells(row, base0 + (c0 + u * CL_WG_WAVES) * CL_STEP + 4 * lane, hi, c);
             t[u] = (c[0] + c[1]) + (c[2] + c[3]);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
-            const u64 inc = wave_scan_incl(t[u]);
+            const u64 inc = wave_scan_incl_u64(t[u]);
             const uint32_t ch = c0 + u * CL_WG_WAVES;
             if (lane == 63 && ch < nchunks) s_chunk[ch] = inc;
         }
@@ -199,7 +151,7 @@ __global__ __launch_bounds__(CL_WG) void k_count_le_block(const CELL *__restrict
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) v[k] = 4 * lane + k < nchunks ? s_chunk[4 * lane + k] : 0;
         const u64 t = (v[0] + v[1]) + (v[2] + v[3]);
-        const u64 inc = wave_scan_incl(t);
+        const u64 inc = wave_scan_incl_u64(t);
         u64 ex = inc - t;
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) {
@@ -219,9 +171,9 @@ __global__ __launch_bounds__(CL_WG) void k_count_le_block(const CELL *__restrict
                 val = tot;
             } else {
                 u64 c[4];
-                load4(row, base0 + ch * CL_STEP + 4 * lane, hi, c);
+                load4_cells(row, base0 + ch * CL_STEP + 4 * lane, hi, c);
                 const u64 t = (c[0] + c[1]) + (c[2] + c[3]);
-                const u64 inc = wave_scan_incl(t);
+                const u64 inc = wave_scan_incl_u64(t);
                 const uint32_t k = idx & 3, f = (idx % CL_STEP) >> 2;
                 const u64 pre = (inc - t) + c[0] + (k >= 1 ? c[1] : 0) + (k >= 2 ? c[2] : 0) + (k >= 3 ? c[3] : 0);
                 val = s_chunk[ch] + readlane_u64(pre, f);
@@ -233,39 +185,25 @@ __global__ __launch_bounds__(CL_WG) void k_count_le_block(const CELL *__restrict
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-// Per-device state of this unit, allocated on first use and kept for the life of the process (the engine's own pinned
-// blocks are not reachable through the ABI).  `mu` is held for the length of a call -- the host form's wait for its
-// results included, so host-form calls on one device take turns even when their snapshots belong to different engines.
+// Per-device state of this unit (device_ctx<CountCtx>).  `mu` is held for the length of a call -- the host form's wait for
+// its results included, so host-form calls on one device take turns even when their snapshots belong to different engines.
 // Snapshots of different engines run on different streams: everything below that outlives a call (the bounds blocks) is
 // guarded by an event, not by stream order.
 struct CountCtx {
     std::mutex mu;
-    u64 *d_res = nullptr, *h_res = nullptr; // host form: the kernel's results in HBM / their pinned landing block
-    size_t d_cap = 0, h_cap = 0;            // (in uint64)
+    ResultBlocks res;                       // host form
     double *h_bounds = nullptr, *d_bounds = nullptr; // per-metric bounds: the caller's, copied (pinned); in HBM for the kernel
-    size_t b_cap = 0;
+    size_t hb_cap = 0, db_cap = 0;          // (in doubles)
     hipEvent_t ev = nullptr;                // behind the last kernel that reads d_bounds, on whichever stream that was
     bool ev_pending = false;                // cleared only by a wait on `ev` itself: another stream's sync says nothing
 };
-CountCtx g_ctx[CL_MAX_DEVICES];
 std::atomic<uint32_t> g_wave_from{CL_WAVE_FROM_DEFAULT};
-
-#define CLCHK(expr)                                                                            \
-    do {                                                                                       \
-        const hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            return _e == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;                         \
-        }                                                                                      \
-    } while (0)
-
-bool misaligned8(const void *p) { return ((uintptr_t)p & 7) != 0; }
 
 // every check that needs neither the snapshot nor a device
 int check_args(lh_snapshot *s, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, const void *cum, const void *total)
 {
     if (!s || nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || (flags & ~(uint32_t)LH_LE_PER_METRIC)) return LH_EINVAL;
-    if (misaligned8(bounds) || misaligned8(cum) || misaligned8(total)) return LH_EINVAL;
+    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32): not a row of bounds is read
     const size_t rows = (flags & LH_LE_PER_METRIC) ? nmetrics : 1;
     for (size_t r = 0; r < rows; r++) {
@@ -276,34 +214,11 @@ int check_args(lh_snapshot *s, size_t nmetrics, const double *bounds, size_t nb,
     return LH_OK;
 }
 
-struct Source {
+struct Source : Opened {
     CountCtx *cx = nullptr;
-    hipStream_t st = nullptr;
     const void *cells = nullptr;
-    const uint32_t *ranges = nullptr;
     uint32_t nrows = 0, cell_bytes = 0;
-    size_t stride = 0;
 };
-
-// cells, spans, device, stream.  Moves nothing.
-int source_open(lh_snapshot *s, Source &q)
-{
-    void *p = nullptr;
-    int rc = lh_snapshot_ranges(s, &p);
-    if (rc) return rc;
-    q.ranges = static_cast<const uint32_t *>(p);
-    hipPointerAttribute_t attr;
-    CLCHK(hipPointerGetAttributes(&attr, p));
-    if (attr.device < 0 || attr.device >= CL_MAX_DEVICES) return LH_EDEVICE;
-    CLCHK(hipSetDevice(attr.device));
-    q.cx = &g_ctx[attr.device];
-    rc = lh_snapshot_stream(s, &p);
-    if (rc) return rc;
-    q.st = static_cast<hipStream_t>(p);
-    q.stride = lh_row_stride();
-    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
-    return LH_OK;
-}
 
 // (cx->mu held) enqueue the count of rows [first, first + nmetrics) on the snapshot's stream
 int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, u64 *d_cum,
@@ -315,25 +230,16 @@ int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *boun
     if (flags & LH_LE_PER_METRIC) {
         const size_t n = nmetrics * nb;
         if (cx->ev_pending) { // an earlier call's copy / kernel may still read the two blocks
-            CLCHK(hipEventSynchronize(cx->ev));
+            LH_BESIDE_CHK(hipEventSynchronize(cx->ev));
             cx->ev_pending = false;
         }
-        if (cx->b_cap < n) {
-            if (cx->h_bounds) CLCHK(hipHostFree(cx->h_bounds));
-            cx->h_bounds = nullptr;
-            if (cx->d_bounds) CLCHK(hipFree(cx->d_bounds));
-            cx->d_bounds = nullptr;
-            cx->b_cap = 0;
-            size_t cap = 4096;
-            while (cap < n) cap <<= 1;
-            CLCHK(hipHostMalloc((void **)&cx->h_bounds, cap * sizeof(double), hipHostMallocDefault));
-            CLCHK(hipMalloc((void **)&cx->d_bounds, cap * sizeof(double)));
-            cx->b_cap = cap;
-        }
-        if (!cx->ev) CLCHK(hipEventCreateWithFlags(&cx->ev, hipEventDisableTiming));
+        int rc = grow_pinned(cx->h_bounds, cx->hb_cap, n, 4096);
+        if (!rc) rc = grow_device(cx->d_bounds, cx->db_cap, n, 4096);
+        if (rc) return rc;
+        if (!cx->ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->ev, hipEventDisableTiming));
         std::memcpy(cx->h_bounds, bounds, n * sizeof(double));
         // (into HBM by the copy engine, not fetched over PCIe by every wave)
-        CLCHK(hipMemcpyAsync(cx->d_bounds, cx->h_bounds, n * sizeof(double), hipMemcpyHostToDevice, q.st));
+        LH_BESIDE_CHK(hipMemcpyAsync(cx->d_bounds, cx->h_bounds, n * sizeof(double), hipMemcpyHostToDevice, q.stream));
         std::memset(sb.b, 0, sizeof sb.b);
         pb = cx->d_bounds;
     } else {
@@ -345,31 +251,19 @@ int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *boun
     const dim3 grid(wave ? (M + CL_WAVES - 1) / CL_WAVES : M), block(wave ? CL_BLOCK : CL_WG);
     if (q.cell_bytes == 4) {
         const uint32_t *c = static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_count_le_wave<uint32_t>, grid, block, 0, q.st, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
-        else hipLaunchKernelGGL(k_count_le_block<uint32_t>, grid, block, 0, q.st, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
+        if (wave) hipLaunchKernelGGL(k_count_le_wave<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
+        else hipLaunchKernelGGL(k_count_le_block<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
     } else {
         const u64 *c = static_cast<const u64 *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_count_le_wave<u64>, grid, block, 0, q.st, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
-        else hipLaunchKernelGGL(k_count_le_block<u64>, grid, block, 0, q.st, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
+        if (wave) hipLaunchKernelGGL(k_count_le_wave<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
+        else hipLaunchKernelGGL(k_count_le_block<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
     }
-    CLCHK(hipGetLastError());
+    LH_BESIDE_CHK(hipGetLastError());
     if (pb) {
-        CLCHK(hipEventRecord(cx->ev, q.st));
+        LH_BESIDE_CHK(hipEventRecord(cx->ev, q.stream));
         cx->ev_pending = true;
     }
     return LH_OK;
-}
-
-// pinned host memory the copy engine can write directly (hipHostMalloc'ed or registered by the caller)
-bool is_pinned(const void *p)
-{
-    if (!p) return true;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeHost;
 }
 
 int count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, uint64_t *cum,
@@ -384,48 +278,20 @@ int count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *boun
     q.cells = cells;
     if (nmetrics > q.nrows || first > q.nrows - nmetrics) return LH_ERANGE;
     if (nmetrics == 0) return LH_OK;
-    rc = source_open(s, q);
+    rc = open_snapshot(s, q, q.cx);
     if (rc) return rc;
+    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
     CountCtx *cx = q.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form)
         return enqueue(q, first, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(cum), reinterpret_cast<u64 *>(total));
 
-    // host form: results to HBM, then one copy per array -- straight into the caller's arrays when those are pinned,
-    // through this unit's pinned block otherwise
-    const size_t ncum = cum ? nmetrics * nb : 0, ntot = total ? nmetrics : 0, need = ncum + ntot;
-    if (cx->d_cap < need) {
-        if (cx->d_res) CLCHK(hipFree(cx->d_res));
-        cx->d_res = nullptr;
-        cx->d_cap = 0;
-        size_t cap = 4096;
-        while (cap < need) cap <<= 1;
-        CLCHK(hipMalloc((void **)&cx->d_res, cap * sizeof(u64)));
-        cx->d_cap = cap;
-    }
-    const bool direct = is_pinned(cum) && is_pinned(total);
-    if (!direct && cx->h_cap < need) {
-        if (cx->h_res) CLCHK(hipHostFree(cx->h_res));
-        cx->h_res = nullptr;
-        cx->h_cap = 0;
-        size_t cap = 4096;
-        while (cap < need) cap <<= 1;
-        CLCHK(hipHostMalloc((void **)&cx->h_res, cap * sizeof(u64), hipHostMallocDefault));
-        cx->h_cap = cap;
-    }
-    u64 *d_cum = cum ? cx->d_res : nullptr, *d_total = total ? cx->d_res + ncum : nullptr;
-    rc = enqueue(q, first, nmetrics, bounds, nb, flags, d_cum, d_total);
+    // host form: results to HBM, then back to the caller's arrays
+    const HostOut out[2] = {{cum, nmetrics * nb * sizeof(u64)}, {total, nmetrics * sizeof(u64)}};
+    rc = host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[2]) {
+        return enqueue(q, first, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(dev[0]), reinterpret_cast<u64 *>(dev[1]));
+    });
     if (rc) return rc;
-    if (direct) {
-        if (cum) CLCHK(hipMemcpyAsync(cum, d_cum, ncum * sizeof(u64), hipMemcpyDeviceToHost, q.st));
-        if (total) CLCHK(hipMemcpyAsync(total, d_total, ntot * sizeof(u64), hipMemcpyDeviceToHost, q.st));
-        CLCHK(hipStreamSynchronize(q.st));
-    } else {
-        CLCHK(hipMemcpyAsync(cx->h_res, cx->d_res, need * sizeof(u64), hipMemcpyDeviceToHost, q.st));
-        CLCHK(hipStreamSynchronize(q.st));
-        if (cum) std::memcpy(cum, cx->h_res, ncum * sizeof(u64));
-        if (total) std::memcpy(total, cx->h_res + ncum, ntot * sizeof(u64));
-    }
     if (flags & LH_LE_PER_METRIC) cx->ev_pending = false; // this call recorded `ev` on the stream it has just waited for
     return LH_OK;
 }
@@ -448,8 +314,7 @@ int lh_count_le_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const do
 
 int lh_tool_count_le_switch(uint32_t wave_from_rows, uint32_t *previous)
 {
-    const uint32_t old = g_wave_from.exchange(wave_from_rows ? wave_from_rows : CL_WAVE_FROM_DEFAULT, std::memory_order_relaxed);
-    if (previous) *previous = old;
+    switch_exchange(g_wave_from, wave_from_rows, CL_WAVE_FROM_DEFAULT, previous);
     return LH_OK;
 }
 

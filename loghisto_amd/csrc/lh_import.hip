@@ -4,9 +4,8 @@
 // and its cells are a commutative integer sum (atomic.AddUint64, metrics.go:278, 292): adding another process's interval,
 // an older interval of one's own, or a checkpoint is  snapshot[id][key] += count  per CELL, not per sample.
 //
-// Built BESIDE the engine, on its public C ABI only (this unit cannot see struct lh_engine / lh_snapshot):
+// Built BESIDE the engine, on its public C ABI only (lh_beside.h), and the one such unit that WRITES:
 //   lh_snapshot_cells       number of rows, without moving anything
-//   lh_snapshot_ranges      the rows' dirty spans [lo, hi]; their address also names the device
 //   lh_snapshot_rows        the uint64 view (a snapshot of 32-bit cells moves to its wide store first)
 //   lh_snapshot_stream      the stream the snapshot's extract / clear work is ordered on: the adds go there
 //   lh_snapshot_mark_dirty  declares the buffer's cell sizes unknown to a later lh_snapshot_merge.  Called on ONE touched
@@ -20,6 +19,7 @@
 // segments).  The loads are therefore 8 / 4 / 2 bytes per lane, each instruction contiguous over the wave, several groups
 // in flight.  The 64-bit adds return nothing (global_atomic_add_x2 without glc).
 #include "../../include/loghisto_gpu.h"
+#include "lh_beside.h"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,8 @@
 
 namespace {
 
+using namespace lh::beside;
+
 typedef unsigned long long u64;
 
 constexpr int IM_BLOCK = 256;          // 4 waves
@@ -36,7 +38,6 @@ constexpr int IM_UNROLL = 8;           // groups of 64 entries a wave keeps in f
 constexpr uint32_t IM_NOID = 0xffffffffu;
 constexpr uint32_t IM_EMPTY_LO = LH_NKEYS, IM_EMPTY_HI = 0;
 constexpr size_t IM_STAGE_CELLS = size_t(1) << 21; // host forms: entries per pinned staging chunk (28 MiB)
-constexpr int IM_MAX_DEVICES = 64;
 
 // what the validation pre-pass of the device forms brings back (one small copy, one stream wait per call)
 struct ImportResult {
@@ -254,9 +255,8 @@ __global__ void k_locate(const uint32_t *__restrict__ ids, const u64 *__restrict
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-// Per-device state of this unit, allocated on first use and kept for the life of the process (the engine's own pinned
-// blocks are not reachable through the ABI).  `mu` is held for the length of a call: the staging and the result word
-// are one per device.
+// Per-device state of this unit (device_ctx<ImportCtx>).  `mu` is held for the length of a call: the staging and the
+// result word are one per device.
 struct ImportCtx {
     std::mutex mu;
     int cus = 0;
@@ -264,45 +264,19 @@ struct ImportCtx {
     char *h_stage = nullptr; // pinned; the kernels read it in place over PCIe, as the ingest lanes' buffers are read
     size_t stage_cells = 0;
 };
-ImportCtx g_ctx[IM_MAX_DEVICES];
 
-#define IMCHK(expr)                                                                            \
-    do {                                                                                       \
-        const hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            return _e == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;                         \
-        }                                                                                      \
-    } while (0)
-
-struct Target {
+struct Target : Opened {
     lh_snapshot *s = nullptr;
     ImportCtx *cx = nullptr;
-    hipStream_t st = nullptr;
-    uint32_t *ranges = nullptr;
     u64 *rows = nullptr;
     uint32_t nrows = 0;
-    size_t stride = 0;
 };
 
 // device, stream, spans.  Moves nothing yet.
 int target_open(lh_snapshot *s, Target &t)
 {
     t.s = s;
-    void *p = nullptr;
-    int rc = lh_snapshot_ranges(s, &p);
-    if (rc) return rc;
-    t.ranges = static_cast<uint32_t *>(p);
-    hipPointerAttribute_t attr;
-    IMCHK(hipPointerGetAttributes(&attr, p));
-    if (attr.device < 0 || attr.device >= IM_MAX_DEVICES) return LH_EDEVICE;
-    IMCHK(hipSetDevice(attr.device));
-    t.cx = &g_ctx[attr.device];
-    rc = lh_snapshot_stream(s, &p);
-    if (rc) return rc;
-    t.st = static_cast<hipStream_t>(p);
-    t.stride = lh_row_stride();
-    return LH_OK;
+    return open_snapshot(s, t, t.cx);
 }
 
 // (cx->mu held)
@@ -310,12 +284,12 @@ int ctx_ready(ImportCtx *cx)
 {
     if (!cx->cus) {
         int dev = 0, cus = 0;
-        IMCHK(hipGetDevice(&dev));
-        IMCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        LH_BESIDE_CHK(hipGetDevice(&dev));
+        LH_BESIDE_CHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         cx->cus = cus > 0 ? cus : 256;
     }
-    if (!cx->d_res) IMCHK(hipMalloc((void **)&cx->d_res, sizeof(ImportResult)));
-    if (!cx->h_res) IMCHK(hipHostMalloc((void **)&cx->h_res, sizeof(ImportResult), hipHostMallocDefault));
+    if (!cx->d_res) LH_BESIDE_CHK(hipMalloc((void **)&cx->d_res, sizeof(ImportResult)));
+    if (!cx->h_res) LH_BESIDE_CHK(hipHostMalloc((void **)&cx->h_res, sizeof(ImportResult), hipHostMallocDefault));
     return LH_OK;
 }
 
@@ -339,9 +313,9 @@ unsigned grid_for(const ImportCtx *cx, size_t items, size_t per_block)
 
 int launch_add_coo(const Target &t, const uint32_t *ids, const int16_t *keys, const u64 *counts, size_t n)
 {
-    hipLaunchKernelGGL(k_add_coo, dim3(grid_for(t.cx, n, (IM_BLOCK / 64) * 64 * IM_UNROLL)), dim3(IM_BLOCK), 0, t.st, ids, keys,
-                       counts, n, t.rows, t.ranges, t.nrows, t.stride);
-    IMCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_add_coo, dim3(grid_for(t.cx, n, (IM_BLOCK / 64) * 64 * IM_UNROLL)), dim3(IM_BLOCK), 0, t.stream, ids,
+                       keys, counts, n, t.rows, t.ranges, t.nrows, t.stride);
+    LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
 }
 
@@ -351,15 +325,8 @@ template <typename Next> int add_staged(Target &t, size_t nnz, Next next)
 {
     ImportCtx *cx = t.cx;
     const size_t want = std::min(nnz, IM_STAGE_CELLS);
-    if (cx->stage_cells < want) {
-        if (cx->h_stage) IMCHK(hipHostFree(cx->h_stage));
-        cx->h_stage = nullptr;
-        cx->stage_cells = 0;
-        size_t cells = 4096;
-        while (cells < want) cells <<= 1;
-        IMCHK(hipHostMalloc((void **)&cx->h_stage, cells * 14, hipHostMallocDefault));
-        cx->stage_cells = cells;
-    }
+    const int grc = grow_pinned(cx->h_stage, cx->stage_cells, want, 4096, 14); // 14 bytes per entry
+    if (grc) return grc;
     const size_t cap = cx->stage_cells;
     u64 *h_counts = reinterpret_cast<u64 *>(cx->h_stage);
     uint32_t *h_ids = reinterpret_cast<uint32_t *>(cx->h_stage + cap * 8);
@@ -369,19 +336,17 @@ template <typename Next> int add_staged(Target &t, size_t nnz, Next next)
         if (!k) break;
         int rc = launch_add_coo(t, h_ids, h_keys, h_counts, k);
         if (rc) return rc;
-        IMCHK(hipStreamSynchronize(t.st)); // the staging is rewritten / the caller's arrays are the caller's again
+        LH_BESIDE_CHK(hipStreamSynchronize(t.stream)); // the staging is rewritten / the caller's arrays are the caller's again
     }
     return LH_OK;
 }
-
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 // device forms: run the pre-pass that was enqueued, bring the result back
 int result_fetch(const Target &t, ImportResult &out)
 {
     ImportCtx *cx = t.cx;
-    IMCHK(hipMemcpyAsync(cx->h_res, cx->d_res, sizeof(ImportResult), hipMemcpyDeviceToHost, t.st));
-    IMCHK(hipStreamSynchronize(t.st));
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_res, cx->d_res, sizeof(ImportResult), hipMemcpyDeviceToHost, t.stream));
+    LH_BESIDE_CHK(hipStreamSynchronize(t.stream));
     out = *cx->h_res;
     return LH_OK;
 }
@@ -514,11 +479,11 @@ int lh_snapshot_add_buckets_device(lh_snapshot *s, const uint32_t *d_ids, const 
     rc = ctx_ready(t.cx);
     if (rc) return rc;
     ImportResult *res = t.cx->d_res;
-    hipLaunchKernelGGL(k_result_init, dim3(1), dim3(1), 0, t.st, res);
-    hipLaunchKernelGGL(k_check_coo, dim3(grid_for(t.cx, n, IM_BLOCK * 8)), dim3(IM_BLOCK), 0, t.st, d_ids,
+    hipLaunchKernelGGL(k_result_init, dim3(1), dim3(1), 0, t.stream, res);
+    hipLaunchKernelGGL(k_check_coo, dim3(grid_for(t.cx, n, IM_BLOCK * 8)), dim3(IM_BLOCK), 0, t.stream, d_ids,
                        reinterpret_cast<const u64 *>(d_counts), n, t.nrows, res);
-    hipLaunchKernelGGL(k_locate, dim3(1), dim3(1), 0, t.st, d_ids, static_cast<const u64 *>(nullptr), 0u, 0u, d_keys, res);
-    IMCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_locate, dim3(1), dim3(1), 0, t.stream, d_ids, static_cast<const u64 *>(nullptr), 0u, 0u, d_keys, res);
+    LH_BESIDE_CHK(hipGetLastError());
     ImportResult r;
     rc = result_fetch(t, r);
     if (rc) return rc;
@@ -553,11 +518,11 @@ int lh_snapshot_add_buckets_csr_device(lh_snapshot *s, uint32_t first, size_t nm
     const u64 *offs = reinterpret_cast<const u64 *>(d_offsets);
     const u64 *cnt = d_keys && d_counts ? reinterpret_cast<const u64 *>(d_counts) : nullptr;
     const uint32_t M = (uint32_t)nmetrics;
-    hipLaunchKernelGGL(k_result_init, dim3(1), dim3(1), 0, t.st, res);
-    hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(t.cx, nmetrics, IM_BLOCK)), dim3(IM_BLOCK), 0, t.st, offs, M, res);
-    hipLaunchKernelGGL(k_check_csr_counts, dim3((unsigned)t.cx->cus * 8), dim3(IM_BLOCK), 0, t.st, offs, M, cnt, res);
-    hipLaunchKernelGGL(k_locate, dim3(1), dim3(1), 0, t.st, static_cast<const uint32_t *>(nullptr), offs, first, M, d_keys, res);
-    IMCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_result_init, dim3(1), dim3(1), 0, t.stream, res);
+    hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(t.cx, nmetrics, IM_BLOCK)), dim3(IM_BLOCK), 0, t.stream, offs, M, res);
+    hipLaunchKernelGGL(k_check_csr_counts, dim3((unsigned)t.cx->cus * 8), dim3(IM_BLOCK), 0, t.stream, offs, M, cnt, res);
+    hipLaunchKernelGGL(k_locate, dim3(1), dim3(1), 0, t.stream, static_cast<const uint32_t *>(nullptr), offs, first, M, d_keys, res);
+    LH_BESIDE_CHK(hipGetLastError());
     ImportResult r;
     rc = result_fetch(t, r);
     if (rc) return rc;
@@ -565,9 +530,9 @@ int lh_snapshot_add_buckets_csr_device(lh_snapshot *s, uint32_t first, size_t nm
     if (!r.nnz) return LH_OK;
     rc = target_rows(t);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_add_csr, dim3(grid_for(t.cx, nmetrics, IM_BLOCK / 64)), dim3(IM_BLOCK), 0, t.st, offs, d_keys, cnt,
+    hipLaunchKernelGGL(k_add_csr, dim3(grid_for(t.cx, nmetrics, IM_BLOCK / 64)), dim3(IM_BLOCK), 0, t.stream, offs, d_keys, cnt,
                        first, M, t.rows, t.ranges, t.stride);
-    IMCHK(hipGetLastError());
+    LH_BESIDE_CHK(hipGetLastError());
     return lh_snapshot_mark_dirty(s, r.touch_row, 1, r.touch_bin, r.touch_bin);
 }
 

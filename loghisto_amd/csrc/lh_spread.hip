@@ -8,12 +8,7 @@
 // caller has statsd's std / mean_90 / sum_90 / count_90 / upper_90, a registry's stddev and the mean of the tail.
 // RESOLUTION IS THE BUCKET, as for lh_count_le: every sample of the selected bucket is taken in.
 //
-// Built BESIDE the engine, on its public C ABI only, as lh_count.hip is (this unit cannot see struct lh_snapshot):
-//   lh_snapshot_cells    the cells AS THEY ARE, 4 or 8 bytes wide (nothing moves: a narrow snapshot stays narrow)
-//   lh_snapshot_ranges   the rows' dirty spans [lo, hi] -- cells outside are zero; their address also names the device
-//   lh_snapshot_stream   the stream the snapshot's extract / clear work is ordered on: the walks go there
-//   lh_row_stride        >= LH_NKEYS + 4
-// Read-only: no store goes to a cell, a span or the engine.
+// Built BESIDE the engine, on its public C ABI only: lh_beside.h says what that gives a reader.  Read-only.
 //
 // D[b] = decompress(bin_to_key(b)) comes from a table this unit generates once per device with lh::d_decompress_bin (this
 // file is built with -ffp-contract=off like the engine's own generator: the same instructions, the same bits as the D[] of
@@ -28,14 +23,16 @@
 //                   scans the chunk totals in LDS, and each percentile then costs one more read of the one chunk its
 //                   threshold falls into.  For calls of few rows, which may span all 65 536 bins.
 // Each row takes two walks.  Walk 1 gives count and sum, hence the mean and the thresholds T = the smallest prefix count
-// that reaches p (pct_threshold: tests/test_pct_threshold_model.py has the arithmetic).  Walk 2 re-reads the window
+// that reaches p (pct_threshold, lh_wave.h: tests/test_pct_threshold_model.py has the arithmetic).  Walk 2 re-reads the window
 // (L2-resident at typical spans) for m2 and, in the steps a threshold falls into, the key, count_le and sum_le.
 // Every floating-point sum is taken in a fixed order (per lane over the steps in ascending order, then one DPP tree over
 // the lanes; chunk totals in ascending order), so a result does not depend on timing -- but the two shapes associate
 // differently and agree to rounding only.
 #include "../../include/loghisto_gpu.h"
 #include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
 #include "lh_codec.h"
+#include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
 
@@ -44,6 +41,16 @@
 #include <mutex>
 
 namespace {
+
+using namespace lh::beside;
+using lh::f64x2_a8;
+using lh::load4_cells;
+using lh::PCT_NONE;
+using lh::pct_threshold;
+using lh::readlane_f64;
+using lh::readlane_u64;
+using lh::wave_scan_incl_f64;
+using lh::wave_scan_incl_u64;
 
 typedef unsigned long long u64;
 
@@ -56,8 +63,6 @@ constexpr uint32_t SP_CHUNKS = LH_NKEYS / SP_STEP;      // chunks of the widest 
 // from 1 024 on (16.4 against 23.5); over one full-span row the workgroup is four to five times faster -- so few rows,
 // which may be wide, get workgroups.
 constexpr uint32_t SP_WAVE_FROM_DEFAULT = 1024;
-constexpr int SP_MAX_DEVICES = 64;
-constexpr u64 SP_NONE = ~0ull;
 static_assert(SP_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
 static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
 
@@ -72,103 +77,19 @@ struct SpreadOut {
     double *sum_le;
 };
 
-// 16 bytes at a 4- / 8-byte-aligned address as ONE load (unaligned vector access is on for HSA)
-struct __attribute__((packed, aligned(4))) u32x4_a4 { uint32_t a, b, c, d; };
-struct __attribute__((packed, aligned(8))) u64x2_a8 { u64 a, b; };
-struct __attribute__((packed, aligned(8))) f64x2_a8 { double a, b; };
-
 // bins b0 .. b0 + 3 of a row and their table entries; a lane whose group starts beyond hi asks for nothing.  b0 is a
 // multiple of 4 and hi <= 65 535, so the group ends inside the row (and inside the table's LH_NKEYS entries).
 template <typename CELL>
 __device__ __forceinline__ void load4(const CELL *__restrict__ row, const double *__restrict__ D, uint32_t b0, uint32_t hi,
                                       u64 (&c)[4], double (&d)[4])
 {
-    c[0] = c[1] = c[2] = c[3] = 0;
     d[0] = d[1] = d[2] = d[3] = 0.0;
+    load4_cells(row, b0, hi, c);
     if (b0 <= hi) {
-        if constexpr (sizeof(CELL) == 4) {
-            const u32x4_a4 q = *reinterpret_cast<const u32x4_a4 *>(row + b0);
-            c[0] = q.a; c[1] = q.b; c[2] = q.c; c[3] = q.d;
-        } else {
-            const u64x2_a8 *rp = reinterpret_cast<const u64x2_a8 *>(row + b0);
-            const u64x2_a8 c01 = rp[0], c23 = rp[1];
-            c[0] = c01.a; c[1] = c01.b; c[2] = c23.a; c[3] = c23.b;
-        }
         const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
         const f64x2_a8 d01 = dp[0], d23 = dp[1];
         d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
     }
-}
-
-#define SP_DPP32(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), (rows), 0xf, false))
-template <int CTRL, int ROWS> __device__ __forceinline__ u64 dpp_u64(u64 x)
-{
-    const uint32_t lo = SP_DPP32((uint32_t)x, CTRL, ROWS), hi = SP_DPP32((uint32_t)(x >> 32), CTRL, ROWS);
-    return ((u64)hi << 32) | lo; // lanes without a source (or outside ROWS) get 0
-}
-template <int CTRL, int ROWS> __device__ __forceinline__ double dpp_f64(double x) // ... +0.0
-{
-    return __longlong_as_double((long long)dpp_u64<CTRL, ROWS>((u64)__double_as_longlong(x)));
-}
-// inclusive prefix sum over the 64 lanes: row_shr:1/2/4/8 inside the rows of 16 lanes, then row_bcast:15 and :31
-__device__ __forceinline__ u64 wave_scan_incl(u64 x)
-{
-    x += dpp_u64<0x111, 0xf>(x);
-    x += dpp_u64<0x112, 0xf>(x);
-    x += dpp_u64<0x114, 0xf>(x);
-    x += dpp_u64<0x118, 0xf>(x);
-    x += dpp_u64<0x142, 0xa>(x);
-    x += dpp_u64<0x143, 0xc>(x);
-    return x;
-}
-// the same tree in float64: one fixed association, whatever the timing
-__device__ __forceinline__ double wave_scan_incl_f64(double x)
-{
-    x += dpp_f64<0x111, 0xf>(x);
-    x += dpp_f64<0x112, 0xf>(x);
-    x += dpp_f64<0x114, 0xf>(x);
-    x += dpp_f64<0x118, 0xf>(x);
-    x += dpp_f64<0x142, 0xa>(x);
-    x += dpp_f64<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ u64 readlane_u64(u64 x, uint32_t src) // src wave-uniform
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)src);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ double readlane_f64(double x, uint32_t src)
-{
-    return __longlong_as_double((long long)readlane_u64((u64)__double_as_longlong(x), src));
-}
-
-// metrics.go:413 as an INTEGER threshold, restated from lh_kernels.hip (tests/test_pct_threshold_model.py holds the
-// arithmetic against the reference's per-bucket loop): float64(sofar) / float64(total) >= p is monotone in sofar, so there
-// is a smallest prefix count T in [1, total] that reaches p, and the bucket percentile() selects is the first bin whose
-// inclusive prefix is >= T.  SP_NONE: no prefix reaches p (p > 1 or NaN: "Invalid percentile", metrics.go:417).
-__device__ __forceinline__ bool pct_reached(u64 s, double ft, double p) { return (double)s / ft >= p; }
-__device__ inline u64 pct_threshold(double p, u64 total)
-{
-    if (!(1.0 >= p)) return SP_NONE; // the largest quotient is float64(total) / float64(total) == 1
-    if (p <= 0.0) return 1;          // the first occupied bucket
-    const double ft = (double)total, est = p * ft;
-    u64 s = est >= 18446744073709549568.0 ? total : (u64)est;
-    if ((double)s < est) s++; // ceil(p * total): the threshold itself unless a rounding went the other way
-    s = s < 1 ? 1 : (s > total ? total : s);
-    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s;
-#pragma unroll 1
-    for (int it = 0; it < 4 && s > 1 && pct_reached(s - 1, ft, p); it++) s--;
-#pragma unroll 1
-    for (int it = 0; it < 4 && s < total && !pct_reached(s, ft, p); it++) s++;
-    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s;
-    u64 lo = 0, hi = total; // totals beyond 2^53, where float64(s) moves in steps: bisection; reached(total) holds
-#pragma unroll 1
-    while (hi - lo > 1) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (pct_reached(mid, ft, p)) hi = mid; else lo = mid;
-    }
-    return hi;
 }
 
 // value * float64(count) of a lane's four bins (metrics.go:344) and their sum, always associated the same way
@@ -245,15 +166,15 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict
 #pragma unroll
                 for (int k = 0; k < 4; k++) { c[k] = nc[k]; d[k] = nd[k]; }
             }
-            total = readlane_u64(wave_scan_incl(cnt), 63);
+            total = readlane_u64(wave_scan_incl_u64(cnt), 63);
             sum = readlane_f64(wave_scan_incl_f64(ps), 63);
         }
         if (total) { // wave-uniform
             // ---- walk 2: the centred moment; the steps the thresholds fall into
             const double mean = sum / (double)total;
-            u64 T = SP_NONE;
+            u64 T = PCT_NONE;
             if (lane < np) T = pct_threshold(pa.p[lane], total);
-            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != SP_NONE); // percentiles without a bin yet
+            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
             u64 carry = 0;
             double run = 0.0, q = 0.0; // the lane's terms of the steps so far; its share of m2
             load4(row, D, base0 + 4 * lane, hi, c, d);
@@ -263,7 +184,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict
                 const double ts = terms4(c, d, t);
                 if (todo) { // wave-uniform
                     const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
-                    const u64 inc = wave_scan_incl(tc);
+                    const u64 inc = wave_scan_incl_u64(tc);
                     const u64 end = carry + readlane_u64(inc, 63);
                     // (every open threshold is > carry: it would have ended in an earlier step otherwise)
                     uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= end) & todo;
@@ -340,7 +261,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
             load4(row, D, base0 + (c0 + u * SP_WG_WAVES) * SP_STEP + 4 * lane, hi, c[u], d[u]);
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
-            const u64 inc = wave_scan_incl((c[u][0] + c[u][1]) + (c[u][2] + c[u][3]));
+            const u64 inc = wave_scan_incl_u64((c[u][0] + c[u][1]) + (c[u][2] + c[u][3]));
             const double incs = wave_scan_incl_f64(terms4(c[u], d[u], t));
             const uint32_t ch = c0 + u * SP_WG_WAVES;
             if (lane == 63 && ch < nchunks) {
@@ -360,7 +281,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
             w[k] = in ? s_sum[4 * lane + k] : 0.0;
         }
         const u64 tv = (v[0] + v[1]) + (v[2] + v[3]);
-        const u64 inc = wave_scan_incl(tv);
+        const u64 inc = wave_scan_incl_u64(tv);
         const double incs = wave_scan_incl_f64(((w[0] + w[1]) + w[2]) + w[3]);
         const double up = __shfl_up(incs, 1, 64); // what the lanes below add up to
         u64 ex = inc - tv;
@@ -415,7 +336,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
         uint32_t bin = 0xffffffffu;
         u64 cle = 0;
         double sle = 0.0;
-        if (T != SP_NONE) {
+        if (T != PCT_NONE) {
             // the last chunk with fewer than T samples below it (chunk 0 has none below; T <= total)
             uint32_t nlow = 0;
 #pragma unroll
@@ -427,7 +348,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
             load4(row, D, base0 + ch * SP_STEP + 4 * lane, hi, c, d);
             const double ts = terms4(c, d, t);
             const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
-            u64 sofar = s_cnt[ch] + (wave_scan_incl(tc) - tc);
+            u64 sofar = s_cnt[ch] + (wave_scan_incl_u64(tc) - tc);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 sofar += c[k];
@@ -455,29 +376,16 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-// Per-device state of this unit, allocated on first use and kept for the life of the process.  `mu` is held for the
-// length of a call -- the host form's wait for its results included, so host-form calls on one device take turns even
-// when their snapshots belong to different engines.  The table is complete before the call that generates it goes on (one
-// stream wait, once per device): later calls on other streams need no ordering against it.
+// Per-device state of this unit (device_ctx<SpreadCtx>).  `mu` is held for the length of a call -- the host form's wait
+// for its results included, so host-form calls on one device take turns even when their snapshots belong to different
+// engines.  The table is complete before the call that generates it goes on (one stream wait, once per device): later
+// calls on other streams need no ordering against it.
 struct SpreadCtx {
     std::mutex mu;
-    double *d_table = nullptr;                    // D[LH_NKEYS]
-    unsigned char *d_res = nullptr, *h_res = nullptr; // host form: the kernel's results in HBM / their pinned landing block
-    size_t d_cap = 0, h_cap = 0;                  // (in bytes)
+    double *d_table = nullptr; // D[LH_NKEYS]
+    ResultBlocks res;          // host form
 };
-SpreadCtx g_ctx[SP_MAX_DEVICES];
 std::atomic<uint32_t> g_wave_from{SP_WAVE_FROM_DEFAULT};
-
-#define SPCHK(expr)                                                                            \
-    do {                                                                                       \
-        const hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            return _e == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;                         \
-        }                                                                                      \
-    } while (0)
-
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 // every check that needs neither the snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
 // nulled here, and count for nothing.
@@ -498,34 +406,11 @@ int check_args(lh_snapshot *s, size_t nmetrics, const double *p, size_t np, Spre
     return LH_OK;
 }
 
-struct Source {
+struct Source : Opened {
     SpreadCtx *cx = nullptr;
-    hipStream_t st = nullptr;
     const void *cells = nullptr;
-    const uint32_t *ranges = nullptr;
     uint32_t nrows = 0, cell_bytes = 0;
-    size_t stride = 0;
 };
-
-// cells, spans, device, stream.  Moves nothing.
-int source_open(lh_snapshot *s, Source &q)
-{
-    void *p = nullptr;
-    int rc = lh_snapshot_ranges(s, &p);
-    if (rc) return rc;
-    q.ranges = static_cast<const uint32_t *>(p);
-    hipPointerAttribute_t attr;
-    SPCHK(hipPointerGetAttributes(&attr, p));
-    if (attr.device < 0 || attr.device >= SP_MAX_DEVICES) return LH_EDEVICE;
-    SPCHK(hipSetDevice(attr.device));
-    q.cx = &g_ctx[attr.device];
-    rc = lh_snapshot_stream(s, &p);
-    if (rc) return rc;
-    q.st = static_cast<hipStream_t>(p);
-    q.stride = lh_row_stride();
-    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
-    return LH_OK;
-}
 
 // (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on the snapshot's stream
 int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *p, size_t np, const SpreadOut &o)
@@ -533,10 +418,10 @@ int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *p, s
     SpreadCtx *cx = q.cx;
     if (!cx->d_table) {
         double *t = nullptr;
-        SPCHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
-        hipLaunchKernelGGL(k_spread_table, dim3(LH_NKEYS / 256), dim3(256), 0, q.st, t);
+        LH_BESIDE_CHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
+        hipLaunchKernelGGL(k_spread_table, dim3(LH_NKEYS / 256), dim3(256), 0, q.stream, t);
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(q.st);
+        if (e == hipSuccess) e = hipStreamSynchronize(q.stream);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             (void)hipFree(t);
@@ -553,27 +438,15 @@ int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *p, s
     const dim3 grid(wave ? (M + SP_WAVES - 1) / SP_WAVES : M), block(wave ? SP_BLOCK : SP_WG);
     if (q.cell_bytes == 4) {
         const uint32_t *c = static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_spread_wave<uint32_t>, grid, block, 0, q.st, c, ranges, M, q.stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_spread_block<uint32_t>, grid, block, 0, q.st, c, ranges, M, q.stride, D, pa, NP, o);
+        if (wave) hipLaunchKernelGGL(k_spread_wave<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
+        else hipLaunchKernelGGL(k_spread_block<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
     } else {
         const u64 *c = static_cast<const u64 *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_spread_wave<u64>, grid, block, 0, q.st, c, ranges, M, q.stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_spread_block<u64>, grid, block, 0, q.st, c, ranges, M, q.stride, D, pa, NP, o);
+        if (wave) hipLaunchKernelGGL(k_spread_wave<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
+        else hipLaunchKernelGGL(k_spread_block<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
     }
-    SPCHK(hipGetLastError());
+    LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
-}
-
-// pinned host memory the copy engine can write directly (hipHostMalloc'ed or registered by the caller)
-bool is_pinned(const void *p)
-{
-    if (!p) return true;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeHost;
 }
 
 int spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, SpreadOut o, bool device_form)
@@ -587,65 +460,28 @@ int spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, siz
     q.cells = cells;
     if (nmetrics > q.nrows || first > q.nrows - nmetrics) return LH_ERANGE;
     if (nmetrics == 0) return LH_OK;
-    rc = source_open(s, q);
+    rc = open_snapshot(s, q, q.cx);
     if (rc) return rc;
+    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
     SpreadCtx *cx = q.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(q, first, nmetrics, p, np, o);
 
-    // host form: results to HBM, then one copy per array -- straight into the caller's arrays when those are pinned,
-    // through this unit's pinned block otherwise.  The block's layout: the 8-byte arrays, then the keys, then the flags.
-    void *const host[7] = {o.count, o.sum, o.m2, o.count_le, o.sum_le, o.pkeys, o.pvalid};
-    const size_t width[7] = {8, 8, 8, 8, 8, 2, 1};
-    size_t bytes[7], at[7], need = 0;
-    for (int k = 0; k < 7; k++) {
-        bytes[k] = host[k] ? nmetrics * (k < 3 ? 1 : np) * width[k] : 0;
-        at[k] = need;
-        need += (bytes[k] + 7) & ~(size_t)7;
-    }
-    if (cx->d_cap < need) {
-        if (cx->d_res) SPCHK(hipFree(cx->d_res));
-        cx->d_res = nullptr;
-        cx->d_cap = 0;
-        size_t cap = 32768;
-        while (cap < need) cap <<= 1;
-        SPCHK(hipMalloc((void **)&cx->d_res, cap));
-        cx->d_cap = cap;
-    }
-    bool direct = true;
-    for (int k = 0; k < 7; k++) direct = direct && is_pinned(host[k]);
-    if (!direct && cx->h_cap < need) {
-        if (cx->h_res) SPCHK(hipHostFree(cx->h_res));
-        cx->h_res = nullptr;
-        cx->h_cap = 0;
-        size_t cap = 32768;
-        while (cap < need) cap <<= 1;
-        SPCHK(hipHostMalloc((void **)&cx->h_res, cap, hipHostMallocDefault));
-        cx->h_cap = cap;
-    }
-    unsigned char *dev[7];
-    for (int k = 0; k < 7; k++) dev[k] = host[k] ? cx->d_res + at[k] : nullptr;
-    SpreadOut d;
-    d.count = reinterpret_cast<u64 *>(dev[0]);
-    d.sum = reinterpret_cast<double *>(dev[1]);
-    d.m2 = reinterpret_cast<double *>(dev[2]);
-    d.count_le = reinterpret_cast<u64 *>(dev[3]);
-    d.sum_le = reinterpret_cast<double *>(dev[4]);
-    d.pkeys = reinterpret_cast<int16_t *>(dev[5]);
-    d.pvalid = reinterpret_cast<uint8_t *>(dev[6]);
-    rc = enqueue(q, first, nmetrics, p, np, d);
-    if (rc) return rc;
-    if (direct) {
-        for (int k = 0; k < 7; k++)
-            if (host[k]) SPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, q.st));
-        SPCHK(hipStreamSynchronize(q.st));
-    } else {
-        SPCHK(hipMemcpyAsync(cx->h_res, cx->d_res, need, hipMemcpyDeviceToHost, q.st));
-        SPCHK(hipStreamSynchronize(q.st));
-        for (int k = 0; k < 7; k++)
-            if (host[k]) std::memcpy(host[k], cx->h_res + at[k], bytes[k]);
-    }
-    return LH_OK;
+    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys, then the flags.
+    const size_t per_m = nmetrics, per_p = nmetrics * np;
+    const HostOut out[7] = {{o.count, per_m * 8},    {o.sum, per_m * 8},    {o.m2, per_m * 8},   {o.count_le, per_p * 8},
+                            {o.sum_le, per_p * 8}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
+    return host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[7]) {
+        SpreadOut d;
+        d.count = reinterpret_cast<u64 *>(dev[0]);
+        d.sum = reinterpret_cast<double *>(dev[1]);
+        d.m2 = reinterpret_cast<double *>(dev[2]);
+        d.count_le = reinterpret_cast<u64 *>(dev[3]);
+        d.sum_le = reinterpret_cast<double *>(dev[4]);
+        d.pkeys = reinterpret_cast<int16_t *>(dev[5]);
+        d.pvalid = reinterpret_cast<uint8_t *>(dev[6]);
+        return enqueue(q, first, nmetrics, p, np, d);
+    });
 }
 
 } // namespace
@@ -669,8 +505,7 @@ int lh_spread_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const doub
 
 int lh_tool_spread_switch(uint32_t wave_from_rows, uint32_t *previous)
 {
-    const uint32_t old = g_wave_from.exchange(wave_from_rows ? wave_from_rows : SP_WAVE_FROM_DEFAULT, std::memory_order_relaxed);
-    if (previous) *previous = old;
+    switch_exchange(g_wave_from, wave_from_rows, SP_WAVE_FROM_DEFAULT, previous);
     return LH_OK;
 }
 

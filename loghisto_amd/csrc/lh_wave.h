@@ -1,0 +1,142 @@
+// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip; a new reader
+// starts here and in lh_beside.h): DPP scans, cross-lane reads, the packed 16-byte load types, a row's 4-bin group as one
+// load, and the percentile threshold.  The text is lh_kernels.hip's, which still carries its own copy for K2: that file is
+// one of the sources the committed profiles are stamped with (bench.tree_stamp), so it takes this header in the change that
+// next regenerates them.  Until then a fix to pct_threshold goes to both (tests/test_pct_threshold_model.py has the
+// arithmetic, tests/test_gpu_extract_thresholds.py and tests/test_gpu_spread.py hold both to the oracle).
+// Every unit that includes it is built with -ffp-contract=off (build.py's _COMMON).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+namespace lh {
+
+// ---------------------------------------------------------------------------
+// Wave-level arithmetic that stays in the VALU (DPP): k_extract_wave's scans and reductions.  __shfl_up / __shfl_down
+// compile to ds_bpermute_b32 -- a round trip through the LDS crossbar each, two per 64-bit value -- and round 4's
+// wave kernel issued 216 of them per name.
+// ---------------------------------------------------------------------------
+#define LH_DPP32(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), (rows), 0xf, false))
+template <int CTRL, int ROWS> __device__ __forceinline__ uint64_t dpp_u64(uint64_t x)
+{
+    const uint32_t lo = LH_DPP32((uint32_t)x, CTRL, ROWS), hi = LH_DPP32((uint32_t)(x >> 32), CTRL, ROWS);
+    return ((uint64_t)hi << 32) | lo; // lanes without a source (or outside ROWS) get 0
+}
+template <int CTRL, int ROWS> __device__ __forceinline__ double dpp_f64(double x) // ... +0.0
+{
+    return __longlong_as_double((long long)dpp_u64<CTRL, ROWS>((uint64_t)__double_as_longlong(x)));
+}
+// inclusive prefix sum over the 64 lanes: four steps inside the rows of 16 lanes (row_shr:1/2/4/8), then lane 15 of
+// rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3 (row_bcast:31)
+__device__ __forceinline__ uint64_t wave_scan_incl_u64(uint64_t x)
+{
+    x += dpp_u64<0x111, 0xf>(x);
+    x += dpp_u64<0x112, 0xf>(x);
+    x += dpp_u64<0x114, 0xf>(x);
+    x += dpp_u64<0x118, 0xf>(x);
+    x += dpp_u64<0x142, 0xa>(x);
+    x += dpp_u64<0x143, 0xc>(x);
+    return x;
+}
+__device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t x)
+{
+    x += LH_DPP32(x, 0x111, 0xf);
+    x += LH_DPP32(x, 0x112, 0xf);
+    x += LH_DPP32(x, 0x114, 0xf);
+    x += LH_DPP32(x, 0x118, 0xf);
+    x += LH_DPP32(x, 0x142, 0xa);
+    x += LH_DPP32(x, 0x143, 0xc);
+    return x;
+}
+// the same tree in float64: one fixed association, whatever the timing
+__device__ __forceinline__ double wave_scan_incl_f64(double x)
+{
+    x += dpp_f64<0x111, 0xf>(x);
+    x += dpp_f64<0x112, 0xf>(x);
+    x += dpp_f64<0x114, 0xf>(x);
+    x += dpp_f64<0x118, 0xf>(x);
+    x += dpp_f64<0x142, 0xa>(x);
+    x += dpp_f64<0x143, 0xc>(x);
+    return x;
+}
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t x, uint32_t src) // src wave-uniform
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)src);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)src);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double readlane_f64(double x, uint32_t src)
+{
+    return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), src));
+}
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t x, uint32_t src) // src per lane
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, (int)src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), (int)src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+// x of lane + D for the lanes whose lane + D is in the same row of 16 (what the others get does not matter to the caller)
+template <int D> __device__ __forceinline__ double row_down_f64(double x)
+{
+    return __longlong_as_double((long long)dpp_u64<0x100 + D, 0xf>((uint64_t)__double_as_longlong(x))); // row_shl:D
+}
+
+// metrics.go:413 as an INTEGER threshold: float64(sofar) / float64(total) >= p is monotone in sofar, so there is a
+// smallest prefix count T in [1, total] that reaches percentile p, and "the first bucket that reaches p" is the first
+// bin whose inclusive prefix is >= T (that bin is occupied: the prefix moves there).  One to three IEEE divides per
+// (name, percentile) -- by the lane that owns the percentile -- instead of one per cell.  PCT_NONE: no prefix reaches p
+// (p > 1 or NaN: the key is omitted, metrics.go:417).
+constexpr uint64_t PCT_NONE = ~0ull;
+__device__ __forceinline__ bool pct_reached(uint64_t s, double ft, double p) { return (double)s / ft >= p; }
+__device__ inline uint64_t pct_threshold(double p, uint64_t total)
+{
+    if (!(1.0 >= p)) return PCT_NONE; // the largest quotient is float64(total) / float64(total) == 1
+    if (p <= 0.0) return 1;           // the first occupied bucket
+    const double ft = (double)total, est = p * ft;
+    uint64_t s = est >= 18446744073709549568.0 ? total : (uint64_t)est;
+    if ((double)s < est) s++; // ceil(p * total): the threshold itself unless a rounding went the other way
+    s = s < 1 ? 1 : (s > total ? total : s);
+    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s; // two divides: the usual case
+#pragma unroll 1
+    for (int it = 0; it < 4 && s > 1 && pct_reached(s - 1, ft, p); it++) s--;
+#pragma unroll 1
+    for (int it = 0; it < 4 && s < total && !pct_reached(s, ft, p); it++) s++;
+    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s;
+    // not settled in four steps either way (totals beyond 2^53, where float64(s) moves in steps): bisection;
+    // reached(total) holds
+    uint64_t lo = 0, hi = total;
+#pragma unroll 1
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (pct_reached(mid, ft, p)) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
+// 16 bytes at an 8-byte-aligned address as ONE load (global_load_dwordx4; unaligned vector access is on for HSA)
+struct __attribute__((packed, aligned(8))) u64x2_a8 { uint64_t a, b; };
+struct __attribute__((packed, aligned(8))) f64x2_a8 { double a, b; };
+struct __attribute__((packed, aligned(4))) u32x4_a4 { uint32_t a, b, c, d; };
+
+// bins b0 .. b0 + 3 of a row; a lane whose group starts beyond hi asks for nothing.  The caller keeps hi <= 65 535 and
+// the rows at least LH_NKEYS + 4 cells apart, so the group ends inside the row's own stride.  (ACC: the caller's 64-bit
+// unsigned type -- uint64_t and unsigned long long are distinct.)
+template <typename CELL, typename ACC>
+__device__ __forceinline__ void load4_cells(const CELL *__restrict__ row, uint32_t b0, uint32_t hi, ACC (&c)[4])
+{
+    static_assert(sizeof(ACC) == 8 && (sizeof(CELL) == 4 || sizeof(CELL) == 8), "32- or 64-bit cells into 64-bit counts");
+    c[0] = c[1] = c[2] = c[3] = 0;
+    if (b0 <= hi) {
+        if constexpr (sizeof(CELL) == 4) {
+            const u32x4_a4 q = *reinterpret_cast<const u32x4_a4 *>(row + b0);
+            c[0] = q.a; c[1] = q.b; c[2] = q.c; c[3] = q.d;
+        } else {
+            const u64x2_a8 *rp = reinterpret_cast<const u64x2_a8 *>(row + b0);
+            const u64x2_a8 c01 = rp[0], c23 = rp[1];
+            c[0] = c01.a; c[1] = c01.b; c[2] = c23.a; c[3] = c23.b;
+        }
+    }
+}
+
+} // namespace lh

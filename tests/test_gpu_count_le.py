@@ -404,3 +404,46 @@ def test_per_metric_bounds_of_one_engine_survive_calls_on_another(native_lib, to
                 want = ra.count(ba)
                 assert np.array_equal(cum.cpu().numpy().view(U64), want[0]) and np.array_equal(total.cpu().numpy().view(U64), want[1])
                 assert np.array_equal(got_bb["cum"], rb.count(bb)[0]) and np.array_equal(got_b["total"], rb.count(bb)[1])
+
+
+# ---- 9. the host form's two ways back ----------------------------------------------------------------------------------
+def small_stream():
+    """5 names, 301 samples: name 2 stays empty, name 3 receives a single sample."""
+    rng = np.random.default_rng(91)
+    ids = np.append(rng.choice(np.array([0, 1, 4], dtype=np.uint32), 300), np.uint32(3))
+    v = np.append(rng.lognormal(3.0, 1.5, 300), 42.0)
+    return ids, v
+
+
+def host_arrays(torch, pinned, shape, dtype):
+    """An output array filled with a pattern no result has: pinned (the copy engine writes it) or plain pageable numpy."""
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    raw = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True).numpy() if pinned else np.empty(nbytes, dtype=np.uint8)
+    raw[:] = 0x77
+    return raw.view(dtype).reshape(shape)
+
+
+@pytest.mark.parametrize("per_metric", [False, True])
+def test_pinned_and_pageable_outputs_receive_the_same_counts(native_lib, torch_cuda, per_metric):
+    """lh_count_le through ctypes, cum and total both asked for: into pinned arrays (one copy per array, straight in) and
+    into pageable ones (through the unit's pinned block) -- the same bits, and the oracle's."""
+    M = 5
+    ids, v = small_stream()
+    ref = Ref(ids, v, M)
+    assert ref.rows[2].sum() == 0 and ref.rows[3].sum() == 1
+    b = np.array([-INF, 1.0, 42.0, 100.0, INF])
+    if per_metric:
+        b = np.sort(np.random.default_rng(92).choice(bound_pool(np.random.default_rng(93), v), (M, 5)), axis=1)
+    want_cum, want_total = ref.count(b)
+    got = []
+    with engine(M) as e:
+        e.submit_pairs(ids, v)
+        with e.flip() as snap:
+            for pinned in (True, False, True):
+                cum, total = host_arrays(torch_cuda, pinned, (M, 5), U64), host_arrays(torch_cuda, pinned, (M,), U64)
+                flags = N.LE_PER_METRIC if per_metric else 0
+                assert N.lib().lh_count_le(snap._h, 0, M, b.ctypes.data, 5, flags, cum.ctypes.data, total.ctypes.data) == 0
+                got.append((cum.copy(), total.copy()))
+    for cum, total in got:
+        assert np.array_equal(cum, want_cum) and np.array_equal(total, want_total)
+        assert cum.tobytes() == got[0][0].tobytes() and total.tobytes() == got[0][1].tobytes()

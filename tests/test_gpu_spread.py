@@ -22,7 +22,7 @@ import pytest
 
 import oracle
 from loghisto_amd import _native as N
-from tests.test_gpu_count_le import engine, stream
+from tests.test_gpu_count_le import engine, host_arrays, small_stream, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -356,3 +356,35 @@ def test_crafted_rows_in_32_bit_cells(narrow, kind):
         got = narrow.snap.spread(P_DEFAULT, M)
     assert narrow.snap.device_cells() == narrow.cells and narrow.cells[2] == 4           # still narrow
     check(got, narrow.rows, P_DEFAULT, narrow.snap.extract(P_DEFAULT, M))
+
+
+# ---- the host form's two ways back -------------------------------------------------------------------------------------
+SPREAD_OUT = dict(count=U64, sum=np.float64, m2=np.float64, pkeys=np.int16, pvalid=np.uint8, count_le=U64, sum_le=np.float64)
+
+
+def test_pinned_and_pageable_outputs_receive_the_same_results(native_lib, torch_cuda):
+    """lh_spread with caller-supplied arrays: pinned (one copy per array, straight in) and pageable (through the unit's
+    pinned block) -- the same bits, and the oracle's.  All seven outputs, then four of them: the block's 8-byte-aligned
+    layout with arrays left out."""
+    M = 5
+    ids, v = small_stream()
+    rows = exact_rows(oracle.histogram_pairs(ids, v, M))
+    assert [r.N for r in rows][2:4] == [0, 1]
+    P = [0.5, 0.9, 1.0]
+
+    def arrays(pinned, names):
+        return {k: host_arrays(torch_cuda, pinned, (M,) if k in ("count", "sum", "m2") else (M, len(P)), SPREAD_OUT[k]) for k in names}
+
+    with engine(M) as e:
+        e.submit_pairs(ids, v)
+        with e.flip() as snap:
+            full = [(arrays(pinned, SPREAD_OUT), pinned) for pinned in (True, False)]
+            got = [snap.spread(P, M, out=a) for a, _ in full]
+            some = [arrays(pinned, ("sum", "pkeys", "pvalid", "sum_le")) for pinned in (True, False)]
+            for a in some:
+                snap.spread(P, M, out=a)
+    for g in got:
+        check(g, rows, P)
+    for a in [a for a, _ in full[1:]] + some:
+        for k in a:
+            assert a[k].tobytes() == full[0][0][k].tobytes(), k
