@@ -377,6 +377,58 @@ int lh_spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, 
 int lh_spread_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, uint64_t *d_count,
                      double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
                      double *d_sum_le);
+/* The k names that lead: "which 20 endpoints have the worst p99 this interval", "which names took the most total time",
+ * "which names have the most requests over 250 ms" -- answered on the device, so that k entries travel instead of the
+ * results of every name.  The reference has no counterpart for the SELECTION (its consumers receive every name's
+ * ProcessedMetricSet entries and sort for themselves); what is ranked is what it computes and this library already returns:
+ * the outputs of processHistograms (/root/reference/metrics.go:336-376), the bucket percentile() selects
+ * (metrics.go:389-418), and the running count lh_count_le reads at a value.  Nothing is summed across names and no new
+ * statistic is defined.
+ *   CANDIDATES  the rows of [first, first + nmetrics) with count != 0.  *n_out = min(k, candidates); entries at and beyond
+ *               n_out are not written.
+ *   SCORE, by `by`:
+ *     LH_TOP_BY_COUNT        count (uint64, lh_stats.count)
+ *     LH_TOP_BY_SUM          sum as a float64, compared numerically (-0.0 == +0.0)
+ *     LH_TOP_BY_PERCENTILE   the bin of the bucket lh_extract_rows selects for p = arg; ascending bin is ascending value, so
+ *                            a negative p99 ranks below a positive one
+ *     LH_TOP_BY_COUNT_ABOVE  count minus the name's lh_count_le result at bounds = {arg}: the samples in buckets whose key is
+ *                            > the key of arg, by lh_count_le's bound-to-key rule (+Inf: nothing is above; -Inf: everything;
+ *                            a finite arg whose extended key exceeds 32 767 saturates the same way).  RESOLUTION IS THE
+ *                            BUCKET, as there.
+ *     arg is ignored for the first two.
+ *   ORDER  one total order, so the result never depends on timing or launch shape: descending score, or ascending score with
+ *          LH_TOP_ASCENDING; in BOTH directions equal scores go lowest id first.  out[0] is the leader.
+ *   FIELDS  id is absolute (first + i).  count and sum are filled for every entry whatever `by` is; pkey for
+ *           LH_TOP_BY_PERCENTILE only and above for LH_TOP_BY_COUNT_ABOVE only (0 otherwise); reserved is 0.  sum is taken in
+ *           this unit's own fixed order: it does not depend on timing, and may differ in the last bits from lh_stats.sum and
+ *           lh_spread's.
+ *   LH_EINVAL, checked on the host before the snapshot or a device is touched: NULL s; k == 0 or k > LH_MAX_TOP; unknown `by`;
+ *           unknown flag bits; NULL out or n_out; out not 8-byte aligned; n_out not aligned to its type (size_t in lh_top,
+ *           uint32_t in lh_top_device); arg NaN for LH_TOP_BY_PERCENTILE or LH_TOP_BY_COUNT_ABOVE; arg outside [0, 1] for
+ *           LH_TOP_BY_PERCENTILE (there would be no bucket to rank by).
+ *   LH_ERANGE: first + nmetrics > max_metrics; an nmetrics above 2^32 - 1 before anything is looked at.
+ *   nmetrics == 0 -> LH_OK with *n_out = 0.
+ * READ-ONLY, ordering, threading and staging as for lh_spread*: enqueued on lh_snapshot_stream(s) (a pass that scores every
+ * row, one wave per row, then an exact radix select and a sort of the winners in one workgroup); lh_top returns when the
+ * entries are in `out` -- entries and n_out come back in one copy through a pinned block of the library's, whatever memory
+ * `out` is, because only the first n_out entries may be written; lh_top_device takes device memory for both and returns
+ * after enqueueing (the first call on a device also generates the unit's copy of D[] and waits for it once).  One set of
+ * staging blocks per DEVICE behind the unit's own mutex: calls on snapshots of different engines take turns. */
+#define LH_MAX_TOP 1024
+enum { LH_TOP_BY_COUNT = 0, LH_TOP_BY_SUM = 1, LH_TOP_BY_PERCENTILE = 2, LH_TOP_BY_COUNT_ABOVE = 3 };
+enum { LH_TOP_ASCENDING = 1 };
+typedef struct lh_top_entry {   /* 32 bytes */
+    uint32_t id;        /* absolute metric id (first + i), not the index inside the range */
+    int16_t  pkey;      /* BY_PERCENTILE: the selected int16 key; else 0 */
+    uint16_t reserved;  /* 0 */
+    uint64_t count;     /* lh_stats.count of the name */
+    double   sum;       /* sum of D[b] * float64(c[b]) (metrics.go:344), this unit's fixed order */
+    uint64_t above;     /* BY_COUNT_ABOVE: samples in buckets whose key is > the key of arg; else 0 */
+} lh_top_entry;
+int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
+           lh_top_entry *out, size_t *n_out);
+int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
+                  lh_top_entry *d_out, uint32_t *d_n_out);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

@@ -20,6 +20,9 @@ NTHRESH = 70980
 MAX_PERCENTILES = 32
 MAX_BOUNDS = 64        # lh_count_le*
 LE_PER_METRIC = 1
+MAX_TOP = 1024         # lh_top*
+TOP_BY_COUNT, TOP_BY_SUM, TOP_BY_PERCENTILE, TOP_BY_COUNT_ABOVE = range(4)
+TOP_ASCENDING = 1
 
 OK, EINVAL, ENOMEM, EDEVICE, ENODEVICE, EBUSY, ERANGE, ESTATE = range(8)
 
@@ -123,6 +126,16 @@ class LhStats(C.Structure):
                 ("agg_sum_add", C.c_uint64), ("nbuckets", C.c_uint32), ("present", C.c_uint32)]
 
 
+def __getattr__(name):
+    """TOP_ENTRY: lh_top_entry (32 bytes) as a numpy dtype, built on first use -- this module itself needs ctypes only."""
+    if name == "TOP_ENTRY":
+        import numpy as np
+        dt = np.dtype([("id", "<u4"), ("pkey", "<i2"), ("reserved", "<u2"), ("count", "<u8"), ("sum", "<f8"), ("above", "<u8")])
+        globals()["TOP_ENTRY"] = dt
+        return dt
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 _vp, _sz = C.c_void_p, C.c_size_t
 _dp, _u32p, _u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _i16p, _u8p = C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
@@ -136,6 +149,8 @@ TUNING_SIGNATURES = {
     "lh_tool_last_extract_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_count_le_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_spread_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float)]),
 }
 
 # name -> (restype, argtypes): every symbol include/loghisto_gpu.h declares.
@@ -193,6 +208,8 @@ SIGNATURES = {
     "lh_count_le_device": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
     "lh_spread": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_spread_device": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_top": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
+    "lh_top_device": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

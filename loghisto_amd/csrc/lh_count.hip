@@ -36,6 +36,7 @@
 namespace {
 
 using namespace lh::beside;
+using lh::le_take;
 using lh::load4_cells;
 using lh::readlane_u64;
 using lh::shfl_u64;
@@ -47,7 +48,6 @@ constexpr int CL_BLOCK = 256, CL_WAVES = CL_BLOCK / 64; // k_count_le_wave: four
 constexpr int CL_WG = 1024, CL_WG_WAVES = CL_WG / 64;   // k_count_le_block
 constexpr uint32_t CL_STEP = 256;                       // bins a wave takes per step
 constexpr uint32_t CL_CHUNKS = LH_NKEYS / CL_STEP;      // chunks of the widest span (a span starts at a multiple of 4)
-constexpr uint32_t CL_TAKE_ALL = LH_NKEYS;
 // Rows of a call from which a row gets a wave, not a workgroup.  profiles/count_le.txt has both shapes either side: over
 // windows of a few hundred bins the wave form is ahead from 1 024 rows on and the two are level at 256; over one
 // full-span row the workgroup is several times faster -- so few rows, which may be wide, get workgroups.
@@ -57,16 +57,7 @@ static_assert(CL_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane"
 // shared bounds travel in the kernel arguments (512 bytes); per-metric ones are read from `pb`
 struct LeBounds { double b[LH_MAX_BOUNDS]; };
 
-// How many leading bins bound b takes in: bin(compress(b)) + 1 (metrics.go:316-322 with the extended key before its
-// int16 truncation; -0.0 and 0.0 both give key 0).  The host refused NaN.
-__device__ __forceinline__ uint32_t le_take(double b)
-{
-    const double a = fabs(b);
-    if (!(a <= 1.7976931348623157e308)) return b > 0 ? CL_TAKE_ALL : 0u; // +-Inf
-    const int kext = lh::d_kext_golog(1.0 + a);
-    if (kext > 32767) return b > 0 ? CL_TAKE_ALL : 0u;                     // where the reference's int16 keys wrap
-    return lh::key_to_bin(b < 0 ? -kext : kext) + 1u;
-}
+// (how many leading bins a bound takes in: le_take, lh_wave.h)
 
 template <typename CELL>
 __global__ __launch_bounds__(CL_BLOCK) void k_count_le_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,

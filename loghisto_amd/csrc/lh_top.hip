@@ -1,0 +1,579 @@
+// lh_top.hip -- lh_top* (include/loghisto_gpu.h): the k names of a range that lead by count, by sum, by the bucket a
+// percentile falls into, or by the samples above a value.  The first reader that SELECTS ACROSS names instead of answering
+// per name; the reference has no counterpart for the selection.  What is ranked is what the library already returns:
+//   count, sum   processHistograms (/root/reference/metrics.go:336-376; sum = sum of D[b] * float64(c[b]), metrics.go:344)
+//   percentile   the bucket percentile() selects (metrics.go:389-418): the first bin whose inclusive prefix count reaches
+//                pct_threshold(p, count) -- lh_extract_rows' pkey
+//   count above  count minus the running count lh_count_le reads at the value (le_take, lh_wave.h: the same bound-to-key
+//                rule, +-Inf and the saturation beyond extended key 32 767 included; bucket resolution)
+// Nothing is summed across names, no cell is written and no new statistic is defined.
+//
+// Built BESIDE the engine, on its public C ABI only: lh_beside.h says what that gives a reader.  Read-only.
+//
+// Two passes on the snapshot's stream:
+//   k_top_score   one WAVE per row, four rows per workgroup, 256 bins per step over the row's span (4 consecutive bins per
+//                 lane through load4_cells, the next step's loads issued before the current step is worked on, as
+//                 k_spread_wave does).  Walk 1 gives count and sum (D[] is this unit's own table, generated once per
+//                 device with lh::d_decompress_bin as lh_spread.hip's is) and, for BY_COUNT_ABOVE, the cells of the bins at
+//                 or beyond the bound's take; BY_PERCENTILE takes a second walk to the first bin whose prefix reaches the
+//                 threshold.  Each row leaves a record in a scratch block in HBM: a 64-bit ORDER-PRESERVING key (an integer
+//                 as it is; a float64 by the sign-flip of its bits after -0.0 has become +0.0; complemented for
+//                 LH_TOP_ASCENDING, so that the select pass always takes the LARGEST keys), its count, its sum and its pkey
+//                 or count above.  Whether a row is a candidate is NOT in the key (a complemented key takes any value):
+//                 it is count != 0.
+//   k_top_select  ONE workgroup of 1 024 threads looping over the records.  An exact k-th-key search, MSB first, eight
+//                 passes of 8 bits with a 256-entry histogram in LDS (a wave whose records all fall into one bin adds them
+//                 with one atomic: the high bytes of counts are mostly zero); then one pass in index order that takes every
+//                 record ahead of the k-th key and, of those equal to it, the lowest ids -- a prefix count over the records,
+//                 never an atomic whose order depends on timing; then a bitonic sort of the at most 1 024 winners by (key
+//                 descending, id ascending) in LDS; then the entries and n_out.  One total order: the result depends on
+//                 neither timing nor launch shape.
+// One wave shape and a one-workgroup select are UNMEASURED DEFAULTS: a full-span row costs its wave 256 steps per walk, and
+// the select pass reads the keys nine times with one workgroup.  tools/top_bench.py measures both passes at 65 536 names and
+// a full-span row; that measurement decides whether the workgroup-per-row shape lh_count.hip and lh_spread.hip carry, or a
+// histogram pass over several workgroups, is added.  Every floating-point sum is taken in a fixed order (per lane over the steps in ascending order,
+// then one DPP tree over the lanes).
+#include "../../include/loghisto_gpu.h"
+#include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
+#include "lh_codec.h"
+#include "lh_wave.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+
+namespace {
+
+using namespace lh::beside;
+using lh::f64x2_a8;
+using lh::le_take;
+using lh::load4_cells;
+using lh::pct_threshold;
+using lh::readlane_f64;
+using lh::readlane_u64;
+using lh::u64x2_a8;
+using lh::wave_scan_incl_f64;
+using lh::wave_scan_incl_u32;
+using lh::wave_scan_incl_u64;
+
+typedef unsigned long long u64;
+
+constexpr int TP_BLOCK = 256, TP_WAVES = TP_BLOCK / 64; // k_top_score: four rows per workgroup
+constexpr uint32_t TP_STEP = 256;                       // bins a wave takes per step
+constexpr int SEL_WG = 1024, SEL_WAVES = SEL_WG / 64;   // k_top_select
+constexpr uint32_t SEL_PER = 4;                         // consecutive records per thread and tile
+constexpr uint32_t SEL_TILE = SEL_WG * SEL_PER;
+constexpr uint32_t NO_SLOT = 0xffffffffu;               // the index of a padding slot of the sort: behind every record
+static_assert(sizeof(lh_top_entry) == 32, "lh_top_entry is 32 bytes");
+static_assert(LH_MAX_TOP == SEL_WG, "a thread per winner in the sort");
+static_assert(SEL_TILE <= 0x10000, "a tile's two prefix counts share one 32-bit scan");
+
+// The rows' records, one array per field, each padded to whole groups of SEL_PER (16-byte loads stay inside the block).
+struct TopRecords {
+    u64 *key;    // order-preserving, larger is ahead
+    u64 *count;  // 0: not a candidate
+    double *sum;
+    u64 *aux;    // BY_PERCENTILE: the int16 key's 16 bits; BY_COUNT_ABOVE: the count above; else 0
+};
+
+__global__ __launch_bounds__(256) void k_top_table(double *__restrict__ D)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < LH_NKEYS) D[b] = lh::d_decompress_bin(b);
+}
+
+// bins b0 .. b0 + 3 of a row and their table entries; a lane whose group starts beyond hi asks for nothing.  b0 is a
+// multiple of 4 and hi <= 65 535, so the group ends inside the row (and inside the table's LH_NKEYS entries).
+template <typename CELL>
+__device__ __forceinline__ void load4(const CELL *__restrict__ row, const double *__restrict__ D, uint32_t b0, uint32_t hi,
+                                      u64 (&c)[4], double (&d)[4])
+{
+    d[0] = d[1] = d[2] = d[3] = 0.0;
+    load4_cells(row, b0, hi, c);
+    if (b0 <= hi) {
+        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
+        const f64x2_a8 d01 = dp[0], d23 = dp[1];
+        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
+    }
+}
+
+// a float64 as an unsigned integer of the same order (-0.0 == +0.0; the host sees to it that no NaN is ranked)
+__device__ __forceinline__ u64 order_key_f64(double x)
+{
+    if (x == 0.0) x = 0.0; // -0.0 -> +0.0
+    const u64 b = (u64)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+template <typename CELL>
+__global__ __launch_bounds__(TP_BLOCK) void k_top_score(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+                                                        uint32_t nmetrics, size_t stride, const double *__restrict__ D,
+                                                        uint32_t by, double arg, u64 flip, const TopRecords r)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * TP_WAVES + (threadIdx.x >> 6);
+    if (m >= nmetrics) return; // wave-uniform
+    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    u64 total = 0, above = 0;
+    double sum = 0.0;
+    uint32_t found = 0; // BY_PERCENTILE: the selected bin
+    if (lo <= hi) {     // wave-uniform; an empty row costs two loads and its stores
+        const CELL *__restrict__ row = cells + (size_t)m * stride;
+        const uint32_t base0 = lo & ~3u; // (cells below lo are zero) whole groups: every load is 16-byte aligned
+        u64 c[4], nc[4];
+        double d[4], nd[4];
+        // ---- walk 1: count and sum; the cells at or beyond the bound's take
+        {
+            const bool want_above = by == LH_TOP_BY_COUNT_ABOVE; // wave-uniform
+            const uint32_t take = want_above ? le_take(arg) : 0u;
+            u64 cnt = 0, ab = 0;
+            double ps = 0.0;
+            load4(row, D, base0 + 4 * lane, hi, c, d);
+            for (uint32_t base = base0; base <= hi; base += TP_STEP) {
+                load4(row, D, base + TP_STEP + 4 * lane, hi, nc, nd); // the next step's: in flight under this step's work
+                cnt += (c[0] + c[1]) + (c[2] + c[3]);
+                double t[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) t[k] = d[k] * (double)c[k];
+                ps += (t[0] + t[1]) + (t[2] + t[3]);
+                if (want_above) {
+                    const uint32_t b0 = base + 4 * lane;
+#pragma unroll
+                    for (uint32_t k = 0; k < 4; k++) ab += b0 + k >= take ? c[k] : 0;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) { c[k] = nc[k]; d[k] = nd[k]; }
+            }
+            total = readlane_u64(wave_scan_incl_u64(cnt), 63);
+            sum = readlane_f64(wave_scan_incl_f64(ps), 63);
+            above = readlane_u64(wave_scan_incl_u64(ab), 63);
+        }
+        if (total == 0) sum = 0.0;
+        if (total && by == LH_TOP_BY_PERCENTILE) { // wave-uniform
+            // ---- walk 2: the first bin whose inclusive prefix reaches T (the host keeps arg in [0, 1]: 1 <= T <= total)
+            const u64 T = readlane_u64(pct_threshold(arg, total), 0);
+            u64 carry = 0;
+            found = hi;
+            load4_cells(row, base0 + 4 * lane, hi, c);
+            for (uint32_t base = base0; base <= hi; base += TP_STEP) {
+                load4_cells(row, base + TP_STEP + 4 * lane, hi, nc);
+                const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
+                const u64 inc = wave_scan_incl_u64(tc);
+                const u64 end = carry + readlane_u64(inc, 63);
+                if (T <= end) { // wave-uniform: it is in this step
+                    const u64 p0 = carry + (inc - tc) + c[0], p1 = p0 + c[1], p2 = p1 + c[2], p3 = p2 + c[3];
+                    // the first lane whose last bin reaches T (lane 63's does), and how many of its bins stay below
+                    const uint32_t f = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(p3 >= T));
+                    const uint32_t below = (p0 < T ? 1u : 0u) + (p1 < T ? 1u : 0u) + (p2 < T ? 1u : 0u);
+                    found = base + 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
+                    break;
+                }
+                carry = end;
+#pragma unroll
+                for (int k = 0; k < 4; k++) c[k] = nc[k];
+            }
+        }
+    }
+    if (lane == 0) {
+        u64 key, aux = 0;
+        if (by == LH_TOP_BY_COUNT) {
+            key = total;
+        } else if (by == LH_TOP_BY_SUM) {
+            key = order_key_f64(sum);
+        } else if (by == LH_TOP_BY_PERCENTILE) {
+            key = found;
+            aux = total ? (u64)(uint16_t)(int16_t)lh::bin_to_key(found) : 0;
+        } else {
+            key = above;
+            aux = above;
+        }
+        r.key[m] = key ^ flip;
+        r.count[m] = total;
+        r.sum[m] = sum;
+        r.aux[m] = aux;
+    }
+}
+
+// ---- the select pass ------------------------------------------------------------------------------------------------
+// One more record in bin d of the histogram for the lanes with `in` set.  A wave whose records share the bin (every pass
+// over bytes the keys have in common) adds them with ONE atomic instead of up to 64 on one address.  Called under
+// workgroup-uniform control.  (Integer adds: the histogram does not depend on their order.)
+__device__ __forceinline__ void hist_add(uint32_t *hist, bool in, uint32_t d, uint32_t lane)
+{
+    const unsigned long long act = __builtin_amdgcn_ballot_w64(in);
+    if (!act) return; // wave-uniform
+    const uint32_t lead = (uint32_t)__builtin_ctzll(act);
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)lead);
+    if (__builtin_amdgcn_ballot_w64(in && d == d0) == act) {
+        if (lane == lead) atomicAdd(&hist[d0 & 255u], (uint32_t)__builtin_popcountll(act));
+    } else if (in) {
+        atomicAdd(&hist[d & 255u], 1u);
+    }
+}
+
+// records i0 .. i0 + 3 (i0 a multiple of 4; the arrays are padded to whole groups): their keys, and -- only where some
+// record of the group passes `keep` -- their counts.  ok[j]: record i0 + j exists, passes `keep` and is a candidate.
+template <class Keep>
+__device__ __forceinline__ void load_records(const u64 *__restrict__ key, const u64 *__restrict__ count, size_t i0, uint32_t n,
+                                             u64 (&kk)[SEL_PER], bool (&ok)[SEL_PER], Keep keep)
+{
+#pragma unroll
+    for (uint32_t j = 0; j < SEL_PER; j++) { kk[j] = 0; ok[j] = false; }
+    if (i0 >= n) return;
+    const u64x2_a8 *kp = reinterpret_cast<const u64x2_a8 *>(key + i0);
+    const u64x2_a8 k01 = kp[0], k23 = kp[1];
+    kk[0] = k01.a; kk[1] = k01.b; kk[2] = k23.a; kk[3] = k23.b;
+    bool any = false;
+#pragma unroll
+    for (uint32_t j = 0; j < SEL_PER; j++) {
+        ok[j] = j < n - i0 && keep(kk[j]);
+        any = any || ok[j];
+    }
+    if (!any) return;
+    const u64x2_a8 *cp = reinterpret_cast<const u64x2_a8 *>(count + i0);
+    const u64x2_a8 c01 = cp[0], c23 = cp[1];
+    ok[0] = ok[0] && c01.a != 0; ok[1] = ok[1] && c01.b != 0; ok[2] = ok[2] && c23.a != 0; ok[3] = ok[3] && c23.b != 0;
+}
+
+// (a key, an index) ahead of another in the result: the larger key, then the lower index.  Padding slots (key 0, index
+// NO_SLOT) stay behind every record.
+__device__ __forceinline__ bool ahead(u64 ka, uint32_t ia, u64 kb, uint32_t ib) { return ka > kb || (ka == kb && ia < ib); }
+
+__global__ __launch_bounds__(SEL_WG) void k_top_select(const TopRecords r, uint32_t n, uint32_t first, uint32_t k, uint32_t by,
+                                                       lh_top_entry *__restrict__ out, uint32_t *__restrict__ n_out)
+{
+    __shared__ uint32_t s_hist[256];
+    __shared__ uint32_t s_part[SEL_WAVES];
+    __shared__ uint32_t s_digit, s_rem, s_take;
+    __shared__ u64 s_wkey[LH_MAX_TOP];
+    __shared__ uint32_t s_widx[LH_MAX_TOP];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t ntiles = n / SEL_TILE + (n % SEL_TILE != 0); // (n + SEL_TILE - 1 would wrap near 2^32)
+
+    // ---- the k-th largest key among the candidates: `prefix` holds its bytes above `shift`; of the candidates that share
+    // them, the rem-th largest is looked for
+    u64 prefix = 0;
+    uint32_t rem = k;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) s_hist[tid] = 0;
+        __syncthreads();
+        for (uint32_t t = 0; t < ntiles; t++) { // workgroup-uniform
+            u64 kk[SEL_PER];
+            bool ok[SEL_PER];
+            load_records(r.key, r.count, (size_t)t * SEL_TILE + SEL_PER * tid, n, kk, ok,
+                         [&](u64 x) { return shift == 56 || (x >> (shift + 8)) == prefix; });
+#pragma unroll
+            for (uint32_t j = 0; j < SEL_PER; j++) hist_add(s_hist, ok[j], (uint32_t)(kk[j] >> shift) & 255u, lane);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            // bins in DESCENDING order, four per lane: position q = 4 * lane + j is bin 255 - q
+            uint32_t v[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) v[j] = s_hist[255u - (4 * lane + j)];
+            const uint32_t tv = (v[0] + v[1]) + (v[2] + v[3]);
+            const uint32_t inc = wave_scan_incl_u32(tv);
+            const uint32_t all = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            // (the top byte's pass counts the candidates: fewer than k, and all of them are taken; none, and rem is 0)
+            const uint32_t want = shift == 56 ? min(rem, all) : rem;
+            if (shift == 56 && lane == 0) s_take = want;
+            if (want == 0) {
+                if (lane == 0) s_rem = 0;
+            } else {
+                // the first position whose inclusive count reaches `want` (all >= want: one does)
+                const uint32_t f = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(inc >= want));
+                if (lane == f) {
+                    uint32_t run = inc - tv, j = 0;
+                    while (j < 3 && run + v[j] < want) run += v[j++];
+                    s_digit = 255u - (4 * lane + j);
+                    s_rem = want - run; // among the records of that bin
+                }
+            }
+        }
+        __syncthreads();
+        rem = s_rem;
+        if (rem == 0) { // workgroup-uniform: no candidate at all
+            if (tid == 0) *n_out = 0;
+            return;
+        }
+        prefix = (prefix << 8) | s_digit;
+        // (s_hist, s_digit and s_rem are written again only behind the next pass's first barrier)
+    }
+    // `prefix` is the k-th key (the last candidate's when there are fewer than k), nwin records are taken: the nahead that
+    // are strictly ahead of it and the first rem, in index order, of those equal to it.
+    const u64 kth = prefix;
+    const uint32_t nwin = min(s_take, (uint32_t)LH_MAX_TOP), nahead = nwin - min(rem, nwin);
+
+    // ---- the winners into LDS, by a prefix count over the records in index order
+    uint32_t gt_base = 0, eq_base = 0; // records of either kind in the tiles so far
+    for (uint32_t t = 0; t < ntiles && (gt_base < nahead || eq_base < rem); t++) { // workgroup-uniform
+        u64 kk[SEL_PER];
+        bool ok[SEL_PER];
+        const size_t i0 = (size_t)t * SEL_TILE + SEL_PER * tid; // (the last tile's tail may lie beyond 2^32)
+        load_records(r.key, r.count, i0, n, kk, ok, [&](u64 x) { return x >= kth; });
+        uint32_t mine = 0; // records ahead in the high half, equal ones in the low half (a tile has at most 4 096 of each)
+#pragma unroll
+        for (uint32_t j = 0; j < SEL_PER; j++) mine += ok[j] ? (kk[j] > kth ? 0x10000u : 1u) : 0u;
+        const uint32_t inc = wave_scan_incl_u32(mine);
+        if (lane == 63) s_part[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, tile = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < SEL_WAVES; w++) {
+            const uint32_t p = s_part[w];
+            before += w < wave ? p : 0u;
+            tile += p;
+        }
+        before += inc - mine;
+        uint32_t gpos = gt_base + (before >> 16), epos = eq_base + (before & 0xffffu);
+#pragma unroll
+        for (uint32_t j = 0; j < SEL_PER; j++) {
+            if (!ok[j]) continue;
+            uint32_t slot = NO_SLOT;
+            if (kk[j] > kth) slot = gpos++;
+            else if (epos++ < rem) slot = nahead + (epos - 1);
+            if (slot < nwin) { // (every slot handed out is: the guard keeps a wrong count from writing outside the block)
+                s_wkey[slot] = kk[j];
+                s_widx[slot] = (uint32_t)(i0 + j); // (an existing record: below n)
+            }
+        }
+        gt_base += tile >> 16;
+        eq_base += tile & 0xffffu;
+        __syncthreads(); // s_part is rewritten by the next tile
+    }
+
+    // ---- bitonic sort of the winners by (key descending, index ascending), padded to a power of two
+    uint32_t width = 1;
+    while (width < nwin) width <<= 1;
+    if (tid >= nwin && tid < width) {
+        s_wkey[tid] = 0;
+        s_widx[tid] = NO_SLOT;
+    }
+    for (uint32_t size = 2; size <= width; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            const uint32_t other = tid ^ stride;
+            if (other > tid && other < width) {
+                const u64 ka = s_wkey[tid], kb = s_wkey[other];
+                const uint32_t ia = s_widx[tid], ib = s_widx[other];
+                const bool up = (tid & size) == 0; // this run ends up with its leader first
+                if (ahead(kb, ib, ka, ia) == up) {
+                    s_wkey[tid] = kb; s_widx[tid] = ib;
+                    s_wkey[other] = ka; s_widx[other] = ia;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < nwin && s_widx[tid] < n) { // (every winner's index is: the guard keeps a wrong slot from reading outside the block)
+        const uint32_t i = s_widx[tid];
+        const u64 aux = r.aux[i];
+        lh_top_entry e;
+        e.id = first + i;
+        e.pkey = by == LH_TOP_BY_PERCENTILE ? (int16_t)(uint16_t)aux : (int16_t)0;
+        e.reserved = 0;
+        e.count = r.count[i];
+        e.sum = r.sum[i];
+        e.above = by == LH_TOP_BY_COUNT_ABOVE ? aux : 0;
+        out[tid] = e;
+    }
+    if (tid == 0) *n_out = nwin;
+}
+
+// ---- host side --------------------------------------------------------------------------------------
+// Per-device state of this unit (device_ctx<TopCtx>).  `mu` is held for the length of a call -- the host form's wait for
+// its results included, so host-form calls on one device take turns even when their snapshots belong to different
+// engines.  Snapshots of different engines run on different streams, and the records block outlives a device-form call:
+// it is guarded by an event, not by stream order.  The table is complete before the call that generates it goes on.
+struct TopCtx {
+    std::mutex mu;
+    double *d_table = nullptr;        // D[LH_NKEYS]
+    unsigned char *d_records = nullptr; // four arrays of padded nmetrics 8-byte fields
+    size_t rec_cap = 0;               // (in records)
+    ResultBlocks res;                 // host form: k entries and n_out
+    hipEvent_t ev = nullptr;          // behind the last select pass, on whichever stream that was
+    bool ev_pending = false;
+};
+
+// every check that needs neither the snapshot nor a device
+int check_args(lh_snapshot *s, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out,
+               uintptr_t n_out_align)
+{
+    if (!s || k == 0 || k > LH_MAX_TOP || by > LH_TOP_BY_COUNT_ABOVE || (flags & ~(uint32_t)LH_TOP_ASCENDING)) return LH_EINVAL;
+    if (!out || !n_out || misaligned(out, 8) || misaligned(n_out, n_out_align)) return LH_EINVAL;
+    if (by == LH_TOP_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL; // NaN too: no bucket to rank by
+    if (by == LH_TOP_BY_COUNT_ABOVE && arg != arg) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    return LH_OK;
+}
+
+struct Source : Opened {
+    TopCtx *cx = nullptr;
+    const void *cells = nullptr;
+    uint32_t nrows = 0, cell_bytes = 0;
+};
+
+// (cx->mu held) enqueue both passes over rows [first, first + nmetrics) on the snapshot's stream.  ev[0 .. 2] (may be
+// null): events to record before the score pass, between the passes and behind the select pass (lh_tool_top_passes_ms).
+int enqueue(const Source &q, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, lh_top_entry *d_out,
+            uint32_t *d_n_out, hipEvent_t *ev = nullptr)
+{
+    TopCtx *cx = q.cx;
+    if (!cx->d_table) {
+        double *t = nullptr;
+        LH_BESIDE_CHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
+        hipLaunchKernelGGL(k_top_table, dim3(LH_NKEYS / 256), dim3(256), 0, q.stream, t);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(q.stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(t);
+            return LH_EDEVICE;
+        }
+        cx->d_table = t;
+    }
+    if (!cx->ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->ev, hipEventDisableTiming));
+    const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
+    if (cx->rec_cap < npad && cx->ev_pending) { // the block is about to be freed: an earlier call's passes may still use it
+        LH_BESIDE_CHK(hipEventSynchronize(cx->ev));
+        cx->ev_pending = false;
+    }
+    int rc = grow_device(cx->d_records, cx->rec_cap, npad, 4096, 4 * sizeof(u64));
+    if (rc) return rc;
+    // (another stream's call may still read the records: this one's passes wait for it on the device, not on the host)
+    if (cx->ev_pending) LH_BESIDE_CHK(hipStreamWaitEvent(q.stream, cx->ev, 0));
+    TopRecords r;
+    r.key = reinterpret_cast<u64 *>(cx->d_records);
+    r.count = r.key + npad;
+    r.sum = reinterpret_cast<double *>(r.count + npad);
+    r.aux = reinterpret_cast<u64 *>(r.sum + npad);
+    const uint32_t M = (uint32_t)nmetrics;
+    const uint32_t *ranges = q.ranges + 2 * (size_t)first;
+    const u64 flip = (flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;
+    const dim3 grid((M + TP_WAVES - 1) / TP_WAVES), block(TP_BLOCK);
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[0], q.stream));
+    if (q.cell_bytes == 4) {
+        const uint32_t *c = static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride;
+        hipLaunchKernelGGL(k_top_score<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, cx->d_table, by, arg, flip, r);
+    } else {
+        const u64 *c = static_cast<const u64 *>(q.cells) + (size_t)first * q.stride;
+        hipLaunchKernelGGL(k_top_score<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, cx->d_table, by, arg, flip, r);
+    }
+    LH_BESIDE_CHK(hipGetLastError());
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], q.stream));
+    hipLaunchKernelGGL(k_top_select, dim3(1), dim3(SEL_WG), 0, q.stream, r, M, first, (uint32_t)k, by, d_out, d_n_out);
+    LH_BESIDE_CHK(hipGetLastError());
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], q.stream));
+    LH_BESIDE_CHK(hipEventRecord(cx->ev, q.stream));
+    cx->ev_pending = true;
+    return LH_OK;
+}
+
+// the snapshot's cells, spans, device and stream; LH_ERANGE for rows it does not have
+int open_source(lh_snapshot *s, uint32_t first, size_t nmetrics, Source &q)
+{
+    void *cells = nullptr;
+    int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
+    if (rc) return rc;
+    q.cells = cells;
+    if (nmetrics > q.nrows || first > q.nrows - nmetrics) return LH_ERANGE;
+    rc = open_snapshot(s, q, q.cx);
+    if (rc) return rc;
+    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
+    return LH_OK;
+}
+
+// (cx->mu held) the host form's landing blocks: k entries, then n_out
+int result_blocks(TopCtx *cx, size_t k)
+{
+    const size_t need = k * sizeof(lh_top_entry) + 8;
+    int rc = grow_device(cx->res.d_res, cx->res.d_cap, need, RESULT_FLOOR);
+    if (!rc) rc = grow_pinned(cx->res.h_res, cx->res.h_cap, need, RESULT_FLOOR);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, lh_top_entry *out,
+           size_t *n_out)
+{
+    int rc = check_args(s, nmetrics, by, arg, k, flags, out, n_out, alignof(size_t));
+    if (rc) return rc;
+    Source q;
+    rc = open_source(s, first, nmetrics, q);
+    if (rc) return rc;
+    if (nmetrics == 0) {
+        *n_out = 0;
+        return LH_OK;
+    }
+    TopCtx *cx = q.cx;
+    std::lock_guard<std::mutex> g(cx->mu);
+    // Entries at and beyond n_out are not written, and n_out is known only once the select pass has run: the k entries and
+    // n_out come back in one copy into the unit's pinned block, whatever memory `out` is, and the first n_out entries go
+    // on from there (at most 32 KiB).  A copy straight into a pinned `out` would need n_out first: a second round trip.
+    rc = result_blocks(cx, k);
+    if (rc) return rc;
+    const size_t bytes = k * sizeof(lh_top_entry);
+    rc = enqueue(q, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_top_entry *>(cx->res.d_res),
+                 reinterpret_cast<uint32_t *>(cx->res.d_res + bytes));
+    if (rc) return rc;
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->res.h_res, cx->res.d_res, bytes + 8, hipMemcpyDeviceToHost, q.stream));
+    LH_BESIDE_CHK(hipStreamSynchronize(q.stream));
+    const uint32_t *h_n = reinterpret_cast<const uint32_t *>(cx->res.h_res + bytes);
+    if (*h_n > k) return LH_ESTATE;
+    std::memcpy(out, cx->res.h_res, (size_t)*h_n * sizeof(lh_top_entry));
+    cx->ev_pending = false; // this call recorded `ev` on the stream it has just waited for
+    *n_out = *h_n;
+    return LH_OK;
+}
+
+int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
+                  lh_top_entry *d_out, uint32_t *d_n_out)
+{
+    int rc = check_args(s, nmetrics, by, arg, k, flags, d_out, d_n_out, alignof(uint32_t));
+    if (rc) return rc;
+    Source q;
+    rc = open_source(s, first, nmetrics, q);
+    if (rc) return rc;
+    if (nmetrics == 0) {
+        LH_BESIDE_CHK(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), q.stream));
+        return LH_OK;
+    }
+    std::lock_guard<std::mutex> g(q.cx->mu);
+    return enqueue(q, first, nmetrics, by, arg, k, flags, d_out, d_n_out);
+}
+
+int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
+                          float *score_ms, float *select_ms)
+{
+    alignas(8) unsigned char own[8] = {0}; // (the results stay in the unit's own block)
+    int rc = check_args(s, nmetrics, by, arg, k, flags, own, own, 1);
+    if (rc) return rc;
+    if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
+    Source q;
+    rc = open_source(s, first, nmetrics, q);
+    if (rc) return rc;
+    TopCtx *cx = q.cx;
+    std::lock_guard<std::mutex> g(cx->mu);
+    rc = result_blocks(cx, k);
+    if (rc) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3 && rc == LH_OK; i++)
+        if (hipEventCreate(&ev[i]) != hipSuccess) rc = LH_EDEVICE;
+    if (rc == LH_OK)
+        rc = enqueue(q, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_top_entry *>(cx->res.d_res),
+                     reinterpret_cast<uint32_t *>(cx->res.d_res + k * sizeof(lh_top_entry)), ev);
+    if (rc == LH_OK && (hipStreamSynchronize(q.stream) != hipSuccess || hipEventElapsedTime(score_ms, ev[0], ev[1]) != hipSuccess ||
+                        hipEventElapsedTime(select_ms, ev[1], ev[2]) != hipSuccess))
+        rc = LH_EDEVICE;
+    if (rc == LH_OK) cx->ev_pending = false;
+    for (int i = 0; i < 3; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (rc == LH_EDEVICE) (void)hipGetLastError();
+    return rc;
+}
+
+} // extern "C"

@@ -1,11 +1,14 @@
-// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip; a new reader
-// starts here and in lh_beside.h): DPP scans, cross-lane reads, the packed 16-byte load types, a row's 4-bin group as one
-// load, and the percentile threshold.  The text is lh_kernels.hip's, which still carries its own copy for K2: that file is
-// one of the sources the committed profiles are stamped with (bench.tree_stamp), so it takes this header in the change that
-// next regenerates them.  Until then a fix to pct_threshold goes to both (tests/test_pct_threshold_model.py has the
+// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip; a
+// new reader starts here and in lh_beside.h): DPP scans, cross-lane reads, the packed 16-byte load types, a row's 4-bin
+// group as one load, the percentile threshold and the bound-to-key rule (le_take, which came from lh_count.hip).  The
+// scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the
+// sources the committed profiles are stamped with (bench.tree_stamp), so it takes this header in the change that next
+// regenerates them.  Until then a fix to pct_threshold goes to both (tests/test_pct_threshold_model.py has the
 // arithmetic, tests/test_gpu_extract_thresholds.py and tests/test_gpu_spread.py hold both to the oracle).
 // Every unit that includes it is built with -ffp-contract=off (build.py's _COMMON).
 #pragma once
+
+#include "lh_codec.h"
 
 #include <hip/hip_runtime.h>
 
@@ -112,6 +115,20 @@ __device__ inline uint64_t pct_threshold(double p, uint64_t total)
         if (pct_reached(mid, ft, p)) hi = mid; else lo = mid;
     }
     return hi;
+}
+
+// How many leading bins bound b takes in (0 .. 65 536): bin(compress(b)) + 1 (metrics.go:316-322 with the extended key
+// before its int16 truncation, by the arithmetic the ingest's threshold table is generated with; -0.0 and 0.0 both give
+// key 0).  0 for -Inf and for negative bounds beyond the int16 key range, 65 536 for +Inf and positive ones beyond it.
+// The host refused NaN.  lh_count_le*'s bound-to-key rule, and lh_top's for LH_TOP_BY_COUNT_ABOVE.
+constexpr uint32_t LE_TAKE_ALL = LH_NKEYS;
+__device__ __forceinline__ uint32_t le_take(double b)
+{
+    const double a = fabs(b);
+    if (!(a <= 1.7976931348623157e308)) return b > 0 ? LE_TAKE_ALL : 0u; // +-Inf
+    const int kext = d_kext_golog(1.0 + a);
+    if (kext > 32767) return b > 0 ? LE_TAKE_ALL : 0u;                     // where the reference's int16 keys wrap
+    return key_to_bin(b < 0 ? -kext : kext) + 1u;
 }
 
 // 16 bytes at an 8-byte-aligned address as ONE load (global_load_dwordx4; unaligned vector access is on for HSA)

@@ -426,6 +426,47 @@ class Snapshot:
             res["upper"] = np.where(res["pvalid"] != 0, self.engine._decompress_table[bins], np.nan)
         return res
 
+    # -- the k names that lead (a selection across names; what is ranked is what extract / count_le return) ---------------
+    _TOP_BY = {"count": N.TOP_BY_COUNT, "sum": N.TOP_BY_SUM, "percentile": N.TOP_BY_PERCENTILE,
+               "count_above": N.TOP_BY_COUNT_ABOVE}
+
+    def top(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False,
+            nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """The k names of [first, first+nmetrics) that lead (lh_top*), as a structured array (dtype N.TOP_ENTRY: id, pkey,
+        reserved, count, sum, above) of n_out = min(k, names with samples) entries, the leader first.  by = "count", "sum",
+        "percentile" (arg = p in [0, 1]: ranked by the bucket extract() selects, whose key is `pkey`) or "count_above" (arg =
+        a value: ranked by the samples in buckets above that value's, `above` -- count minus count_le's answer).  Descending
+        score, or ascending with ascending=True; equal scores go lowest id first either way.  ids are absolute.
+        out = a contiguous numpy array of at least k TOP_ENTRY elements takes the host form into it (its first n_out
+        entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
+        k * 32 and 4 bytes takes the device form: enqueued on the snapshot's stream, the pair is returned as it is."""
+        L = N.lib()
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        if by not in self._TOP_BY:
+            raise ValueError("by is one of " + ", ".join(self._TOP_BY))
+        if arg is None:
+            if by in ("percentile", "count_above"):
+                raise ValueError(f"by={by!r} takes an arg")
+            arg = 0.0
+        flags = N.TOP_ASCENDING if ascending else 0
+        if isinstance(out, tuple):
+            entries, n = out
+            for t, need in ((entries, k * N.TOP_ENTRY.itemsize), (n, 4)):
+                if not t.is_contiguous() or t.element_size() * int(t.numel()) < need:
+                    raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4")
+            N.check(L.lh_top_device(self._h, first, nmetrics, self._TOP_BY[by], float(arg), k, flags, _ptr(entries), _ptr(n)),
+                    "lh_top_device")
+            return out
+        if out is None:
+            out = np.zeros(max(k, 1), dtype=N.TOP_ENTRY)
+        elif not (isinstance(out, np.ndarray) and out.dtype == N.TOP_ENTRY and out.size >= k and out.flags.c_contiguous):
+            raise ValueError("out holds at least k contiguous TOP_ENTRY elements")
+        n = C.c_size_t(0)
+        N.check(L.lh_top(self._h, first, nmetrics, self._TOP_BY[by], float(arg), k, flags, out.ctypes.data,
+                         C.addressof(n)), "lh_top")
+        return out.reshape(-1)[:n.value]
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
