@@ -429,6 +429,52 @@ int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double 
            lh_top_entry *out, size_t *n_out);
 int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
                   lh_top_entry *d_out, uint32_t *d_n_out);
+/* How a name's distribution in one snapshot differs from its distribution in another: "which names changed against the
+ * previous interval", "does the canary's latency match the baseline's", "did the deploy shift p-anything" -- answered on the
+ * device, where both intervals already are (num_buffers >= 3 keeps the previous snapshot alive across a flip;
+ * lh_snapshot_add_buckets* puts a stored baseline into a snapshot), instead of pulling both intervals' cells to the host with
+ * lh_buckets_all.  One more bucket walk of the kind percentile() does (/root/reference/metrics.go:389-418), over two rows at
+ * once.  For metric first + m, with a[j] the cells of `base` and b[j] the cells of `cur` in ascending bin order (ascending bin
+ * is ascending value), A_j and B_j their inclusive prefix counts and na, nb the totals:
+ *   count_a[m], count_b[m]   na and nb
+ *   Kolmogorov-Smirnov, decided in exact integers: X_j = |A_j nb - B_j na| (128 bits), j* = the LOWEST bin at which X_j
+ *   reaches its maximum;
+ *   ks_key[m]                the int16 key of bin j*
+ *   ks_below_a[m], ks_below_b[m]   A_j* and B_j*
+ *   ks[m]                    fabs((double)A_j* / (double)na - (double)B_j* / (double)nb), both divides IEEE
+ *                            A maximum of 0 means the two normalised distributions are identical: ks = 0, the key and both
+ *                            prefixes are 0 (whatever the rows' dirty spans are).  The argmax is never taken in floating point.
+ *   w1[m]                    sum over the bins j of |A_j / na - B_j / nb|: the earth mover's distance in BUCKETS (100 buckets
+ *                            are one e-fold, so w1 per cent is roughly the mean relative shift)
+ *   shift[m]                 the same sum without the absolute value: positive means `cur` sits higher; |shift| <= w1
+ * Each term of the two sums is X_j / (na nb) with the sign of A_j nb - B_j na, rounded three times (no two rounded quotients
+ * cancel).  Bins outside the union of the two rows' dirty spans contribute nothing; empty bins inside it do.  Both sums are
+ * taken in a fixed order: a result does not depend on timing (calls that cover different numbers of rows use differently
+ * shaped kernels and may differ in the last bits).
+ * A name with na == 0 or nb == 0: ks, w1 and shift are NaN, the key and both prefixes 0; the counts are still reported.
+ * Totals that wrap past 2^64: the results are unspecified (nothing faults).
+ *   Any output may be NULL, but not all of them.  flags must be 0.  nmetrics == 0 -> LH_OK, nothing written.
+ *   LH_EINVAL, checked on the host before either snapshot or a device is touched: NULL base or cur; all outputs NULL; unknown
+ *            flag bits; arrays not aligned to their element size.
+ *   LH_ERANGE: an nmetrics above 2^32 - 1 before anything is looked at; first + nmetrics beyond the rows of EITHER snapshot
+ *            (the two engines may have different max_metrics).
+ *   base == cur is allowed: every ks, w1 and shift of a non-empty name is exactly 0.
+ *   Two snapshots on different devices -> LH_EINVAL (after both were opened).
+ * ORDERING: the work is enqueued on lh_snapshot_stream(cur).  When base's stream is another one (a snapshot of another
+ * engine) an event recorded on base's stream is waited for by cur's first, so whatever base's stream held at the call is
+ * complete before a cell of base is read.  base must NOT be released before cur's stream has passed the call
+ * (lh_compare_device; lh_compare has waited already when it returns).  One thread per snapshot, as for the other readers.
+ * READ-ONLY: no cell, span or cell width of either snapshot changes; the kernels read lh_snapshot_cells as they are, in all
+ * four combinations of 4- and 8-byte cells (a narrow snapshot against one that an import has widened).
+ * Staging as for lh_spread*: lh_compare returns when the results are in the caller's arrays (pinned arrays receive them by
+ * one copy each, others go through a pinned block of the library's); lh_compare_device takes device arrays and returns after
+ * enqueueing.  One set of staging blocks per DEVICE behind the unit's own mutex: calls take turns. */
+int lh_compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags, uint64_t *count_a,
+               uint64_t *count_b, double *ks, int16_t *ks_key, uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1,
+               double *shift);
+int lh_compare_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags,
+                      uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key, uint64_t *d_ks_below_a,
+                      uint64_t *d_ks_below_b, double *d_w1, double *d_shift);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

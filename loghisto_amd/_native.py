@@ -149,6 +149,7 @@ TUNING_SIGNATURES = {
     "lh_tool_last_extract_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_count_le_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_spread_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_compare_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
 }
@@ -210,6 +211,8 @@ SIGNATURES = {
     "lh_spread_device": (C.c_int, [_vp, C.c_uint32, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_top": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_top_device": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
+    "lh_compare": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_compare_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

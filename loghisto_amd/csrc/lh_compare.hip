@@ -1,0 +1,523 @@
+// lh_compare.hip -- lh_compare* (include/loghisto_gpu.h): how a name's distribution in one snapshot (`cur`) differs from
+// its distribution in another (`base`): the previous interval, a stored baseline, the canary against the fleet.  One more
+// bucket walk of the kind percentile() does (/root/reference/metrics.go:389-418: `sofar += *count` over the cells in
+// ascending key order), taken over TWO rows at once.  With a[j] / b[j] the cells of base / cur, A_j / B_j their inclusive
+// prefix counts and na / nb the totals, per name:
+//   X_j = |A_j nb - B_j na|        an exact 128-bit integer: na nb times the distance of the two normalised prefixes
+//   j*  = the lowest bin at which X_j is largest  -> ks_key, ks_below_a = A_j*, ks_below_b = B_j*,
+//         ks = |float64(A_j*) / float64(na) - float64(B_j*) / float64(nb)|   (Kolmogorov-Smirnov; the argmax is integer)
+//   w1    = sum over j of X_j / (na nb)            (earth mover's distance, in buckets)
+//   shift = the same sum with the sign of A_j nb - B_j na: positive when cur sits higher
+// A term of the two sums is float64(X_j >> s) / float64(na nb >> s), s = what na nb has beyond 64 bits: the shift drops
+// less than 2^-63 of a term that is at most 1, and the conversions and the divide round three times -- no cancellation of
+// two rounded quotients, whatever the counts.
+//
+// Built BESIDE the engine, on its public C ABI only (lh_beside.h), like lh_spread.hip, whose two shapes these are:
+//   k_compare_wave   one WAVE per row, 256 bins per step (4 consecutive bins per lane and row), the next step's loads issued
+//                    before the current step is worked on.  For calls of many rows.
+//   k_compare_block  one WORKGROUP of 16 waves per row: the waves total the 256-bin chunks, wave 0 scans the chunk totals in
+//                    LDS so that each wave knows the prefixes its chunks start from, then the waves walk their chunks again.
+//                    For calls of few rows, which may span all 65 536 bins.
+// Each row takes two walks over the union of the two dirty spans (from its start aligned down to a multiple of 4): walk 1
+// gives na and nb; walk 2 carries both prefixes, each lane's largest X with its bin and prefixes (strictly larger only: a
+// lane meets its bins in ascending order, so it keeps the lowest), and the lane's share of the two sums.  A row is only
+// read inside its OWN span (its cells outside are zero by the engine's contract, and a row that was never marked has
+// lo > hi: nothing of it is read).  Bins behind the union span need no mask: there A = na and B = nb, X = 0.
+// The wave's best (X, bin) is found without LDS: four DPP max-reductions over the 32-bit words of X from the top, the lanes
+// that fall short dropping out, then a DPP min of the bin among those left.  The sums are taken in a fixed order (per
+// lane over its bins in ascending order, one DPP tree over the lanes, the waves of a workgroup in ascending order), so a
+// result does not depend on timing -- the two shapes associate differently and agree to rounding only.
+// Read-only: no store goes to a cell, a span or either engine.
+#include "../../include/loghisto_gpu.h"
+#include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
+#include "lh_codec.h"
+#include "lh_wave.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cmath>
+#include <mutex>
+
+namespace {
+
+using namespace lh::beside;
+using lh::load4_cells;
+using lh::readlane_f64;
+using lh::readlane_u64;
+using lh::wave_scan_incl_f64;
+using lh::wave_scan_incl_u64;
+
+typedef unsigned long long u64;
+typedef unsigned __int128 u128;
+
+constexpr int CP_BLOCK = 256, CP_WAVES = CP_BLOCK / 64; // k_compare_wave: four rows per workgroup
+constexpr int CP_WG = 1024, CP_WG_WAVES = CP_WG / 64;   // k_compare_block
+constexpr uint32_t CP_STEP = 256;                       // bins a wave takes per step
+constexpr uint32_t CP_CHUNKS = LH_NKEYS / CP_STEP;      // chunks of the widest span (a span starts at a multiple of 4)
+// Rows of a call from which a row gets a wave, not a workgroup: lh_spread's default, whose walks these are, until
+// tools/compare_bench.py has been run (profiles/compare.txt).
+constexpr uint32_t CP_WAVE_FROM_DEFAULT = 1024;
+constexpr uint32_t NO_BIN = 0xffffffffu;
+static_assert(CP_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
+
+struct CompareOut {
+    u64 *count_a, *count_b;
+    double *ks;
+    int16_t *ks_key;
+    u64 *below_a, *below_b;
+    double *w1, *shift;
+};
+
+// One row's own span: [lo4, hi], lo4 = lo aligned down to a multiple of 4; lo4 > hi for a row that was never marked.
+struct Span { uint32_t lo4, hi; };
+__device__ __forceinline__ Span own_span(const uint32_t *__restrict__ ranges, uint32_t m)
+{
+    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    Span s;
+    s.lo4 = lo <= hi ? lo & ~3u : NO_BIN;
+    s.hi = lo <= hi ? hi : 0u;
+    return s;
+}
+// bins b0 .. b0 + 3 of a row, zeros outside its own span (b0 a multiple of 4; hi <= 65 535: the group ends inside the row)
+template <typename CELL>
+__device__ __forceinline__ void load4_in(const CELL *__restrict__ row, uint32_t b0, Span s, u64 (&c)[4])
+{
+    load4_cells(row, b0 >= s.lo4 ? b0 : NO_BIN, s.hi, c); // (NO_BIN > hi: nothing is asked for)
+}
+__device__ __forceinline__ u64 sum4(const u64 (&c)[4]) { return (c[0] + c[1]) + (c[2] + c[3]); }
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) // the maximum in lane 63 (lanes without a source: 0)
+{
+    x = max(x, LH_DPP32(x, 0x111, 0xf));
+    x = max(x, LH_DPP32(x, 0x112, 0xf));
+    x = max(x, LH_DPP32(x, 0x114, 0xf));
+    x = max(x, LH_DPP32(x, 0x118, 0xf));
+    x = max(x, LH_DPP32(x, 0x142, 0xa));
+    x = max(x, LH_DPP32(x, 0x143, 0xc));
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+// What a name's walk is scaled by: the totals, and na nb as the divisor of the sums' terms.
+struct Scale {
+    u64 na, nb;
+    uint32_t sh; // the bits na nb has beyond 64
+    double den;  // float64(na nb >> sh)
+};
+__device__ __forceinline__ Scale make_scale(u64 na, u64 nb)
+{
+    Scale s;
+    s.na = na;
+    s.nb = nb;
+    const u128 p = (u128)na * nb;
+    const u64 ph = (u64)(p >> 64);
+    s.sh = ph ? 64u - (uint32_t)__builtin_clzll(ph) : 0u; // <= 64
+    s.den = (double)(u64)(p >> s.sh);
+    return s;
+}
+
+// A lane's state of walk 2
+struct Best {
+    u128 x;      // the largest X so far
+    uint32_t bin;
+    u64 a, b;    // the prefixes there
+    double w, s; // the lane's share of w1 and of shift
+};
+__device__ __forceinline__ void best_init(Best &r)
+{
+    r.x = 0;
+    r.bin = NO_BIN;
+    r.a = r.b = 0;
+    r.w = r.s = 0.0;
+}
+// the lane's four bins bin0 .. bin0 + 3; pa / pb: the prefixes below them
+__device__ __forceinline__ void take4(Best &r, const Scale &sc, uint32_t bin0, u64 pa, u64 pb, const u64 (&a)[4], const u64 (&b)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        pa += a[k];
+        pb += b[k];
+        const u128 xa = (u128)pa * sc.nb, xb = (u128)pb * sc.na;
+        const bool up = xa >= xb;
+        const u128 x = up ? xa - xb : xb - xa;
+        if (x > r.x) {
+            r.x = x;
+            r.bin = bin0 + k;
+            r.a = pa;
+            r.b = pb;
+        }
+        const double t = (double)(u64)(x >> sc.sh) / sc.den;
+        r.w += t;
+        r.s += up ? t : -t;
+    }
+}
+// The wave's best: the largest X, at the lowest bin among equals (wave-uniform results).  X == 0 everywhere: NO_BIN.
+__device__ __forceinline__ void wave_best(const Best &r, u128 &x, uint32_t &bin, u64 &a, u64 &b)
+{
+    bool in = true;
+#pragma unroll
+    for (int w = 3; w >= 0; w--) {
+        const uint32_t word = (uint32_t)(r.x >> (32 * w));
+        const uint32_t top = wave_max_u32(in ? word : 0u);
+        in = in && word == top;
+    }
+    const uint32_t inv = wave_max_u32(in ? ~r.bin : 0u); // the lowest bin: the largest complement (NO_BIN's is 0)
+    const uint32_t src = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(in && ~r.bin == inv)); // (lane 0 at least, with NO_BIN)
+    bin = ~inv;
+    a = readlane_u64(r.a, src);
+    b = readlane_u64(r.b, src);
+    x = ((u128)readlane_u64((u64)(r.x >> 64), src) << 64) | readlane_u64((u64)r.x, src);
+}
+
+// one lane writes a name's results; bin == NO_BIN: the two normalised distributions are identical
+__device__ __forceinline__ void store_row(const CompareOut &o, uint32_t m, u64 na, u64 nb, uint32_t bin, u64 a, u64 b, double w1,
+                                          double shift)
+{
+    double ks = 0.0;
+    if (na == 0 || nb == 0) {
+        ks = w1 = shift = __builtin_nan("");
+        bin = NO_BIN;
+    }
+    if (bin == NO_BIN) a = b = 0;
+    else ks = fabs((double)a / (double)na - (double)b / (double)nb);
+    if (o.count_a) o.count_a[m] = na;
+    if (o.count_b) o.count_b[m] = nb;
+    if (o.ks) o.ks[m] = ks;
+    if (o.ks_key) o.ks_key[m] = bin == NO_BIN ? (int16_t)0 : (int16_t)lh::bin_to_key(bin);
+    if (o.below_a) o.below_a[m] = a;
+    if (o.below_b) o.below_b[m] = b;
+    if (o.w1) o.w1[m] = w1;
+    if (o.shift) o.shift[m] = shift;
+}
+
+template <typename CA, typename CB>
+__global__ __launch_bounds__(CP_BLOCK) void k_compare_wave(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
+                                                           size_t stride_a, const CB *__restrict__ cells_b,
+                                                           const uint32_t *__restrict__ ranges_b, size_t stride_b,
+                                                           uint32_t nmetrics, const CompareOut o)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * CP_WAVES + (threadIdx.x >> 6);
+    if (m >= nmetrics) return; // wave-uniform
+    const Span sa = own_span(ranges_a, m), sb = own_span(ranges_b, m);
+    const uint32_t base0 = min(sa.lo4, sb.lo4), hi = max(sa.hi, sb.hi); // the union; base0 == NO_BIN: neither row was marked
+    u64 na = 0, nb = 0, ba = 0, bb = 0;
+    uint32_t bin = NO_BIN;
+    double w1 = 0.0, shift = 0.0;
+    if (base0 != NO_BIN) { // wave-uniform
+        const CA *__restrict__ ra = cells_a + (size_t)m * stride_a;
+        const CB *__restrict__ rb = cells_b + (size_t)m * stride_b;
+        u64 a[4], b[4], xa[4], xb[4];
+        // ---- walk 1: the totals
+        {
+            u64 ta = 0, tb = 0;
+            load4_in(ra, base0 + 4 * lane, sa, a);
+            load4_in(rb, base0 + 4 * lane, sb, b);
+            for (uint32_t base = base0; base <= hi; base += CP_STEP) {
+                load4_in(ra, base + CP_STEP + 4 * lane, sa, xa); // the next step's: in flight under this step's work
+                load4_in(rb, base + CP_STEP + 4 * lane, sb, xb);
+                ta += sum4(a);
+                tb += sum4(b);
+#pragma unroll
+                for (int k = 0; k < 4; k++) { a[k] = xa[k]; b[k] = xb[k]; }
+            }
+            na = readlane_u64(wave_scan_incl_u64(ta), 63);
+            nb = readlane_u64(wave_scan_incl_u64(tb), 63);
+        }
+        if (na && nb) { // wave-uniform
+            // ---- walk 2: the prefixes, the largest X and the sums
+            const Scale sc = make_scale(na, nb);
+            Best r;
+            best_init(r);
+            u64 ca = 0, cb = 0; // what lies below the step
+            load4_in(ra, base0 + 4 * lane, sa, a);
+            load4_in(rb, base0 + 4 * lane, sb, b);
+            for (uint32_t base = base0; base <= hi; base += CP_STEP) {
+                load4_in(ra, base + CP_STEP + 4 * lane, sa, xa);
+                load4_in(rb, base + CP_STEP + 4 * lane, sb, xb);
+                const u64 ta = sum4(a), tb = sum4(b);
+                const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+                take4(r, sc, base + 4 * lane, ca + (ia - ta), cb + (ib - tb), a, b);
+                ca += readlane_u64(ia, 63);
+                cb += readlane_u64(ib, 63);
+#pragma unroll
+                for (int k = 0; k < 4; k++) { a[k] = xa[k]; b[k] = xb[k]; }
+            }
+            u128 x;
+            wave_best(r, x, bin, ba, bb);
+            w1 = readlane_f64(wave_scan_incl_f64(r.w), 63);
+            shift = readlane_f64(wave_scan_incl_f64(r.s), 63);
+        }
+    }
+    if (lane == 0) store_row(o, m, na, nb, bin, ba, bb, w1, shift);
+}
+
+template <typename CA, typename CB>
+__global__ __launch_bounds__(CP_WG) void k_compare_block(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
+                                                         size_t stride_a, const CB *__restrict__ cells_b,
+                                                         const uint32_t *__restrict__ ranges_b, size_t stride_b,
+                                                         uint32_t nmetrics, const CompareOut o)
+{
+    __shared__ u64 s_a[CP_CHUNKS], s_b[CP_CHUNKS]; // the chunks' totals, then their exclusive prefixes
+    __shared__ u64 s_na, s_nb;
+    __shared__ u64 s_xh[CP_WG_WAVES], s_xl[CP_WG_WAVES], s_ba[CP_WG_WAVES], s_bb[CP_WG_WAVES]; // the waves' bests
+    __shared__ uint32_t s_bin[CP_WG_WAVES];
+    __shared__ double s_w[CP_WG_WAVES], s_s[CP_WG_WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
+    if (m >= nmetrics) return;
+    const Span sa = own_span(ranges_a, m), sb = own_span(ranges_b, m);
+    const uint32_t base0 = min(sa.lo4, sb.lo4), hi = max(sa.hi, sb.hi);
+    const uint32_t nchunks = base0 != NO_BIN ? (hi - base0) / CP_STEP + 1 : 0; // <= CP_CHUNKS
+    const CA *__restrict__ ra = cells_a + (size_t)m * stride_a;
+    const CB *__restrict__ rb = cells_b + (size_t)m * stride_b;
+    constexpr uint32_t U = 2;
+    // ---- walk 1: every chunk's totals
+    for (uint32_t c0 = wave; c0 < nchunks; c0 += CP_WG_WAVES * U) { // wave-uniform
+        u64 a[U][4], b[U][4];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) { // (a chunk beyond the span starts beyond hi: nothing is read)
+            const uint32_t b0 = base0 + (c0 + u * CP_WG_WAVES) * CP_STEP + 4 * lane;
+            load4_in(ra, b0, sa, a[u]);
+            load4_in(rb, b0, sb, b[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            const u64 ia = wave_scan_incl_u64(sum4(a[u])), ib = wave_scan_incl_u64(sum4(b[u]));
+            const uint32_t ch = c0 + u * CP_WG_WAVES;
+            if (lane == 63 && ch < nchunks) {
+                s_a[ch] = ia;
+                s_b[ch] = ib;
+            }
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        u64 va[4], vb[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const bool in = 4 * lane + k < nchunks;
+            va[k] = in ? s_a[4 * lane + k] : 0;
+            vb[k] = in ? s_b[4 * lane + k] : 0;
+        }
+        const u64 ta = sum4(va), tb = sum4(vb);
+        const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+        u64 ea = ia - ta, eb = ib - tb;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            s_a[4 * lane + k] = ea;
+            s_b[4 * lane + k] = eb;
+            ea += va[k];
+            eb += vb[k];
+        }
+        if (lane == 63) {
+            s_na = ia;
+            s_nb = ib;
+        }
+    }
+    __syncthreads();
+    const u64 na = s_na, nb = s_nb;
+    if (na == 0 || nb == 0) { // workgroup-uniform
+        if (threadIdx.x == 0) store_row(o, m, na, nb, NO_BIN, 0, 0, 0.0, 0.0);
+        return;
+    }
+    // ---- walk 2, by the same chunks
+    {
+        const Scale sc = make_scale(na, nb);
+        Best r;
+        best_init(r);
+        for (uint32_t c0 = wave; c0 < nchunks; c0 += CP_WG_WAVES * U) {
+            u64 a[U][4], b[U][4];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t b0 = base0 + (c0 + u * CP_WG_WAVES) * CP_STEP + 4 * lane;
+                load4_in(ra, b0, sa, a[u]);
+                load4_in(rb, b0, sb, b[u]);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t ch = c0 + u * CP_WG_WAVES;
+                if (ch < nchunks) { // wave-uniform
+                    const u64 ta = sum4(a[u]), tb = sum4(b[u]);
+                    const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+                    take4(r, sc, base0 + ch * CP_STEP + 4 * lane, s_a[ch] + (ia - ta), s_b[ch] + (ib - tb), a[u], b[u]);
+                }
+            }
+        }
+        u128 x;
+        uint32_t bin;
+        u64 ba, bb;
+        wave_best(r, x, bin, ba, bb);
+        const double w = wave_scan_incl_f64(r.w), s = wave_scan_incl_f64(r.s);
+        if (lane == 63) {
+            s_xh[wave] = (u64)(x >> 64);
+            s_xl[wave] = (u64)x;
+            s_bin[wave] = bin;
+            s_ba[wave] = ba;
+            s_bb[wave] = bb;
+            s_w[wave] = w;
+            s_s[wave] = s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u128 x = 0;
+        uint32_t bin = NO_BIN;
+        u64 ba = 0, bb = 0;
+        double w1 = 0.0, shift = 0.0;
+        for (int w = 0; w < CP_WG_WAVES; w++) { // (a wave without a chunk left X = 0, NO_BIN and +0)
+            const u128 xw = ((u128)s_xh[w] << 64) | s_xl[w];
+            if (xw > x || (xw == x && s_bin[w] < bin)) {
+                x = xw;
+                bin = s_bin[w];
+                ba = s_ba[w];
+                bb = s_bb[w];
+            }
+            w1 += s_w[w];
+            shift += s_s[w];
+        }
+        store_row(o, m, na, nb, bin, ba, bb, w1, shift);
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------
+// Per-device state of this unit (device_ctx<CompareCtx>).  `mu` is held for the length of a call, the host form's wait for
+// its results included.  `order`: the event that puts cur's stream behind base's when the two differ.
+struct CompareCtx {
+    std::mutex mu;
+    hipEvent_t order = nullptr;
+    ResultBlocks res; // host form
+};
+std::atomic<uint32_t> g_wave_from{CP_WAVE_FROM_DEFAULT};
+
+// every check that needs neither a snapshot nor a device
+int check_args(lh_snapshot *base, lh_snapshot *cur, size_t nmetrics, uint32_t flags, const CompareOut &o)
+{
+    if (!base || !cur || flags != 0) return LH_EINVAL;
+    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
+    if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
+        misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
+        return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    return LH_OK;
+}
+
+struct Source : Opened {
+    CompareCtx *cx = nullptr;
+    const void *cells = nullptr;
+    uint32_t nrows = 0, cell_bytes = 0;
+};
+
+int cells_of(lh_snapshot *s, Source &q, uint32_t first, size_t nmetrics)
+{
+    void *cells = nullptr;
+    const int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
+    if (rc) return rc;
+    q.cells = cells;
+    return nmetrics > q.nrows || first > q.nrows - nmetrics ? LH_ERANGE : LH_OK;
+}
+
+template <typename CA, typename CB>
+void launch(bool wave, const Source &a, const Source &b, uint32_t first, uint32_t M, const CompareOut &o)
+{
+    const CA *ca = static_cast<const CA *>(a.cells) + (size_t)first * a.stride;
+    const CB *cb = static_cast<const CB *>(b.cells) + (size_t)first * b.stride;
+    const uint32_t *ra = a.ranges + 2 * (size_t)first, *rb = b.ranges + 2 * (size_t)first;
+    if (wave)
+        hipLaunchKernelGGL((k_compare_wave<CA, CB>), dim3((M + CP_WAVES - 1) / CP_WAVES), dim3(CP_BLOCK), 0, b.stream, ca, ra,
+                           a.stride, cb, rb, b.stride, M, o);
+    else
+        hipLaunchKernelGGL((k_compare_block<CA, CB>), dim3(M), dim3(CP_WG), 0, b.stream, ca, ra, a.stride, cb, rb, b.stride, M, o);
+}
+
+// (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on cur's stream, behind what base's stream holds
+int enqueue(const Source &a, const Source &b, uint32_t first, size_t nmetrics, const CompareOut &o)
+{
+    CompareCtx *cx = b.cx;
+    if (a.stream != b.stream) {
+        if (!cx->order) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->order, hipEventDisableTiming));
+        LH_BESIDE_CHK(hipEventRecord(cx->order, a.stream));
+        LH_BESIDE_CHK(hipStreamWaitEvent(b.stream, cx->order, 0));
+    }
+    const uint32_t M = (uint32_t)nmetrics;
+    const bool wave = M >= g_wave_from.load(std::memory_order_relaxed);
+    if (a.cell_bytes == 4) {
+        if (b.cell_bytes == 4) launch<uint32_t, uint32_t>(wave, a, b, first, M, o);
+        else launch<uint32_t, u64>(wave, a, b, first, M, o);
+    } else {
+        if (b.cell_bytes == 4) launch<u64, uint32_t>(wave, a, b, first, M, o);
+        else launch<u64, u64>(wave, a, b, first, M, o);
+    }
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+bool usable(const Source &q) { return q.stride >= (size_t)LH_NKEYS + 4 && q.cells && (q.cell_bytes == 4 || q.cell_bytes == 8); }
+
+int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags, const CompareOut &o,
+            bool device_form)
+{
+    int rc = check_args(base, cur, nmetrics, flags, o);
+    if (rc) return rc;
+    Source a, b;
+    rc = cells_of(base, a, first, nmetrics);
+    if (rc) return rc;
+    rc = cells_of(cur, b, first, nmetrics);
+    if (rc) return rc;
+    if (nmetrics == 0) return LH_OK;
+    rc = open_snapshot(base, a, a.cx);
+    if (rc) return rc;
+    rc = open_snapshot(cur, b, b.cx);
+    if (rc) return rc;
+    if (a.device != b.device) return LH_EINVAL;
+    if (!usable(a) || !usable(b)) return LH_ESTATE;
+    CompareCtx *cx = b.cx;
+    std::lock_guard<std::mutex> g(cx->mu);
+    if (device_form) return enqueue(a, b, first, nmetrics, o);
+
+    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys.
+    const size_t n8 = nmetrics * 8;
+    const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
+                            {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
+    return host_results(cx->res, b.stream, out, [&](unsigned char *const(&dev)[8]) {
+        CompareOut d;
+        d.count_a = reinterpret_cast<u64 *>(dev[0]);
+        d.count_b = reinterpret_cast<u64 *>(dev[1]);
+        d.ks = reinterpret_cast<double *>(dev[2]);
+        d.below_a = reinterpret_cast<u64 *>(dev[3]);
+        d.below_b = reinterpret_cast<u64 *>(dev[4]);
+        d.w1 = reinterpret_cast<double *>(dev[5]);
+        d.shift = reinterpret_cast<double *>(dev[6]);
+        d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
+        return enqueue(a, b, first, nmetrics, d);
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int lh_compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags, uint64_t *count_a,
+               uint64_t *count_b, double *ks, int16_t *ks_key, uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1,
+               double *shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
+                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+    return compare(base, cur, first, nmetrics, flags, o, false);
+}
+
+int lh_compare_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags, uint64_t *d_count_a,
+                      uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b,
+                      double *d_w1, double *d_shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
+                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
+    return compare(base, cur, first, nmetrics, flags, o, true);
+}
+
+int lh_tool_compare_switch(uint32_t wave_from_rows, uint32_t *previous)
+{
+    switch_exchange(g_wave_from, wave_from_rows, CP_WAVE_FROM_DEFAULT, previous);
+    return LH_OK;
+}
+
+} // extern "C"

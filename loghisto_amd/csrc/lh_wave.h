@@ -1,4 +1,4 @@
-// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip; a
+// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip; a
 // new reader starts here and in lh_beside.h): DPP scans, cross-lane reads, the packed 16-byte load types, a row's 4-bin
 // group as one load, the percentile threshold and the bound-to-key rule (le_take, which came from lh_count.hip).  The
 // scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the

@@ -467,6 +467,64 @@ class Snapshot:
                          C.addressof(n)), "lh_top")
         return out.reshape(-1)[:n.value]
 
+    # -- distribution shift against another snapshot (percentile()'s bucket walk, metrics.go:389-418, over two rows at once) --
+    _COMPARE_OUT = (("count_a", 8, np.uint64), ("count_b", 8, np.uint64), ("ks", 8, np.float64), ("key", 2, np.int16),
+                    ("below_a", 8, np.uint64), ("below_b", 8, np.uint64), ("w1", 8, np.float64), ("shift", 8, np.float64))
+
+    def compare(self, base: "Snapshot", nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """How metrics [first, first+nmetrics) of THIS snapshot differ from the same names of `base` (lh_compare*), as a
+        dict of numpy arrays: count_a / count_b (the totals in base / here), ks (the Kolmogorov-Smirnov distance of the two
+        normalised distributions, its bin chosen in exact integers), key (the int16 key of that bin: the lowest at which
+        the distance is reached), below_a / below_b (the inclusive prefix counts there), ks_value = decompress(key) from the
+        engine's codec_tables, w1 (earth mover's distance in buckets: 100 buckets are one e-fold) and shift (the signed
+        form: positive when this snapshot sits higher).  ks, w1, shift and ks_value are NaN for a name that is empty on
+        either side; identical distributions give ks = 0 with key 0.  `base` may belong to another engine on the same
+        device, and may be this snapshot.
+        out = a dict with any of count_a, count_b, ks, key, below_a, below_b, w1, shift -> contiguous arrays of nmetrics
+        elements of 8 bytes (key: 2); outputs left out are not computed.  torch device tensors take the device form:
+        enqueued on this snapshot's stream (`base` must stay unreleased until that stream has passed the call), the
+        tensors are returned as they are and nothing is derived.  numpy arrays take the host form."""
+        L = N.lib()
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        if out is not None:
+            if not out or set(out) - {k for k, _, _ in self._COMPARE_OUT}:
+                raise ValueError("out holds some of count_a, count_b, ks, key, below_a, below_b, w1, shift")
+            device = [hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()]
+            if any(device) != all(device):
+                raise ValueError("out holds device tensors or host arrays, not both")
+            args = []
+            for k, width, _ in self._COMPARE_OUT:
+                t = out.get(k)
+                if t is not None:
+                    if hasattr(t, "data_ptr"):
+                        ok = t.element_size() == width and int(t.numel()) == nmetrics and t.is_contiguous()
+                    else:
+                        ok = isinstance(t, np.ndarray) and t.itemsize == width and t.size == nmetrics and t.flags.c_contiguous
+                    if not ok:
+                        raise ValueError(f"out[{k!r}] holds {nmetrics} contiguous elements of {width} bytes")
+                args.append(_ptr(t))
+            if all(device):
+                N.check(L.lh_compare_device(base._h, self._h, first, nmetrics, 0, *args), "lh_compare_device")
+                return dict(out)
+            N.check(L.lh_compare(base._h, self._h, first, nmetrics, 0, *args), "lh_compare")
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()).reshape(nmetrics)
+                   for k, v in out.items() if v is not None}
+        else:
+            import torch
+            res = {}
+            for k, width, dt in self._COMPARE_OUT:     # (an element more than an empty call needs: the arrays have addresses)
+                res[k] = torch.zeros((max(nmetrics, 1) * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
+            N.check(L.lh_compare(base._h, self._h, first, nmetrics, 0, *[res[k].ctypes.data for k, _, _ in self._COMPARE_OUT]),
+                    "lh_compare")
+            res = {k: v[:nmetrics] for k, v in res.items()}
+        if "key" in res:
+            if getattr(self.engine, "_decompress_table", None) is None:
+                self.engine._decompress_table = self.engine.codec_tables()[1]
+            value = self.engine._decompress_table[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
+            res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
+        return res
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
