@@ -9,15 +9,21 @@
 // A reader is read-only: no store goes to a cell, a span or the engine.  (lh_import.hip writes, and says how.)
 //
 // What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
-// way a host form's results travel back, and the measurement switch's exchange.
+// way a host form's results travel back, the event that guards a block across streams, and the measurement switch's
+// exchange.  For the readers, which all walk rows [first, first + nmetrics): their source record and its two-step opener
+// (Source, source_cells, source_open), the launch shape (row_shape), the dispatch on the cells' width (with_cells) and the
+// value table's set-up (ensure_table).  A reader itself has its context, its argument checks, its kernels and its entry
+// points.
 #pragma once
 
 #include "../../include/loghisto_gpu.h"
+#include "lh_wave.h" // the launch geometry (row_shape)
 
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 namespace lh {
 namespace beside {
@@ -157,6 +163,111 @@ template <size_t N, class Enqueue> int host_results(ResultBlocks &rb, hipStream_
         for (size_t k = 0; k < N; k++)
             if (out[k].host) std::memcpy(out[k].host, rb.h_res + at[k], out[k].bytes);
     }
+    return LH_OK;
+}
+
+// A block that outlives a device-form call, while snapshots of different engines run on different streams: it is guarded
+// by an event, not by stream order.  `pending` is cleared only after a wait that covers the event itself (host_wait, or the
+// caller's synchronize of the very stream it was last recorded on: covered()) -- another stream's sync says nothing.
+struct __attribute__((visibility("hidden"))) EventGuard { // (hidden: the library exports nothing of this header)
+    hipEvent_t ev = nullptr; // behind the last work that uses the block, on whichever stream that was
+    bool pending = false;
+    int create()
+    {
+        if (!ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return LH_OK;
+    }
+    int host_wait() // before the host frees or rewrites the block
+    {
+        if (pending) {
+            LH_BESIDE_CHK(hipEventSynchronize(ev));
+            pending = false;
+        }
+        return LH_OK;
+    }
+    int stream_wait(hipStream_t st) // before work on `st` uses the block: on the device, not on the host
+    {
+        if (pending) LH_BESIDE_CHK(hipStreamWaitEvent(st, ev, 0));
+        return LH_OK;
+    }
+    int record(hipStream_t st)
+    {
+        LH_BESIDE_CHK(hipEventRecord(ev, st));
+        pending = true;
+        return LH_OK;
+    }
+    void covered() { pending = false; }
+};
+
+// ---- the readers' front end --------------------------------------------------------------------------
+// What a reader's call works on: the opened snapshot, the unit's context on its device, and the cells as they are.
+template <class Ctx> struct Source : Opened {
+    Ctx *cx = nullptr;
+    const void *cells = nullptr;
+    uint32_t nrows = 0, cell_bytes = 0;
+};
+// Step one, before any device call: the cells, and LH_ERANGE for rows the snapshot does not have.
+template <class Ctx> int source_cells(lh_snapshot *s, uint32_t first, size_t nmetrics, Source<Ctx> &q)
+{
+    void *cells = nullptr;
+    const int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
+    if (rc) return rc;
+    q.cells = cells;
+    return nmetrics > q.nrows || first > q.nrows - nmetrics ? LH_ERANGE : LH_OK;
+}
+// whole 4-bin groups are readable up to bin 65 535, and the cells have one of the two widths the kernels are built for
+template <class Ctx> bool usable(const Source<Ctx> &q)
+{
+    return q.stride >= (size_t)LH_NKEYS + 4 && q.cells && (q.cell_bytes == 4 || q.cell_bytes == 8);
+}
+// Step two: spans, device, context, stream and stride; LH_ESTATE for a snapshot the kernels cannot walk.  (A reader of
+// two snapshots takes the two parts apart: lh_compare.hip.)
+template <class Ctx> int source_open(lh_snapshot *s, Source<Ctx> &q)
+{
+    const int rc = open_snapshot(s, q, q.cx);
+    if (rc) return rc;
+    return usable(q) ? LH_OK : LH_ESTATE;
+}
+inline const uint32_t *ranges_from(const Opened &o, uint32_t first) { return o.ranges + 2 * (size_t)first; }
+
+// f(c): c the cells of row `first`, typed by their width (const uint32_t * or const unsigned long long *).  A generic
+// lambda names the type as cell_of<decltype(c)>.
+template <class P> using cell_of = std::remove_cv_t<std::remove_pointer_t<P>>;
+template <class Ctx, class F> void with_cells(const Source<Ctx> &q, uint32_t first, F f)
+{
+    if (q.cell_bytes == 4) f(static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride);
+    else f(static_cast<const lh::u64 *>(q.cells) + (size_t)first * q.stride);
+}
+
+// The launch shape of a call of M rows: a wave per row from `wave_from` rows on (the unit's switch), a workgroup per row
+// below.
+struct RowShape {
+    bool wave;
+    dim3 grid, block;
+};
+inline RowShape row_shape(uint32_t M, uint32_t wave_from)
+{
+    const bool wave = M >= wave_from;
+    return {wave, dim3(wave ? (M + lh::ROW_WAVES - 1) / lh::ROW_WAVES : M), dim3(wave ? lh::ROW_BLOCK : lh::WG)};
+}
+
+// (the context's mutex held)  The unit's value table on this device (`slot`, null until the first call that needs it),
+// generated by `kernel` (lh::k_value_table of the unit) on `st`.  The table is complete before the call that generates it
+// goes on (one stream wait, once per device): later calls on other streams need no ordering against it.
+static inline int ensure_table(double *&slot, hipStream_t st, void (*kernel)(double *))
+{
+    if (slot) return LH_OK;
+    double *t = nullptr;
+    LH_BESIDE_CHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
+    hipLaunchKernelGGL(kernel, dim3(LH_NKEYS / 256), dim3(256), 0, st, t);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(t);
+        return LH_EDEVICE;
+    }
+    slot = t;
     return LH_OK;
 }
 

@@ -42,25 +42,14 @@
 
 namespace {
 
+using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
-using lh::load4_cells;
-using lh::readlane_f64;
-using lh::readlane_u64;
-using lh::wave_scan_incl_f64;
-using lh::wave_scan_incl_u64;
 
-typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
-constexpr int CP_BLOCK = 256, CP_WAVES = CP_BLOCK / 64; // k_compare_wave: four rows per workgroup
-constexpr int CP_WG = 1024, CP_WG_WAVES = CP_WG / 64;   // k_compare_block
-constexpr uint32_t CP_STEP = 256;                       // bins a wave takes per step
-constexpr uint32_t CP_CHUNKS = LH_NKEYS / CP_STEP;      // chunks of the widest span (a span starts at a multiple of 4)
 // Rows of a call from which a row gets a wave, not a workgroup: lh_spread's default, whose walks these are, until
 // tools/compare_bench.py has been run (profiles/compare.txt).
 constexpr uint32_t CP_WAVE_FROM_DEFAULT = 1024;
-constexpr uint32_t NO_BIN = 0xffffffffu;
-static_assert(CP_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
 
 struct CompareOut {
     u64 *count_a, *count_b;
@@ -69,24 +58,6 @@ struct CompareOut {
     u64 *below_a, *below_b;
     double *w1, *shift;
 };
-
-// One row's own span: [lo4, hi], lo4 = lo aligned down to a multiple of 4; lo4 > hi for a row that was never marked.
-struct Span { uint32_t lo4, hi; };
-__device__ __forceinline__ Span own_span(const uint32_t *__restrict__ ranges, uint32_t m)
-{
-    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
-    Span s;
-    s.lo4 = lo <= hi ? lo & ~3u : NO_BIN;
-    s.hi = lo <= hi ? hi : 0u;
-    return s;
-}
-// bins b0 .. b0 + 3 of a row, zeros outside its own span (b0 a multiple of 4; hi <= 65 535: the group ends inside the row)
-template <typename CELL>
-__device__ __forceinline__ void load4_in(const CELL *__restrict__ row, uint32_t b0, Span s, u64 (&c)[4])
-{
-    load4_cells(row, b0 >= s.lo4 ? b0 : NO_BIN, s.hi, c); // (NO_BIN > hi: nothing is asked for)
-}
-__device__ __forceinline__ u64 sum4(const u64 (&c)[4]) { return (c[0] + c[1]) + (c[2] + c[3]); }
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) // the maximum in lane 63 (lanes without a source: 0)
 {
@@ -192,15 +163,15 @@ __device__ __forceinline__ void store_row(const CompareOut &o, uint32_t m, u64 n
 }
 
 template <typename CA, typename CB>
-__global__ __launch_bounds__(CP_BLOCK) void k_compare_wave(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
+__global__ __launch_bounds__(ROW_BLOCK) void k_compare_wave(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
                                                            size_t stride_a, const CB *__restrict__ cells_b,
                                                            const uint32_t *__restrict__ ranges_b, size_t stride_b,
                                                            uint32_t nmetrics, const CompareOut o)
 {
-    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * CP_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const Span sa = own_span(ranges_a, m), sb = own_span(ranges_b, m);
-    const uint32_t base0 = min(sa.lo4, sb.lo4), hi = max(sa.hi, sb.hi); // the union; base0 == NO_BIN: neither row was marked
+    const Span sa = or_empty(own_span(ranges_a, m)), sb = or_empty(own_span(ranges_b, m));
+    const uint32_t base0 = min(sa.lo, sb.lo), hi = max(sa.hi, sb.hi); // the union; base0 == NO_BIN: neither row was marked
     u64 na = 0, nb = 0, ba = 0, bb = 0;
     uint32_t bin = NO_BIN;
     double w1 = 0.0, shift = 0.0;
@@ -213,9 +184,9 @@ __global__ __launch_bounds__(CP_BLOCK) void k_compare_wave(const CA *__restrict_
             u64 ta = 0, tb = 0;
             load4_in(ra, base0 + 4 * lane, sa, a);
             load4_in(rb, base0 + 4 * lane, sb, b);
-            for (uint32_t base = base0; base <= hi; base += CP_STEP) {
-                load4_in(ra, base + CP_STEP + 4 * lane, sa, xa); // the next step's: in flight under this step's work
-                load4_in(rb, base + CP_STEP + 4 * lane, sb, xb);
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4_in(ra, base + STEP + 4 * lane, sa, xa); // the next step's: in flight under this step's work
+                load4_in(rb, base + STEP + 4 * lane, sb, xb);
                 ta += sum4(a);
                 tb += sum4(b);
 #pragma unroll
@@ -232,9 +203,9 @@ __global__ __launch_bounds__(CP_BLOCK) void k_compare_wave(const CA *__restrict_
             u64 ca = 0, cb = 0; // what lies below the step
             load4_in(ra, base0 + 4 * lane, sa, a);
             load4_in(rb, base0 + 4 * lane, sb, b);
-            for (uint32_t base = base0; base <= hi; base += CP_STEP) {
-                load4_in(ra, base + CP_STEP + 4 * lane, sa, xa);
-                load4_in(rb, base + CP_STEP + 4 * lane, sb, xb);
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4_in(ra, base + STEP + 4 * lane, sa, xa);
+                load4_in(rb, base + STEP + 4 * lane, sb, xb);
                 const u64 ta = sum4(a), tb = sum4(b);
                 const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
                 take4(r, sc, base + 4 * lane, ca + (ia - ta), cb + (ib - tb), a, b);
@@ -253,37 +224,37 @@ __global__ __launch_bounds__(CP_BLOCK) void k_compare_wave(const CA *__restrict_
 }
 
 template <typename CA, typename CB>
-__global__ __launch_bounds__(CP_WG) void k_compare_block(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
+__global__ __launch_bounds__(WG) void k_compare_block(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,
                                                          size_t stride_a, const CB *__restrict__ cells_b,
                                                          const uint32_t *__restrict__ ranges_b, size_t stride_b,
                                                          uint32_t nmetrics, const CompareOut o)
 {
-    __shared__ u64 s_a[CP_CHUNKS], s_b[CP_CHUNKS]; // the chunks' totals, then their exclusive prefixes
+    __shared__ u64 s_a[CHUNKS], s_b[CHUNKS]; // the chunks' totals, then their exclusive prefixes
     __shared__ u64 s_na, s_nb;
-    __shared__ u64 s_xh[CP_WG_WAVES], s_xl[CP_WG_WAVES], s_ba[CP_WG_WAVES], s_bb[CP_WG_WAVES]; // the waves' bests
-    __shared__ uint32_t s_bin[CP_WG_WAVES];
-    __shared__ double s_w[CP_WG_WAVES], s_s[CP_WG_WAVES];
+    __shared__ u64 s_xh[WG_WAVES], s_xl[WG_WAVES], s_ba[WG_WAVES], s_bb[WG_WAVES]; // the waves' bests
+    __shared__ uint32_t s_bin[WG_WAVES];
+    __shared__ double s_w[WG_WAVES], s_s[WG_WAVES];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
     if (m >= nmetrics) return;
-    const Span sa = own_span(ranges_a, m), sb = own_span(ranges_b, m);
-    const uint32_t base0 = min(sa.lo4, sb.lo4), hi = max(sa.hi, sb.hi);
-    const uint32_t nchunks = base0 != NO_BIN ? (hi - base0) / CP_STEP + 1 : 0; // <= CP_CHUNKS
+    const Span sa = or_empty(own_span(ranges_a, m)), sb = or_empty(own_span(ranges_b, m));
+    const uint32_t base0 = min(sa.lo, sb.lo), hi = max(sa.hi, sb.hi);
+    const uint32_t nchunks = base0 != NO_BIN ? (hi - base0) / STEP + 1 : 0; // <= CHUNKS
     const CA *__restrict__ ra = cells_a + (size_t)m * stride_a;
     const CB *__restrict__ rb = cells_b + (size_t)m * stride_b;
     constexpr uint32_t U = 2;
     // ---- walk 1: every chunk's totals
-    for (uint32_t c0 = wave; c0 < nchunks; c0 += CP_WG_WAVES * U) { // wave-uniform
+    for (uint32_t c0 = wave; c0 < nchunks; c0 += WG_WAVES * U) { // wave-uniform
         u64 a[U][4], b[U][4];
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) { // (a chunk beyond the span starts beyond hi: nothing is read)
-            const uint32_t b0 = base0 + (c0 + u * CP_WG_WAVES) * CP_STEP + 4 * lane;
+            const uint32_t b0 = base0 + (c0 + u * WG_WAVES) * STEP + 4 * lane;
             load4_in(ra, b0, sa, a[u]);
             load4_in(rb, b0, sb, b[u]);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
             const u64 ia = wave_scan_incl_u64(sum4(a[u])), ib = wave_scan_incl_u64(sum4(b[u]));
-            const uint32_t ch = c0 + u * CP_WG_WAVES;
+            const uint32_t ch = c0 + u * WG_WAVES;
             if (lane == 63 && ch < nchunks) {
                 s_a[ch] = ia;
                 s_b[ch] = ib;
@@ -325,21 +296,21 @@ __global__ __launch_bounds__(CP_WG) void k_compare_block(const CA *__restrict__ 
         const Scale sc = make_scale(na, nb);
         Best r;
         best_init(r);
-        for (uint32_t c0 = wave; c0 < nchunks; c0 += CP_WG_WAVES * U) {
+        for (uint32_t c0 = wave; c0 < nchunks; c0 += WG_WAVES * U) {
             u64 a[U][4], b[U][4];
 #pragma unroll
             for (uint32_t u = 0; u < U; u++) {
-                const uint32_t b0 = base0 + (c0 + u * CP_WG_WAVES) * CP_STEP + 4 * lane;
+                const uint32_t b0 = base0 + (c0 + u * WG_WAVES) * STEP + 4 * lane;
                 load4_in(ra, b0, sa, a[u]);
                 load4_in(rb, b0, sb, b[u]);
             }
 #pragma unroll
             for (uint32_t u = 0; u < U; u++) {
-                const uint32_t ch = c0 + u * CP_WG_WAVES;
+                const uint32_t ch = c0 + u * WG_WAVES;
                 if (ch < nchunks) { // wave-uniform
                     const u64 ta = sum4(a[u]), tb = sum4(b[u]);
                     const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
-                    take4(r, sc, base0 + ch * CP_STEP + 4 * lane, s_a[ch] + (ia - ta), s_b[ch] + (ib - tb), a[u], b[u]);
+                    take4(r, sc, base0 + ch * STEP + 4 * lane, s_a[ch] + (ia - ta), s_b[ch] + (ib - tb), a[u], b[u]);
                 }
             }
         }
@@ -364,7 +335,7 @@ __global__ __launch_bounds__(CP_WG) void k_compare_block(const CA *__restrict__ 
         uint32_t bin = NO_BIN;
         u64 ba = 0, bb = 0;
         double w1 = 0.0, shift = 0.0;
-        for (int w = 0; w < CP_WG_WAVES; w++) { // (a wave without a chunk left X = 0, NO_BIN and +0)
+        for (int w = 0; w < WG_WAVES; w++) { // (a wave without a chunk left X = 0, NO_BIN and +0)
             const u128 xw = ((u128)s_xh[w] << 64) | s_xl[w];
             if (xw > x || (xw == x && s_bin[w] < bin)) {
                 x = xw;
@@ -401,33 +372,7 @@ int check_args(lh_snapshot *base, lh_snapshot *cur, size_t nmetrics, uint32_t fl
     return LH_OK;
 }
 
-struct Source : Opened {
-    CompareCtx *cx = nullptr;
-    const void *cells = nullptr;
-    uint32_t nrows = 0, cell_bytes = 0;
-};
-
-int cells_of(lh_snapshot *s, Source &q, uint32_t first, size_t nmetrics)
-{
-    void *cells = nullptr;
-    const int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
-    if (rc) return rc;
-    q.cells = cells;
-    return nmetrics > q.nrows || first > q.nrows - nmetrics ? LH_ERANGE : LH_OK;
-}
-
-template <typename CA, typename CB>
-void launch(bool wave, const Source &a, const Source &b, uint32_t first, uint32_t M, const CompareOut &o)
-{
-    const CA *ca = static_cast<const CA *>(a.cells) + (size_t)first * a.stride;
-    const CB *cb = static_cast<const CB *>(b.cells) + (size_t)first * b.stride;
-    const uint32_t *ra = a.ranges + 2 * (size_t)first, *rb = b.ranges + 2 * (size_t)first;
-    if (wave)
-        hipLaunchKernelGGL((k_compare_wave<CA, CB>), dim3((M + CP_WAVES - 1) / CP_WAVES), dim3(CP_BLOCK), 0, b.stream, ca, ra,
-                           a.stride, cb, rb, b.stride, M, o);
-    else
-        hipLaunchKernelGGL((k_compare_block<CA, CB>), dim3(M), dim3(CP_WG), 0, b.stream, ca, ra, a.stride, cb, rb, b.stride, M, o);
-}
+typedef lh::beside::Source<CompareCtx> Source;
 
 // (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on cur's stream, behind what base's stream holds
 int enqueue(const Source &a, const Source &b, uint32_t first, size_t nmetrics, const CompareOut &o)
@@ -439,19 +384,21 @@ int enqueue(const Source &a, const Source &b, uint32_t first, size_t nmetrics, c
         LH_BESIDE_CHK(hipStreamWaitEvent(b.stream, cx->order, 0));
     }
     const uint32_t M = (uint32_t)nmetrics;
-    const bool wave = M >= g_wave_from.load(std::memory_order_relaxed);
-    if (a.cell_bytes == 4) {
-        if (b.cell_bytes == 4) launch<uint32_t, uint32_t>(wave, a, b, first, M, o);
-        else launch<uint32_t, u64>(wave, a, b, first, M, o);
-    } else {
-        if (b.cell_bytes == 4) launch<u64, uint32_t>(wave, a, b, first, M, o);
-        else launch<u64, u64>(wave, a, b, first, M, o);
-    }
+    const uint32_t *ra = ranges_from(a, first), *rb = ranges_from(b, first);
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    with_cells(a, first, [&](auto *ca) {
+        with_cells(b, first, [&](auto *cb) {
+            typedef cell_of<decltype(ca)> CA;
+            typedef cell_of<decltype(cb)> CB;
+            if (sh.wave)
+                hipLaunchKernelGGL((k_compare_wave<CA, CB>), sh.grid, sh.block, 0, b.stream, ca, ra, a.stride, cb, rb, b.stride, M, o);
+            else
+                hipLaunchKernelGGL((k_compare_block<CA, CB>), sh.grid, sh.block, 0, b.stream, ca, ra, a.stride, cb, rb, b.stride, M, o);
+        });
+    });
     LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
 }
-
-bool usable(const Source &q) { return q.stride >= (size_t)LH_NKEYS + 4 && q.cells && (q.cell_bytes == 4 || q.cell_bytes == 8); }
 
 int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags, const CompareOut &o,
             bool device_form)
@@ -459,17 +406,17 @@ int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics
     int rc = check_args(base, cur, nmetrics, flags, o);
     if (rc) return rc;
     Source a, b;
-    rc = cells_of(base, a, first, nmetrics);
+    rc = source_cells(base, first, nmetrics, a);
     if (rc) return rc;
-    rc = cells_of(cur, b, first, nmetrics);
+    rc = source_cells(cur, first, nmetrics, b);
     if (rc) return rc;
-    if (nmetrics == 0) return LH_OK;
+    if (nmetrics == 0) return LH_OK; // before any device call
     rc = open_snapshot(base, a, a.cx);
     if (rc) return rc;
     rc = open_snapshot(cur, b, b.cx);
     if (rc) return rc;
     if (a.device != b.device) return LH_EINVAL;
-    if (!usable(a) || !usable(b)) return LH_ESTATE;
+    if (!usable(a) || !usable(b)) return LH_ESTATE; // (source_open's two parts, around the check that needs both opened)
     CompareCtx *cx = b.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(a, b, first, nmetrics, o);

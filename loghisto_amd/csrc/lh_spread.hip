@@ -42,28 +42,14 @@
 
 namespace {
 
+using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
-using lh::f64x2_a8;
-using lh::load4_cells;
-using lh::PCT_NONE;
-using lh::pct_threshold;
-using lh::readlane_f64;
-using lh::readlane_u64;
-using lh::wave_scan_incl_f64;
-using lh::wave_scan_incl_u64;
 
-typedef unsigned long long u64;
-
-constexpr int SP_BLOCK = 256, SP_WAVES = SP_BLOCK / 64; // k_spread_wave: four rows per workgroup
-constexpr int SP_WG = 1024, SP_WG_WAVES = SP_WG / 64;   // k_spread_block
-constexpr uint32_t SP_STEP = 256;                       // bins a wave takes per step
-constexpr uint32_t SP_CHUNKS = LH_NKEYS / SP_STEP;      // chunks of the widest span (a span starts at a multiple of 4)
 // Rows of a call from which a row gets a wave, not a workgroup.  profiles/spread.txt has both shapes either side: over
 // windows of a few hundred bins the workgroup is ahead at 256 rows (13.4 against 16.6 us at nine percentiles) and the wave
 // from 1 024 on (16.4 against 23.5); over one full-span row the workgroup is four to five times faster -- so few rows,
 // which may be wide, get workgroups.
 constexpr uint32_t SP_WAVE_FROM_DEFAULT = 1024;
-static_assert(SP_CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
 static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
 
 struct SpreadP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
@@ -77,29 +63,7 @@ struct SpreadOut {
     double *sum_le;
 };
 
-// bins b0 .. b0 + 3 of a row and their table entries; a lane whose group starts beyond hi asks for nothing.  b0 is a
-// multiple of 4 and hi <= 65 535, so the group ends inside the row (and inside the table's LH_NKEYS entries).
-template <typename CELL>
-__device__ __forceinline__ void load4(const CELL *__restrict__ row, const double *__restrict__ D, uint32_t b0, uint32_t hi,
-                                      u64 (&c)[4], double (&d)[4])
-{
-    d[0] = d[1] = d[2] = d[3] = 0.0;
-    load4_cells(row, b0, hi, c);
-    if (b0 <= hi) {
-        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
-        const f64x2_a8 d01 = dp[0], d23 = dp[1];
-        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
-    }
-}
-
-// value * float64(count) of a lane's four bins (metrics.go:344) and their sum, always associated the same way
-__device__ __forceinline__ double terms4(const u64 (&c)[4], const double (&d)[4], double (&t)[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) t[k] = d[k] * (double)c[k];
-    return (t[0] + t[1]) + (t[2] + t[3]);
-}
-// float64(count) * (value - mean)^2 of the same bins (an empty cell adds +0)
+// float64(count) * (value - mean)^2 of a lane's four bins (an empty cell adds +0)
 __device__ __forceinline__ double central4(const u64 (&c)[4], const double (&d)[4], double mean)
 {
     double q[4];
@@ -132,26 +96,21 @@ __device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], const doub
     return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
 }
 
-__global__ __launch_bounds__(256) void k_spread_table(double *__restrict__ D)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < LH_NKEYS) D[b] = lh::d_decompress_bin(b);
-}
-
 template <typename CELL>
-__global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+__global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                           uint32_t nmetrics, size_t stride, const double *__restrict__ D,
                                                           const SpreadP pa, uint32_t np, const SpreadOut o)
 {
-    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * SP_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    const Span sp = own_span(ranges, m);
+    const uint32_t hi = sp.hi;
     u64 total = 0, r_cle = 0;
     double sum = 0.0, m2 = 0.0, r_sle = 0.0;
     uint32_t found = 0xffffffffu; // lane i < np: the bin of percentile i
-    if (lo <= hi) {               // wave-uniform; an empty row costs two loads and its stores
+    if (sp.any()) {               // wave-uniform; an empty row costs two loads and its stores
         const CELL *__restrict__ row = cells + (size_t)m * stride;
-        const uint32_t base0 = lo & ~3u; // (cells below lo are zero) whole groups: every load is 16-byte aligned
+        const uint32_t base0 = sp.base0();
         u64 c[4], nc[4];
         double d[4], nd[4], t[4];
         // ---- walk 1: count and sum
@@ -159,8 +118,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict
             u64 cnt = 0;
             double ps = 0.0;
             load4(row, D, base0 + 4 * lane, hi, c, d);
-            for (uint32_t base = base0; base <= hi; base += SP_STEP) {
-                load4(row, D, base + SP_STEP + 4 * lane, hi, nc, nd); // the next step's: in flight under this step's work
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4(row, D, base + STEP + 4 * lane, hi, nc, nd); // the next step's: in flight under this step's work
                 cnt += (c[0] + c[1]) + (c[2] + c[3]);
                 ps += terms4(c, d, t);
 #pragma unroll
@@ -178,8 +137,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict
             u64 carry = 0;
             double run = 0.0, q = 0.0; // the lane's terms of the steps so far; its share of m2
             load4(row, D, base0 + 4 * lane, hi, c, d);
-            for (uint32_t base = base0; base <= hi; base += SP_STEP) {
-                load4(row, D, base + SP_STEP + 4 * lane, hi, nc, nd);
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4(row, D, base + STEP + 4 * lane, hi, nc, nd);
                 q += central4(c, d, mean);
                 const double ts = terms4(c, d, t);
                 if (todo) { // wave-uniform
@@ -237,33 +196,34 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_wave(const CELL *__restrict
 }
 
 template <typename CELL>
-__global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+__global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                         uint32_t nmetrics, size_t stride, const double *__restrict__ D,
                                                         const SpreadP pa, uint32_t np, const SpreadOut o)
 {
-    __shared__ u64 s_cnt[SP_CHUNKS];    // the chunks' counts, then their exclusive prefix
-    __shared__ double s_sum[SP_CHUNKS]; // the chunks' sums, then their exclusive prefix (ascending order)
-    __shared__ double s_m2[SP_WG_WAVES];
+    __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
+    __shared__ double s_sum[CHUNKS]; // the chunks' sums, then their exclusive prefix (ascending order)
+    __shared__ double s_m2[WG_WAVES];
     __shared__ u64 s_total;
     __shared__ double s_tsum;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
     if (m >= nmetrics) return;
-    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    const Span sp = own_span(ranges, m);
+    const uint32_t hi = sp.hi;
     const CELL *__restrict__ row = cells + (size_t)m * stride;
-    const uint32_t base0 = lo & ~3u, nchunks = lo <= hi ? (hi - base0) / SP_STEP + 1 : 0; // <= SP_CHUNKS
+    const uint32_t base0 = sp.base0(), nchunks = sp.any() ? (hi - base0) / STEP + 1 : 0; // <= CHUNKS
     constexpr uint32_t U = 2;
     // ---- walk 1: every chunk's count and sum
-    for (uint32_t c0 = wave; c0 < nchunks; c0 += SP_WG_WAVES * U) { // wave-uniform
+    for (uint32_t c0 = wave; c0 < nchunks; c0 += WG_WAVES * U) { // wave-uniform
         u64 c[U][4];
         double d[U][4], t[4];
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) // (a chunk beyond the span starts beyond hi: nothing is read)
-            load4(row, D, base0 + (c0 + u * SP_WG_WAVES) * SP_STEP + 4 * lane, hi, c[u], d[u]);
+            load4(row, D, base0 + (c0 + u * WG_WAVES) * STEP + 4 * lane, hi, c[u], d[u]);
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
             const u64 inc = wave_scan_incl_u64((c[u][0] + c[u][1]) + (c[u][2] + c[u][3]));
             const double incs = wave_scan_incl_f64(terms4(c[u], d[u], t));
-            const uint32_t ch = c0 + u * SP_WG_WAVES;
+            const uint32_t ch = c0 + u * WG_WAVES;
             if (lane == 63 && ch < nchunks) {
                 s_cnt[ch] = inc;
                 s_sum[ch] = incs;
@@ -319,11 +279,11 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
     // ---- walk 2: the centred moment, by the same chunks
     {
         double q = 0.0;
-        for (uint32_t c0 = wave; c0 < nchunks; c0 += SP_WG_WAVES * U) {
+        for (uint32_t c0 = wave; c0 < nchunks; c0 += WG_WAVES * U) {
             u64 c[U][4];
             double d[U][4];
 #pragma unroll
-            for (uint32_t u = 0; u < U; u++) load4(row, D, base0 + (c0 + u * SP_WG_WAVES) * SP_STEP + 4 * lane, hi, c[u], d[u]);
+            for (uint32_t u = 0; u < U; u++) load4(row, D, base0 + (c0 + u * WG_WAVES) * STEP + 4 * lane, hi, c[u], d[u]);
 #pragma unroll
             for (uint32_t u = 0; u < U; u++) q += central4(c[u], d[u], mean);
         }
@@ -331,7 +291,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
         if (lane == 63) s_m2[wave] = qs;
     }
     // ---- a wave per percentile (wave-uniform throughout): the chunk its threshold falls into, read once more
-    for (uint32_t i = wave; i < np; i += SP_WG_WAVES) {
+    for (uint32_t i = wave; i < np; i += WG_WAVES) {
         const u64 T = pct_threshold(pa.p[i], total);
         uint32_t bin = 0xffffffffu;
         u64 cle = 0;
@@ -345,7 +305,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
             const uint32_t ch = nlow - 1;
             u64 c[4], pre[4];
             double d[4], t[4];
-            load4(row, D, base0 + ch * SP_STEP + 4 * lane, hi, c, d);
+            load4(row, D, base0 + ch * STEP + 4 * lane, hi, c, d);
             const double ts = terms4(c, d, t);
             const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
             u64 sofar = s_cnt[ch] + (wave_scan_incl_u64(tc) - tc);
@@ -354,7 +314,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
                 sofar += c[k];
                 pre[k] = sofar;
             }
-            bin = base0 + ch * SP_STEP + find_in_step(pre, t, wave_scan_incl_f64(ts), s_sum[ch], T, cle, sle);
+            bin = base0 + ch * STEP + find_in_step(pre, t, wave_scan_incl_f64(ts), s_sum[ch], T, cle, sle);
         }
         if (lane == 0) {
             const size_t at = (size_t)m * np + i;
@@ -368,7 +328,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
     __syncthreads();
     if (threadIdx.x == 0) {
         double m2 = 0.0;
-        for (int w = 0; w < SP_WG_WAVES; w++) m2 += s_m2[w]; // (a wave without a chunk left +0)
+        for (int w = 0; w < WG_WAVES; w++) m2 += s_m2[w]; // (a wave without a chunk left +0)
         if (o.count) o.count[m] = total;
         if (o.sum) o.sum[m] = sum;
         if (o.m2) o.m2[m] = m2;
@@ -378,8 +338,7 @@ __global__ __launch_bounds__(SP_WG) void k_spread_block(const CELL *__restrict__
 // ---- host side --------------------------------------------------------------------------------------
 // Per-device state of this unit (device_ctx<SpreadCtx>).  `mu` is held for the length of a call -- the host form's wait
 // for its results included, so host-form calls on one device take turns even when their snapshots belong to different
-// engines.  The table is complete before the call that generates it goes on (one stream wait, once per device): later
-// calls on other streams need no ordering against it.
+// engines.
 struct SpreadCtx {
     std::mutex mu;
     double *d_table = nullptr; // D[LH_NKEYS]
@@ -406,45 +365,25 @@ int check_args(lh_snapshot *s, size_t nmetrics, const double *p, size_t np, Spre
     return LH_OK;
 }
 
-struct Source : Opened {
-    SpreadCtx *cx = nullptr;
-    const void *cells = nullptr;
-    uint32_t nrows = 0, cell_bytes = 0;
-};
+typedef lh::beside::Source<SpreadCtx> Source;
 
 // (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on the snapshot's stream
 int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *p, size_t np, const SpreadOut &o)
 {
     SpreadCtx *cx = q.cx;
-    if (!cx->d_table) {
-        double *t = nullptr;
-        LH_BESIDE_CHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
-        hipLaunchKernelGGL(k_spread_table, dim3(LH_NKEYS / 256), dim3(256), 0, q.stream, t);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(q.stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(t);
-            return LH_EDEVICE;
-        }
-        cx->d_table = t;
-    }
+    const int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<SpreadCtx>);
+    if (rc) return rc;
     SpreadP pa;
     for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
-    const uint32_t *ranges = q.ranges + 2 * (size_t)first;
+    const uint32_t *ranges = ranges_from(q, first);
     const double *D = cx->d_table;
-    const bool wave = M >= g_wave_from.load(std::memory_order_relaxed);
-    const dim3 grid(wave ? (M + SP_WAVES - 1) / SP_WAVES : M), block(wave ? SP_BLOCK : SP_WG);
-    if (q.cell_bytes == 4) {
-        const uint32_t *c = static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_spread_wave<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_spread_block<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-    } else {
-        const u64 *c = static_cast<const u64 *>(q.cells) + (size_t)first * q.stride;
-        if (wave) hipLaunchKernelGGL(k_spread_wave<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_spread_block<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-    }
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    with_cells(q, first, [&](auto *c) {
+        typedef cell_of<decltype(c)> CELL;
+        if (sh.wave) hipLaunchKernelGGL(k_spread_wave<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
+        else hipLaunchKernelGGL(k_spread_block<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
+    });
     LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
 }
@@ -454,15 +393,11 @@ int spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, siz
     int rc = check_args(s, nmetrics, p, np, o);
     if (rc) return rc;
     Source q;
-    void *cells = nullptr;
-    rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
+    rc = source_cells(s, first, nmetrics, q);
     if (rc) return rc;
-    q.cells = cells;
-    if (nmetrics > q.nrows || first > q.nrows - nmetrics) return LH_ERANGE;
-    if (nmetrics == 0) return LH_OK;
-    rc = open_snapshot(s, q, q.cx);
+    if (nmetrics == 0) return LH_OK; // before any device call
+    rc = source_open(s, q);
     if (rc) return rc;
-    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
     SpreadCtx *cx = q.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(q, first, nmetrics, p, np, o);

@@ -46,22 +46,9 @@
 
 namespace {
 
+using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
-using lh::f64x2_a8;
-using lh::le_take;
-using lh::load4_cells;
-using lh::pct_threshold;
-using lh::readlane_f64;
-using lh::readlane_u64;
-using lh::u64x2_a8;
-using lh::wave_scan_incl_f64;
-using lh::wave_scan_incl_u32;
-using lh::wave_scan_incl_u64;
 
-typedef unsigned long long u64;
-
-constexpr int TP_BLOCK = 256, TP_WAVES = TP_BLOCK / 64; // k_top_score: four rows per workgroup
-constexpr uint32_t TP_STEP = 256;                       // bins a wave takes per step
 constexpr int SEL_WG = 1024, SEL_WAVES = SEL_WG / 64;   // k_top_select
 constexpr uint32_t SEL_PER = 4;                         // consecutive records per thread and tile
 constexpr uint32_t SEL_TILE = SEL_WG * SEL_PER;
@@ -78,27 +65,6 @@ struct TopRecords {
     u64 *aux;    // BY_PERCENTILE: the int16 key's 16 bits; BY_COUNT_ABOVE: the count above; else 0
 };
 
-__global__ __launch_bounds__(256) void k_top_table(double *__restrict__ D)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < LH_NKEYS) D[b] = lh::d_decompress_bin(b);
-}
-
-// bins b0 .. b0 + 3 of a row and their table entries; a lane whose group starts beyond hi asks for nothing.  b0 is a
-// multiple of 4 and hi <= 65 535, so the group ends inside the row (and inside the table's LH_NKEYS entries).
-template <typename CELL>
-__device__ __forceinline__ void load4(const CELL *__restrict__ row, const double *__restrict__ D, uint32_t b0, uint32_t hi,
-                                      u64 (&c)[4], double (&d)[4])
-{
-    d[0] = d[1] = d[2] = d[3] = 0.0;
-    load4_cells(row, b0, hi, c);
-    if (b0 <= hi) {
-        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
-        const f64x2_a8 d01 = dp[0], d23 = dp[1];
-        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
-    }
-}
-
 // a float64 as an unsigned integer of the same order (-0.0 == +0.0; the host sees to it that no NaN is ranked)
 __device__ __forceinline__ u64 order_key_f64(double x)
 {
@@ -108,19 +74,20 @@ __device__ __forceinline__ u64 order_key_f64(double x)
 }
 
 template <typename CELL>
-__global__ __launch_bounds__(TP_BLOCK) void k_top_score(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+__global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                         uint32_t nmetrics, size_t stride, const double *__restrict__ D,
                                                         uint32_t by, double arg, u64 flip, const TopRecords r)
 {
-    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * TP_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const uint32_t lo = ranges[2 * (size_t)m], hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    const Span sp = own_span(ranges, m);
+    const uint32_t hi = sp.hi;
     u64 total = 0, above = 0;
     double sum = 0.0;
     uint32_t found = 0; // BY_PERCENTILE: the selected bin
-    if (lo <= hi) {     // wave-uniform; an empty row costs two loads and its stores
+    if (sp.any()) {     // wave-uniform; an empty row costs two loads and its stores
         const CELL *__restrict__ row = cells + (size_t)m * stride;
-        const uint32_t base0 = lo & ~3u; // (cells below lo are zero) whole groups: every load is 16-byte aligned
+        const uint32_t base0 = sp.base0();
         u64 c[4], nc[4];
         double d[4], nd[4];
         // ---- walk 1: count and sum; the cells at or beyond the bound's take
@@ -130,10 +97,10 @@ __global__ __launch_bounds__(TP_BLOCK) void k_top_score(const CELL *__restrict__
             u64 cnt = 0, ab = 0;
             double ps = 0.0;
             load4(row, D, base0 + 4 * lane, hi, c, d);
-            for (uint32_t base = base0; base <= hi; base += TP_STEP) {
-                load4(row, D, base + TP_STEP + 4 * lane, hi, nc, nd); // the next step's: in flight under this step's work
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4(row, D, base + STEP + 4 * lane, hi, nc, nd); // the next step's: in flight under this step's work
                 cnt += (c[0] + c[1]) + (c[2] + c[3]);
-                double t[4];
+                double t[4]; // (terms4, lh_wave.h, written out: through the helper this kernel's code comes out reordered)
 #pragma unroll
                 for (int k = 0; k < 4; k++) t[k] = d[k] * (double)c[k];
                 ps += (t[0] + t[1]) + (t[2] + t[3]);
@@ -156,8 +123,8 @@ __global__ __launch_bounds__(TP_BLOCK) void k_top_score(const CELL *__restrict__
             u64 carry = 0;
             found = hi;
             load4_cells(row, base0 + 4 * lane, hi, c);
-            for (uint32_t base = base0; base <= hi; base += TP_STEP) {
-                load4_cells(row, base + TP_STEP + 4 * lane, hi, nc);
+            for (uint32_t base = base0; base <= hi; base += STEP) {
+                load4_cells(row, base + STEP + 4 * lane, hi, nc);
                 const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
                 const u64 inc = wave_scan_incl_u64(tc);
                 const u64 end = carry + readlane_u64(inc, 63);
@@ -385,15 +352,14 @@ __global__ __launch_bounds__(SEL_WG) void k_top_select(const TopRecords r, uint3
 // Per-device state of this unit (device_ctx<TopCtx>).  `mu` is held for the length of a call -- the host form's wait for
 // its results included, so host-form calls on one device take turns even when their snapshots belong to different
 // engines.  Snapshots of different engines run on different streams, and the records block outlives a device-form call:
-// it is guarded by an event, not by stream order.  The table is complete before the call that generates it goes on.
+// it is guarded by an event, not by stream order.
 struct TopCtx {
     std::mutex mu;
     double *d_table = nullptr;        // D[LH_NKEYS]
     unsigned char *d_records = nullptr; // four arrays of padded nmetrics 8-byte fields
     size_t rec_cap = 0;               // (in records)
     ResultBlocks res;                 // host form: k entries and n_out
-    hipEvent_t ev = nullptr;          // behind the last select pass, on whichever stream that was
-    bool ev_pending = false;
+    EventGuard guard;                 // behind the last select pass
 };
 
 // every check that needs neither the snapshot nor a device
@@ -408,80 +374,51 @@ int check_args(lh_snapshot *s, size_t nmetrics, uint32_t by, double arg, size_t 
     return LH_OK;
 }
 
-struct Source : Opened {
-    TopCtx *cx = nullptr;
-    const void *cells = nullptr;
-    uint32_t nrows = 0, cell_bytes = 0;
-};
+typedef Source<TopCtx> TopSource;
 
 // (cx->mu held) enqueue both passes over rows [first, first + nmetrics) on the snapshot's stream.  ev[0 .. 2] (may be
 // null): events to record before the score pass, between the passes and behind the select pass (lh_tool_top_passes_ms).
-int enqueue(const Source &q, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, lh_top_entry *d_out,
+int enqueue(const TopSource &q, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, lh_top_entry *d_out,
             uint32_t *d_n_out, hipEvent_t *ev = nullptr)
 {
     TopCtx *cx = q.cx;
-    if (!cx->d_table) {
-        double *t = nullptr;
-        LH_BESIDE_CHK(hipMalloc((void **)&t, (size_t)LH_NKEYS * sizeof(double)));
-        hipLaunchKernelGGL(k_top_table, dim3(LH_NKEYS / 256), dim3(256), 0, q.stream, t);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(q.stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(t);
-            return LH_EDEVICE;
-        }
-        cx->d_table = t;
-    }
-    if (!cx->ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->ev, hipEventDisableTiming));
-    const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
-    if (cx->rec_cap < npad && cx->ev_pending) { // the block is about to be freed: an earlier call's passes may still use it
-        LH_BESIDE_CHK(hipEventSynchronize(cx->ev));
-        cx->ev_pending = false;
-    }
-    int rc = grow_device(cx->d_records, cx->rec_cap, npad, 4096, 4 * sizeof(u64));
+    int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<TopCtx>);
+    if (!rc) rc = cx->guard.create();
     if (rc) return rc;
+    const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
+    if (cx->rec_cap < npad) rc = cx->guard.host_wait(); // the block is about to be freed: an earlier call's passes may still use it
+    if (!rc) rc = grow_device(cx->d_records, cx->rec_cap, npad, 4096, 4 * sizeof(u64));
     // (another stream's call may still read the records: this one's passes wait for it on the device, not on the host)
-    if (cx->ev_pending) LH_BESIDE_CHK(hipStreamWaitEvent(q.stream, cx->ev, 0));
+    if (!rc) rc = cx->guard.stream_wait(q.stream);
+    if (rc) return rc;
     TopRecords r;
     r.key = reinterpret_cast<u64 *>(cx->d_records);
     r.count = r.key + npad;
     r.sum = reinterpret_cast<double *>(r.count + npad);
     r.aux = reinterpret_cast<u64 *>(r.sum + npad);
     const uint32_t M = (uint32_t)nmetrics;
-    const uint32_t *ranges = q.ranges + 2 * (size_t)first;
+    const uint32_t *ranges = ranges_from(q, first);
     const u64 flip = (flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;
-    const dim3 grid((M + TP_WAVES - 1) / TP_WAVES), block(TP_BLOCK);
+    const RowShape sh = row_shape(M, 0); // (one shape: a wave per row whatever M)
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[0], q.stream));
-    if (q.cell_bytes == 4) {
-        const uint32_t *c = static_cast<const uint32_t *>(q.cells) + (size_t)first * q.stride;
-        hipLaunchKernelGGL(k_top_score<uint32_t>, grid, block, 0, q.stream, c, ranges, M, q.stride, cx->d_table, by, arg, flip, r);
-    } else {
-        const u64 *c = static_cast<const u64 *>(q.cells) + (size_t)first * q.stride;
-        hipLaunchKernelGGL(k_top_score<u64>, grid, block, 0, q.stream, c, ranges, M, q.stride, cx->d_table, by, arg, flip, r);
-    }
+    with_cells(q, first, [&](auto *c) {
+        hipLaunchKernelGGL(k_top_score<cell_of<decltype(c)>>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, cx->d_table, by, arg,
+                           flip, r);
+    });
     LH_BESIDE_CHK(hipGetLastError());
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], q.stream));
     hipLaunchKernelGGL(k_top_select, dim3(1), dim3(SEL_WG), 0, q.stream, r, M, first, (uint32_t)k, by, d_out, d_n_out);
     LH_BESIDE_CHK(hipGetLastError());
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], q.stream));
-    LH_BESIDE_CHK(hipEventRecord(cx->ev, q.stream));
-    cx->ev_pending = true;
-    return LH_OK;
+    return cx->guard.record(q.stream);
 }
 
-// the snapshot's cells, spans, device and stream; LH_ERANGE for rows it does not have
-int open_source(lh_snapshot *s, uint32_t first, size_t nmetrics, Source &q)
+// the snapshot's cells, spans, device and stream; LH_ERANGE for rows it does not have.  (The empty call comes behind it:
+// it writes n_out.)
+int open_source(lh_snapshot *s, uint32_t first, size_t nmetrics, TopSource &q)
 {
-    void *cells = nullptr;
-    int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
-    if (rc) return rc;
-    q.cells = cells;
-    if (nmetrics > q.nrows || first > q.nrows - nmetrics) return LH_ERANGE;
-    rc = open_snapshot(s, q, q.cx);
-    if (rc) return rc;
-    if (q.stride < (size_t)LH_NKEYS + 4 || !q.cells || (q.cell_bytes != 4 && q.cell_bytes != 8)) return LH_ESTATE;
-    return LH_OK;
+    const int rc = source_cells(s, first, nmetrics, q);
+    return rc ? rc : source_open(s, q);
 }
 
 // (cx->mu held) the host form's landing blocks: k entries, then n_out
@@ -502,7 +439,7 @@ int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double 
 {
     int rc = check_args(s, nmetrics, by, arg, k, flags, out, n_out, alignof(size_t));
     if (rc) return rc;
-    Source q;
+    TopSource q;
     rc = open_source(s, first, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) {
@@ -525,7 +462,7 @@ int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double 
     const uint32_t *h_n = reinterpret_cast<const uint32_t *>(cx->res.h_res + bytes);
     if (*h_n > k) return LH_ESTATE;
     std::memcpy(out, cx->res.h_res, (size_t)*h_n * sizeof(lh_top_entry));
-    cx->ev_pending = false; // this call recorded `ev` on the stream it has just waited for
+    cx->guard.covered(); // this call recorded the event on the stream it has just waited for
     *n_out = *h_n;
     return LH_OK;
 }
@@ -535,7 +472,7 @@ int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, 
 {
     int rc = check_args(s, nmetrics, by, arg, k, flags, d_out, d_n_out, alignof(uint32_t));
     if (rc) return rc;
-    Source q;
+    TopSource q;
     rc = open_source(s, first, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) {
@@ -553,7 +490,7 @@ int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint3
     int rc = check_args(s, nmetrics, by, arg, k, flags, own, own, 1);
     if (rc) return rc;
     if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
-    Source q;
+    TopSource q;
     rc = open_source(s, first, nmetrics, q);
     if (rc) return rc;
     TopCtx *cx = q.cx;
@@ -569,7 +506,7 @@ int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint3
     if (rc == LH_OK && (hipStreamSynchronize(q.stream) != hipSuccess || hipEventElapsedTime(score_ms, ev[0], ev[1]) != hipSuccess ||
                         hipEventElapsedTime(select_ms, ev[1], ev[2]) != hipSuccess))
         rc = LH_EDEVICE;
-    if (rc == LH_OK) cx->ev_pending = false;
+    if (rc == LH_OK) cx->guard.covered();
     for (int i = 0; i < 3; i++)
         if (ev[i]) (void)hipEventDestroy(ev[i]);
     if (rc == LH_EDEVICE) (void)hipGetLastError();

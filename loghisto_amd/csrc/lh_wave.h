@@ -1,7 +1,11 @@
-// lh_wave.h -- device-only wave primitives of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip; a
-// new reader starts here and in lh_beside.h): DPP scans, cross-lane reads, the packed 16-byte load types, a row's 4-bin
-// group as one load, the percentile threshold and the bound-to-key rule (le_take, which came from lh_count.hip).  The
-// scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the
+// lh_wave.h -- the device side of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip; a
+// new reader starts here and in lh_beside.h):
+//   wave primitives   DPP scans, cross-lane reads, the packed 16-byte load types
+//   the arithmetic    the percentile threshold (pct_threshold) and the bound-to-key rule (le_take)
+//   the row walk      the geometry of the two launch shapes, a row's own span (Span, own_span), a row's 4-bin group as one
+//                     load (load4_cells; load4_in inside a span; load4 with the bins' values), a group's count and weighted
+//                     sum (sum4, terms4) and the generator of the value table (k_value_table)
+// The scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the
 // sources the committed profiles are stamped with (bench.tree_stamp), so it takes this header in the change that next
 // regenerates them.  Until then a fix to pct_threshold goes to both (tests/test_pct_threshold_model.py has the
 // arithmetic, tests/test_gpu_extract_thresholds.py and tests/test_gpu_spread.py hold both to the oracle).
@@ -15,6 +19,17 @@
 #include <stdint.h>
 
 namespace lh {
+
+typedef unsigned long long u64; // (uint64_t is unsigned long: a distinct type)
+
+// The two launch shapes of a reader.  Wave form: a wave per row, ROW_WAVES rows per workgroup.  Workgroup form: WG_WAVES
+// waves per row.  Either way a wave takes STEP bins per step, four consecutive ones per lane.
+constexpr int ROW_BLOCK = 256, ROW_WAVES = ROW_BLOCK / 64;
+constexpr int WG = 1024, WG_WAVES = WG / 64;
+constexpr uint32_t STEP = 256;
+constexpr uint32_t CHUNKS = LH_NKEYS / STEP; // chunks of the widest span (a span starts at a multiple of 4)
+static_assert(CHUNKS == 4 * 64, "wave 0 scans the chunk totals four per lane");
+constexpr uint32_t NO_BIN = 0xffffffffu;
 
 // ---------------------------------------------------------------------------
 // Wave-level arithmetic that stays in the VALU (DPP): k_extract_wave's scans and reductions.  __shfl_up / __shfl_down
@@ -154,6 +169,71 @@ __device__ __forceinline__ void load4_cells(const CELL *__restrict__ row, uint32
             c[0] = c01.a; c[1] = c01.b; c[2] = c23.a; c[3] = c23.b;
         }
     }
+}
+
+// One row's own span [lo, hi]: its cells outside are zero, and a row that was never marked has lo > hi -- nothing of it may
+// be read.  A walk enters at base0(), lo aligned down to a multiple of 4: whole groups, every load 16-byte aligned.
+struct Span {
+    uint32_t lo, hi;
+    __device__ __forceinline__ bool any() const { return lo <= hi; }
+    __device__ __forceinline__ uint32_t base0() const { return lo & ~3u; }
+};
+__device__ __forceinline__ Span own_span(const uint32_t *__restrict__ ranges, uint32_t m)
+{
+    Span s;
+    s.lo = ranges[2 * (size_t)m];
+    s.hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
+    return s;
+}
+// the same, entered at a multiple of 4, with lo = NO_BIN > hi = 0 for a row that was never marked: what a union of spans
+// (the least lo, the largest hi) and load4_in take
+__device__ __forceinline__ Span or_empty(Span s)
+{
+    Span r;
+    r.lo = s.any() ? s.base0() : NO_BIN;
+    r.hi = s.any() ? s.hi : 0u;
+    return r;
+}
+// bins b0 .. b0 + 3 of a row, zeros outside its own span `s` (from or_empty; b0 a multiple of 4; hi <= 65 535: the group ends inside the row).
+// For a walk that may leave the span at its lower end (lh_compare.hip's, over the union of two); one that starts at
+// base0() calls load4_cells.
+template <typename CELL>
+__device__ __forceinline__ void load4_in(const CELL *__restrict__ row, uint32_t b0, Span s, u64 (&c)[4])
+{
+    load4_cells(row, b0 >= s.lo ? b0 : NO_BIN, s.hi, c); // (NO_BIN > hi: nothing is asked for)
+}
+// bins b0 .. b0 + 3 of a row and their entries of the value table; a lane whose group starts beyond hi asks for nothing.
+// b0 is a multiple of 4 and hi <= 65 535, so the group ends inside the row (and inside the table's LH_NKEYS entries).
+// (d is zeroed BEFORE load4_cells: behind it the compiler keeps two guarded regions apart, profiles/shared_headers_isa.txt)
+template <typename CELL>
+__device__ __forceinline__ void load4(const CELL *__restrict__ row, const double *__restrict__ D, uint32_t b0, uint32_t hi,
+                                      u64 (&c)[4], double (&d)[4])
+{
+    d[0] = d[1] = d[2] = d[3] = 0.0;
+    load4_cells(row, b0, hi, c);
+    if (b0 <= hi) {
+        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
+        const f64x2_a8 d01 = dp[0], d23 = dp[1];
+        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
+    }
+}
+// The value table: D[b] = decompress(bin_to_key(b)), the bits of lh_codec_tables' D[] (-ffp-contract=off).  512 KiB,
+// resident in L2 beside the windows; evaluating exp() per cell would cost an IEEE divide each.  A unit that weighs cells
+// generates its own, once per device (beside::ensure_table), with k_value_table<its context type>: an instantiation per
+// unit, none in a unit that has no use for it.
+template <class Unit> __global__ __launch_bounds__(256) void k_value_table(double *__restrict__ D)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < LH_NKEYS) D[b] = d_decompress_bin(b);
+}
+
+__device__ __forceinline__ u64 sum4(const u64 (&c)[4]) { return (c[0] + c[1]) + (c[2] + c[3]); }
+// value * float64(count) of a lane's four bins (metrics.go:344) and their sum, always associated the same way
+__device__ __forceinline__ double terms4(const u64 (&c)[4], const double (&d)[4], double (&t)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = d[k] * (double)c[k];
+    return (t[0] + t[1]) + (t[2] + t[3]);
 }
 
 } // namespace lh
