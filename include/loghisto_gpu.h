@@ -475,6 +475,60 @@ int lh_compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetr
 int lh_compare_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t flags,
                       uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key, uint64_t *d_ks_below_a,
                       uint64_t *d_ks_below_b, double *d_w1, double *d_shift);
+/* The k names whose distribution moved most between two snapshots: "which 20 of my 65 536 endpoints changed most since the
+ * last interval, or against the baseline", "whose p99 moved most" -- lh_compare* and lh_top* joined on the device, so that k
+ * entries travel instead of eight arrays over every name (or two full extracts and a host join).  The walk is lh_compare's:
+ * the bucket walk of percentile() (/root/reference/metrics.go:389-418) over two rows at once.  The reference has no
+ * counterpart for the SELECTION.  Nothing is summed across names, no cell is written and no new statistic is defined: every
+ * score is a value lh_compare or lh_extract_rows already returns.
+ *   CANDIDATES  the rows of [first, first + nmetrics) with count_a != 0 and count_b != 0 (for the others lh_compare returns
+ *               NaN, and a NaN is never ranked).  *n_out = min(k, candidates); entries at and beyond n_out are not written.
+ *   SCORE, always a float64, by `by`:
+ *     LH_MOVERS_BY_KS          ks[m] of lh_compare(base, cur, ...): bit-equal to it in either of its kernel shapes (a fixed
+ *                              function of exact integers)
+ *     LH_MOVERS_BY_W1          w1[m], bit-equal to what lh_compare returns from its wave-per-row kernel (calls of 1 024 rows
+ *                              or more by default): the same steps, the same per-lane order and the same tree over the lanes
+ *     LH_MOVERS_BY_SHIFT       shift[m], as w1; the SIGNED value is ranked: descending gives the names that moved up most,
+ *                              LH_MOVERS_ASCENDING those that moved down most
+ *     LH_MOVERS_BY_PERCENTILE  (double)((int64)bin_cur - (int64)bin_base), bin_x the bin of the bucket lh_extract_rows selects
+ *                              for p = arg in that snapshot: an exact integer in BUCKETS (100 buckets are one e-fold, so
+ *                              score / 100 is roughly the log ratio of the two percentile values)
+ *     arg is ignored for the first three.
+ *   ORDER  one total order, so the result never depends on timing or launch shape: descending score, or ascending score with
+ *          LH_MOVERS_ASCENDING; in BOTH directions equal scores go lowest id first.  Scores compare numerically
+ *          (-0.0 == +0.0).  out[0] is the leader.
+ *   FIELDS  id is absolute (first + i).  count_a and count_b are the name's totals in base and cur, whatever `by` is.  key is
+ *           lh_compare's ks_key for LH_MOVERS_BY_KS and the int16 key selected in cur for LH_MOVERS_BY_PERCENTILE; key_base
+ *           the one selected in base for LH_MOVERS_BY_PERCENTILE; both 0 otherwise.
+ *   LH_EINVAL, checked on the host before either snapshot or a device is touched: NULL base or cur; k == 0 or
+ *           k > LH_MAX_TOP; unknown `by`; unknown flag bits; NULL out or n_out; out not 8-byte aligned; n_out not aligned to
+ *           its type (size_t in lh_movers, uint32_t in lh_movers_device); LH_MOVERS_BY_PERCENTILE with arg NaN or outside
+ *           [0, 1].
+ *   LH_ERANGE: an nmetrics above 2^32 - 1 before anything is looked at (a cause of LH_EINVAL wins over it); first + nmetrics
+ *           beyond the rows of EITHER snapshot.
+ *   Two snapshots on different devices -> LH_EINVAL (after both were opened).  nmetrics == 0 -> LH_OK with *n_out = 0.
+ *   base == cur is allowed: every candidate scores 0 and the lowest ids win.
+ *   Totals that wrap past 2^64: the results are unspecified (nothing faults).
+ * ORDERING and threading as for lh_compare*: enqueued on lh_snapshot_stream(cur), behind an event on base's stream when the
+ * two differ; base must not be released before cur's stream has passed the call.  READ-ONLY in all four combinations of 4- and
+ * 8-byte cells.  Staging as for lh_top*: a pass that scores every row (one wave per row) into a records block in device
+ * memory, then lh_top's exact radix select and sort in one workgroup; lh_movers returns when the entries are in `out` --
+ * entries and n_out come back in one copy through a pinned block of the library's; lh_movers_device takes device memory
+ * for both and returns after enqueueing.  One records block per DEVICE behind the unit's own mutex: calls take turns. */
+enum { LH_MOVERS_BY_KS = 0, LH_MOVERS_BY_W1 = 1, LH_MOVERS_BY_SHIFT = 2, LH_MOVERS_BY_PERCENTILE = 3 };
+enum { LH_MOVERS_ASCENDING = 1 };
+typedef struct lh_mover_entry {   /* 32 bytes */
+    uint32_t id;        /* absolute metric id (first + i) */
+    int16_t  key;       /* BY_KS: ks_key of lh_compare; BY_PERCENTILE: the key selected in cur; else 0 */
+    int16_t  key_base;  /* BY_PERCENTILE: the key selected in base; else 0 */
+    uint64_t count_a;   /* the name's total in base */
+    uint64_t count_b;   /* ... in cur */
+    double   score;     /* what was ranked */
+} lh_mover_entry;
+int lh_movers(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+              uint32_t flags, lh_mover_entry *out, size_t *n_out);
+int lh_movers_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                     uint32_t flags, lh_mover_entry *d_out, uint32_t *d_n_out);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

@@ -147,6 +147,10 @@ int lh_tool_compare_switch(uint32_t wave_from_rows, uint32_t *previous);
  * lh_top_device, its entries left in the unit's own block; returns when both times are known.  nmetrics >= 1. */
 int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
                           float *score_ms, float *select_ms);
+/* The same for lh_movers*'s two passes, on cur's stream: one call with the arguments of lh_movers_device, its entries left in
+ * the unit's own block; returns when both times are known.  nmetrics >= 1. */
+int lh_tool_movers_passes_ms(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg,
+                             size_t k, uint32_t flags, float *score_ms, float *select_ms);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,8 @@ LE_PER_METRIC = 1
 MAX_TOP = 1024         # lh_top*
 TOP_BY_COUNT, TOP_BY_SUM, TOP_BY_PERCENTILE, TOP_BY_COUNT_ABOVE = range(4)
 TOP_ASCENDING = 1
+MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   # lh_movers* (k <= MAX_TOP)
+MOVERS_ASCENDING = 1
 
 OK, EINVAL, ENOMEM, EDEVICE, ENODEVICE, EBUSY, ERANGE, ESTATE = range(8)
 
@@ -127,11 +129,17 @@ class LhStats(C.Structure):
 
 
 def __getattr__(name):
-    """TOP_ENTRY: lh_top_entry (32 bytes) as a numpy dtype, built on first use -- this module itself needs ctypes only."""
+    """TOP_ENTRY / MOVER_ENTRY: lh_top_entry / lh_mover_entry (32 bytes each) as numpy dtypes, built on first use -- this
+    module itself needs ctypes only."""
     if name == "TOP_ENTRY":
         import numpy as np
         dt = np.dtype([("id", "<u4"), ("pkey", "<i2"), ("reserved", "<u2"), ("count", "<u8"), ("sum", "<f8"), ("above", "<u8")])
         globals()["TOP_ENTRY"] = dt
+        return dt
+    if name == "MOVER_ENTRY":
+        import numpy as np
+        dt = np.dtype([("id", "<u4"), ("key", "<i2"), ("key_base", "<i2"), ("count_a", "<u8"), ("count_b", "<u8"), ("score", "<f8")])
+        globals()["MOVER_ENTRY"] = dt
         return dt
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
@@ -152,6 +160,8 @@ TUNING_SIGNATURES = {
     "lh_tool_compare_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
+    "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float)]),
 }
 
 # name -> (restype, argtypes): every symbol include/loghisto_gpu.h declares.
@@ -213,6 +223,8 @@ SIGNATURES = {
     "lh_top_device": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_compare": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_compare_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_movers": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
+    "lh_movers_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

@@ -1,5 +1,5 @@
-// lh_beside.h -- host-only plumbing of the units built BESIDE the engine (lh_import.hip, lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip; a
-// new reader of a snapshot starts here and in lh_wave.h).  Such a unit sees the engine through its public C ABI only
+// lh_beside.h -- host-only plumbing of the units built BESIDE the engine (lh_import.hip, lh_count.hip, lh_spread.hip, lh_top.hip,
+// lh_compare.hip, lh_movers.hip; a new reader of a snapshot starts here and in lh_wave.h).  Such a unit sees the engine through its public C ABI only
 // (include/loghisto_gpu.h: it cannot see struct lh_engine / lh_snapshot):
 //   lh_snapshot_cells    the cells AS THEY ARE, 4 or 8 bytes wide (nothing moves: a narrow snapshot stays narrow), and the
 //                        number of rows

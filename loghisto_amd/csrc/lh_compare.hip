@@ -32,6 +32,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
+#include "lh_pair.h"
 #include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
@@ -45,8 +46,6 @@ namespace {
 using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
 
-typedef unsigned __int128 u128;
-
 // Rows of a call from which a row gets a wave, not a workgroup: lh_spread's default, whose walks these are, until
 // tools/compare_bench.py has been run (profiles/compare.txt).
 constexpr uint32_t CP_WAVE_FROM_DEFAULT = 1024;
@@ -58,88 +57,6 @@ struct CompareOut {
     u64 *below_a, *below_b;
     double *w1, *shift;
 };
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) // the maximum in lane 63 (lanes without a source: 0)
-{
-    x = max(x, LH_DPP32(x, 0x111, 0xf));
-    x = max(x, LH_DPP32(x, 0x112, 0xf));
-    x = max(x, LH_DPP32(x, 0x114, 0xf));
-    x = max(x, LH_DPP32(x, 0x118, 0xf));
-    x = max(x, LH_DPP32(x, 0x142, 0xa));
-    x = max(x, LH_DPP32(x, 0x143, 0xc));
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-
-// What a name's walk is scaled by: the totals, and na nb as the divisor of the sums' terms.
-struct Scale {
-    u64 na, nb;
-    uint32_t sh; // the bits na nb has beyond 64
-    double den;  // float64(na nb >> sh)
-};
-__device__ __forceinline__ Scale make_scale(u64 na, u64 nb)
-{
-    Scale s;
-    s.na = na;
-    s.nb = nb;
-    const u128 p = (u128)na * nb;
-    const u64 ph = (u64)(p >> 64);
-    s.sh = ph ? 64u - (uint32_t)__builtin_clzll(ph) : 0u; // <= 64
-    s.den = (double)(u64)(p >> s.sh);
-    return s;
-}
-
-// A lane's state of walk 2
-struct Best {
-    u128 x;      // the largest X so far
-    uint32_t bin;
-    u64 a, b;    // the prefixes there
-    double w, s; // the lane's share of w1 and of shift
-};
-__device__ __forceinline__ void best_init(Best &r)
-{
-    r.x = 0;
-    r.bin = NO_BIN;
-    r.a = r.b = 0;
-    r.w = r.s = 0.0;
-}
-// the lane's four bins bin0 .. bin0 + 3; pa / pb: the prefixes below them
-__device__ __forceinline__ void take4(Best &r, const Scale &sc, uint32_t bin0, u64 pa, u64 pb, const u64 (&a)[4], const u64 (&b)[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        pa += a[k];
-        pb += b[k];
-        const u128 xa = (u128)pa * sc.nb, xb = (u128)pb * sc.na;
-        const bool up = xa >= xb;
-        const u128 x = up ? xa - xb : xb - xa;
-        if (x > r.x) {
-            r.x = x;
-            r.bin = bin0 + k;
-            r.a = pa;
-            r.b = pb;
-        }
-        const double t = (double)(u64)(x >> sc.sh) / sc.den;
-        r.w += t;
-        r.s += up ? t : -t;
-    }
-}
-// The wave's best: the largest X, at the lowest bin among equals (wave-uniform results).  X == 0 everywhere: NO_BIN.
-__device__ __forceinline__ void wave_best(const Best &r, u128 &x, uint32_t &bin, u64 &a, u64 &b)
-{
-    bool in = true;
-#pragma unroll
-    for (int w = 3; w >= 0; w--) {
-        const uint32_t word = (uint32_t)(r.x >> (32 * w));
-        const uint32_t top = wave_max_u32(in ? word : 0u);
-        in = in && word == top;
-    }
-    const uint32_t inv = wave_max_u32(in ? ~r.bin : 0u); // the lowest bin: the largest complement (NO_BIN's is 0)
-    const uint32_t src = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(in && ~r.bin == inv)); // (lane 0 at least, with NO_BIN)
-    bin = ~inv;
-    a = readlane_u64(r.a, src);
-    b = readlane_u64(r.b, src);
-    x = ((u128)readlane_u64((u64)(r.x >> 64), src) << 64) | readlane_u64((u64)r.x, src);
-}
 
 // one lane writes a name's results; bin == NO_BIN: the two normalised distributions are identical
 __device__ __forceinline__ void store_row(const CompareOut &o, uint32_t m, u64 na, u64 nb, uint32_t bin, u64 a, u64 b, double w1,

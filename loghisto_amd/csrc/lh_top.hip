@@ -21,13 +21,10 @@
 //                 LH_TOP_ASCENDING, so that the select pass always takes the LARGEST keys), its count, its sum and its pkey
 //                 or count above.  Whether a row is a candidate is NOT in the key (a complemented key takes any value):
 //                 it is count != 0.
-//   k_top_select  ONE workgroup of 1 024 threads looping over the records.  An exact k-th-key search, MSB first, eight
-//                 passes of 8 bits with a 256-entry histogram in LDS (a wave whose records all fall into one bin adds them
-//                 with one atomic: the high bytes of counts are mostly zero); then one pass in index order that takes every
-//                 record ahead of the k-th key and, of those equal to it, the lowest ids -- a prefix count over the records,
-//                 never an atomic whose order depends on timing; then a bitonic sort of the at most 1 024 winners by (key
-//                 descending, id ascending) in LDS; then the entries and n_out.  One total order: the result depends on
-//                 neither timing nor launch shape.
+//   k_select      (lh_select.h, shared with lh_movers.hip) ONE workgroup of 1 024 threads looping over the records: an exact
+//                 k-th-key search by radix, the winners by a prefix count in index order, a bitonic sort by (key descending, id
+//                 ascending); this unit's TopEmit writes a winner's entry.  One total order: the result depends on neither
+//                 timing nor launch shape.
 // One wave shape and a one-workgroup select are UNMEASURED DEFAULTS: a full-span row costs its wave 256 steps per walk, and
 // the select pass reads the keys nine times with one workgroup.  tools/top_bench.py measures both passes at 65 536 names and
 // a full-span row; that measurement decides whether the workgroup-per-row shape lh_count.hip and lh_spread.hip carry, or a
@@ -37,6 +34,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
+#include "lh_select.h"
 #include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
@@ -49,13 +47,7 @@ namespace {
 using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
 
-constexpr int SEL_WG = 1024, SEL_WAVES = SEL_WG / 64;   // k_top_select
-constexpr uint32_t SEL_PER = 4;                         // consecutive records per thread and tile
-constexpr uint32_t SEL_TILE = SEL_WG * SEL_PER;
-constexpr uint32_t NO_SLOT = 0xffffffffu;               // the index of a padding slot of the sort: behind every record
 static_assert(sizeof(lh_top_entry) == 32, "lh_top_entry is 32 bytes");
-static_assert(LH_MAX_TOP == SEL_WG, "a thread per winner in the sort");
-static_assert(SEL_TILE <= 0x10000, "a tile's two prefix counts share one 32-bit scan");
 
 // The rows' records, one array per field, each padded to whole groups of SEL_PER (16-byte loads stay inside the block).
 struct TopRecords {
@@ -64,14 +56,6 @@ struct TopRecords {
     double *sum;
     u64 *aux;    // BY_PERCENTILE: the int16 key's 16 bits; BY_COUNT_ABOVE: the count above; else 0
 };
-
-// a float64 as an unsigned integer of the same order (-0.0 == +0.0; the host sees to it that no NaN is ranked)
-__device__ __forceinline__ u64 order_key_f64(double x)
-{
-    if (x == 0.0) x = 0.0; // -0.0 -> +0.0
-    const u64 b = (u64)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 template <typename CELL>
 __global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
@@ -162,179 +146,14 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict_
     }
 }
 
-// ---- the select pass ------------------------------------------------------------------------------------------------
-// One more record in bin d of the histogram for the lanes with `in` set.  A wave whose records share the bin (every pass
-// over bytes the keys have in common) adds them with ONE atomic instead of up to 64 on one address.  Called under
-// workgroup-uniform control.  (Integer adds: the histogram does not depend on their order.)
-__device__ __forceinline__ void hist_add(uint32_t *hist, bool in, uint32_t d, uint32_t lane)
-{
-    const unsigned long long act = __builtin_amdgcn_ballot_w64(in);
-    if (!act) return; // wave-uniform
-    const uint32_t lead = (uint32_t)__builtin_ctzll(act);
-    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)lead);
-    if (__builtin_amdgcn_ballot_w64(in && d == d0) == act) {
-        if (lane == lead) atomicAdd(&hist[d0 & 255u], (uint32_t)__builtin_popcountll(act));
-    } else if (in) {
-        atomicAdd(&hist[d & 255u], 1u);
-    }
-}
-
-// records i0 .. i0 + 3 (i0 a multiple of 4; the arrays are padded to whole groups): their keys, and -- only where some
-// record of the group passes `keep` -- their counts.  ok[j]: record i0 + j exists, passes `keep` and is a candidate.
-template <class Keep>
-__device__ __forceinline__ void load_records(const u64 *__restrict__ key, const u64 *__restrict__ count, size_t i0, uint32_t n,
-                                             u64 (&kk)[SEL_PER], bool (&ok)[SEL_PER], Keep keep)
-{
-#pragma unroll
-    for (uint32_t j = 0; j < SEL_PER; j++) { kk[j] = 0; ok[j] = false; }
-    if (i0 >= n) return;
-    const u64x2_a8 *kp = reinterpret_cast<const u64x2_a8 *>(key + i0);
-    const u64x2_a8 k01 = kp[0], k23 = kp[1];
-    kk[0] = k01.a; kk[1] = k01.b; kk[2] = k23.a; kk[3] = k23.b;
-    bool any = false;
-#pragma unroll
-    for (uint32_t j = 0; j < SEL_PER; j++) {
-        ok[j] = j < n - i0 && keep(kk[j]);
-        any = any || ok[j];
-    }
-    if (!any) return;
-    const u64x2_a8 *cp = reinterpret_cast<const u64x2_a8 *>(count + i0);
-    const u64x2_a8 c01 = cp[0], c23 = cp[1];
-    ok[0] = ok[0] && c01.a != 0; ok[1] = ok[1] && c01.b != 0; ok[2] = ok[2] && c23.a != 0; ok[3] = ok[3] && c23.b != 0;
-}
-
-// (a key, an index) ahead of another in the result: the larger key, then the lower index.  Padding slots (key 0, index
-// NO_SLOT) stay behind every record.
-__device__ __forceinline__ bool ahead(u64 ka, uint32_t ia, u64 kb, uint32_t ib) { return ka > kb || (ka == kb && ia < ib); }
-
-__global__ __launch_bounds__(SEL_WG) void k_top_select(const TopRecords r, uint32_t n, uint32_t first, uint32_t k, uint32_t by,
-                                                       lh_top_entry *__restrict__ out, uint32_t *__restrict__ n_out)
-{
-    __shared__ uint32_t s_hist[256];
-    __shared__ uint32_t s_part[SEL_WAVES];
-    __shared__ uint32_t s_digit, s_rem, s_take;
-    __shared__ u64 s_wkey[LH_MAX_TOP];
-    __shared__ uint32_t s_widx[LH_MAX_TOP];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t ntiles = n / SEL_TILE + (n % SEL_TILE != 0); // (n + SEL_TILE - 1 would wrap near 2^32)
-
-    // ---- the k-th largest key among the candidates: `prefix` holds its bytes above `shift`; of the candidates that share
-    // them, the rem-th largest is looked for
-    u64 prefix = 0;
-    uint32_t rem = k;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        if (tid < 256) s_hist[tid] = 0;
-        __syncthreads();
-        for (uint32_t t = 0; t < ntiles; t++) { // workgroup-uniform
-            u64 kk[SEL_PER];
-            bool ok[SEL_PER];
-            load_records(r.key, r.count, (size_t)t * SEL_TILE + SEL_PER * tid, n, kk, ok,
-                         [&](u64 x) { return shift == 56 || (x >> (shift + 8)) == prefix; });
-#pragma unroll
-            for (uint32_t j = 0; j < SEL_PER; j++) hist_add(s_hist, ok[j], (uint32_t)(kk[j] >> shift) & 255u, lane);
-        }
-        __syncthreads();
-        if (wave == 0) {
-            // bins in DESCENDING order, four per lane: position q = 4 * lane + j is bin 255 - q
-            uint32_t v[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; j++) v[j] = s_hist[255u - (4 * lane + j)];
-            const uint32_t tv = (v[0] + v[1]) + (v[2] + v[3]);
-            const uint32_t inc = wave_scan_incl_u32(tv);
-            const uint32_t all = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            // (the top byte's pass counts the candidates: fewer than k, and all of them are taken; none, and rem is 0)
-            const uint32_t want = shift == 56 ? min(rem, all) : rem;
-            if (shift == 56 && lane == 0) s_take = want;
-            if (want == 0) {
-                if (lane == 0) s_rem = 0;
-            } else {
-                // the first position whose inclusive count reaches `want` (all >= want: one does)
-                const uint32_t f = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(inc >= want));
-                if (lane == f) {
-                    uint32_t run = inc - tv, j = 0;
-                    while (j < 3 && run + v[j] < want) run += v[j++];
-                    s_digit = 255u - (4 * lane + j);
-                    s_rem = want - run; // among the records of that bin
-                }
-            }
-        }
-        __syncthreads();
-        rem = s_rem;
-        if (rem == 0) { // workgroup-uniform: no candidate at all
-            if (tid == 0) *n_out = 0;
-            return;
-        }
-        prefix = (prefix << 8) | s_digit;
-        // (s_hist, s_digit and s_rem are written again only behind the next pass's first barrier)
-    }
-    // `prefix` is the k-th key (the last candidate's when there are fewer than k), nwin records are taken: the nahead that
-    // are strictly ahead of it and the first rem, in index order, of those equal to it.
-    const u64 kth = prefix;
-    const uint32_t nwin = min(s_take, (uint32_t)LH_MAX_TOP), nahead = nwin - min(rem, nwin);
-
-    // ---- the winners into LDS, by a prefix count over the records in index order
-    uint32_t gt_base = 0, eq_base = 0; // records of either kind in the tiles so far
-    for (uint32_t t = 0; t < ntiles && (gt_base < nahead || eq_base < rem); t++) { // workgroup-uniform
-        u64 kk[SEL_PER];
-        bool ok[SEL_PER];
-        const size_t i0 = (size_t)t * SEL_TILE + SEL_PER * tid; // (the last tile's tail may lie beyond 2^32)
-        load_records(r.key, r.count, i0, n, kk, ok, [&](u64 x) { return x >= kth; });
-        uint32_t mine = 0; // records ahead in the high half, equal ones in the low half (a tile has at most 4 096 of each)
-#pragma unroll
-        for (uint32_t j = 0; j < SEL_PER; j++) mine += ok[j] ? (kk[j] > kth ? 0x10000u : 1u) : 0u;
-        const uint32_t inc = wave_scan_incl_u32(mine);
-        if (lane == 63) s_part[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0, tile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SEL_WAVES; w++) {
-            const uint32_t p = s_part[w];
-            before += w < wave ? p : 0u;
-            tile += p;
-        }
-        before += inc - mine;
-        uint32_t gpos = gt_base + (before >> 16), epos = eq_base + (before & 0xffffu);
-#pragma unroll
-        for (uint32_t j = 0; j < SEL_PER; j++) {
-            if (!ok[j]) continue;
-            uint32_t slot = NO_SLOT;
-            if (kk[j] > kth) slot = gpos++;
-            else if (epos++ < rem) slot = nahead + (epos - 1);
-            if (slot < nwin) { // (every slot handed out is: the guard keeps a wrong count from writing outside the block)
-                s_wkey[slot] = kk[j];
-                s_widx[slot] = (uint32_t)(i0 + j); // (an existing record: below n)
-            }
-        }
-        gt_base += tile >> 16;
-        eq_base += tile & 0xffffu;
-        __syncthreads(); // s_part is rewritten by the next tile
-    }
-
-    // ---- bitonic sort of the winners by (key descending, index ascending), padded to a power of two
-    uint32_t width = 1;
-    while (width < nwin) width <<= 1;
-    if (tid >= nwin && tid < width) {
-        s_wkey[tid] = 0;
-        s_widx[tid] = NO_SLOT;
-    }
-    for (uint32_t size = 2; size <= width; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            const uint32_t other = tid ^ stride;
-            if (other > tid && other < width) {
-                const u64 ka = s_wkey[tid], kb = s_wkey[other];
-                const uint32_t ia = s_widx[tid], ib = s_widx[other];
-                const bool up = (tid & size) == 0; // this run ends up with its leader first
-                if (ahead(kb, ib, ka, ia) == up) {
-                    s_wkey[tid] = kb; s_widx[tid] = ib;
-                    s_wkey[other] = ka; s_widx[other] = ia;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (tid < nwin && s_widx[tid] < n) { // (every winner's index is: the guard keeps a wrong slot from reading outside the block)
-        const uint32_t i = s_widx[tid];
+// ---- the select pass: lh_select.h's, with this unit's last step ---------------------------------------------------
+// winner i lands in slot t
+struct TopEmit {
+    TopRecords r;
+    uint32_t first, by;
+    lh_top_entry *out;
+    __device__ __forceinline__ void operator()(uint32_t i, uint32_t t) const
+    {
         const u64 aux = r.aux[i];
         lh_top_entry e;
         e.id = first + i;
@@ -343,10 +162,9 @@ __global__ __launch_bounds__(SEL_WG) void k_top_select(const TopRecords r, uint3
         e.count = r.count[i];
         e.sum = r.sum[i];
         e.above = by == LH_TOP_BY_COUNT_ABOVE ? aux : 0;
-        out[tid] = e;
+        out[t] = e;
     }
-    if (tid == 0) *n_out = nwin;
-}
+};
 
 // ---- host side --------------------------------------------------------------------------------------
 // Per-device state of this unit (device_ctx<TopCtx>).  `mu` is held for the length of a call -- the host form's wait for
@@ -407,7 +225,8 @@ int enqueue(const TopSource &q, uint32_t first, size_t nmetrics, uint32_t by, do
     });
     LH_BESIDE_CHK(hipGetLastError());
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], q.stream));
-    hipLaunchKernelGGL(k_top_select, dim3(1), dim3(SEL_WG), 0, q.stream, r, M, first, (uint32_t)k, by, d_out, d_n_out);
+    hipLaunchKernelGGL(k_select<TopEmit>, dim3(1), dim3(SEL_WG), 0, q.stream, r.key, r.count, M, (uint32_t)k, TopEmit{r, first, by, d_out},
+                       d_n_out);
     LH_BESIDE_CHK(hipGetLastError());
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], q.stream));
     return cx->guard.record(q.stream);

@@ -1,4 +1,5 @@
-// lh_wave.h -- the device side of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip; a
+// lh_wave.h -- the device side of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip,
+// lh_movers.hip -- with lh_pair.h for a walk over two rows and lh_select.h for a selection across names; a
 // new reader starts here and in lh_beside.h):
 //   wave primitives   DPP scans, cross-lane reads, the packed 16-byte load types
 //   the arithmetic    the percentile threshold (pct_threshold) and the bound-to-key rule (le_take)

@@ -525,6 +525,50 @@ class Snapshot:
             res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
         return res
 
+    # -- the k names whose distribution moved most against another snapshot (compare's scores, top's selection) ------------
+    _MOVERS_BY = {"ks": N.MOVERS_BY_KS, "w1": N.MOVERS_BY_W1, "shift": N.MOVERS_BY_SHIFT, "percentile": N.MOVERS_BY_PERCENTILE}
+
+    def movers(self, base: "Snapshot", k: int, by: str = "ks", arg: Optional[float] = None, ascending: bool = False,
+               nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """The k names of [first, first+nmetrics) whose distribution in THIS snapshot moved most against the same names of
+        `base` (lh_movers*), as a structured array (dtype N.MOVER_ENTRY: id, key, key_base, count_a, count_b, score) of
+        n_out = min(k, names with samples on both sides) entries, the leader first.  by = "ks", "w1" or "shift" (score = that
+        output of compare(); for "ks" `key` is compare's key; "shift" ranks the signed value: descending gives the names
+        that moved up most, ascending=True those that moved down most) or "percentile" (arg = p in [0, 1]: score = the
+        number of buckets the bucket extract() selects for p moved, bin here minus bin in base -- 100 buckets are one e-fold;
+        `key` / `key_base` are the two selected keys).  Equal scores go lowest id first either way.  ids are absolute.
+        `base` may belong to another engine on the same device, and may be this snapshot.
+        out = a contiguous numpy array of at least k MOVER_ENTRY elements takes the host form into it (its first n_out
+        entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
+        k * 32 and 4 bytes takes the device form: enqueued on this snapshot's stream (`base` must stay unreleased until
+        that stream has passed the call), the pair is returned as it is."""
+        L = N.lib()
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        if by not in self._MOVERS_BY:
+            raise ValueError("by is one of " + ", ".join(self._MOVERS_BY))
+        if arg is None:
+            if by == "percentile":
+                raise ValueError(f"by={by!r} takes an arg")
+            arg = 0.0
+        flags = N.MOVERS_ASCENDING if ascending else 0
+        if isinstance(out, tuple):
+            entries, n = out
+            for t, need in ((entries, k * N.MOVER_ENTRY.itemsize), (n, 4)):
+                if not t.is_contiguous() or t.element_size() * int(t.numel()) < need:
+                    raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4")
+            N.check(L.lh_movers_device(base._h, self._h, first, nmetrics, self._MOVERS_BY[by], float(arg), k, flags, _ptr(entries),
+                                       _ptr(n)), "lh_movers_device")
+            return out
+        if out is None:
+            out = np.zeros(max(k, 1), dtype=N.MOVER_ENTRY)
+        elif not (isinstance(out, np.ndarray) and out.dtype == N.MOVER_ENTRY and out.size >= k and out.flags.c_contiguous):
+            raise ValueError("out holds at least k contiguous MOVER_ENTRY elements")
+        n = C.c_size_t(0)
+        N.check(L.lh_movers(base._h, self._h, first, nmetrics, self._MOVERS_BY[by], float(arg), k, flags, out.ctypes.data,
+                            C.addressof(n)), "lh_movers")
+        return out.reshape(-1)[:n.value]
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
