@@ -11,9 +11,10 @@
 // What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
 // way a host form's results travel back, the event that guards a block across streams, and the measurement switch's
 // exchange.  For the readers, which all walk rows [first, first + nmetrics): their source record and its two-step opener
-// (Source, source_cells, source_open), the launch shape (row_shape), the dispatch on the cells' width (with_cells) and the
-// value table's set-up (ensure_table).  A reader itself has its context, its argument checks, its kernels and its entry
-// points.
+// (Source, source_cells, source_open), the same two steps for a reader of two snapshots (pair_cells, pair_open) with the
+// event that puts one snapshot's stream behind the other's (order_behind), the launch shape (row_shape), the dispatch on
+// the cells' width (with_cells) and the value table's set-up (ensure_table).  A reader itself has its context, its
+// argument checks, its kernels and its entry points; one that selects k names has the rest of its host side in lh_select.h.
 #pragma once
 
 #include "../../include/loghisto_gpu.h"
@@ -220,13 +221,40 @@ template <class Ctx> bool usable(const Source<Ctx> &q)
 {
     return q.stride >= (size_t)LH_NKEYS + 4 && q.cells && (q.cell_bytes == 4 || q.cell_bytes == 8);
 }
-// Step two: spans, device, context, stream and stride; LH_ESTATE for a snapshot the kernels cannot walk.  (A reader of
-// two snapshots takes the two parts apart: lh_compare.hip.)
+// Step two: spans, device, context, stream and stride; LH_ESTATE for a snapshot the kernels cannot walk.
 template <class Ctx> int source_open(lh_snapshot *s, Source<Ctx> &q)
 {
     const int rc = open_snapshot(s, q, q.cx);
     if (rc) return rc;
     return usable(q) ? LH_OK : LH_ESTATE;
+}
+// The two steps for a reader of two snapshots (`a` of base, `b` of cur; the unit's context is b.cx).  Between them a
+// reader whose empty call writes nothing returns (lh_compare.hip); one whose empty call writes n_out takes both first
+// (lh_movers.hip).  Step one: LH_ERANGE for rows either snapshot does not have.
+template <class Ctx>
+int pair_cells(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, Source<Ctx> &a, Source<Ctx> &b)
+{
+    const int rc = source_cells(base, first, nmetrics, a);
+    return rc ? rc : source_cells(cur, first, nmetrics, b);
+}
+// Step two: both opened, then LH_EINVAL for two devices (the check that needs both), then LH_ESTATE.
+template <class Ctx> int pair_open(lh_snapshot *base, lh_snapshot *cur, Source<Ctx> &a, Source<Ctx> &b)
+{
+    int rc = open_snapshot(base, a, a.cx);
+    if (!rc) rc = open_snapshot(cur, b, b.cx);
+    if (rc) return rc;
+    if (a.device != b.device) return LH_EINVAL;
+    return usable(a) && usable(b) ? LH_OK : LH_ESTATE;
+}
+// (the context's mutex held)  What is enqueued on `to` from here on runs behind what `from` holds now.  `ev`: the unit's
+// event for this, created on first use.
+static inline int order_behind(hipEvent_t &ev, hipStream_t from, hipStream_t to)
+{
+    if (from == to) return LH_OK;
+    if (!ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    LH_BESIDE_CHK(hipEventRecord(ev, from));
+    LH_BESIDE_CHK(hipStreamWaitEvent(to, ev, 0));
+    return LH_OK;
 }
 inline const uint32_t *ranges_from(const Opened &o, uint32_t first) { return o.ranges + 2 * (size_t)first; }
 

@@ -294,12 +294,8 @@ typedef lh::beside::Source<CompareCtx> Source;
 // (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on cur's stream, behind what base's stream holds
 int enqueue(const Source &a, const Source &b, uint32_t first, size_t nmetrics, const CompareOut &o)
 {
-    CompareCtx *cx = b.cx;
-    if (a.stream != b.stream) {
-        if (!cx->order) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->order, hipEventDisableTiming));
-        LH_BESIDE_CHK(hipEventRecord(cx->order, a.stream));
-        LH_BESIDE_CHK(hipStreamWaitEvent(b.stream, cx->order, 0));
-    }
+    const int rc = order_behind(b.cx->order, a.stream, b.stream);
+    if (rc) return rc;
     const uint32_t M = (uint32_t)nmetrics;
     const uint32_t *ra = ranges_from(a, first), *rb = ranges_from(b, first);
     const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
@@ -323,17 +319,11 @@ int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics
     int rc = check_args(base, cur, nmetrics, flags, o);
     if (rc) return rc;
     Source a, b;
-    rc = source_cells(base, first, nmetrics, a);
-    if (rc) return rc;
-    rc = source_cells(cur, first, nmetrics, b);
+    rc = pair_cells(base, cur, first, nmetrics, a, b);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any device call
-    rc = open_snapshot(base, a, a.cx);
+    rc = pair_open(base, cur, a, b);
     if (rc) return rc;
-    rc = open_snapshot(cur, b, b.cx);
-    if (rc) return rc;
-    if (a.device != b.device) return LH_EINVAL;
-    if (!usable(a) || !usable(b)) return LH_ESTATE; // (source_open's two parts, around the check that needs both opened)
     CompareCtx *cx = b.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(a, b, first, nmetrics, o);

@@ -35,7 +35,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <mutex>
 
 namespace {
@@ -190,30 +189,22 @@ struct MoversEmit {
     }
 };
 
-// ---- host side --------------------------------------------------------------------------------------
+// ---- host side: lh_select.h's, around this unit's enqueue --------------------------------------------------------
 // Per-device state of this unit (device_ctx<MoversCtx>).  `mu` is held for the length of a call, the host form's wait for
-// its results included.  `order`: the event that puts cur's stream behind base's when the two differ.  The records block
-// outlives a device-form call while snapshots of different engines run on different streams: it is guarded by an event,
-// not by stream order.
+// its results included.  `order`: the event that puts cur's stream behind base's when the two differ.
 struct MoversCtx {
     std::mutex mu;
     hipEvent_t order = nullptr;
-    unsigned char *d_records = nullptr; // five arrays of padded nmetrics 8-byte fields
-    size_t rec_cap = 0;                 // (in records)
-    ResultBlocks res;                   // host form: k entries and n_out
-    EventGuard guard;                   // behind the last select pass
+    SelectState sel; // the records: five arrays (MoversRecords)
 };
 
 // every check that needs neither a snapshot nor a device
 int check_args(lh_snapshot *base, lh_snapshot *cur, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, const void *out,
                const void *n_out, uintptr_t n_out_align)
 {
-    if (!base || !cur || k == 0 || k > LH_MAX_TOP || by > LH_MOVERS_BY_PERCENTILE || (flags & ~(uint32_t)LH_MOVERS_ASCENDING))
-        return LH_EINVAL;
-    if (!out || !n_out || misaligned(out, 8) || misaligned(n_out, n_out_align)) return LH_EINVAL;
+    if (!base || !cur || by > LH_MOVERS_BY_PERCENTILE || (flags & ~(uint32_t)LH_MOVERS_ASCENDING)) return LH_EINVAL;
     if (by == LH_MOVERS_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL; // NaN too: no bucket to rank by
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    return LH_OK;
+    return select_check_args(nmetrics, k, out, n_out, n_out_align);
 }
 
 typedef Source<MoversCtx> MoversSource;
@@ -222,13 +213,8 @@ typedef Source<MoversCtx> MoversSource;
 // LH_ESTATE for cells the kernels cannot walk.  (The empty call comes behind it: it writes n_out.)
 int open_sources(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, MoversSource &a, MoversSource &b)
 {
-    int rc = source_cells(base, first, nmetrics, a);
-    if (!rc) rc = source_cells(cur, first, nmetrics, b);
-    if (!rc) rc = open_snapshot(base, a, a.cx);
-    if (!rc) rc = open_snapshot(cur, b, b.cx);
-    if (rc) return rc;
-    if (a.device != b.device) return LH_EINVAL;
-    return usable(a) && usable(b) ? LH_OK : LH_ESTATE;
+    const int rc = pair_cells(base, cur, first, nmetrics, a, b);
+    return rc ? rc : pair_open(base, cur, a, b);
 }
 
 // (cx->mu held) enqueue both passes over rows [first, first + nmetrics) on cur's stream, behind what base's stream holds.
@@ -238,21 +224,13 @@ int enqueue(const MoversSource &a, const MoversSource &b, uint32_t first, size_t
             lh_mover_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev = nullptr)
 {
     MoversCtx *cx = b.cx;
-    int rc = cx->guard.create();
-    if (rc) return rc;
-    if (a.stream != b.stream) {
-        if (!cx->order) LH_BESIDE_CHK(hipEventCreateWithFlags(&cx->order, hipEventDisableTiming));
-        LH_BESIDE_CHK(hipEventRecord(cx->order, a.stream));
-        LH_BESIDE_CHK(hipStreamWaitEvent(b.stream, cx->order, 0));
-    }
-    const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
-    if (cx->rec_cap < npad) rc = cx->guard.host_wait(); // the block is about to be freed: an earlier call's passes may still use it
-    if (!rc) rc = grow_device(cx->d_records, cx->rec_cap, npad, 4096, 5 * sizeof(u64));
-    // (another stream's call may still read the records: this one's passes wait for it on the device, not on the host)
-    if (!rc) rc = cx->guard.stream_wait(b.stream);
+    u64 *base = nullptr;
+    size_t npad = 0;
+    int rc = order_behind(cx->order, a.stream, b.stream);
+    if (!rc) rc = select_records(cx->sel, b.stream, nmetrics, 5, base, npad);
     if (rc) return rc;
     MoversRecords r;
-    r.key = reinterpret_cast<u64 *>(cx->d_records);
+    r.key = base;
     r.cand = r.key + npad;
     r.count_a = r.cand + npad;
     r.count_b = r.count_a + npad;
@@ -271,21 +249,7 @@ int enqueue(const MoversSource &a, const MoversSource &b, uint32_t first, size_t
         });
     });
     LH_BESIDE_CHK(hipGetLastError());
-    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], b.stream));
-    hipLaunchKernelGGL(k_select<MoversEmit>, dim3(1), dim3(SEL_WG), 0, b.stream, r.key, r.cand, M, (uint32_t)k, MoversEmit{r, first, d_out},
-                       d_n_out);
-    LH_BESIDE_CHK(hipGetLastError());
-    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], b.stream));
-    return cx->guard.record(b.stream);
-}
-
-// (cx->mu held) the host form's landing blocks: k entries, then n_out
-int result_blocks(MoversCtx *cx, size_t k)
-{
-    const size_t need = k * sizeof(lh_mover_entry) + 8;
-    int rc = grow_device(cx->res.d_res, cx->res.d_cap, need, RESULT_FLOOR);
-    if (!rc) rc = grow_pinned(cx->res.h_res, cx->res.h_cap, need, RESULT_FLOOR);
-    return rc;
+    return select_pass(cx->sel, b.stream, r.key, r.cand, M, k, MoversEmit{r, first, d_out}, d_n_out, ev);
 }
 
 } // namespace
@@ -304,25 +268,11 @@ int lh_movers(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetri
         *n_out = 0;
         return LH_OK;
     }
-    MoversCtx *cx = b.cx;
-    std::lock_guard<std::mutex> g(cx->mu);
-    // Entries at and beyond n_out are not written, and n_out is known only once the select pass has run: the k entries and
-    // n_out come back in one copy into the unit's pinned block, whatever memory `out` is, and the first n_out entries go
-    // on from there (at most 32 KiB), as in lh_top.
-    rc = result_blocks(cx, k);
-    if (rc) return rc;
-    const size_t bytes = k * sizeof(lh_mover_entry);
-    rc = enqueue(a, b, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_mover_entry *>(cx->res.d_res),
-                 reinterpret_cast<uint32_t *>(cx->res.d_res + bytes));
-    if (rc) return rc;
-    LH_BESIDE_CHK(hipMemcpyAsync(cx->res.h_res, cx->res.d_res, bytes + 8, hipMemcpyDeviceToHost, b.stream));
-    LH_BESIDE_CHK(hipStreamSynchronize(b.stream));
-    const uint32_t *h_n = reinterpret_cast<const uint32_t *>(cx->res.h_res + bytes);
-    if (*h_n > k) return LH_ESTATE;
-    std::memcpy(out, cx->res.h_res, (size_t)*h_n * sizeof(lh_mover_entry));
-    cx->guard.covered(); // this call recorded the event on the stream it has just waited for
-    *n_out = *h_n;
-    return LH_OK;
+    std::lock_guard<std::mutex> g(b.cx->mu);
+    const auto both = [&](lh_mover_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+        return enqueue(a, b, first, nmetrics, by, arg, k, flags, d_out, d_n_out, ev);
+    };
+    return select_host_form(b.cx->sel, b.stream, k, out, n_out, both);
 }
 
 int lh_movers_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
@@ -351,24 +301,11 @@ int lh_tool_movers_passes_ms(lh_snapshot *base, lh_snapshot *cur, uint32_t first
     MoversSource a, b;
     rc = open_sources(base, cur, first, nmetrics, a, b);
     if (rc) return rc;
-    MoversCtx *cx = b.cx;
-    std::lock_guard<std::mutex> g(cx->mu);
-    rc = result_blocks(cx, k);
-    if (rc) return rc;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3 && rc == LH_OK; i++)
-        if (hipEventCreate(&ev[i]) != hipSuccess) rc = LH_EDEVICE;
-    if (rc == LH_OK)
-        rc = enqueue(a, b, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_mover_entry *>(cx->res.d_res),
-                     reinterpret_cast<uint32_t *>(cx->res.d_res + k * sizeof(lh_mover_entry)), ev);
-    if (rc == LH_OK && (hipStreamSynchronize(b.stream) != hipSuccess || hipEventElapsedTime(score_ms, ev[0], ev[1]) != hipSuccess ||
-                        hipEventElapsedTime(select_ms, ev[1], ev[2]) != hipSuccess))
-        rc = LH_EDEVICE;
-    if (rc == LH_OK) cx->guard.covered();
-    for (int i = 0; i < 3; i++)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (rc == LH_EDEVICE) (void)hipGetLastError();
-    return rc;
+    std::lock_guard<std::mutex> g(b.cx->mu);
+    const auto both = [&](lh_mover_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+        return enqueue(a, b, first, nmetrics, by, arg, k, flags, d_out, d_n_out, ev);
+    };
+    return select_passes_ms<lh_mover_entry>(b.cx->sel, b.stream, k, score_ms, select_ms, both);
 }
 
 } // extern "C"

@@ -10,12 +10,19 @@
 //             ascending) in LDS; then emit(i, t) for the winner i of every slot t, and n_out.  One total order: the result
 //             depends on neither timing nor launch shape.
 // Both arrays are padded to whole groups of SEL_PER records (16-byte loads stay inside the block).
+//
+// Behind the kernels, the host side of "score pass, then k_select" (a new selecting reader starts there): SelectState,
+// select_check_args, select_records, select_pass, select_host_form and select_passes_ms.  The unit keeps its context type
+// with its own mutex, its record struct, its score kernel, its Emit and its enqueue.
 #pragma once
 
 #include "../../include/loghisto_gpu.h"
+#include "lh_beside.h"
 #include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 namespace lh {
 
@@ -212,4 +219,109 @@ __global__ __launch_bounds__(SEL_WG) void k_select(const u64 *__restrict__ key, 
     if (tid == 0) *n_out = nwin;
 }
 
+// ---- host side --------------------------------------------------------------------------------------
+namespace beside {
+
+// What a selecting unit keeps per device beside its own mutex and extras (a member of its context: device_ctx hands out
+// one slot array per context type, so units never wait for each other).  Snapshots of different engines run on
+// different streams, and the records block outlives a device-form call: it is guarded by an event, not by stream order.
+struct __attribute__((visibility("hidden"))) SelectState { // (hidden: the library exports nothing of this header)
+    u64 *d_records = nullptr; // the unit's arrays of padded nmetrics 8-byte fields, one behind the other
+    size_t rec_cap = 0;       // (in records)
+    ResultBlocks res;         // host form: k entries and n_out
+    EventGuard guard;         // behind the last select pass
+};
+
+// The checks of a selecting call that need neither a snapshot nor what is ranked.  A unit returns this AFTER its own
+// LH_EINVAL causes (handles, `by`, `arg`, flags): every LH_EINVAL wins over the early LH_ERANGE.
+static inline int select_check_args(size_t nmetrics, size_t k, const void *out, const void *n_out, uintptr_t n_out_align)
+{
+    if (k == 0 || k > LH_MAX_TOP) return LH_EINVAL;
+    if (!out || !n_out || misaligned(out, 8) || misaligned(n_out, n_out_align)) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    return LH_OK;
+}
+
+// (the context's mutex held)  The records of a call of nmetrics rows whose passes go on `st`: `fields` arrays of npad
+// 8-byte fields from `base` on, npad = nmetrics padded to whole groups of SEL_PER.  The unit carves its fields out of that.
+static inline int select_records(SelectState &ss, hipStream_t st, size_t nmetrics, size_t fields, u64 *&base, size_t &npad)
+{
+    int rc = ss.guard.create();
+    if (rc) return rc;
+    npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
+    if (ss.rec_cap < npad) rc = ss.guard.host_wait(); // the block is about to be freed: an earlier call's passes may still use it
+    if (!rc) rc = grow_device(ss.d_records, ss.rec_cap, npad, 4096, fields * sizeof(u64));
+    // (another stream's call may still read the records: this one's passes wait for it on the device, not on the host)
+    if (!rc) rc = ss.guard.stream_wait(st);
+    base = ss.d_records;
+    return rc;
+}
+
+// (the context's mutex held; behind the unit's score launch)  The second pass over the n records on `st`, and the guard's
+// event behind it.  ev (may be null): ev[1] is recorded between the passes and ev[2] behind the select pass; ev[0], before
+// the score pass, is the unit's.
+template <class Emit>
+int select_pass(SelectState &ss, hipStream_t st, const u64 *key, const u64 *cand, uint32_t n, size_t k, const Emit &emit,
+                uint32_t *d_n_out, hipEvent_t *ev)
+{
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(k_select<Emit>, dim3(1), dim3(SEL_WG), 0, st, key, cand, n, (uint32_t)k, emit, d_n_out);
+    LH_BESIDE_CHK(hipGetLastError());
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], st));
+    return ss.guard.record(st);
+}
+
+// (the context's mutex held) the host form's landing blocks: k entries, then n_out
+static inline int select_result_blocks(ResultBlocks &res, size_t need)
+{
+    int rc = grow_device(res.d_res, res.d_cap, need, RESULT_FLOOR);
+    if (!rc) rc = grow_pinned(res.h_res, res.h_cap, need, RESULT_FLOOR);
+    return rc;
+}
+
+// (the context's mutex held, the wait included)  The host form around the unit's enqueue(d_out, d_n_out, ev) -> status,
+// which puts both passes on `st`.  Entries at and beyond n_out are not written, and n_out is known only once the select
+// pass has run: the k entries and n_out come back in one copy into the unit's pinned block, whatever memory `out` is, and
+// the first n_out entries go on from there (at most 32 KiB; straight into a pinned `out` would be a second round trip).
+template <class Entry, class Enqueue>
+int select_host_form(SelectState &ss, hipStream_t st, size_t k, Entry *out, size_t *n_out, Enqueue enqueue)
+{
+    const size_t bytes = k * sizeof(Entry);
+    int rc = select_result_blocks(ss.res, bytes + 8);
+    if (rc) return rc;
+    rc = enqueue(reinterpret_cast<Entry *>(ss.res.d_res), reinterpret_cast<uint32_t *>(ss.res.d_res + bytes), (hipEvent_t *)nullptr);
+    if (rc) return rc;
+    LH_BESIDE_CHK(hipMemcpyAsync(ss.res.h_res, ss.res.d_res, bytes + 8, hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    const uint32_t *h_n = reinterpret_cast<const uint32_t *>(ss.res.h_res + bytes);
+    if (*h_n > k) return LH_ESTATE;
+    std::memcpy(out, ss.res.h_res, (size_t)*h_n * sizeof(Entry));
+    ss.guard.covered(); // this call recorded the event on the stream it has just waited for
+    *n_out = *h_n;
+    return LH_OK;
+}
+
+// (the context's mutex held)  lh_tool_*_passes_ms: both passes once, the results left in the unit's own block, with the
+// device time of each.  A failure before the times are read leaves score_ms / select_ms untouched.
+template <class Entry, class Enqueue>
+int select_passes_ms(SelectState &ss, hipStream_t st, size_t k, float *score_ms, float *select_ms, Enqueue enqueue)
+{
+    const size_t bytes = k * sizeof(Entry);
+    int rc = select_result_blocks(ss.res, bytes + 8);
+    if (rc) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3 && rc == LH_OK; i++)
+        if (hipEventCreate(&ev[i]) != hipSuccess) rc = LH_EDEVICE;
+    if (rc == LH_OK) rc = enqueue(reinterpret_cast<Entry *>(ss.res.d_res), reinterpret_cast<uint32_t *>(ss.res.d_res + bytes), ev);
+    if (rc == LH_OK && (hipStreamSynchronize(st) != hipSuccess || hipEventElapsedTime(score_ms, ev[0], ev[1]) != hipSuccess ||
+                        hipEventElapsedTime(select_ms, ev[1], ev[2]) != hipSuccess))
+        rc = LH_EDEVICE;
+    if (rc == LH_OK) ss.guard.covered();
+    for (int i = 0; i < 3; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (rc == LH_EDEVICE) (void)hipGetLastError();
+    return rc;
+}
+
+} // namespace beside
 } // namespace lh

@@ -39,7 +39,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <mutex>
 
 namespace {
@@ -166,30 +165,24 @@ struct TopEmit {
     }
 };
 
-// ---- host side --------------------------------------------------------------------------------------
+// ---- host side: lh_select.h's, around this unit's enqueue --------------------------------------------------------
 // Per-device state of this unit (device_ctx<TopCtx>).  `mu` is held for the length of a call -- the host form's wait for
 // its results included, so host-form calls on one device take turns even when their snapshots belong to different
-// engines.  Snapshots of different engines run on different streams, and the records block outlives a device-form call:
-// it is guarded by an event, not by stream order.
+// engines.
 struct TopCtx {
     std::mutex mu;
-    double *d_table = nullptr;        // D[LH_NKEYS]
-    unsigned char *d_records = nullptr; // four arrays of padded nmetrics 8-byte fields
-    size_t rec_cap = 0;               // (in records)
-    ResultBlocks res;                 // host form: k entries and n_out
-    EventGuard guard;                 // behind the last select pass
+    double *d_table = nullptr; // D[LH_NKEYS]
+    SelectState sel;           // the records: four arrays (TopRecords)
 };
 
 // every check that needs neither the snapshot nor a device
 int check_args(lh_snapshot *s, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out,
                uintptr_t n_out_align)
 {
-    if (!s || k == 0 || k > LH_MAX_TOP || by > LH_TOP_BY_COUNT_ABOVE || (flags & ~(uint32_t)LH_TOP_ASCENDING)) return LH_EINVAL;
-    if (!out || !n_out || misaligned(out, 8) || misaligned(n_out, n_out_align)) return LH_EINVAL;
+    if (!s || by > LH_TOP_BY_COUNT_ABOVE || (flags & ~(uint32_t)LH_TOP_ASCENDING)) return LH_EINVAL;
     if (by == LH_TOP_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL; // NaN too: no bucket to rank by
     if (by == LH_TOP_BY_COUNT_ABOVE && arg != arg) return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    return LH_OK;
+    return select_check_args(nmetrics, k, out, n_out, n_out_align);
 }
 
 typedef Source<TopCtx> TopSource;
@@ -200,17 +193,13 @@ int enqueue(const TopSource &q, uint32_t first, size_t nmetrics, uint32_t by, do
             uint32_t *d_n_out, hipEvent_t *ev = nullptr)
 {
     TopCtx *cx = q.cx;
+    u64 *base = nullptr;
+    size_t npad = 0;
     int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<TopCtx>);
-    if (!rc) rc = cx->guard.create();
-    if (rc) return rc;
-    const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1);
-    if (cx->rec_cap < npad) rc = cx->guard.host_wait(); // the block is about to be freed: an earlier call's passes may still use it
-    if (!rc) rc = grow_device(cx->d_records, cx->rec_cap, npad, 4096, 4 * sizeof(u64));
-    // (another stream's call may still read the records: this one's passes wait for it on the device, not on the host)
-    if (!rc) rc = cx->guard.stream_wait(q.stream);
+    if (!rc) rc = select_records(cx->sel, q.stream, nmetrics, 4, base, npad);
     if (rc) return rc;
     TopRecords r;
-    r.key = reinterpret_cast<u64 *>(cx->d_records);
+    r.key = base;
     r.count = r.key + npad;
     r.sum = reinterpret_cast<double *>(r.count + npad);
     r.aux = reinterpret_cast<u64 *>(r.sum + npad);
@@ -224,12 +213,7 @@ int enqueue(const TopSource &q, uint32_t first, size_t nmetrics, uint32_t by, do
                            flip, r);
     });
     LH_BESIDE_CHK(hipGetLastError());
-    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], q.stream));
-    hipLaunchKernelGGL(k_select<TopEmit>, dim3(1), dim3(SEL_WG), 0, q.stream, r.key, r.count, M, (uint32_t)k, TopEmit{r, first, by, d_out},
-                       d_n_out);
-    LH_BESIDE_CHK(hipGetLastError());
-    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], q.stream));
-    return cx->guard.record(q.stream);
+    return select_pass(cx->sel, q.stream, r.key, r.count, M, k, TopEmit{r, first, by, d_out}, d_n_out, ev);
 }
 
 // the snapshot's cells, spans, device and stream; LH_ERANGE for rows it does not have.  (The empty call comes behind it:
@@ -238,15 +222,6 @@ int open_source(lh_snapshot *s, uint32_t first, size_t nmetrics, TopSource &q)
 {
     const int rc = source_cells(s, first, nmetrics, q);
     return rc ? rc : source_open(s, q);
-}
-
-// (cx->mu held) the host form's landing blocks: k entries, then n_out
-int result_blocks(TopCtx *cx, size_t k)
-{
-    const size_t need = k * sizeof(lh_top_entry) + 8;
-    int rc = grow_device(cx->res.d_res, cx->res.d_cap, need, RESULT_FLOOR);
-    if (!rc) rc = grow_pinned(cx->res.h_res, cx->res.h_cap, need, RESULT_FLOOR);
-    return rc;
 }
 
 } // namespace
@@ -265,25 +240,11 @@ int lh_top(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double 
         *n_out = 0;
         return LH_OK;
     }
-    TopCtx *cx = q.cx;
-    std::lock_guard<std::mutex> g(cx->mu);
-    // Entries at and beyond n_out are not written, and n_out is known only once the select pass has run: the k entries and
-    // n_out come back in one copy into the unit's pinned block, whatever memory `out` is, and the first n_out entries go
-    // on from there (at most 32 KiB).  A copy straight into a pinned `out` would need n_out first: a second round trip.
-    rc = result_blocks(cx, k);
-    if (rc) return rc;
-    const size_t bytes = k * sizeof(lh_top_entry);
-    rc = enqueue(q, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_top_entry *>(cx->res.d_res),
-                 reinterpret_cast<uint32_t *>(cx->res.d_res + bytes));
-    if (rc) return rc;
-    LH_BESIDE_CHK(hipMemcpyAsync(cx->res.h_res, cx->res.d_res, bytes + 8, hipMemcpyDeviceToHost, q.stream));
-    LH_BESIDE_CHK(hipStreamSynchronize(q.stream));
-    const uint32_t *h_n = reinterpret_cast<const uint32_t *>(cx->res.h_res + bytes);
-    if (*h_n > k) return LH_ESTATE;
-    std::memcpy(out, cx->res.h_res, (size_t)*h_n * sizeof(lh_top_entry));
-    cx->guard.covered(); // this call recorded the event on the stream it has just waited for
-    *n_out = *h_n;
-    return LH_OK;
+    std::lock_guard<std::mutex> g(q.cx->mu);
+    const auto both = [&](lh_top_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+        return enqueue(q, first, nmetrics, by, arg, k, flags, d_out, d_n_out, ev);
+    };
+    return select_host_form(q.cx->sel, q.stream, k, out, n_out, both);
 }
 
 int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,
@@ -312,24 +273,11 @@ int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint3
     TopSource q;
     rc = open_source(s, first, nmetrics, q);
     if (rc) return rc;
-    TopCtx *cx = q.cx;
-    std::lock_guard<std::mutex> g(cx->mu);
-    rc = result_blocks(cx, k);
-    if (rc) return rc;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3 && rc == LH_OK; i++)
-        if (hipEventCreate(&ev[i]) != hipSuccess) rc = LH_EDEVICE;
-    if (rc == LH_OK)
-        rc = enqueue(q, first, nmetrics, by, arg, k, flags, reinterpret_cast<lh_top_entry *>(cx->res.d_res),
-                     reinterpret_cast<uint32_t *>(cx->res.d_res + k * sizeof(lh_top_entry)), ev);
-    if (rc == LH_OK && (hipStreamSynchronize(q.stream) != hipSuccess || hipEventElapsedTime(score_ms, ev[0], ev[1]) != hipSuccess ||
-                        hipEventElapsedTime(select_ms, ev[1], ev[2]) != hipSuccess))
-        rc = LH_EDEVICE;
-    if (rc == LH_OK) cx->guard.covered();
-    for (int i = 0; i < 3; i++)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (rc == LH_EDEVICE) (void)hipGetLastError();
-    return rc;
+    std::lock_guard<std::mutex> g(q.cx->mu);
+    const auto both = [&](lh_top_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+        return enqueue(q, first, nmetrics, by, arg, k, flags, d_out, d_n_out, ev);
+    };
+    return select_passes_ms<lh_top_entry>(q.cx->sel, q.stream, k, score_ms, select_ms, both);
 }
 
 } // extern "C"

@@ -37,6 +37,28 @@ def _stream_handle(stream) -> int:
     raise TypeError(f"not a stream: {type(stream)!r}")
 
 
+def _out_arrays(out: dict, spec):
+    """out= of spread / compare, a dict of per-name output arrays, against spec = (key, element width, elements or None:
+    not measured) per output in the library's order -> (the library's pointer arguments, device form?)."""
+    if not out or set(out) - {k for k, _, _ in spec}:
+        raise ValueError("out holds some of " + ", ".join(k for k, _, _ in spec))
+    device = [hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()]
+    if any(device) != all(device):
+        raise ValueError("out holds device tensors or host arrays, not both")
+    args = []
+    for k, width, n in spec:
+        t = out.get(k)
+        if t is not None and n is not None:
+            if hasattr(t, "data_ptr"):
+                ok = t.element_size() == width and int(t.numel()) == n and t.is_contiguous()
+            else:
+                ok = isinstance(t, np.ndarray) and t.itemsize == width and t.size == n and t.flags.c_contiguous
+            if not ok:
+                raise ValueError(f"out[{k!r}] holds {n} contiguous elements of {width} bytes")
+        args.append(_ptr(t))
+    return args, all(device)
+
+
 class Snapshot:
     """One interval's cells, stolen at the epoch flip (metrics.go:460-463)."""
 
@@ -376,25 +398,10 @@ class Snapshot:
             nmetrics = self.engine.num_metrics() - first
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
         np_ = int(p.size)
-        if out is not None:
-            if not out or set(out) - {k for k, _, _ in self._SPREAD_OUT}:
-                raise ValueError("out holds some of count, sum, m2, pkeys, pvalid, count_le, sum_le")
-            device = [hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()]
-            if any(device) != all(device):
-                raise ValueError("out holds device tensors or host arrays, not both")
-            args = []
-            for k, width, per_p in self._SPREAD_OUT:
-                t = out.get(k)
-                if t is not None and not (per_p and np_ == 0):
-                    n = nmetrics * np_ if per_p else nmetrics
-                    if hasattr(t, "data_ptr"):
-                        ok = t.element_size() == width and int(t.numel()) == n and t.is_contiguous()
-                    else:
-                        ok = isinstance(t, np.ndarray) and t.itemsize == width and t.size == n and t.flags.c_contiguous
-                    if not ok:
-                        raise ValueError(f"out[{k!r}] holds {n} contiguous elements of {width} bytes")
-                args.append(_ptr(t))
-            if all(device):
+        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
+            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
+                                             for k, width, per_p in self._SPREAD_OUT])
+            if device:
                 N.check(L.lh_spread_device(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread_device")
                 return dict(out)
             N.check(L.lh_spread(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread")
@@ -420,11 +427,15 @@ class Snapshot:
             if "sum_le" in res and "count_le" in res:
                 res["mean_le"] = res["sum_le"] / res["count_le"].view(np.uint64).astype(np.float64)
         if "pkeys" in res and "pvalid" in res:
-            if getattr(self.engine, "_decompress_table", None) is None:
-                self.engine._decompress_table = self.engine.codec_tables()[1]
             bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
-            res["upper"] = np.where(res["pvalid"] != 0, self.engine._decompress_table[bins], np.nan)
+            res["upper"] = np.where(res["pvalid"] != 0, self._decompress_table()[bins], np.nan)
         return res
+
+    def _decompress_table(self) -> np.ndarray:
+        """decompress() by bin (the engine's codec_tables), fetched once per engine."""
+        if getattr(self.engine, "_decompress_table", None) is None:
+            self.engine._decompress_table = self.engine.codec_tables()[1]
+        return self.engine._decompress_table
 
     # -- the k names that lead (a selection across names; what is ranked is what extract / count_le return) ---------------
     _TOP_BY = {"count": N.TOP_BY_COUNT, "sum": N.TOP_BY_SUM, "percentile": N.TOP_BY_PERCENTILE,
@@ -440,31 +451,37 @@ class Snapshot:
         out = a contiguous numpy array of at least k TOP_ENTRY elements takes the host form into it (its first n_out
         entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
         k * 32 and 4 bytes takes the device form: enqueued on the snapshot's stream, the pair is returned as it is."""
+        return self._leaders("lh_top", (self._h,), self._TOP_BY, ("percentile", "count_above"), "TOP_ENTRY", k, by, arg,
+                             N.TOP_ASCENDING if ascending else 0, nmetrics, first, out)
+
+    def _leaders(self, fn, handles, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out):
+        """top / movers: the k leaders of [first, first+nmetrics) from library call `fn` (host form) or fn + "_device", whose
+        arguments begin with `handles`.  by_codes: the names `by` takes -> the library's; takes_arg: those that need an
+        arg; entry: the name of the entry dtype in N."""
         L = N.lib()
         if nmetrics is None:
             nmetrics = self.engine.num_metrics() - first
-        if by not in self._TOP_BY:
-            raise ValueError("by is one of " + ", ".join(self._TOP_BY))
+        if by not in by_codes:
+            raise ValueError("by is one of " + ", ".join(by_codes))
         if arg is None:
-            if by in ("percentile", "count_above"):
+            if by in takes_arg:
                 raise ValueError(f"by={by!r} takes an arg")
             arg = 0.0
-        flags = N.TOP_ASCENDING if ascending else 0
+        dtype = getattr(N, entry)
+        lead = (*handles, first, nmetrics, by_codes[by], float(arg), k, flags)
         if isinstance(out, tuple):
             entries, n = out
-            for t, need in ((entries, k * N.TOP_ENTRY.itemsize), (n, 4)):
+            for t, need in ((entries, k * dtype.itemsize), (n, 4)):
                 if not t.is_contiguous() or t.element_size() * int(t.numel()) < need:
                     raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4")
-            N.check(L.lh_top_device(self._h, first, nmetrics, self._TOP_BY[by], float(arg), k, flags, _ptr(entries), _ptr(n)),
-                    "lh_top_device")
+            N.check(getattr(L, fn + "_device")(*lead, _ptr(entries), _ptr(n)), fn + "_device")
             return out
         if out is None:
-            out = np.zeros(max(k, 1), dtype=N.TOP_ENTRY)
-        elif not (isinstance(out, np.ndarray) and out.dtype == N.TOP_ENTRY and out.size >= k and out.flags.c_contiguous):
-            raise ValueError("out holds at least k contiguous TOP_ENTRY elements")
+            out = np.zeros(max(k, 1), dtype=dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size >= k and out.flags.c_contiguous):
+            raise ValueError(f"out holds at least k contiguous {entry} elements")
         n = C.c_size_t(0)
-        N.check(L.lh_top(self._h, first, nmetrics, self._TOP_BY[by], float(arg), k, flags, out.ctypes.data,
-                         C.addressof(n)), "lh_top")
+        N.check(getattr(L, fn)(*lead, out.ctypes.data, C.addressof(n)), fn)
         return out.reshape(-1)[:n.value]
 
     # -- distribution shift against another snapshot (percentile()'s bucket walk, metrics.go:389-418, over two rows at once) --
@@ -488,23 +505,8 @@ class Snapshot:
         if nmetrics is None:
             nmetrics = self.engine.num_metrics() - first
         if out is not None:
-            if not out or set(out) - {k for k, _, _ in self._COMPARE_OUT}:
-                raise ValueError("out holds some of count_a, count_b, ks, key, below_a, below_b, w1, shift")
-            device = [hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()]
-            if any(device) != all(device):
-                raise ValueError("out holds device tensors or host arrays, not both")
-            args = []
-            for k, width, _ in self._COMPARE_OUT:
-                t = out.get(k)
-                if t is not None:
-                    if hasattr(t, "data_ptr"):
-                        ok = t.element_size() == width and int(t.numel()) == nmetrics and t.is_contiguous()
-                    else:
-                        ok = isinstance(t, np.ndarray) and t.itemsize == width and t.size == nmetrics and t.flags.c_contiguous
-                    if not ok:
-                        raise ValueError(f"out[{k!r}] holds {nmetrics} contiguous elements of {width} bytes")
-                args.append(_ptr(t))
-            if all(device):
+            args, device = _out_arrays(out, [(k, width, nmetrics) for k, width, _ in self._COMPARE_OUT])
+            if device:
                 N.check(L.lh_compare_device(base._h, self._h, first, nmetrics, 0, *args), "lh_compare_device")
                 return dict(out)
             N.check(L.lh_compare(base._h, self._h, first, nmetrics, 0, *args), "lh_compare")
@@ -519,9 +521,7 @@ class Snapshot:
                     "lh_compare")
             res = {k: v[:nmetrics] for k, v in res.items()}
         if "key" in res:
-            if getattr(self.engine, "_decompress_table", None) is None:
-                self.engine._decompress_table = self.engine.codec_tables()[1]
-            value = self.engine._decompress_table[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
+            value = self._decompress_table()[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
             res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
         return res
 
@@ -542,32 +542,8 @@ class Snapshot:
         entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
         k * 32 and 4 bytes takes the device form: enqueued on this snapshot's stream (`base` must stay unreleased until
         that stream has passed the call), the pair is returned as it is."""
-        L = N.lib()
-        if nmetrics is None:
-            nmetrics = self.engine.num_metrics() - first
-        if by not in self._MOVERS_BY:
-            raise ValueError("by is one of " + ", ".join(self._MOVERS_BY))
-        if arg is None:
-            if by == "percentile":
-                raise ValueError(f"by={by!r} takes an arg")
-            arg = 0.0
-        flags = N.MOVERS_ASCENDING if ascending else 0
-        if isinstance(out, tuple):
-            entries, n = out
-            for t, need in ((entries, k * N.MOVER_ENTRY.itemsize), (n, 4)):
-                if not t.is_contiguous() or t.element_size() * int(t.numel()) < need:
-                    raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4")
-            N.check(L.lh_movers_device(base._h, self._h, first, nmetrics, self._MOVERS_BY[by], float(arg), k, flags, _ptr(entries),
-                                       _ptr(n)), "lh_movers_device")
-            return out
-        if out is None:
-            out = np.zeros(max(k, 1), dtype=N.MOVER_ENTRY)
-        elif not (isinstance(out, np.ndarray) and out.dtype == N.MOVER_ENTRY and out.size >= k and out.flags.c_contiguous):
-            raise ValueError("out holds at least k contiguous MOVER_ENTRY elements")
-        n = C.c_size_t(0)
-        N.check(L.lh_movers(base._h, self._h, first, nmetrics, self._MOVERS_BY[by], float(arg), k, flags, out.ctypes.data,
-                            C.addressof(n)), "lh_movers")
-        return out.reshape(-1)[:n.value]
+        return self._leaders("lh_movers", (base._h, self._h), self._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
+                             N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out)
 
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).

@@ -286,6 +286,17 @@ def test_range_errors_and_the_empty_call(crafted):
     assert int(cnt.cpu()[0]) == 0
 
 
+def test_the_timing_hook_runs_both_passes(crafted):
+    import ctypes as C
+    snap = crafted.snap
+    before = snap.top(20, "sum", None, False, M_BIG).copy()
+    a, b = C.c_float(-1.0), C.c_float(-1.0)
+    assert N.lib().lh_tool_top_passes_ms(snap._h, 0, M_BIG, N.TOP_BY_SUM, 0.0, 20, 0, C.byref(a), C.byref(b)) == 0
+    assert a.value > 0 and b.value > 0
+    run(snap, crafted.ref, "sum", None, 20)                                              # the unit's blocks are as they were
+    assert snap.top(20, "sum", None, False, M_BIG).tobytes() == before.tobytes()
+
+
 # ---- ties across the cut ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bits", BITS)
 def test_a_tie_group_that_straddles_the_cut(native_lib, torch_cuda, bits):
@@ -427,6 +438,31 @@ def test_crafted_rows_in_32_bit_cells(narrow):
     at = {int(e["id"]): int(oracle.key_to_bin(int(e["pkey"]))) for e in got}
     assert (at[30], at[31], at[32]) == (40300, 40256, kb(50))
     assert snap.device_cells()[2] == 4                                               # a snapshot of 32-bit cells stays one
+
+
+# ---- two engines on one device: two streams, one records block -------------------------------------------------------------
+def test_the_records_block_regrows_behind_a_pending_device_form_call(native_lib, torch_cuda):
+    """A device-form call on a snapshot of 300 names, then -- nothing waited for -- a host-form call on another engine's
+    snapshot of 4 100 names: just past the records block's floor of 4 096, so the block the first call's passes may still be
+    using is freed and allocated again (in a process whose calls so far stayed below the floor: every test above does).
+    Both results are what the same calls return afterwards, with nothing in flight."""
+    torch, k = torch_cuda, 50
+    with engine(300) as e1, engine(4100) as e2:
+        e1.submit_pairs(*stream(31, 300, 30_000))
+        e2.submit_pairs(*stream(32, 4100, 40_000))
+        with e1.flip() as s1, e2.flip() as s2:
+            assert s1.stream() != s2.stream()
+            ent = torch.full((k * 32,), 0x77, dtype=torch.uint8, device="cuda")
+            cnt = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            s1.top(k, "sum", None, False, 300, out=(ent, cnt))
+            large = s2.top(k, "sum", None, False, 4100).copy()
+            torch.cuda.ExternalStream(s1.stream()).synchronize()
+            small = ent.cpu().numpy().view(N.TOP_ENTRY)[:int(cnt.cpu()[0])]
+            torch.cuda.synchronize()
+            assert small.size == large.size == k
+            assert small.tobytes() == s1.top(k, "sum", None, False, 300).tobytes()
+            assert large.tobytes() == s2.top(k, "sum", None, False, 4100).tobytes()
 
 
 # ---- more records than one tile of the select pass ---------------------------------------------------------------------
