@@ -529,6 +529,56 @@ int lh_movers(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetri
               uint32_t flags, lh_mover_entry *out, size_t *n_out);
 int lh_movers_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
                      uint32_t flags, lh_mover_entry *d_out, uint32_t *d_n_out);
+/* Stats and percentiles of a name over SEVERAL snapshots at once: "p99 over the last 10 seconds while emitting every second",
+ * or one answer over the ranks and engines of one device.  Counts add across intervals (lh_count_le) and percentiles do not:
+ * a percentile over K intervals needs the K rows of cells added together and walked once.  The rows are already side by side
+ * in device memory (num_buffers >= K + 1 keeps K snapshots alive; an engine has at most 16 buffers, so a list of 16 takes
+ * snapshots of more than one engine, or one of them twice), so the walk of lh_compare* is taken over up to
+ * LH_MAX_ACROSS rows and gives what lh_extract_rows gives, for the summed row.  Nothing is summed across names, no cell is
+ * written and no new statistic is defined: the sum is over time (or ranks) for ONE name, the cell atomic.AddUint64 would have
+ * left had the samples arrived in one interval (metrics.go:278, 292).
+ * With c_i[b] the cells of metric first + m in snaps[i] and C[b] = sum over i of c_i[b], taken in 64 bits (two narrow cells
+ * of 0xffffffff give 0x1fffffffe, not a 32-bit wrap), and D[b] bit for bit the D[] of lh_codec_tables:
+ *   count[m]         sum of C[b] (uint64; wraps past 2^64 as the reference's would)
+ *   sum[m]           sum of D[b] * float64(C[b]) (metrics.go:344), in one fixed order: it does not depend on timing (it may
+ *                    differ in the last bits between calls that cover different numbers of rows, which use differently shaped
+ *                    kernels, and from lh_stats.sum)
+ *   nbuckets[m]      the number of bins with C[b] != 0
+ *   present_bits[m]  bit i set iff snaps[i] holds at least one sample of the name
+ *   pkeys[m * np + i], pvalid[m * np + i]   the bucket percentile() selects on C (metrics.go:389-418): the first bin whose
+ *                    inclusive prefix count reaches T = min{s in [1, count] : float64(s) / float64(count) >= p[i]} -- bit
+ *                    for bit what lh_extract_rows returns for a snapshot that holds C (p unsorted, repeated, 0, 1, > 1 or NaN
+ *                    included: the last two have no bucket, pvalid 0 and key 0)
+ *   count == 0: sum 0, nbuckets 0, present_bits 0, every pvalid and key 0.
+ *   1 <= nsnaps <= LH_MAX_ACROSS.  A snapshot may appear more than once and counts that often; nsnaps == 1 gives that
+ *   snapshot's own lh_extract_rows keys.  np <= LH_MAX_PERCENTILES; np == 0 is allowed: the two per-percentile outputs are
+ *   ignored.  Any output may be NULL, but not all of them.  flags must be 0.  nmetrics == 0 -> LH_OK, nothing written.
+ *   Totals that wrap past 2^64: count wraps, the percentile outputs are unspecified (nothing faults).
+ *   LH_EINVAL, checked on the host before any snapshot or a device is touched: NULL snaps or a NULL entry; nsnaps 0 or too
+ *            large; np too large; np > 0 with NULL p; all outputs NULL; unknown flag bits; arrays not aligned to their
+ *            element size.
+ *   LH_ERANGE: an nmetrics above 2^32 - 1 before anything is looked at (a cause of LH_EINVAL wins over it); first + nmetrics
+ *            beyond the rows of ANY snapshot (the engines may have different max_metrics).
+ *   Snapshots on different devices -> LH_EINVAL (after all were opened).
+ * THE WINDOW IS BOUNDED BY DEVICE MEMORY, not by this call: K snapshots must be alive at once, and at 8 192 names a buffer of
+ * 64-bit cells is 4 GiB, at 65 536 names a narrow one 16 GiB.  LH_MAX_ACROSS = 16 is for small and mid name counts and
+ * roll-ups of 1 s into 10 s; a minute of history belongs in imports (lh_snapshot_add_buckets*).
+ * ORDERING: the work is enqueued on lh_snapshot_stream(snaps[nsnaps - 1]); for every other distinct stream of the list an
+ * event recorded there is waited for first.  No snapshot of the list may be released before that stream has passed the call
+ * (lh_across_device; lh_across has waited already when it returns).  One thread per snapshot, as for the other readers.
+ * READ-ONLY: no cell, span or cell width of any snapshot changes; every snapshot is read at its own width through
+ * lh_snapshot_cells, 4 or 8 bytes, in any mixture.
+ * Staging as for lh_spread*: lh_across returns when the results are in the caller's arrays (pinned arrays receive them by
+ * one copy each, others go through a pinned block of the library's); lh_across_device takes device arrays and returns after
+ * enqueueing (the first call on a device also generates the unit's copy of D[] and waits for it once).  p is a HOST array in
+ * both forms and travels by value.  One set of staging blocks per DEVICE behind the unit's own mutex: calls take turns. */
+#define LH_MAX_ACROSS 16
+int lh_across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np,
+              uint32_t flags, uint64_t *count, double *sum, uint32_t *nbuckets, uint32_t *present_bits, int16_t *pkeys,
+              uint8_t *pvalid);
+int lh_across_device(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                     uint32_t flags, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets, uint32_t *d_present_bits,
+                     int16_t *d_pkeys, uint8_t *d_pvalid);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

@@ -25,6 +25,7 @@ TOP_BY_COUNT, TOP_BY_SUM, TOP_BY_PERCENTILE, TOP_BY_COUNT_ABOVE = range(4)
 TOP_ASCENDING = 1
 MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   # lh_movers* (k <= MAX_TOP)
 MOVERS_ASCENDING = 1
+MAX_ACROSS = 16        # lh_across*: snapshots of one call
 
 OK, EINVAL, ENOMEM, EDEVICE, ENODEVICE, EBUSY, ERANGE, ESTATE = range(8)
 
@@ -158,6 +159,7 @@ TUNING_SIGNATURES = {
     "lh_tool_count_le_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_spread_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_compare_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_across_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
@@ -225,6 +227,8 @@ SIGNATURES = {
     "lh_compare_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_movers": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_movers_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
+    "lh_across": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_across_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

@@ -1,0 +1,508 @@
+// lh_across.hip -- lh_across* (include/loghisto_gpu.h): count, sum, nbuckets and the percentile buckets of a name over SEVERAL
+// snapshots at once -- p99 over the last 10 seconds while emitting every second, or over the ranks and engines of one device.
+// Counts add across intervals and percentiles do not (that is why lh_count_le exists): a percentile over K intervals needs
+// the K rows of cells added together and walked once.  With c_i[b] the cells of the name in snaps[i]:
+//   C[b] = sum over i of c_i[b], in 64 bits -- the cell atomic.AddUint64 would have left had the samples arrived in one
+//          interval (metrics.go:278, 292); two narrow cells of 0xffffffff give 0x1fffffffe
+//   count = sum of C[b]        sum = sum of D[b] * float64(C[b])  (metrics.go:344)        nbuckets = bins with C[b] != 0
+//   present_bits: bit i set iff snaps[i] holds a sample of the name
+//   per percentile the bucket percentile() selects on C (metrics.go:389-418): the first bin whose inclusive prefix reaches
+//   pct_threshold(p, count) -- bit for bit what lh_extract_rows returns for a snapshot that holds C.
+// Nothing is summed across names, no cell is written and no new statistic is defined.
+//
+// Built BESIDE the engine, on its public C ABI only (lh_beside.h), like lh_spread.hip, whose two shapes these are:
+//   k_across_wave   one WAVE per row, 256 bins per step (4 consecutive bins per lane).  For calls of many rows.
+//   k_across_block  one WORKGROUP of 16 waves per row: the waves reduce the 256-bin chunks independently, wave 0 scans the
+//                   chunk totals in LDS, and each percentile then costs one more read of the one chunk its threshold falls
+//                   into.  For calls of few rows, which may span all 65 536 bins.
+// The snapshots travel as ONE by-value record (AcrossSnaps: 16 row-0 addresses, 16 span addresses, their number and a mask
+// of the narrow ones).  A wave opens a name by having lane i read snapshot i's own span and work out the address of its
+// row (Rows); the walk then runs over the UNION of the spans, from the least lo aligned down to a multiple of 4 to the
+// largest hi, and takes snapshot i's span and address out of lane i (v_readlane: scalar registers, no array of 16 in
+// anybody's registers).  A row is only read inside its OWN span (or_empty's, by load4_in's rule; the loads are this unit's
+// own because of what fetch4 says): a name never marked in some snapshot has lo > hi there, and nothing of it is read.
+// Per step and lane the 16-byte loads of IN_FLIGHT snapshots are issued back to back and only then added up, so they are
+// under way together; lanes n .. of a last, partial set hold empty spans and ask for nothing.
+// Three builds of each shape: every snapshot narrow (uint32 cells), every snapshot wide, or a mixture -- there the width is
+// a wave-uniform branch per snapshot, and both arms leave the loaded 16 / 32 bytes as they came (unpacked when they are
+// added), so that no arm has to wait for its load.
+// Each row takes two walks.  Walk 1 gives count, sum, nbuckets and present_bits, hence the thresholds; walk 2 re-reads the
+// windows (L2-resident at typical spans) up to the step the last threshold falls into.  The sum is taken in a fixed order
+// (per lane over the steps in ascending order, then one DPP tree over the lanes; chunk totals in ascending order): a
+// result does not depend on timing -- the two shapes associate differently and agree to rounding only.
+// Read-only: no store goes to a cell, a span or any engine.
+#include "../../include/loghisto_gpu.h"
+#include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
+#include "lh_codec.h"
+#include "lh_wave.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <mutex>
+
+namespace {
+
+using namespace lh; // (lh_wave.h)
+using namespace lh::beside;
+
+// Rows of a call from which a row gets a wave, not a workgroup: lh_spread's default, whose walks these are
+// (profiles/across.txt).
+constexpr uint32_t AC_WAVE_FROM_DEFAULT = 1024;
+static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
+static_assert(LH_MAX_ACROSS <= 32, "a snapshot per lane, their set in one 32-bit mask");
+
+constexpr uint32_t IN_FLIGHT = 8; // snapshots whose loads a lane has under way together
+static_assert(LH_MAX_ACROSS % IN_FLIGHT == 0 && LH_MAX_ACROSS <= 64, "the lanes of a last, partial set exist");
+
+enum { ALL_NARROW = 0, ALL_WIDE = 1, MIXED = 2 };
+
+struct AcrossP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
+
+struct AcrossSnaps { // by value in the kernel arguments (264 bytes)
+    const void *cells[LH_MAX_ACROSS];      // row `first` of snapshot i, at the snapshot's own width
+    const uint32_t *ranges[LH_MAX_ACROSS]; // the span of row `first`
+    uint32_t n, narrow;                    // bit i of narrow: snapshot i has 4-byte cells
+};
+
+struct AcrossOut {
+    u64 *count;
+    double *sum;
+    uint32_t *nbuckets, *present;
+    int16_t *pkeys;
+    uint8_t *pvalid;
+};
+
+// 16 bytes of a row as they lie in memory (4-byte aligned at least), through a pointer that says GLOBAL: an address taken out
+// of a lane is an integer, and a load through a generic pointer made of it would be a flat one, which every LDS wait then
+// waits for too
+typedef uint32_t u32x4_a4v __attribute__((ext_vector_type(4), aligned(4)));
+typedef const __attribute__((address_space(1))) u32x4_a4v *gcells;
+
+// One name in the n snapshots, as a wave holds it: lane i has snapshot i's own span (or_empty; lanes from n on: empty) and
+// the address of its row; every lane has the union.
+struct Rows {
+    uint32_t lo, hi;
+    u64 row;
+    uint32_t base0, uhi; // base0 == NO_BIN: the name was never marked in any of them
+};
+template <int MODE> __device__ __forceinline__ Rows open_rows(const AcrossSnaps &s, uint32_t m, size_t stride, uint32_t lane)
+{
+    Rows r;
+    r.lo = NO_BIN;
+    r.hi = 0;
+    r.row = 0;
+    if (lane < s.n) {
+        const Span sp = or_empty(own_span(s.ranges[lane], m));
+        const bool narrow = MODE == ALL_NARROW || (MODE == MIXED && ((s.narrow >> lane) & 1u));
+        r.lo = sp.lo;
+        r.hi = sp.hi;
+        r.row = (u64)(uintptr_t)s.cells[lane] + (u64)m * stride * (narrow ? 4u : 8u);
+    }
+    r.base0 = ~wave_max_u32(~r.lo); // the least lo (NO_BIN's complement is 0)
+    r.uhi = wave_max_u32(r.hi);
+    return r;
+}
+
+// What a lane has under way of one snapshot: the 16 bytes of four narrow cells, or the 32 of four wide ones, AS THEY CAME,
+// each load's four words one value -- widening them (or moving single words) inside the guarded load would make every
+// load wait for itself.
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+template <int MODE> struct Raw { u32x4v a, b; }; // (b: bins 2 and 3 of wide cells; unused, and gone, in the narrow build)
+// bins b0 .. b0 + 3 of the name in snapshot i (wave-uniform i), zeros outside its own span (load4_in's rule: b0 a multiple
+// of 4 at or above the span's lo aligned down, and at or below its hi <= 65 535, so the group ends inside the row)
+template <int MODE> __device__ __forceinline__ void fetch4(const Rows &r, uint32_t narrow, uint32_t i, uint32_t b0, Raw<MODE> &x)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)r.lo, (int)i);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)r.hi, (int)i);
+    const u64 row = readlane_u64(r.row, i);
+    x.a = 0;
+    x.b = 0;
+    if (b0 >= lo && b0 <= hi) {
+        if (MODE == ALL_NARROW || (MODE == MIXED && ((narrow >> i) & 1u))) { // wave-uniform
+            x.a = *(gcells)(row + 4ull * b0);
+        } else {
+            const gcells rp = (gcells)(row + 8ull * b0);
+            x.a = rp[0];
+            x.b = rp[1];
+        }
+    }
+}
+// (the empty asm keeps the compiler from moving the widening up into fetch4's guarded region)
+template <int MODE> __device__ __forceinline__ void unpack4(Raw<MODE> &x, uint32_t narrow, uint32_t i, u64 (&c)[4])
+{
+    asm volatile("" : "+v"(x.a));
+    if (MODE != ALL_NARROW) asm volatile("" : "+v"(x.b));
+    if (MODE == ALL_NARROW || (MODE == MIXED && ((narrow >> i) & 1u))) {
+        c[0] = x.a.x; c[1] = x.a.y; c[2] = x.a.z; c[3] = x.a.w;
+    } else {
+        c[0] = (u64)x.a.x | (u64)x.a.y << 32; c[1] = (u64)x.a.z | (u64)x.a.w << 32;
+        c[2] = (u64)x.b.x | (u64)x.b.y << 32; c[3] = (u64)x.b.z | (u64)x.b.w << 32;
+    }
+}
+// C[b0 .. b0 + 3]: the lane's four bins summed over the snapshots in list order, in 64 bits.  SEEN: bit i of `seen` is set
+// when snapshot i has a sample in them.
+template <int MODE, bool SEEN>
+__device__ __forceinline__ void sum_rows(const Rows &r, uint32_t n, uint32_t narrow, uint32_t b0, u64 (&C)[4], uint32_t &seen)
+{
+    C[0] = C[1] = C[2] = C[3] = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += IN_FLIGHT) { // wave-uniform
+        Raw<MODE> x[IN_FLIGHT];
+#pragma unroll
+        for (uint32_t j = 0; j < IN_FLIGHT; j++) fetch4<MODE>(r, narrow, i0 + j, b0, x[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < IN_FLIGHT; j++) {
+            u64 c[4];
+            unpack4<MODE>(x[j], narrow, i0 + j, c);
+            if (SEEN) seen |= (((c[0] | c[1]) | (c[2] | c[3])) != 0 ? 1u : 0u) << (i0 + j);
+#pragma unroll
+            for (int k = 0; k < 4; k++) C[k] += c[k];
+        }
+    }
+}
+// the value table's entries of bins b0 .. b0 + 3; a lane whose group starts beyond hi asks for nothing
+__device__ __forceinline__ void load4_values(const double *__restrict__ D, uint32_t b0, uint32_t hi, double (&d)[4])
+{
+    d[0] = d[1] = d[2] = d[3] = 0.0;
+    if (b0 <= hi) {
+        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
+        const f64x2_a8 d01 = dp[0], d23 = dp[1];
+        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
+    }
+}
+__device__ __forceinline__ uint32_t occupied4(const u64 (&C)[4])
+{
+    return (C[0] ? 1u : 0u) + (C[1] ? 1u : 0u) + (C[2] ? 1u : 0u) + (C[3] ? 1u : 0u);
+}
+// The bin, inside a step of 256, of the first inclusive prefix that reaches T (wave-uniform T).  pre[k]: the prefix at the
+// lane's bin k.  The caller knows that the step's last prefix reaches T; with a total that wrapped none may, and the answer
+// is then unspecified (lane 63's group).
+__device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
+{
+    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
+    const uint32_t f = reach ? (uint32_t)__builtin_ctzll(reach) : 63u;
+    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
+    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
+                                                          const double *__restrict__ D, const AcrossP pa, uint32_t np,
+                                                          const AcrossOut o)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nmetrics) return; // wave-uniform
+    const Rows r = open_rows<MODE>(s, m, stride, lane);
+    const uint32_t hi = r.uhi;
+    u64 total = 0;
+    double sum = 0.0;
+    uint32_t nb = 0, present = 0, none = 0;
+    uint32_t found = NO_BIN; // lane i < np: the bin of percentile i
+    if (r.base0 != NO_BIN) { // wave-uniform
+        u64 C[4];
+        // ---- walk 1: count, sum, the occupied bins and who has a sample
+        {
+            u64 cnt = 0;
+            double ps = 0.0, d[4], t[4];
+            uint32_t occ = 0, seen = 0;
+            for (uint32_t base = r.base0; base <= hi; base += STEP) {
+                load4_values(D, base + 4 * lane, hi, d);
+                sum_rows<MODE, true>(r, s.n, s.narrow, base + 4 * lane, C, seen);
+                cnt += sum4(C);
+                ps += terms4(C, d, t);
+                occ += occupied4(C);
+            }
+            total = readlane_u64(wave_scan_incl_u64(cnt), 63);
+            sum = readlane_f64(wave_scan_incl_f64(ps), 63);
+            nb = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl_u32(occ), 63);
+            present = wave_or_u32(seen);
+        }
+        if (total) { // wave-uniform
+            // ---- walk 2: up to the step the last threshold falls into
+            u64 T = PCT_NONE;
+            if (lane < np) T = pct_threshold(pa.p[lane], total);
+            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
+            u64 carry = 0;
+            for (uint32_t base = r.base0; base <= hi && todo; base += STEP) {
+                sum_rows<MODE, false>(r, s.n, s.narrow, base + 4 * lane, C, none);
+                const u64 tc = sum4(C);
+                const u64 inc = wave_scan_incl_u64(tc);
+                const u64 end = carry + readlane_u64(inc, 63);
+                // (every open threshold is > carry: it would have ended in an earlier step otherwise)
+                uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= end) & todo;
+                todo &= ~here;
+                if (here) {
+                    u64 pre[4], sofar = carry + (inc - tc);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        sofar += C[k];
+                        pre[k] = sofar;
+                    }
+                    for (; here; here &= here - 1) {
+                        const uint32_t i = (uint32_t)__builtin_ctz(here);
+                        const uint32_t idx = find_in_step(pre, readlane_u64(T, i));
+                        if (lane == i) found = base + idx;
+                    }
+                }
+                carry = end;
+            }
+        } else {
+            sum = 0.0;
+            nb = 0;
+            present = 0;
+        }
+    }
+    if (lane == 0) {
+        if (o.count) o.count[m] = total;
+        if (o.sum) o.sum[m] = sum;
+        if (o.nbuckets) o.nbuckets[m] = nb;
+        if (o.present) o.present[m] = present;
+    }
+    if (lane < np) {
+        const size_t at = (size_t)m * np + lane;
+        const bool ok = found != NO_BIN;
+        if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(found) : (int16_t)0;
+        if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
+                                                        const double *__restrict__ D, const AcrossP pa, uint32_t np,
+                                                        const AcrossOut o)
+{
+    __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
+    __shared__ double s_sum[CHUNKS]; // the chunks' sums, then their exclusive prefix (ascending order)
+    __shared__ uint32_t s_occ[WG_WAVES], s_seen[WG_WAVES];
+    __shared__ u64 s_total;
+    __shared__ double s_tsum;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
+    if (m >= nmetrics) return;
+    const Rows r = open_rows<MODE>(s, m, stride, lane); // (every wave for itself)
+    const uint32_t hi = r.uhi, base0 = r.base0;
+    const uint32_t nchunks = base0 != NO_BIN ? (hi - base0) / STEP + 1 : 0; // <= CHUNKS
+    uint32_t none = 0;
+    // ---- walk 1: every chunk's count and sum
+    {
+        uint32_t occ = 0, seen = 0;
+        for (uint32_t ch = wave; ch < nchunks; ch += WG_WAVES) { // wave-uniform
+            u64 C[4];
+            double d[4], t[4];
+            load4_values(D, base0 + ch * STEP + 4 * lane, hi, d);
+            sum_rows<MODE, true>(r, s.n, s.narrow, base0 + ch * STEP + 4 * lane, C, seen);
+            const u64 inc = wave_scan_incl_u64(sum4(C));
+            const double incs = wave_scan_incl_f64(terms4(C, d, t));
+            occ += occupied4(C);
+            if (lane == 63) {
+                s_cnt[ch] = inc;
+                s_sum[ch] = incs;
+            }
+        }
+        occ = wave_scan_incl_u32(occ);
+        seen = wave_or_u32(seen);
+        if (lane == 63) {
+            s_occ[wave] = occ;
+            s_seen[wave] = seen;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        u64 v[4];
+        double w[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const bool in = 4 * lane + k < nchunks;
+            v[k] = in ? s_cnt[4 * lane + k] : 0;
+            w[k] = in ? s_sum[4 * lane + k] : 0.0;
+        }
+        const u64 tv = (v[0] + v[1]) + (v[2] + v[3]);
+        const u64 inc = wave_scan_incl_u64(tv);
+        const double incs = wave_scan_incl_f64(((w[0] + w[1]) + w[2]) + w[3]);
+        const double up = __shfl_up(incs, 1, 64); // what the lanes below add up to
+        u64 ex = inc - tv;
+        double exs = lane ? up : 0.0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            s_cnt[4 * lane + k] = ex;
+            s_sum[4 * lane + k] = exs;
+            ex += v[k];
+            exs += w[k];
+        }
+        if (lane == 63) {
+            s_total = inc;
+            s_tsum = incs;
+        }
+    }
+    __syncthreads();
+    const u64 total = s_total;
+    if (threadIdx.x == 0) {
+        uint32_t nb = 0, present = 0;
+        for (int w = 0; w < WG_WAVES; w++) { // (a wave without a chunk left 0)
+            nb += s_occ[w];
+            present |= s_seen[w];
+        }
+        if (o.count) o.count[m] = total;
+        if (o.sum) o.sum[m] = total ? s_tsum : 0.0;
+        if (o.nbuckets) o.nbuckets[m] = total ? nb : 0;
+        if (o.present) o.present[m] = total ? present : 0;
+    }
+    // ---- a wave per percentile (wave-uniform throughout): the chunk its threshold falls into, read once more
+    for (uint32_t i = wave; i < np; i += WG_WAVES) {
+        uint32_t bin = NO_BIN;
+        const u64 T = total ? pct_threshold(pa.p[i], total) : PCT_NONE;
+        if (T != PCT_NONE) {
+            // the last chunk with fewer than T samples below it (chunk 0 has none below: there is one)
+            uint32_t nlow = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                nlow += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(4 * lane + k < nchunks && s_cnt[4 * lane + k] < T));
+            const uint32_t ch = nlow - 1;
+            u64 C[4], pre[4];
+            sum_rows<MODE, false>(r, s.n, s.narrow, base0 + ch * STEP + 4 * lane, C, none);
+            const u64 tc = sum4(C);
+            u64 sofar = s_cnt[ch] + (wave_scan_incl_u64(tc) - tc);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                sofar += C[k];
+                pre[k] = sofar;
+            }
+            bin = base0 + ch * STEP + find_in_step(pre, T);
+        }
+        if (lane == 0) {
+            const size_t at = (size_t)m * np + i;
+            const bool ok = bin != NO_BIN;
+            if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(bin) : (int16_t)0;
+            if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+        }
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------
+// Per-device state of this unit (device_ctx<AcrossCtx>).  `mu` is held for the length of a call, the host form's wait for
+// its results included.  `order`: the events that put the last snapshot's stream behind the others'.
+struct AcrossCtx {
+    std::mutex mu;
+    double *d_table = nullptr; // D[LH_NKEYS]
+    hipEvent_t order[LH_MAX_ACROSS] = {};
+    ResultBlocks res;          // host form
+};
+std::atomic<uint32_t> g_wave_from{AC_WAVE_FROM_DEFAULT};
+
+// every check that needs neither a snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
+// nulled here, and count for nothing.
+int check_args(lh_snapshot *const *snaps, size_t nsnaps, size_t nmetrics, const double *p, size_t np, uint32_t flags, AcrossOut &o)
+{
+    if (!snaps || misaligned(snaps, alignof(lh_snapshot *)) || nsnaps == 0 || nsnaps > LH_MAX_ACROSS) return LH_EINVAL;
+    for (size_t i = 0; i < nsnaps; i++)
+        if (!snaps[i]) return LH_EINVAL;
+    if (np > LH_MAX_PERCENTILES || (np && !p) || flags != 0) return LH_EINVAL;
+    if (np == 0) {
+        o.pkeys = nullptr;
+        o.pvalid = nullptr;
+    }
+    if (!o.count && !o.sum && !o.nbuckets && !o.present && !o.pkeys && !o.pvalid) return LH_EINVAL;
+    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.nbuckets, 4) ||
+        misaligned(o.present, 4) || misaligned(o.pkeys, 2))
+        return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    return LH_OK;
+}
+
+typedef lh::beside::Source<AcrossCtx> Source;
+
+// (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on the last snapshot's stream, behind what the others'
+// streams hold
+int enqueue(const Source *q, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np, const AcrossOut &o)
+{
+    const Source &last = q[nsnaps - 1];
+    AcrossCtx *cx = last.cx;
+    hipStream_t from[LH_MAX_ACROSS];
+    for (size_t i = 0; i < nsnaps; i++) from[i] = q[i].stream;
+    int rc = order_behind(cx->order, from, nsnaps, last.stream);
+    if (!rc) rc = ensure_table(cx->d_table, last.stream, lh::k_value_table<AcrossCtx>);
+    if (rc) return rc;
+    AcrossP pa;
+    for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
+    AcrossSnaps s;
+    s.n = (uint32_t)nsnaps;
+    s.narrow = 0;
+    for (size_t i = 0; i < LH_MAX_ACROSS; i++) {
+        const bool in = i < nsnaps;
+        s.cells[i] = in ? static_cast<const unsigned char *>(q[i].cells) + (size_t)first * q[i].stride * q[i].cell_bytes : nullptr;
+        s.ranges[i] = in ? ranges_from(q[i], first) : nullptr;
+        if (in && q[i].cell_bytes == 4) s.narrow |= 1u << i;
+    }
+    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
+    const double *D = cx->d_table;
+    const size_t stride = last.stride; // (lh_row_stride(): one for all)
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    const auto launch = [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (sh.wave) hipLaunchKernelGGL(k_across_wave<MODE>, sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o);
+        else hipLaunchKernelGGL(k_across_block<MODE>, sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o);
+    };
+    if (s.narrow == (1u << nsnaps) - 1u) launch(std::integral_constant<int, ALL_NARROW>());
+    else if (s.narrow == 0) launch(std::integral_constant<int, ALL_WIDE>());
+    else launch(std::integral_constant<int, MIXED>());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+int across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+           AcrossOut o, bool device_form)
+{
+    int rc = check_args(snaps, nsnaps, nmetrics, p, np, flags, o);
+    if (rc) return rc;
+    Source q[LH_MAX_ACROSS];
+    rc = list_cells(snaps, nsnaps, first, nmetrics, q);
+    if (rc) return rc;
+    if (nmetrics == 0) return LH_OK; // before any device call
+    rc = list_open(snaps, nsnaps, q);
+    if (rc) return rc;
+    AcrossCtx *cx = q[nsnaps - 1].cx;
+    std::lock_guard<std::mutex> g(cx->mu);
+    if (device_form) return enqueue(q, nsnaps, first, nmetrics, p, np, o);
+
+    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, the 4-byte ones, the keys, the flags.
+    const size_t per_m = nmetrics, per_p = nmetrics * np;
+    const HostOut out[6] = {{o.count, per_m * 8}, {o.sum, per_m * 8},   {o.nbuckets, per_m * 4},
+                            {o.present, per_m * 4}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
+    return host_results(cx->res, q[nsnaps - 1].stream, out, [&](unsigned char *const(&dev)[6]) {
+        AcrossOut d;
+        d.count = reinterpret_cast<u64 *>(dev[0]);
+        d.sum = reinterpret_cast<double *>(dev[1]);
+        d.nbuckets = reinterpret_cast<uint32_t *>(dev[2]);
+        d.present = reinterpret_cast<uint32_t *>(dev[3]);
+        d.pkeys = reinterpret_cast<int16_t *>(dev[4]);
+        d.pvalid = reinterpret_cast<uint8_t *>(dev[5]);
+        return enqueue(q, nsnaps, first, nmetrics, p, np, d);
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int lh_across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+              uint64_t *count, double *sum, uint32_t *nbuckets, uint32_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
+{
+    const AcrossOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, present_bits, pkeys, pvalid};
+    return across(snaps, nsnaps, first, nmetrics, p, np, flags, o, false);
+}
+
+int lh_across_device(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                     uint32_t flags, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets, uint32_t *d_present_bits,
+                     int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const AcrossOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid};
+    return across(snaps, nsnaps, first, nmetrics, p, np, flags, o, true);
+}
+
+int lh_tool_across_switch(uint32_t wave_from_rows, uint32_t *previous)
+{
+    switch_exchange(g_wave_from, wave_from_rows, AC_WAVE_FROM_DEFAULT, previous);
+    return LH_OK;
+}
+
+} // extern "C"

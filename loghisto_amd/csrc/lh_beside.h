@@ -1,6 +1,6 @@
 // lh_beside.h -- host-only plumbing of the units built BESIDE the engine (lh_import.hip, lh_count.hip, lh_spread.hip, lh_top.hip,
-// lh_compare.hip, lh_movers.hip; a new reader of a snapshot starts here and in lh_wave.h).  Such a unit sees the engine through its public C ABI only
-// (include/loghisto_gpu.h: it cannot see struct lh_engine / lh_snapshot):
+// lh_compare.hip, lh_movers.hip, lh_across.hip; a new reader of a snapshot starts here and in lh_wave.h).  Such a unit sees
+// the engine through its public C ABI only (include/loghisto_gpu.h: it cannot see struct lh_engine / lh_snapshot):
 //   lh_snapshot_cells    the cells AS THEY ARE, 4 or 8 bytes wide (nothing moves: a narrow snapshot stays narrow), and the
 //                        number of rows
 //   lh_snapshot_ranges   the rows' dirty spans [lo, hi] -- cells outside are zero; their address also names the device
@@ -11,10 +11,11 @@
 // What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
 // way a host form's results travel back, the event that guards a block across streams, and the measurement switch's
 // exchange.  For the readers, which all walk rows [first, first + nmetrics): their source record and its two-step opener
-// (Source, source_cells, source_open), the same two steps for a reader of two snapshots (pair_cells, pair_open) with the
-// event that puts one snapshot's stream behind the other's (order_behind), the launch shape (row_shape), the dispatch on
-// the cells' width (with_cells) and the value table's set-up (ensure_table).  A reader itself has its context, its
-// argument checks, its kernels and its entry points; one that selects k names has the rest of its host side in lh_select.h.
+// (Source, source_cells, source_open), the same two steps for a reader of a list of snapshots (list_cells, list_open: two
+// for lh_compare.hip and lh_movers.hip, up to 16 for lh_across.hip) with the events that put the last snapshot's stream
+// behind the others' (order_behind), the launch shape (row_shape), the dispatch on the cells' width (with_cells) and the
+// value table's set-up (ensure_table).  A reader itself has its context, its argument checks, its kernels and its entry
+// points; one that selects k names has the rest of its host side in lh_select.h.
 #pragma once
 
 #include "../../include/loghisto_gpu.h"
@@ -228,34 +229,48 @@ template <class Ctx> int source_open(lh_snapshot *s, Source<Ctx> &q)
     if (rc) return rc;
     return usable(q) ? LH_OK : LH_ESTATE;
 }
-// The two steps for a reader of two snapshots (`a` of base, `b` of cur; the unit's context is b.cx).  Between them a
-// reader whose empty call writes nothing returns (lh_compare.hip); one whose empty call writes n_out takes both first
-// (lh_movers.hip).  Step one: LH_ERANGE for rows either snapshot does not have.
-template <class Ctx>
-int pair_cells(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, Source<Ctx> &a, Source<Ctx> &b)
+// The two steps for a reader of a list of snapshots, q[i] the source of snaps[i]; the work goes on the LAST one's stream and
+// the unit's context is q[n - 1].cx (lh_compare.hip, lh_movers.hip: {base, cur}).  Between the steps a reader whose empty
+// call writes nothing returns (lh_compare.hip, lh_across.hip); one whose empty call writes n_out takes both first
+// (lh_movers.hip).  Step one: LH_ERANGE for rows any of the snapshots does not have, the first in list order.
+template <class Ctx> int list_cells(lh_snapshot *const *snaps, size_t n, uint32_t first, size_t nmetrics, Source<Ctx> *q)
 {
-    const int rc = source_cells(base, first, nmetrics, a);
-    return rc ? rc : source_cells(cur, first, nmetrics, b);
-}
-// Step two: both opened, then LH_EINVAL for two devices (the check that needs both), then LH_ESTATE.
-template <class Ctx> int pair_open(lh_snapshot *base, lh_snapshot *cur, Source<Ctx> &a, Source<Ctx> &b)
-{
-    int rc = open_snapshot(base, a, a.cx);
-    if (!rc) rc = open_snapshot(cur, b, b.cx);
-    if (rc) return rc;
-    if (a.device != b.device) return LH_EINVAL;
-    return usable(a) && usable(b) ? LH_OK : LH_ESTATE;
-}
-// (the context's mutex held)  What is enqueued on `to` from here on runs behind what `from` holds now.  `ev`: the unit's
-// event for this, created on first use.
-static inline int order_behind(hipEvent_t &ev, hipStream_t from, hipStream_t to)
-{
-    if (from == to) return LH_OK;
-    if (!ev) LH_BESIDE_CHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    LH_BESIDE_CHK(hipEventRecord(ev, from));
-    LH_BESIDE_CHK(hipStreamWaitEvent(to, ev, 0));
+    for (size_t i = 0; i < n; i++) {
+        const int rc = source_cells(snaps[i], first, nmetrics, q[i]);
+        if (rc) return rc;
+    }
     return LH_OK;
 }
+// Step two: all opened in list order (the last one's device stays current), then LH_EINVAL for more than one device (the
+// check that needs them all), then LH_ESTATE.
+template <class Ctx> int list_open(lh_snapshot *const *snaps, size_t n, Source<Ctx> *q)
+{
+    for (size_t i = 0; i < n; i++) {
+        const int rc = open_snapshot(snaps[i], q[i], q[i].cx);
+        if (rc) return rc;
+    }
+    for (size_t i = 0; i + 1 < n; i++)
+        if (q[i].device != q[n - 1].device) return LH_EINVAL;
+    for (size_t i = 0; i < n; i++)
+        if (!usable(q[i])) return LH_ESTATE;
+    return LH_OK;
+}
+// (the context's mutex held)  What is enqueued on `to` from here on runs behind what every stream of from[0 .. n) holds now:
+// an event per distinct stream other than `to` is recorded there and waited for by `to`.  ev[0 .. n): the unit's events for
+// this, each created on first use.
+static inline int order_behind(hipEvent_t *ev, const hipStream_t *from, size_t n, hipStream_t to)
+{
+    for (size_t i = 0; i < n; i++) {
+        bool done = from[i] == to;
+        for (size_t j = 0; j < i && !done; j++) done = from[j] == from[i];
+        if (done) continue;
+        if (!ev[i]) LH_BESIDE_CHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+        LH_BESIDE_CHK(hipEventRecord(ev[i], from[i]));
+        LH_BESIDE_CHK(hipStreamWaitEvent(to, ev[i], 0));
+    }
+    return LH_OK;
+}
+static inline int order_behind(hipEvent_t &ev, hipStream_t from, hipStream_t to) { return order_behind(&ev, &from, 1, to); }
 inline const uint32_t *ranges_from(const Opened &o, uint32_t first) { return o.ranges + 2 * (size_t)first; }
 
 // f(c): c the cells of row `first`, typed by their width (const uint32_t * or const unsigned long long *).  A generic

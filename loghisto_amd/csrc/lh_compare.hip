@@ -318,11 +318,13 @@ int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics
 {
     int rc = check_args(base, cur, nmetrics, flags, o);
     if (rc) return rc;
-    Source a, b;
-    rc = pair_cells(base, cur, first, nmetrics, a, b);
+    lh_snapshot *const snaps[2] = {base, cur};
+    Source q[2];
+    const Source &a = q[0], &b = q[1];
+    rc = list_cells(snaps, 2, first, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any device call
-    rc = pair_open(base, cur, a, b);
+    rc = list_open(snaps, 2, q);
     if (rc) return rc;
     CompareCtx *cx = b.cx;
     std::lock_guard<std::mutex> g(cx->mu);

@@ -211,10 +211,11 @@ typedef Source<MoversCtx> MoversSource;
 
 // both snapshots' cells, spans, device and stream: LH_ERANGE for rows either does not have, LH_EINVAL for two devices,
 // LH_ESTATE for cells the kernels cannot walk.  (The empty call comes behind it: it writes n_out.)
-int open_sources(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, MoversSource &a, MoversSource &b)
+int open_sources(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, MoversSource (&q)[2])
 {
-    const int rc = pair_cells(base, cur, first, nmetrics, a, b);
-    return rc ? rc : pair_open(base, cur, a, b);
+    lh_snapshot *const snaps[2] = {base, cur};
+    const int rc = list_cells(snaps, 2, first, nmetrics, q);
+    return rc ? rc : list_open(snaps, 2, q);
 }
 
 // (cx->mu held) enqueue both passes over rows [first, first + nmetrics) on cur's stream, behind what base's stream holds.
@@ -261,8 +262,9 @@ int lh_movers(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetri
 {
     int rc = check_args(base, cur, nmetrics, by, arg, k, flags, out, n_out, alignof(size_t));
     if (rc) return rc;
-    MoversSource a, b;
-    rc = open_sources(base, cur, first, nmetrics, a, b);
+    MoversSource q[2];
+    const MoversSource &a = q[0], &b = q[1];
+    rc = open_sources(base, cur, first, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) {
         *n_out = 0;
@@ -280,8 +282,9 @@ int lh_movers_device(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t
 {
     int rc = check_args(base, cur, nmetrics, by, arg, k, flags, d_out, d_n_out, alignof(uint32_t));
     if (rc) return rc;
-    MoversSource a, b;
-    rc = open_sources(base, cur, first, nmetrics, a, b);
+    MoversSource q[2];
+    const MoversSource &a = q[0], &b = q[1];
+    rc = open_sources(base, cur, first, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) {
         LH_BESIDE_CHK(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), b.stream));
@@ -298,8 +301,9 @@ int lh_tool_movers_passes_ms(lh_snapshot *base, lh_snapshot *cur, uint32_t first
     int rc = check_args(base, cur, nmetrics, by, arg, k, flags, own, own, 1);
     if (rc) return rc;
     if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
-    MoversSource a, b;
-    rc = open_sources(base, cur, first, nmetrics, a, b);
+    MoversSource q[2];
+    const MoversSource &a = q[0], &b = q[1];
+    rc = open_sources(base, cur, first, nmetrics, q);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(b.cx->mu);
     const auto both = [&](lh_mover_entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {

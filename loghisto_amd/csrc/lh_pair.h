@@ -1,7 +1,7 @@
 // lh_pair.h -- the device side of the units that walk TWO rows at once, a name in one snapshot against the same name in
 // another (lh_compare.hip, lh_movers.hip): what the walk is scaled by (Scale), a lane's state of it (Best), a lane's four
-// bins (take4) and the wave's largest X at its lowest bin (wave_best, without LDS: DPP max-reductions over the 32-bit words
-// of X from the top).  lh_compare.hip's header says what X, ks, w1 and shift are; a unit that wants the bits of
+// bins (take4) and the wave's largest X at its lowest bin (wave_best, without LDS: DPP max-reductions, lh_wave.h's wave_max_u32, over the
+// 32-bit words of X from the top).  lh_compare.hip's header says what X, ks, w1 and shift are; a unit that wants the bits of
 // k_compare_wave's sums calls these in its order: the steps in ascending order per lane, then one DPP tree over the lanes.
 #pragma once
 
@@ -12,17 +12,6 @@
 namespace lh {
 
 typedef unsigned __int128 u128;
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) // the maximum in lane 63 (lanes without a source: 0)
-{
-    x = max(x, LH_DPP32(x, 0x111, 0xf));
-    x = max(x, LH_DPP32(x, 0x112, 0xf));
-    x = max(x, LH_DPP32(x, 0x114, 0xf));
-    x = max(x, LH_DPP32(x, 0x118, 0xf));
-    x = max(x, LH_DPP32(x, 0x142, 0xa));
-    x = max(x, LH_DPP32(x, 0x143, 0xc));
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
 
 // What a name's walk is scaled by: the totals, and na nb as the divisor of the sums' terms.
 struct Scale {

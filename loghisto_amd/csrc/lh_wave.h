@@ -1,5 +1,5 @@
 // lh_wave.h -- the device side of the units that read a snapshot (lh_count.hip, lh_spread.hip, lh_top.hip, lh_compare.hip,
-// lh_movers.hip -- with lh_pair.h for a walk over two rows and lh_select.h for a selection across names; a
+// lh_movers.hip, lh_across.hip -- with lh_pair.h for a walk over two rows and lh_select.h for a selection across names; a
 // new reader starts here and in lh_beside.h):
 //   wave primitives   DPP scans, cross-lane reads, the packed 16-byte load types
 //   the arithmetic    the percentile threshold (pct_threshold) and the bound-to-key rule (le_take)
@@ -79,6 +79,27 @@ __device__ __forceinline__ double wave_scan_incl_f64(double x)
     x += dpp_f64<0x142, 0xa>(x);
     x += dpp_f64<0x143, 0xc>(x);
     return x;
+}
+// the maximum / the bitwise OR over the 64 lanes, wave-uniform (the same tree; lanes without a source add 0)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x)
+{
+    x = max(x, LH_DPP32(x, 0x111, 0xf));
+    x = max(x, LH_DPP32(x, 0x112, 0xf));
+    x = max(x, LH_DPP32(x, 0x114, 0xf));
+    x = max(x, LH_DPP32(x, 0x118, 0xf));
+    x = max(x, LH_DPP32(x, 0x142, 0xa));
+    x = max(x, LH_DPP32(x, 0x143, 0xc));
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t x)
+{
+    x |= LH_DPP32(x, 0x111, 0xf);
+    x |= LH_DPP32(x, 0x112, 0xf);
+    x |= LH_DPP32(x, 0x114, 0xf);
+    x |= LH_DPP32(x, 0x118, 0xf);
+    x |= LH_DPP32(x, 0x142, 0xa);
+    x |= LH_DPP32(x, 0x143, 0xc);
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 __device__ __forceinline__ uint64_t readlane_u64(uint64_t x, uint32_t src) // src wave-uniform
 {
@@ -198,6 +219,7 @@ __device__ __forceinline__ Span or_empty(Span s)
 // bins b0 .. b0 + 3 of a row, zeros outside its own span `s` (from or_empty; b0 a multiple of 4; hi <= 65 535: the group ends inside the row).
 // For a walk that may leave the span at its lower end (lh_compare.hip's, over the union of two); one that starts at
 // base0() calls load4_cells.
+// (lh_across.hip's fetch4 restates this rule for a row whose address comes out of a lane: a change here goes there too.)
 template <typename CELL>
 __device__ __forceinline__ void load4_in(const CELL *__restrict__ row, uint32_t b0, Span s, u64 (&c)[4])
 {

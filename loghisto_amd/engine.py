@@ -545,6 +545,59 @@ class Snapshot:
         return self._leaders("lh_movers", (base._h, self._h), self._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
                              N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out)
 
+    # -- one name over several snapshots (the cells added up, then processHistograms' walks, metrics.go:342-346, 389-418) ---
+    _ACROSS_OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("nbuckets", 4, 0, np.uint32),
+                   ("present_bits", 4, 0, np.uint32), ("pkeys", 2, 1, np.int16), ("pvalid", 1, 1, np.uint8))
+
+    def across(self, earlier, percentiles, nmetrics: Optional[int] = None, first: int = 0, out=None):
+        """dict(count, sum, avg, nbuckets, present_bits, pkeys, pvalid, pvals) for metrics [first, first+nmetrics) over the
+        snapshots list(earlier) + [self] taken together (lh_across*, at most N.MAX_ACROSS of them): per name the cells of
+        all of them are added up in 64 bits, and count, sum, nbuckets and the percentile keys are what extract() returns
+        for a snapshot that holds those sums -- p99 over the last 10 intervals while emitting every interval.
+        present_bits has bit i set where snapshot i of the list holds a sample of the name; avg = sum / count (NaN at 0);
+        pvals = decompress(pkey) from the engine's codec_tables, NaN where the percentile has no bucket.  A snapshot may
+        appear more than once and counts that often; the snapshots may belong to other engines on the same device.
+        `percentiles` may be empty.  No snapshot is changed.
+        out = a dict with any of count, sum, nbuckets, present_bits, pkeys, pvalid -> contiguous arrays of nmetrics (the
+        first four) or nmetrics * np elements of 8, 8, 4, 4, 2, 1 bytes; outputs left out are not computed.  torch device
+        tensors take the device form: enqueued on this snapshot's stream (the others must stay unreleased until that stream
+        has passed the call), the tensors are returned as they are and nothing is derived.  numpy arrays (pinned ones
+        receive their results by one copy) take the host form."""
+        L = N.lib()
+        snaps = list(earlier) + [self]
+        handles = (C.c_void_p * len(snaps))(*[s._h.value for s in snaps])
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        np_ = int(p.size)
+        lead = (C.addressof(handles), len(snaps), first, nmetrics, p.ctypes.data, np_, 0)
+        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
+            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
+                                             for k, width, per_p, _ in self._ACROSS_OUT])
+            if device:
+                N.check(L.lh_across_device(*lead, *args), "lh_across_device")
+                return dict(out)
+            N.check(L.lh_across(*lead, *args), "lh_across")
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
+                   if v is not None and (np_ or k not in ("pkeys", "pvalid"))}
+        else:
+            import torch
+            res = {}
+            for k, width, per_p, dt in self._ACROSS_OUT:   # (a row more than an empty call needs: the arrays have addresses)
+                n = max(nmetrics, 1) * (np_ if per_p else 1)
+                res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
+            N.check(L.lh_across(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._ACROSS_OUT]), "lh_across")
+            res = {k: v[:nmetrics * (np_ if per_p else 1)] for (k, _, per_p, _), v in zip(self._ACROSS_OUT, res.values())}
+        per_p = {k: c for k, _, c, _ in self._ACROSS_OUT}
+        res = {k: (v.reshape(nmetrics, np_) if per_p[k] else v.reshape(nmetrics)) for k, v in res.items()}
+        if "sum" in res and "count" in res:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res["avg"] = res["sum"] / res["count"].view(np.uint64).astype(np.float64)
+        if "pkeys" in res and "pvalid" in res:
+            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
+            res["pvals"] = np.where(res["pvalid"] != 0, self._decompress_table()[bins], np.nan)
+        return res
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
