@@ -579,6 +579,54 @@ int lh_across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t n
 int lh_across_device(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np,
                      uint32_t flags, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets, uint32_t *d_present_bits,
                      int16_t *d_pkeys, uint8_t *d_pvalid);
+/* ROWS BY ID LIST: lh_across_ids*, lh_count_le_ids*, lh_spread_ids*.  The base forms above address names as one block
+ * [first, first + nmetrics); ids are handed out in lh_intern order, so the names a caller wants together -- the k ids lh_top* or
+ * lh_movers* returned, the endpoints of a dashboard, the names that have an SLO -- are almost never one block.  These forms
+ * take the rows from an array of n ids instead of (first, nmetrics) and are otherwise the base form, word for word: the same
+ * kernels read row ids[m] where the base form reads row first + m (one uniform load per row), nothing is summed across names
+ * and no new statistic is defined.  lh_across_ids with nsnaps == 1 is the id-list form of the compact extract (count, sum,
+ * nbuckets and the percentile keys of lh_extract_rows_compact).
+ *   Entry m of every output describes row ids[m], bit for bit what the base form returns for that row in a call of the same
+ *   kernel shape (the shape is chosen by n, the number of entries, as the base form's is by nmetrics).  Per-percentile and
+ *   per-bound outputs are [n * np] / [n * nb], row m for ids[m]; with LH_LE_PER_METRIC row m of `bounds` ([n * nb]) belongs to
+ *   ids[m].  ids may be in any order and may hold an id more than once -- each occurrence gets its own, equal entry -- and n is
+ *   not bounded by the number of rows.  n == 0 -> LH_OK, nothing written, before any device call.
+ *   HOST FORMS (lh_*_ids: ids is a host array): ids is copied before the call returns.  Every id is checked against the rows
+ *   of the snapshot -- for lh_across_ids of every snapshot of the list, i.e. against the smallest number of rows: an id at or
+ *   beyond it -> LH_ERANGE, nothing is enqueued and no output is written.
+ *   DEVICE FORMS (lh_*_ids_device: d_ids is a device array, valid until the stream has passed the call): the call returns
+ *   after enqueueing, like the base device forms -- no pre-pass and no host wait, so the ids lh_top_device has just written
+ *   can be used on the same stream without a round trip.  The host never sees these ids (the stance lh_reserve_pairs takes):
+ *   THE KERNEL READS NOTHING FOR AN ID AT OR BEYOND THE ROWS of the snapshot (for lh_across_ids_device: of the shortest
+ *   snapshot of the list), and that entry comes out as a row that was never marked does: count / total 0, sum, m2 0,
+ *   nbuckets 0, present_bits 0, every key, pvalid, count_le, sum_le and cum 0.
+ *   LH_EINVAL, decided on the host before a snapshot or a device is touched: every cause the base form has; ids NULL with
+ *            n > 0; ids not 4-byte aligned.
+ *   LH_ERANGE: n above 2^32 - 1, before anything is looked at (a cause of LH_EINVAL wins over it); a host form's bad id.
+ *   READ-ONLY, ordering, threading, staging and the fixed order of every floating-point sum are the base form's: the same
+ *   context and mutex per unit and device, the work on the same stream (for a list of snapshots behind the others' streams), a
+ *   host form's id list copied into a block of the unit's that only grows. */
+/* lh_across over rows ids[0 .. n) */
+int lh_across_ids(lh_snapshot *const *snaps, size_t nsnaps, const uint32_t *ids, size_t n, const double *p, size_t np,
+                  uint32_t flags, uint64_t *count, double *sum, uint32_t *nbuckets, uint32_t *present_bits, int16_t *pkeys,
+                  uint8_t *pvalid);
+/* lh_across_device over rows d_ids[0 .. n), a device array */
+int lh_across_ids_device(lh_snapshot *const *snaps, size_t nsnaps, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                         uint32_t flags, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets, uint32_t *d_present_bits,
+                         int16_t *d_pkeys, uint8_t *d_pvalid);
+/* lh_count_le over rows ids[0 .. n); per-metric bounds hold a row per entry */
+int lh_count_le_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *bounds, size_t nb, uint32_t flags,
+                    uint64_t *cum, uint64_t *total);
+/* lh_count_le_device over rows d_ids[0 .. n), a device array (bounds stay a host array) */
+int lh_count_le_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *bounds, size_t nb, uint32_t flags,
+                           uint64_t *d_cum, uint64_t *d_total);
+/* lh_spread over rows ids[0 .. n) */
+int lh_spread_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *p, size_t np, uint64_t *count, double *sum,
+                  double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le);
+/* lh_spread_device over rows d_ids[0 .. n), a device array */
+int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *p, size_t np, uint64_t *d_count,
+                         double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
+                         double *d_sum_le);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

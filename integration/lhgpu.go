@@ -333,3 +333,29 @@ func (ms *MetricSystem) registerEngineGauges() {
 	ms.RegisterGaugeFunc("lhgpu.flips_busy", get(func(c *C.lh_counters) float64 { return float64(c.flips_busy) }))
 }
 
+// Stats of chosen names (rows by id list): lh_across_ids / lh_count_le_ids / lh_spread_ids take (ids, n) where the base forms
+// take (first, nmetrics); entry m of every output describes name ids[m].  "Top, then details" without a host round trip:
+// lh_top_device writes k entries of 32 bytes whose first field is the id, one strided device-to-device copy makes the id
+// array, lh_across_ids_device reads it on the same stream.  lh_top_device does not write entries beyond n_out, so they are
+// filled with 0xff first: those ids stay 0xffffffff, no snapshot has such a row, and their result rows are zeros.
+// dEntries: k * 32 bytes, dN: 4 bytes, dIds: k * 4 bytes, out.*: k (or k * len(ps)) elements -- all device memory.
+func (ms *MetricSystem) topThenDetails(prev, snap *C.lh_snapshot, k int, ps []C.double, dEntries, dN, dIds unsafe.Pointer, out *acrossDeviceOut) {
+	n := len(ms.gpu.names)
+	st := C.hipStream_t(nil)
+	C.lh_snapshot_stream(snap, (*unsafe.Pointer)(unsafe.Pointer(&st)))
+	C.hipMemsetAsync(dEntries, 0xff, C.size_t(k*32), st)
+	C.lh_top_device(snap, 0, C.size_t(n), C.LH_TOP_BY_PERCENTILE, 0.99, C.size_t(k), 0, (*C.lh_top_entry)(dEntries), (*C.uint32_t)(dN))
+	C.hipMemcpy2DAsync(dIds, 4, dEntries, 32, 4, C.size_t(k), C.hipMemcpyDeviceToDevice, st) // entry i's id -> dIds[i]
+	snaps := []*C.lh_snapshot{prev, snap} // the k leaders' stats over the last two intervals
+	C.lh_across_ids_device(&snaps[0], 2, (*C.uint32_t)(dIds), C.size_t(k), &ps[0], C.size_t(len(ps)), 0,
+		out.count, out.sum, out.nbuckets, out.present, out.pkeys, out.pvalid) // same stream: behind the copy, no host wait
+}
+
+// acrossDeviceOut: the device arrays lh_across_device / lh_across_ids_device fill.
+type acrossDeviceOut struct {
+	count             *C.uint64_t
+	sum               *C.double
+	nbuckets, present *C.uint32_t
+	pkeys             *C.int16_t
+	pvalid            *C.uint8_t
+}

@@ -229,6 +229,12 @@ SIGNATURES = {
     "lh_movers_device": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp]),
     "lh_across": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_across_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_count_le_ids": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
+    "lh_count_le_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
+    "lh_spread_ids": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_spread_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

@@ -41,6 +41,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -87,18 +88,20 @@ struct Rows {
     u64 row;
     uint32_t base0, uhi; // base0 == NO_BIN: the name was never marked in any of them
 };
-template <int MODE> __device__ __forceinline__ Rows open_rows(const AcrossSnaps &s, uint32_t m, size_t stride, uint32_t lane)
+// `at`: the row, from lh::row_of -- row m of the block, or (IDS) row ids[m] of the snapshots, NO_ROW for an id at or beyond
+// the rows of the shortest of them: every lane's span is then empty (row_span) and no address is made
+template <int MODE, bool IDS> __device__ __forceinline__ Rows open_rows(const AcrossSnaps &s, uint32_t at, size_t stride, uint32_t lane)
 {
     Rows r;
     r.lo = NO_BIN;
     r.hi = 0;
     r.row = 0;
     if (lane < s.n) {
-        const Span sp = or_empty(own_span(s.ranges[lane], m));
+        const Span sp = or_empty(row_span<IDS>(s.ranges[lane], at));
         const bool narrow = MODE == ALL_NARROW || (MODE == MIXED && ((s.narrow >> lane) & 1u));
         r.lo = sp.lo;
         r.hi = sp.hi;
-        r.row = (u64)(uintptr_t)s.cells[lane] + (u64)m * stride * (narrow ? 4u : 8u);
+        if (!IDS || at != NO_ROW) r.row = (u64)(uintptr_t)s.cells[lane] + (u64)at * stride * (narrow ? 4u : 8u);
     }
     r.base0 = ~wave_max_u32(~r.lo); // the least lo (NO_BIN's complement is 0)
     r.uhi = wave_max_u32(r.hi);
@@ -186,14 +189,16 @@ __device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
     return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
 }
 
-template <int MODE>
+// (Both kernels, IDS: entry m reads row ids[m] of every snapshot, `nrows` the rows of the shortest of them; m still indexes
+// the outputs.  Otherwise row m of the blocks; ids and nrows are not looked at.)
+template <int MODE, bool IDS>
 __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
                                                           const double *__restrict__ D, const AcrossP pa, uint32_t np,
-                                                          const AcrossOut o)
+                                                          const AcrossOut o, const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const Rows r = open_rows<MODE>(s, m, stride, lane);
+    const Rows r = open_rows<MODE, IDS>(s, row_of<IDS>(ids, nrows, m), stride, lane);
     const uint32_t hi = r.uhi;
     u64 total = 0;
     double sum = 0.0;
@@ -267,10 +272,10 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, 
     }
 }
 
-template <int MODE>
+template <int MODE, bool IDS>
 __global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
                                                         const double *__restrict__ D, const AcrossP pa, uint32_t np,
-                                                        const AcrossOut o)
+                                                        const AcrossOut o, const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
     __shared__ double s_sum[CHUNKS]; // the chunks' sums, then their exclusive prefix (ascending order)
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32
     __shared__ double s_tsum;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
     if (m >= nmetrics) return;
-    const Rows r = open_rows<MODE>(s, m, stride, lane); // (every wave for itself)
+    const Rows r = open_rows<MODE, IDS>(s, row_of<IDS>(ids, nrows, m), stride, lane); // (every wave for itself)
     const uint32_t hi = r.uhi, base0 = r.base0;
     const uint32_t nchunks = base0 != NO_BIN ? (hi - base0) / STEP + 1 : 0; // <= CHUNKS
     uint32_t none = 0;
@@ -386,13 +391,16 @@ struct AcrossCtx {
     double *d_table = nullptr; // D[LH_NKEYS]
     hipEvent_t order[LH_MAX_ACROSS] = {};
     ResultBlocks res;          // host form
+    IdBlocks ids;              // host form of lh_across_ids
 };
 std::atomic<uint32_t> g_wave_from{AC_WAVE_FROM_DEFAULT};
 
 // every check that needs neither a snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
 // nulled here, and count for nothing.
-int check_args(lh_snapshot *const *snaps, size_t nsnaps, size_t nmetrics, const double *p, size_t np, uint32_t flags, AcrossOut &o)
+int check_args(lh_snapshot *const *snaps, size_t nsnaps, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
+               uint32_t flags, AcrossOut &o)
 {
+    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
     if (!snaps || misaligned(snaps, alignof(lh_snapshot *)) || nsnaps == 0 || nsnaps > LH_MAX_ACROSS) return LH_EINVAL;
     for (size_t i = 0; i < nsnaps; i++)
         if (!snaps[i]) return LH_EINVAL;
@@ -411,9 +419,9 @@ int check_args(lh_snapshot *const *snaps, size_t nsnaps, size_t nmetrics, const 
 
 typedef lh::beside::Source<AcrossCtx> Source;
 
-// (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on the last snapshot's stream, behind what the others'
-// streams hold
-int enqueue(const Source *q, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np, const AcrossOut &o)
+// (cx->mu held) enqueue the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on the last snapshot's
+// stream, behind what the others' streams hold
+int enqueue(const Source *q, size_t nsnaps, const RowSel &sel, size_t nmetrics, const double *p, size_t np, const AcrossOut &o)
 {
     const Source &last = q[nsnaps - 1];
     AcrossCtx *cx = last.cx;
@@ -421,7 +429,12 @@ int enqueue(const Source *q, size_t nsnaps, uint32_t first, size_t nmetrics, con
     for (size_t i = 0; i < nsnaps; i++) from[i] = q[i].stream;
     int rc = order_behind(cx->order, from, nsnaps, last.stream);
     if (!rc) rc = ensure_table(cx->d_table, last.stream, lh::k_value_table<AcrossCtx>);
+    const uint32_t *ids = nullptr;
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, last.stream, ids);
     if (rc) return rc;
+    const uint32_t first = sel.first;
+    uint32_t nrows = last.nrows; // what an id is guarded against: the rows of the shortest snapshot
+    for (size_t i = 0; i < nsnaps; i++) nrows = q[i].nrows < nrows ? q[i].nrows : nrows;
     AcrossP pa;
     for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
     AcrossSnaps s;
@@ -437,10 +450,15 @@ int enqueue(const Source *q, size_t nsnaps, uint32_t first, size_t nmetrics, con
     const double *D = cx->d_table;
     const size_t stride = last.stride; // (lh_row_stride(): one for all)
     const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    const auto launch = [&](auto mode) {
+    const auto launch_as = [&](auto mode, auto by_id) {
         constexpr int MODE = decltype(mode)::value;
-        if (sh.wave) hipLaunchKernelGGL(k_across_wave<MODE>, sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_across_block<MODE>, sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o);
+        constexpr bool IDS = decltype(by_id)::value;
+        if (sh.wave) hipLaunchKernelGGL((k_across_wave<MODE, IDS>), sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o, ids, nrows);
+        else hipLaunchKernelGGL((k_across_block<MODE, IDS>), sh.grid, sh.block, 0, last.stream, s, M, stride, D, pa, NP, o, ids, nrows);
+    };
+    const auto launch = [&](auto mode) {
+        if (sel.by_id) launch_as(mode, std::true_type());
+        else launch_as(mode, std::false_type());
     };
     if (s.narrow == (1u << nsnaps) - 1u) launch(std::integral_constant<int, ALL_NARROW>());
     else if (s.narrow == 0) launch(std::integral_constant<int, ALL_WIDE>());
@@ -449,26 +467,26 @@ int enqueue(const Source *q, size_t nsnaps, uint32_t first, size_t nmetrics, con
     return LH_OK;
 }
 
-int across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+int across(lh_snapshot *const *snaps, size_t nsnaps, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
            AcrossOut o, bool device_form)
 {
-    int rc = check_args(snaps, nsnaps, nmetrics, p, np, flags, o);
+    int rc = check_args(snaps, nsnaps, sel, nmetrics, p, np, flags, o);
     if (rc) return rc;
     Source q[LH_MAX_ACROSS];
-    rc = list_cells(snaps, nsnaps, first, nmetrics, q);
+    rc = list_cells(snaps, nsnaps, sel, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any device call
     rc = list_open(snaps, nsnaps, q);
     if (rc) return rc;
     AcrossCtx *cx = q[nsnaps - 1].cx;
     std::lock_guard<std::mutex> g(cx->mu);
-    if (device_form) return enqueue(q, nsnaps, first, nmetrics, p, np, o);
+    if (device_form) return enqueue(q, nsnaps, sel, nmetrics, p, np, o);
 
     // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, the 4-byte ones, the keys, the flags.
     const size_t per_m = nmetrics, per_p = nmetrics * np;
     const HostOut out[6] = {{o.count, per_m * 8}, {o.sum, per_m * 8},   {o.nbuckets, per_m * 4},
                             {o.present, per_m * 4}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
-    return host_results(cx->res, q[nsnaps - 1].stream, out, [&](unsigned char *const(&dev)[6]) {
+    rc = host_results(cx->res, q[nsnaps - 1].stream, out, [&](unsigned char *const(&dev)[6]) {
         AcrossOut d;
         d.count = reinterpret_cast<u64 *>(dev[0]);
         d.sum = reinterpret_cast<double *>(dev[1]);
@@ -476,8 +494,9 @@ int across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmet
         d.present = reinterpret_cast<uint32_t *>(dev[3]);
         d.pkeys = reinterpret_cast<int16_t *>(dev[4]);
         d.pvalid = reinterpret_cast<uint8_t *>(dev[5]);
-        return enqueue(q, nsnaps, first, nmetrics, p, np, d);
+        return enqueue(q, nsnaps, sel, nmetrics, p, np, d);
     });
+    return settle_ids(rc, sel, q[nsnaps - 1].stream);
 }
 
 } // namespace
@@ -488,7 +507,7 @@ int lh_across(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t n
               uint64_t *count, double *sum, uint32_t *nbuckets, uint32_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
 {
     const AcrossOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, present_bits, pkeys, pvalid};
-    return across(snaps, nsnaps, first, nmetrics, p, np, flags, o, false);
+    return across(snaps, nsnaps, rows_from(first), nmetrics, p, np, flags, o, false);
 }
 
 int lh_across_device(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, size_t nmetrics, const double *p, size_t np,
@@ -496,7 +515,22 @@ int lh_across_device(lh_snapshot *const *snaps, size_t nsnaps, uint32_t first, s
                      int16_t *d_pkeys, uint8_t *d_pvalid)
 {
     const AcrossOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid};
-    return across(snaps, nsnaps, first, nmetrics, p, np, flags, o, true);
+    return across(snaps, nsnaps, rows_from(first), nmetrics, p, np, flags, o, true);
+}
+
+int lh_across_ids(lh_snapshot *const *snaps, size_t nsnaps, const uint32_t *ids, size_t n, const double *p, size_t np, uint32_t flags,
+                  uint64_t *count, double *sum, uint32_t *nbuckets, uint32_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
+{
+    const AcrossOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, present_bits, pkeys, pvalid};
+    return across(snaps, nsnaps, rows_by_id(ids, false), n, p, np, flags, o, false);
+}
+
+int lh_across_ids_device(lh_snapshot *const *snaps, size_t nsnaps, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                         uint32_t flags, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets, uint32_t *d_present_bits,
+                         int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const AcrossOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid};
+    return across(snaps, nsnaps, rows_by_id(d_ids, true), n, p, np, flags, o, true);
 }
 
 int lh_tool_across_switch(uint32_t wave_from_rows, uint32_t *previous)

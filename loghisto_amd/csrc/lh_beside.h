@@ -10,7 +10,8 @@
 //
 // What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
 // way a host form's results travel back, the event that guards a block across streams, and the measurement switch's
-// exchange.  For the readers, which all walk rows [first, first + nmetrics): their source record and its two-step opener
+// exchange.  For the readers, which all walk rows [first, first + nmetrics) or a list of row ids (RowSel, rows_in; stage_ids
+// brings a host list to the device): their source record and its two-step opener
 // (Source, source_cells, source_open), the same two steps for a reader of a list of snapshots (list_cells, list_open: two
 // for lh_compare.hip and lh_movers.hip, up to 16 for lh_across.hip) with the events that put the last snapshot's stream
 // behind the others' (order_behind), the launch shape (row_shape), the dispatch on the cells' width (with_cells) and the
@@ -208,14 +209,39 @@ template <class Ctx> struct Source : Opened {
     const void *cells = nullptr;
     uint32_t nrows = 0, cell_bytes = 0;
 };
+// Which rows a call reads: [first, first + n), or -- the *_ids forms -- rows ids[0 .. n) in that order, from a host array
+// (checked and copied by the call) or a device array (read by the kernel, which guards every id itself: lh::row_of).
+struct RowSel {
+    uint32_t first = 0;
+    const uint32_t *ids = nullptr;
+    bool by_id = false, on_device = false;
+};
+inline RowSel rows_from(uint32_t first) { return RowSel{first, nullptr, false, false}; }
+inline RowSel rows_by_id(const uint32_t *ids, bool on_device) { return RowSel{0, ids, true, on_device}; }
+// the *_ids forms' own causes of LH_EINVAL, decided before anything else (so that they win over the early LH_ERANGE)
+inline bool bad_ids(const RowSel &sel, size_t n) { return sel.by_id && ((!sel.ids && n > 0) || misaligned(sel.ids, 4)); }
+// LH_ERANGE for rows a snapshot of `nrows` rows does not have: the end of the block, or the first id of a host list at or
+// beyond nrows.  (A device list is not looked at.)  n <= 2^32 - 1: the units' argument checks came first.
+inline int rows_in(const RowSel &sel, size_t n, uint32_t nrows)
+{
+    if (!sel.by_id) return n > nrows || sel.first > nrows - n ? LH_ERANGE : LH_OK;
+    if (!sel.on_device)
+        for (size_t m = 0; m < n; m++)
+            if (sel.ids[m] >= nrows) return LH_ERANGE;
+    return LH_OK;
+}
 // Step one, before any device call: the cells, and LH_ERANGE for rows the snapshot does not have.
-template <class Ctx> int source_cells(lh_snapshot *s, uint32_t first, size_t nmetrics, Source<Ctx> &q)
+template <class Ctx> int source_cells(lh_snapshot *s, const RowSel &sel, size_t nmetrics, Source<Ctx> &q)
 {
     void *cells = nullptr;
     const int rc = lh_snapshot_cells(s, &cells, &q.nrows, &q.cell_bytes);
     if (rc) return rc;
     q.cells = cells;
-    return nmetrics > q.nrows || first > q.nrows - nmetrics ? LH_ERANGE : LH_OK;
+    return rows_in(sel, nmetrics, q.nrows);
+}
+template <class Ctx> int source_cells(lh_snapshot *s, uint32_t first, size_t nmetrics, Source<Ctx> &q)
+{
+    return source_cells(s, rows_from(first), nmetrics, q);
 }
 // whole 4-bin groups are readable up to bin 65 535, and the cells have one of the two widths the kernels are built for
 template <class Ctx> bool usable(const Source<Ctx> &q)
@@ -233,13 +259,17 @@ template <class Ctx> int source_open(lh_snapshot *s, Source<Ctx> &q)
 // the unit's context is q[n - 1].cx (lh_compare.hip, lh_movers.hip: {base, cur}).  Between the steps a reader whose empty
 // call writes nothing returns (lh_compare.hip, lh_across.hip); one whose empty call writes n_out takes both first
 // (lh_movers.hip).  Step one: LH_ERANGE for rows any of the snapshots does not have, the first in list order.
-template <class Ctx> int list_cells(lh_snapshot *const *snaps, size_t n, uint32_t first, size_t nmetrics, Source<Ctx> *q)
+template <class Ctx> int list_cells(lh_snapshot *const *snaps, size_t n, const RowSel &sel, size_t nmetrics, Source<Ctx> *q)
 {
     for (size_t i = 0; i < n; i++) {
-        const int rc = source_cells(snaps[i], first, nmetrics, q[i]);
+        const int rc = source_cells(snaps[i], sel, nmetrics, q[i]);
         if (rc) return rc;
     }
     return LH_OK;
+}
+template <class Ctx> int list_cells(lh_snapshot *const *snaps, size_t n, uint32_t first, size_t nmetrics, Source<Ctx> *q)
+{
+    return list_cells(snaps, n, rows_from(first), nmetrics, q);
 }
 // Step two: all opened in list order (the last one's device stays current), then LH_EINVAL for more than one device (the
 // check that needs them all), then LH_ESTATE.
@@ -272,6 +302,35 @@ static inline int order_behind(hipEvent_t *ev, const hipStream_t *from, size_t n
 }
 static inline int order_behind(hipEvent_t &ev, hipStream_t from, hipStream_t to) { return order_behind(&ev, &from, 1, to); }
 inline const uint32_t *ranges_from(const Opened &o, uint32_t first) { return o.ranges + 2 * (size_t)first; }
+
+// A host id list on its way to the kernel: the unit's two grown blocks (part of its context).
+struct IdBlocks {
+    uint32_t *h_ids = nullptr, *d_ids = nullptr; // the caller's list, copied (pinned); in HBM for the kernel
+    size_t h_cap = 0, d_cap = 0;
+};
+// (the context's mutex held)  The id array the kernel of an id-list call reads, n > 0 entries: the caller's own device array,
+// or the host list -- which rows_in has checked -- copied into the pinned block before this returns and from there into HBM
+// by a copy on `st`, ahead of the kernel.  Only a host form stages, and it waits for `st` before it returns (after a failure
+// too: settle_ids), so the two blocks are free again when the mutex is.  The kernel guards every id it reads whatever the
+// host saw (lh::row_of): a list the caller changes under the call reads other rows, or none, never beyond the snapshot.
+inline int stage_ids(IdBlocks &b, const RowSel &sel, size_t n, hipStream_t st, const uint32_t *&ids)
+{
+    ids = sel.ids;
+    if (!sel.by_id || sel.on_device) return LH_OK;
+    int rc = grow_pinned(b.h_ids, b.h_cap, n, 1024);
+    if (!rc) rc = grow_device(b.d_ids, b.d_cap, n, 1024);
+    if (rc) return rc;
+    std::memcpy(b.h_ids, sel.ids, n * sizeof(uint32_t));
+    LH_BESIDE_CHK(hipMemcpyAsync(b.d_ids, b.h_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ids = b.d_ids;
+    return LH_OK;
+}
+// a host form's way out: after a failure behind stage_ids the copy may still be under way
+inline int settle_ids(int rc, const RowSel &sel, hipStream_t st)
+{
+    if (rc && sel.by_id && !sel.on_device && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    return rc;
+}
 
 // f(c): c the cells of row `first`, typed by their width (const uint32_t * or const unsigned long long *).  A generic
 // lambda names the type as cell_of<decltype(c)>.

@@ -32,6 +32,7 @@
 #include <atomic>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -46,19 +47,23 @@ constexpr uint32_t CL_WAVE_FROM_DEFAULT = 1024;
 // shared bounds travel in the kernel arguments (512 bytes); per-metric ones are read from `pb`
 struct LeBounds { double b[LH_MAX_BOUNDS]; };
 
-template <typename CELL>
+// (Both kernels, IDS: entry m reads row ids[m] of the snapshot -- lh::row_of, whose guard against `nrows` leaves an empty span;
+// m still indexes the outputs and the per-metric bounds.  Otherwise row m of the block; ids and nrows are not looked at.)
+template <typename CELL, bool IDS>
 __global__ __launch_bounds__(ROW_BLOCK) void k_count_le_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                             uint32_t nmetrics, size_t stride, const LeBounds sb,
                                                             const double *__restrict__ pb, uint32_t nb, u64 *__restrict__ cum,
-                                                            u64 *__restrict__ total)
+                                                            u64 *__restrict__ total, const uint32_t *__restrict__ ids,
+                                                            uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const Span sp = own_span(ranges, m);
+    const uint32_t r = row_of<IDS>(ids, nrows, m);
+    const Span sp = row_span<IDS>(ranges, r);
     const uint32_t hi = sp.hi;
     u64 res = 0, carry = 0;
     if (sp.any()) { // wave-uniform; an empty row costs two loads and two stores
-        const CELL *__restrict__ row = cells + (size_t)m * stride;
+        const CELL *__restrict__ row = cells + (size_t)r * stride;
         const uint32_t base0 = sp.base0();
         u64 c[4], nx[4];
         load4_cells(row, base0 + 4 * lane, hi, c);
@@ -90,24 +95,26 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_count_le_wave(const CELL *__restr
     if (total && lane == 0) total[m] = carry;
 }
 
-template <typename CELL>
+template <typename CELL, bool IDS>
 __global__ __launch_bounds__(WG) void k_count_le_block(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                           uint32_t nmetrics, size_t stride, const LeBounds sb,
                                                           const double *__restrict__ pb, uint32_t nb, u64 *__restrict__ cum,
-                                                          u64 *__restrict__ total)
+                                                          u64 *__restrict__ total, const uint32_t *__restrict__ ids,
+                                                          uint32_t nrows)
 {
     __shared__ u64 s_chunk[CHUNKS]; // the chunks' totals, then their exclusive prefix
     __shared__ u64 s_total;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
     if (m >= nmetrics) return;
-    const Span sp = own_span(ranges, m);
+    const uint32_t r = row_of<IDS>(ids, nrows, m);
+    const Span sp = row_span<IDS>(ranges, r);
     const uint32_t hi = sp.hi;
     if (!sp.any()) { // workgroup-uniform
         if (cum && threadIdx.x < nb) cum[(size_t)m * nb + threadIdx.x] = 0;
         if (total && threadIdx.x == 0) total[m] = 0;
         return;
     }
-    const CELL *__restrict__ row = cells + (size_t)m * stride;
+    const CELL *__restrict__ row = cells + (size_t)r * stride;
     const uint32_t base0 = sp.base0(), nchunks = (hi - base0) / STEP + 1; // <= CHUNKS
     constexpr uint32_t U = 4;
     for (uint32_t c0 = wave; c0 < nchunks; c0 += WG_WAVES * U) { // wave-uniform
@@ -175,12 +182,15 @@ struct CountCtx {
     double *h_bounds = nullptr, *d_bounds = nullptr; // per-metric bounds: the caller's, copied (pinned); in HBM for the kernel
     size_t hb_cap = 0, db_cap = 0;          // (in doubles)
     EventGuard guard;                       // behind the last kernel that reads d_bounds
+    IdBlocks ids;                           // host form of lh_count_le_ids
 };
 std::atomic<uint32_t> g_wave_from{CL_WAVE_FROM_DEFAULT};
 
 // every check that needs neither the snapshot nor a device
-int check_args(lh_snapshot *s, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, const void *cum, const void *total)
+int check_args(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, const void *cum,
+               const void *total)
 {
+    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
     if (!s || nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || (flags & ~(uint32_t)LH_LE_PER_METRIC)) return LH_EINVAL;
     if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32): not a row of bounds is read
@@ -195,11 +205,14 @@ int check_args(lh_snapshot *s, size_t nmetrics, const double *bounds, size_t nb,
 
 typedef lh::beside::Source<CountCtx> Source;
 
-// (cx->mu held) enqueue the count of rows [first, first + nmetrics) on the snapshot's stream
-int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, u64 *d_cum,
+// (cx->mu held) enqueue the count of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on the snapshot's stream
+int enqueue(const Source &q, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, u64 *d_cum,
             u64 *d_total)
 {
     CountCtx *cx = q.cx;
+    const uint32_t *ids = nullptr;
+    const int ri = stage_ids(cx->ids, sel, nmetrics, q.stream, ids);
+    if (ri) return ri;
     LeBounds sb;
     const double *pb = nullptr;
     if (flags & LH_LE_PER_METRIC) {
@@ -218,24 +231,33 @@ int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *boun
         for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
     }
     const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
-    const uint32_t *ranges = ranges_from(q, first);
+    const uint32_t *ranges = ranges_from(q, sel.first);
     const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    with_cells(q, first, [&](auto *c) {
-        typedef cell_of<decltype(c)> CELL;
-        if (sh.wave) hipLaunchKernelGGL(k_count_le_wave<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
-        else hipLaunchKernelGGL(k_count_le_block<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum, d_total);
-    });
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        with_cells(q, sel.first, [&](auto *c) {
+            typedef cell_of<decltype(c)> CELL;
+            if (sh.wave)
+                hipLaunchKernelGGL((k_count_le_wave<CELL, IDS>), sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum,
+                                   d_total, ids, q.nrows);
+            else
+                hipLaunchKernelGGL((k_count_le_block<CELL, IDS>), sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, sb, pb, NB, d_cum,
+                                   d_total, ids, q.nrows);
+        });
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
     LH_BESIDE_CHK(hipGetLastError());
     return pb ? cx->guard.record(q.stream) : LH_OK;
 }
 
-int count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, uint64_t *cum,
+int count_le(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, uint64_t *cum,
              uint64_t *total, bool device_form)
 {
-    int rc = check_args(s, nmetrics, bounds, nb, flags, cum, total);
+    int rc = check_args(s, sel, nmetrics, bounds, nb, flags, cum, total);
     if (rc) return rc;
     Source q;
-    rc = source_cells(s, first, nmetrics, q);
+    rc = source_cells(s, sel, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any device call
     rc = source_open(s, q);
@@ -243,14 +265,14 @@ int count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *boun
     CountCtx *cx = q.cx;
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form)
-        return enqueue(q, first, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(cum), reinterpret_cast<u64 *>(total));
+        return enqueue(q, sel, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(cum), reinterpret_cast<u64 *>(total));
 
     // host form: results to HBM, then back to the caller's arrays
     const HostOut out[2] = {{cum, nmetrics * nb * sizeof(u64)}, {total, nmetrics * sizeof(u64)}};
     rc = host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[2]) {
-        return enqueue(q, first, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(dev[0]), reinterpret_cast<u64 *>(dev[1]));
+        return enqueue(q, sel, nmetrics, bounds, nb, flags, reinterpret_cast<u64 *>(dev[0]), reinterpret_cast<u64 *>(dev[1]));
     });
-    if (rc) return rc;
+    if (rc) return settle_ids(rc, sel, q.stream);
     if (flags & LH_LE_PER_METRIC) cx->guard.covered(); // this call recorded the event on the stream it has just waited for
     return LH_OK;
 }
@@ -262,13 +284,25 @@ extern "C" {
 int lh_count_le(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags, uint64_t *cum,
                 uint64_t *total)
 {
-    return count_le(s, first, nmetrics, bounds, nb, flags, cum, total, false);
+    return count_le(s, rows_from(first), nmetrics, bounds, nb, flags, cum, total, false);
 }
 
 int lh_count_le_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *bounds, size_t nb, uint32_t flags,
                        uint64_t *d_cum, uint64_t *d_total)
 {
-    return count_le(s, first, nmetrics, bounds, nb, flags, d_cum, d_total, true);
+    return count_le(s, rows_from(first), nmetrics, bounds, nb, flags, d_cum, d_total, true);
+}
+
+int lh_count_le_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *bounds, size_t nb, uint32_t flags, uint64_t *cum,
+                    uint64_t *total)
+{
+    return count_le(s, rows_by_id(ids, false), n, bounds, nb, flags, cum, total, false);
+}
+
+int lh_count_le_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *bounds, size_t nb, uint32_t flags,
+                           uint64_t *d_cum, uint64_t *d_total)
+{
+    return count_le(s, rows_by_id(d_ids, true), n, bounds, nb, flags, d_cum, d_total, true);
 }
 
 int lh_tool_count_le_switch(uint32_t wave_from_rows, uint32_t *previous)

@@ -39,6 +39,7 @@
 #include <atomic>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -96,20 +97,24 @@ __device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], const doub
     return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
 }
 
-template <typename CELL>
+// (Both kernels, IDS: entry m reads row ids[m] of the snapshot -- lh::row_of, whose guard against `nrows` leaves an empty span;
+// m still indexes the outputs.  Otherwise row m of the block; ids and nrows are not looked at.)
+template <typename CELL, bool IDS>
 __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                           uint32_t nmetrics, size_t stride, const double *__restrict__ D,
-                                                          const SpreadP pa, uint32_t np, const SpreadOut o)
+                                                          const SpreadP pa, uint32_t np, const SpreadOut o,
+                                                          const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (m >= nmetrics) return; // wave-uniform
-    const Span sp = own_span(ranges, m);
+    const uint32_t r = row_of<IDS>(ids, nrows, m);
+    const Span sp = row_span<IDS>(ranges, r);
     const uint32_t hi = sp.hi;
     u64 total = 0, r_cle = 0;
     double sum = 0.0, m2 = 0.0, r_sle = 0.0;
     uint32_t found = 0xffffffffu; // lane i < np: the bin of percentile i
     if (sp.any()) {               // wave-uniform; an empty row costs two loads and its stores
-        const CELL *__restrict__ row = cells + (size_t)m * stride;
+        const CELL *__restrict__ row = cells + (size_t)r * stride;
         const uint32_t base0 = sp.base0();
         u64 c[4], nc[4];
         double d[4], nd[4], t[4];
@@ -195,10 +200,11 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restric
     }
 }
 
-template <typename CELL>
+template <typename CELL, bool IDS>
 __global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                         uint32_t nmetrics, size_t stride, const double *__restrict__ D,
-                                                        const SpreadP pa, uint32_t np, const SpreadOut o)
+                                                        const SpreadP pa, uint32_t np, const SpreadOut o,
+                                                        const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
     __shared__ double s_sum[CHUNKS]; // the chunks' sums, then their exclusive prefix (ascending order)
@@ -207,9 +213,10 @@ __global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ ce
     __shared__ double s_tsum;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
     if (m >= nmetrics) return;
-    const Span sp = own_span(ranges, m);
+    const uint32_t r = row_of<IDS>(ids, nrows, m);
+    const Span sp = row_span<IDS>(ranges, r);
     const uint32_t hi = sp.hi;
-    const CELL *__restrict__ row = cells + (size_t)m * stride;
+    const CELL *__restrict__ row = cells + (size_t)(IDS && r == NO_ROW ? 0 : r) * stride; // (no row: never read, nchunks is 0)
     const uint32_t base0 = sp.base0(), nchunks = sp.any() ? (hi - base0) / STEP + 1 : 0; // <= CHUNKS
     constexpr uint32_t U = 2;
     // ---- walk 1: every chunk's count and sum
@@ -343,13 +350,15 @@ struct SpreadCtx {
     std::mutex mu;
     double *d_table = nullptr; // D[LH_NKEYS]
     ResultBlocks res;          // host form
+    IdBlocks ids;              // host form of lh_spread_ids
 };
 std::atomic<uint32_t> g_wave_from{SP_WAVE_FROM_DEFAULT};
 
 // every check that needs neither the snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
 // nulled here, and count for nothing.
-int check_args(lh_snapshot *s, size_t nmetrics, const double *p, size_t np, SpreadOut &o)
+int check_args(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *p, size_t np, SpreadOut &o)
 {
+    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
     if (!s || np > LH_MAX_PERCENTILES || (np && !p)) return LH_EINVAL;
     if (np == 0) {
         o.pkeys = nullptr;
@@ -367,46 +376,57 @@ int check_args(lh_snapshot *s, size_t nmetrics, const double *p, size_t np, Spre
 
 typedef lh::beside::Source<SpreadCtx> Source;
 
-// (cx->mu held) enqueue the walks of rows [first, first + nmetrics) on the snapshot's stream
-int enqueue(const Source &q, uint32_t first, size_t nmetrics, const double *p, size_t np, const SpreadOut &o)
+// (cx->mu held) enqueue the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on the snapshot's stream
+int enqueue(const Source &q, const RowSel &sel, size_t nmetrics, const double *p, size_t np, const SpreadOut &o)
 {
     SpreadCtx *cx = q.cx;
-    const int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<SpreadCtx>);
+    const uint32_t *ids = nullptr;
+    int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<SpreadCtx>);
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, q.stream, ids);
     if (rc) return rc;
     SpreadP pa;
     for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
-    const uint32_t *ranges = ranges_from(q, first);
+    const uint32_t *ranges = ranges_from(q, sel.first);
     const double *D = cx->d_table;
     const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    with_cells(q, first, [&](auto *c) {
-        typedef cell_of<decltype(c)> CELL;
-        if (sh.wave) hipLaunchKernelGGL(k_spread_wave<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-        else hipLaunchKernelGGL(k_spread_block<CELL>, sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o);
-    });
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        with_cells(q, sel.first, [&](auto *c) {
+            typedef cell_of<decltype(c)> CELL;
+            if (sh.wave)
+                hipLaunchKernelGGL((k_spread_wave<CELL, IDS>), sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o, ids,
+                                   q.nrows);
+            else
+                hipLaunchKernelGGL((k_spread_block<CELL, IDS>), sh.grid, sh.block, 0, q.stream, c, ranges, M, q.stride, D, pa, NP, o, ids,
+                                   q.nrows);
+        });
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
     LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
 }
 
-int spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, SpreadOut o, bool device_form)
+int spread(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *p, size_t np, SpreadOut o, bool device_form)
 {
-    int rc = check_args(s, nmetrics, p, np, o);
+    int rc = check_args(s, sel, nmetrics, p, np, o);
     if (rc) return rc;
     Source q;
-    rc = source_cells(s, first, nmetrics, q);
+    rc = source_cells(s, sel, nmetrics, q);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any device call
     rc = source_open(s, q);
     if (rc) return rc;
     SpreadCtx *cx = q.cx;
     std::lock_guard<std::mutex> g(cx->mu);
-    if (device_form) return enqueue(q, first, nmetrics, p, np, o);
+    if (device_form) return enqueue(q, sel, nmetrics, p, np, o);
 
     // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys, then the flags.
     const size_t per_m = nmetrics, per_p = nmetrics * np;
     const HostOut out[7] = {{o.count, per_m * 8},    {o.sum, per_m * 8},    {o.m2, per_m * 8},   {o.count_le, per_p * 8},
                             {o.sum_le, per_p * 8}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
-    return host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[7]) {
+    rc = host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[7]) {
         SpreadOut d;
         d.count = reinterpret_cast<u64 *>(dev[0]);
         d.sum = reinterpret_cast<double *>(dev[1]);
@@ -415,8 +435,9 @@ int spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, siz
         d.sum_le = reinterpret_cast<double *>(dev[4]);
         d.pkeys = reinterpret_cast<int16_t *>(dev[5]);
         d.pvalid = reinterpret_cast<uint8_t *>(dev[6]);
-        return enqueue(q, first, nmetrics, p, np, d);
+        return enqueue(q, sel, nmetrics, p, np, d);
     });
+    return settle_ids(rc, sel, q.stream);
 }
 
 } // namespace
@@ -427,7 +448,7 @@ int lh_spread(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, 
               double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
 {
     const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
-    return spread(s, first, nmetrics, p, np, o, false);
+    return spread(s, rows_from(first), nmetrics, p, np, o, false);
 }
 
 int lh_spread_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const double *p, size_t np, uint64_t *d_count,
@@ -435,7 +456,22 @@ int lh_spread_device(lh_snapshot *s, uint32_t first, size_t nmetrics, const doub
 {
     const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
                          d_sum_le};
-    return spread(s, first, nmetrics, p, np, o, true);
+    return spread(s, rows_from(first), nmetrics, p, np, o, true);
+}
+
+int lh_spread_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *p, size_t np, uint64_t *count, double *sum,
+                  double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
+    return spread(s, rows_by_id(ids, false), n, p, np, o, false);
+}
+
+int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *p, size_t np, uint64_t *d_count,
+                         double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
+                         d_sum_le};
+    return spread(s, rows_by_id(d_ids, true), n, p, np, o, true);
 }
 
 int lh_tool_spread_switch(uint32_t wave_from_rows, uint32_t *previous)

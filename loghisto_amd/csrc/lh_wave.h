@@ -3,7 +3,8 @@
 // new reader starts here and in lh_beside.h):
 //   wave primitives   DPP scans, cross-lane reads, the packed 16-byte load types
 //   the arithmetic    the percentile threshold (pct_threshold) and the bound-to-key rule (le_take)
-//   the row walk      the geometry of the two launch shapes, a row's own span (Span, own_span), a row's 4-bin group as one
+//   the row walk      the geometry of the two launch shapes, a row's own span (Span, own_span), which row an entry of a call
+//                     reads (row_of, row_span: the block's m-th, or -- the *_ids forms -- the one an id array names), a row's 4-bin group as one
 //                     load (load4_cells; load4_in inside a span; load4 with the bins' values), a group's count and weighted
 //                     sum (sum4, terms4) and the generator of the value table (k_value_table)
 // The scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the
@@ -206,6 +207,34 @@ __device__ __forceinline__ Span own_span(const uint32_t *__restrict__ ranges, ui
     s.lo = ranges[2 * (size_t)m];
     s.hi = min(ranges[2 * (size_t)m + 1], (uint32_t)LH_NKEYS - 1);
     return s;
+}
+// Which row entry m of a call reads.  A contiguous call (IDS false) reads row m of the block it was handed; an id-list call
+// (the *_ids forms) reads row ids[m] of the snapshot -- m is wave-uniform, so that is one uniform load per row and the row's
+// address is scalar from there on.  An id at or beyond `nrows` gives NO_ROW: row_span then returns an empty span, the one a
+// row that was never marked has, and by the rule above nothing of such a row is read -- not its span either.  m stays the
+// index of every output (and of a per-entry input such as lh_count_le's bounds row).
+constexpr uint32_t NO_ROW = 0xffffffffu;
+template <bool IDS> __device__ __forceinline__ uint32_t row_of(const uint32_t *__restrict__ ids, uint32_t nrows, uint32_t m)
+{
+    if constexpr (!IDS) {
+        return m;
+    } else {
+        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)m); // (unsigned: a list may pass 2^31 entries)
+        const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[at]);
+        return r < nrows ? r : NO_ROW;
+    }
+}
+template <bool IDS> __device__ __forceinline__ Span row_span(const uint32_t *__restrict__ ranges, uint32_t r)
+{
+    if constexpr (IDS) {
+        if (r == NO_ROW) {
+            Span s;
+            s.lo = NO_BIN;
+            s.hi = 0;
+            return s;
+        }
+    }
+    return own_span(ranges, r);
 }
 // the same, entered at a multiple of 4, with lo = NO_BIN > hi = 0 for a row that was never marked: what a union of spans
 // (the least lo, the largest hi) and load4_in take

@@ -59,6 +59,20 @@ def _out_arrays(out: dict, spec):
     return args, all(device)
 
 
+def _id_list(ids):
+    """ids of an *_ids call -> (what keeps the array alive, its address, n, device array?): a torch device tensor of 4-byte
+    elements is handed over as it is, anything else becomes a contiguous uint32 host array."""
+    if hasattr(ids, "data_ptr") and getattr(ids, "is_cuda", False):
+        if ids.element_size() != 4 or not ids.is_contiguous():
+            raise ValueError("device ids are contiguous 4-byte elements")
+        return ids, int(ids.data_ptr()), int(ids.numel()), True
+    a = np.asarray(ids.numpy() if hasattr(ids, "data_ptr") else ids)
+    if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+        raise ValueError("ids are unsigned 32-bit integers")
+    a = np.ascontiguousarray(a, dtype=np.uint32).ravel()
+    return a, int(a.ctypes.data), int(a.size), False
+
+
 class Snapshot:
     """One interval's cells, stolen at the epoch flip (metrics.go:460-463)."""
 
@@ -348,18 +362,31 @@ class Snapshot:
         non-decreasing.  out=(cum, total) of contiguous 8-byte torch device tensors (either may be None) takes the device
         form: enqueued on the snapshot's stream, the tensors are returned as they are.  The host form's arrays are pinned
         host memory, so that the results arrive by one copy."""
-        L = N.lib()
         b = np.ascontiguousarray(bounds, dtype=np.float64)
+        if nmetrics is None:
+            nmetrics = int(b.shape[0]) if b.ndim == 2 else self.engine.num_metrics() - first
+        return self._count_le("lh_count_le", (first, nmetrics), nmetrics, b, out)
+
+    def count_le_ids(self, ids, bounds, out=None):
+        """count_le for the metrics `ids`, in that order (lh_count_le_ids*): row m of cum / total describes metric ids[m],
+        and a 2-D `bounds` holds a row per entry of ids.  ids may repeat and come in any order.  A host list (anything
+        numpy takes) is checked: an id the snapshot has no row for raises.  A torch device tensor of 4-byte ids goes with
+        out=(cum, total) of device tensors (the device form): nothing comes back to the host, and an entry whose id is
+        beyond the rows comes out as zeros."""
+        keep, addr, n, device_ids = _id_list(ids)
+        if device_ids != (out is not None):
+            raise ValueError("device ids go with out= device tensors, host ids without out=")
+        return self._count_le("lh_count_le_ids", (addr, n), n, np.ascontiguousarray(bounds, dtype=np.float64), out)
+
+    def _count_le(self, fn, rows, nmetrics, b, out):
+        """count_le / count_le_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments."""
+        L = N.lib()
         if b.ndim == 2:
             flags, nb = N.LE_PER_METRIC, int(b.shape[1])
-            if nmetrics is None:
-                nmetrics = int(b.shape[0])
             if int(b.shape[0]) != nmetrics:
                 raise ValueError("per-metric bounds hold one row per metric")
         elif b.ndim == 1:
             flags, nb = 0, int(b.size)
-            if nmetrics is None:
-                nmetrics = self.engine.num_metrics() - first
         else:
             raise ValueError("bounds are 1-D (shared) or 2-D [nmetrics, nb]")
         if out is not None:
@@ -367,14 +394,12 @@ class Snapshot:
             for t, n in ((cum, nmetrics * nb), (total, nmetrics)):
                 if t is not None and (t.element_size() != 8 or int(t.numel()) != n or not t.is_contiguous()):
                     raise ValueError("device form: cum holds nmetrics * nb and total nmetrics contiguous 8-byte elements")
-            N.check(L.lh_count_le_device(self._h, first, nmetrics, b.ctypes.data, nb, flags, _ptr(cum), _ptr(total)),
-                    "lh_count_le_device")
+            N.check(getattr(L, fn + "_device")(self._h, *rows, b.ctypes.data, nb, flags, _ptr(cum), _ptr(total)), fn + "_device")
             return dict(cum=cum, total=total)
         import torch
         cum = torch.empty((nmetrics, nb), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)
         total = torch.empty((nmetrics,), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)
-        N.check(L.lh_count_le(self._h, first, nmetrics, b.ctypes.data, nb, flags, cum.ctypes.data, total.ctypes.data),
-                "lh_count_le")
+        N.check(getattr(L, fn)(self._h, *rows, b.ctypes.data, nb, flags, cum.ctypes.data, total.ctypes.data), fn)
         return dict(cum=cum, total=total)
 
     # -- spread and percentile-trimmed sums (the weighted walk of metrics.go:342-346, cut where percentile() cuts) --------
@@ -393,18 +418,35 @@ class Snapshot:
         (the first three) or nmetrics * np elements of 8, 8, 8, 2, 1, 8, 8 bytes; outputs left out are not computed.
         torch device tensors take the device form: enqueued on the snapshot's stream, the tensors are returned as they are
         and nothing is derived.  numpy arrays (pinned ones receive their results by one copy) take the host form."""
-        L = N.lib()
         if nmetrics is None:
             nmetrics = self.engine.num_metrics() - first
+        return self._spread("lh_spread", (first, nmetrics), nmetrics, percentiles, out)
+
+    def spread_ids(self, ids, percentiles, out=None):
+        """spread for the metrics `ids`, in that order (lh_spread_ids*): row m of every array describes metric ids[m].  ids
+        may repeat and come in any order.  A host list (anything numpy takes) is checked: an id the snapshot has no row
+        for raises.  A torch device tensor of 4-byte ids goes with an `out` of device tensors (the device form): nothing
+        comes back to the host, and an entry whose id is beyond the rows comes out as zeros."""
+        keep, addr, n, device_ids = _id_list(ids)
+        return self._spread("lh_spread_ids", (addr, n), n, percentiles, out, device_ids)
+
+    def _spread(self, fn, rows, nmetrics, percentiles, out, device_ids=None):
+        """spread / spread_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments.
+        device_ids: whether an id list lies on the device, which the outputs then do too (None: there is none)."""
+        L = N.lib()
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
         np_ = int(p.size)
+        if device_ids and out is None:
+            raise ValueError("device ids go with an out= of device tensors")
         if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
             args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
                                              for k, width, per_p in self._SPREAD_OUT])
+            if device_ids is not None and device != device_ids:
+                raise ValueError("ids and out are both on the device or both on the host")
             if device:
-                N.check(L.lh_spread_device(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread_device")
+                N.check(getattr(L, fn + "_device")(self._h, *rows, p.ctypes.data, np_, *args), fn + "_device")
                 return dict(out)
-            N.check(L.lh_spread(self._h, first, nmetrics, p.ctypes.data, np_, *args), "lh_spread")
+            N.check(getattr(L, fn)(self._h, *rows, p.ctypes.data, np_, *args), fn)
             res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
                    if v is not None and (np_ or k in ("count", "sum", "m2"))}
         else:
@@ -416,8 +458,8 @@ class Snapshot:
             for k, _, per_p in self._SPREAD_OUT:       # (a row more than an empty call needs: the arrays have addresses)
                 shape = (max(nmetrics, 1), np_) if per_p else (max(nmetrics, 1),)
                 res[k] = torch.zeros(shape, dtype=kinds[k][0], pin_memory=True).numpy().view(kinds[k][1])
-            N.check(L.lh_spread(self._h, first, nmetrics, p.ctypes.data, np_,
-                                *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in self._SPREAD_OUT]), "lh_spread")
+            N.check(getattr(L, fn)(self._h, *rows, p.ctypes.data, np_,
+                                   *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in self._SPREAD_OUT]), fn)
             res = {k: v[:nmetrics] for k, v in res.items()}
         res = {k: (v.reshape(nmetrics, np_) if dict((a, c) for a, _, c in self._SPREAD_OUT)[k] else v.reshape(nmetrics))
                for k, v in res.items()}
@@ -563,21 +605,40 @@ class Snapshot:
         tensors take the device form: enqueued on this snapshot's stream (the others must stay unreleased until that stream
         has passed the call), the tensors are returned as they are and nothing is derived.  numpy arrays (pinned ones
         receive their results by one copy) take the host form."""
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        return self._across("lh_across", earlier, (first, nmetrics), nmetrics, percentiles, out)
+
+    def across_ids(self, ids, earlier, percentiles, out=None):
+        """across for the metrics `ids`, in that order (lh_across_ids*): row m of every array describes metric ids[m] over
+        list(earlier) + [self]; with earlier=() this is the compact extract of chosen names.  ids may repeat and come in
+        any order.  A host list (anything numpy takes) is checked: an id that some snapshot of the list has no row for
+        raises.  A torch device tensor of 4-byte ids -- the ids top(..., out=...) has just written, on the same stream --
+        goes with an `out` of device tensors (the device form): nothing comes back to the host, and an entry whose id is
+        beyond the rows of the shortest snapshot comes out as zeros."""
+        keep, addr, n, device_ids = _id_list(ids)
+        return self._across("lh_across_ids", earlier, (addr, n), n, percentiles, out, device_ids)
+
+    def _across(self, fn, earlier, rows, nmetrics, percentiles, out, device_ids=None):
+        """across / across_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments.
+        device_ids: whether an id list lies on the device, which the outputs then do too (None: there is none)."""
         L = N.lib()
         snaps = list(earlier) + [self]
         handles = (C.c_void_p * len(snaps))(*[s._h.value for s in snaps])
-        if nmetrics is None:
-            nmetrics = self.engine.num_metrics() - first
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
         np_ = int(p.size)
-        lead = (C.addressof(handles), len(snaps), first, nmetrics, p.ctypes.data, np_, 0)
+        lead = (C.addressof(handles), len(snaps), *rows, p.ctypes.data, np_, 0)
+        if device_ids and out is None:
+            raise ValueError("device ids go with an out= of device tensors")
         if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
             args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
                                              for k, width, per_p, _ in self._ACROSS_OUT])
+            if device_ids is not None and device != device_ids:
+                raise ValueError("ids and out are both on the device or both on the host")
             if device:
-                N.check(L.lh_across_device(*lead, *args), "lh_across_device")
+                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
                 return dict(out)
-            N.check(L.lh_across(*lead, *args), "lh_across")
+            N.check(getattr(L, fn)(*lead, *args), fn)
             res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
                    if v is not None and (np_ or k not in ("pkeys", "pvalid"))}
         else:
@@ -586,7 +647,7 @@ class Snapshot:
             for k, width, per_p, dt in self._ACROSS_OUT:   # (a row more than an empty call needs: the arrays have addresses)
                 n = max(nmetrics, 1) * (np_ if per_p else 1)
                 res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
-            N.check(L.lh_across(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._ACROSS_OUT]), "lh_across")
+            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._ACROSS_OUT]), fn)
             res = {k: v[:nmetrics * (np_ if per_p else 1)] for (k, _, per_p, _), v in zip(self._ACROSS_OUT, res.values())}
         per_p = {k: c for k, _, c, _ in self._ACROSS_OUT}
         res = {k: (v.reshape(nmetrics, np_) if per_p[k] else v.reshape(nmetrics)) for k, v in res.items()}
