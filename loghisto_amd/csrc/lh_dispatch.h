@@ -15,6 +15,8 @@
 //   DIRECT  no scratch, no survey: whole tiles through a per-workgroup LDS table of (name, bin) cells, the rest one global
 //           atomic per sample (launch_ingest_pairs_cells): small or misaligned launches, and any launch whose scratch
 //           cannot be had.  The minimum sizes are where each path overtakes it: profiles/r06_small_calls.txt
+//           More than 65 536 names: every mixed launch is DIRECT (no partitioned path plans for them), and DIRECT is then one
+//           global atomic per sample for the whole launch -- the table's 32-bit key (name << 16 | bin) holds names < 2^16
 #pragma once
 
 #include "lh_kernels.h"

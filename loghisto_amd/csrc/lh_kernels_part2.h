@@ -1448,12 +1448,14 @@ __global__ __launch_bounds__(1024) void k_scatter_clustered(const IDT *__restric
             const uint32_t k = (id[j] << 16) | bin;
             const uint32_t h0 = (k * 2654435761u) >> 16; // (the slot mask takes its low bits: 12 or 14 of the product's top 16)
             bool placed = false;
+            if (k != OV_EMPTY) { // (name 65 535, bin 65 535) packs to the empty-slot marker: no probe, the global add below
 #pragma unroll 1
-            for (uint32_t probe = 0; probe < CL_PROBES && !placed; probe++) {
-                const uint32_t sl = (h0 + probe) & (SLOTS - 1u);
-                const uint32_t prev = atomicCAS(&key[sl], OV_EMPTY, k);
-                if (prev == OV_EMPTY) atomicAdd(used, 1u);
-                if (prev == OV_EMPTY || prev == k) { atomicAdd(&cnt[sl], 1u); placed = true; }
+                for (uint32_t probe = 0; probe < CL_PROBES && !placed; probe++) {
+                    const uint32_t sl = (h0 + probe) & (SLOTS - 1u);
+                    const uint32_t prev = atomicCAS(&key[sl], OV_EMPTY, k);
+                    if (prev == OV_EMPTY) atomicAdd(used, 1u);
+                    if (prev == OV_EMPTY || prev == k) { atomicAdd(&cnt[sl], 1u); placed = true; }
+                }
             }
             if (!placed) { v2_global_add(counts, ranges, id[j], bin, 1); atomicAdd(gadds, 1u); }
         }
@@ -1469,7 +1471,8 @@ __global__ __launch_bounds__(1024) void k_scatter_clustered(const IDT *__restric
     // 20 samples).  Runs of 64 .. 256 pairs put 32 .. 128 names into every tile: nearly every sample is its own cell (0.7 ..
     // 0.9 adds per sample, 35 .. 43 ms per 1e9 pairs where the exact-layout path takes 10).  Such a launch reports what it
     // counted here as overflow, and the engine leaves the region scatter at the next flip as it did before this kernel
-    // existed (profiles/r06_first_call.txt, section F).
+    // existed (profiles/r06_first_call.txt, section F).  (The samples of the one cell the table cannot store -- name 65 535 at
+    // key +32767 -- are global adds too: a workgroup whose tiles are mostly that cell reports them the same way.)
     if (tid == 0 && g_ovf) {
         const size_t mine = ((tile - first_tile) / gridDim.x) * TILE;
         if ((size_t)*gadds * 2 > mine) atomicAdd(g_ovf, (uint32_t)mine);
@@ -1482,6 +1485,8 @@ __global__ __launch_bounds__(1024) void k_scatter_clustered(const IDT *__restric
 // cell: same-address atomics serialise) the table adds what meets in a cell BEFORE it goes to memory.  Tiles of 8 192 pairs
 // when there are enough of them to fill the device, of 1 024 otherwise; the pairs behind the last whole tile take
 // k_ingest_pairs.  profiles/r06_small_calls.txt
+// The table's key is name << 16 | bin in 32 bits: it holds names below 65 536.  An engine of more names takes k_ingest_pairs
+// for the whole call (launch_ingest_pairs_cells) -- exact, one global atomic per sample; a wider key is not built.
 template <typename IDT>
 static hipError_t launch_cells_t(const IDT *d_ids, const double *d_v, size_t n, uint64_t *counts, uint32_t *ranges,
                                  uint32_t nmetrics, const double *d_Tx, uint32_t *d_err, int num_cus, hipStream_t s, size_t *done)
@@ -1525,6 +1530,8 @@ hipError_t launch_ingest_pairs_cells(Ids d_ids, const double *d_v, size_t n, uin
                                      uint32_t nmetrics, const double *d_Tx, uint32_t *d_err, int num_cus, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
+    if (nmetrics > 65536u) // (id << 16 would drop the id's high bits: name 65 536 + i counted in row i)
+        return launch_ingest_pairs(d_ids, d_v, n, counts, ranges, nmetrics, d_Tx, d_err, num_cus, s);
     size_t done = 0;
     hipError_t e = d_ids.width == 2 ? launch_cells_t(d_ids.u16(), d_v, n, counts, ranges, nmetrics, d_Tx, d_err, num_cus, s, &done)
                                     : launch_cells_t(d_ids.u32(), d_v, n, counts, ranges, nmetrics, d_Tx, d_err, num_cus, s, &done);

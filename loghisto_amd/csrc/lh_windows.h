@@ -88,9 +88,13 @@ __device__ __forceinline__ void choose_windows(uint32_t *h, uint32_t *s_org, uin
 // open-addressed LDS table keyed by (name << 16 | bin) aggregates them per workgroup; only a record
 // that finds its four probe slots taken by other keys goes to the global atomic.  Flushed with the
 // windows.
+//
+// The empty-slot marker IS a real key where the caller packs a global name: name 65 535 of a 65 536-name engine at
+// key +32767 (bin 65 535) is 0xffffffff.  ov_add does not absorb that one key -- its caller's exact global add takes it
+// like any record the table has no room for -- so a slot that reads OV_EMPTY never carries a count.
 // ---------------------------------------------------------------------------
 constexpr uint32_t OV_SLOTS = 512;
-constexpr uint32_t OV_EMPTY = 0xffffffffu; // never a real key: names are < 2^16
+constexpr uint32_t OV_EMPTY = 0xffffffffu; // (name 65 535, bin 65 535) packs to the same word: never stored, see above
 
 __device__ __forceinline__ void ov_init(uint32_t *ov_key, uint32_t *ov_cnt, uint32_t tid, uint32_t nthreads)
 {
@@ -100,6 +104,7 @@ __device__ __forceinline__ void ov_init(uint32_t *ov_key, uint32_t *ov_cnt, uint
 // true if the record was absorbed by the table
 __device__ __forceinline__ bool ov_add(uint32_t *ov_key, uint32_t *ov_cnt, uint32_t key, uint32_t c)
 {
+    if (key == OV_EMPTY) return false;
     const uint32_t h0 = (key * 2654435761u) >> 23; // 9 bits
 #pragma unroll
     for (uint32_t probe = 0; probe < 4; probe++) {

@@ -19,6 +19,8 @@ CASES = [
     (1000, 1024, "lognormal", 1.0),
     (1000, 5_001, "edge", 1.0),
     (65536, 70_000, "lognormal", 1.0),
+    (65536, 70_000, "edge", 1.0),             # key +-32767, NaN, Inf, wrap at config 4's name count: keys 0xXXXXffff far above 0x03e7ffff
+    (65536, (1 << 17) + 1025, "edge", 1.0),   # (the cell (65 535, bin 65 535) itself: tests/test_gpu_key_edges.py)
     (300, (1 << 17) - 1, "kvalues2", 1.0),
     (300, (1 << 17) + 1025, "loguniform", 1.0),
     (8192, 900_001, "lognormal", 0.0),        # no skew: nearly every sample its own cell, the table empties every other tile

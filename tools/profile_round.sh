@@ -142,7 +142,7 @@ PY
 cd $R
 for f in k1_pmc c3_pmc c4_pmc c4_names_1e9_pmc; do cp $OUT/$f.json $R/profiles/r06_$f.json; done
 python bench.py --full 2> $OUT/bench.err | grep "^{" | tail -1 > $OUT/bench.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/bench20.err | grep "^{" | tail -1 > $OUT/bench_steps20_warmup5.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $OUT/bench20.err | grep "^{" | tail -1 > $OUT/bench_steps20_warmup5.json
 python bench.py --full --workload c4 2> $OUT/c4_bench.err | grep "^{" | tail -1 > $OUT/c4_bench.json
 # first calls of fresh engines and clustered streams (sweeps drop their first calls): per-call times of four calls each
 cd $R
