@@ -627,6 +627,94 @@ int lh_spread_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *p
 int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *p, size_t np, uint64_t *d_count,
                          double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
                          double *d_sum_le);
+/* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
+ *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
+ *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise
+ *   ProcessedMetricSet  /root/reference/metrics.go:62-66     map[string]float64: gauges and whatever a subscriber added too
+ * lh_serialize (K6, below) is that loop for the keys processMetrics makes.  lh_lines* is that loop for ARBITRARY columns that
+ * already lie in device memory -- the arrays the readers above return from their _device forms (count_le's cum / total, spread's
+ * m2 / sum_le / pkeys, the records of lh_top_device, lh_across' count / sum / pkeys): each per-name key / value pair becomes
+ * one line, assembled and formatted on the device as K6 does it.  No statistic is defined and nothing is summed across names.
+ *   NAMES.  A unit beside the engine cannot see the engine's name table: an lh_names handle holds a device copy of the names
+ *   [0, lh_num_metrics) at the time of lh_names_create, fetched through lh_metric_name, on device `device` (the engine's
+ *   lh_config.device).  lh_names_refresh appends the names interned since (*count, may be NULL: the names held).  The engine
+ *   must be alive for create and refresh only; lh_lines* never touches it.  A name longer than 16 MiB - 8 KiB, or more than
+ *   4 GiB of names -> LH_ERANGE from create / refresh.
+ *   LINES.  One line per (entry, column):  prefix  key  sep  %f  suffix  with key = fmt.Sprintf(label, name) and the value
+ *   printed as Go's %f prints a float64 (as lh_serialize).  LH_FMT_UNDERSCORE_TO_DOT is applied to the whole key, name and
+ *   label text alike (graphite.go:42), as lh_serialize does.  Lines are entry-major, columns in the order given; no trailing
+ *   NUL.  prefix + sep + suffix + all labels: at most 4 KiB.
+ *   VALUES.  A source element becomes a float64 the way the reference converts a count, float64(count) (metrics.go:349):
+ *     LH_OP_VALUE       a
+ *     LH_OP_RATIO       a / b, an IEEE divide
+ *     LH_OP_SQRT_RATIO  sqrt(a / b), correctly rounded
+ *     LH_OP_DIFF        a - b: in uint64 (wrapping), then converted, when both elements are integers; in float64 otherwise
+ *   LH_COL_KEY (an int16 bucket key, printed as its value D[(uint16)key ^ 0x8000], D bit for bit lh_codec_tables' D) is allowed
+ *   for `a` under LH_OP_VALUE only.  NaN prints as "NaN", +-Inf as "+Inf" / "-Inf", as Go does; with LH_LINES_SKIP_NAN a
+ *   NaN line is omitted instead (lh_compare returns NaN for a name that is empty on one side).
+ *   WHICH ENTRIES EMIT.  Entry m's name is first + m, or (lh_lines_ids*) the uint32 at (char *)d_ids + m * id_stride -- so the
+ *   `id` field of lh_top_entry / lh_mover_entry records is used directly with id_stride 32.  An entry whose
+ *   d_row_count element (at byte stride row_count_stride; usually the count / total array a reader returned) is 0 emits nothing,
+ *   as lh_serialize omits names without samples; d_row_count NULL: every entry emits.  A column's line is omitted where
+ *   valid[m * valid_stride] == 0.  An id at or beyond the names held emits nothing (the host never sees device ids: the
+ *   stance of the *_ids_device forms above).  first + n beyond the names held -> LH_ERANGE.
+ *   EVERYTHING DATA-SHAPED IS DEVICE MEMORY IN ALL FOUR FORMS: columns, valid arrays, row counts and ids are the outputs of
+ *   the readers' _device forms, valid until `stream` has passed the call.  The work goes on `stream` (a hipStream_t; usually
+ *   lh_snapshot_stream(s), so that it runs behind the reader that fills the columns); NULL: the null stream of the handle's
+ *   device.
+ *   TEXT.  Host forms (lh_lines, lh_lines_ids): lh_serialize's size-then-call protocol -- *len always receives the byte
+ *   count; when it exceeds cap, or out is NULL, nothing is written and the status is LH_OK.  They return when the text is
+ *   in `out`.  Device forms (lh_lines_device, lh_lines_ids_device) return after enqueueing and never wait for their own work:
+ *   *d_len (8-byte aligned device memory) always receives the total, d_out is written only when the total fits cap (d_out
+ *   may be NULL to size).
+ *   LH_EINVAL, decided on the host before the handle is dereferenced or a device is touched: nm, cols, fmt (or one of its
+ *            three pieces) or len / d_len NULL; ncols 0 or above LH_MAX_COLUMNS; an unknown type, op or flag bit; a non-zero
+ *            reserved field; a label without exactly one %s (or with a % that is neither %s nor %%); prefix + sep + suffix +
+ *            labels above 4 KiB; `a` NULL; an op other than LH_OP_VALUE with b NULL; LH_COL_KEY anywhere but `a` under
+ *            LH_OP_VALUE; a, b, d_row_count or their strides not a multiple of the element size (8 / 8 / 4 / 2 bytes for
+ *            F64 / U64 / U32 / KEY); d_ids NULL with n > 0; d_ids or id_stride not a multiple of 4; len / d_len misaligned.
+ *   LH_ERANGE: n above 2^32 - 1 (a cause of LH_EINVAL wins over it); a block of names the handle does not hold.
+ *   n == 0 -> LH_OK with *len = 0 before any device call (a device form enqueues the one store of *d_len = 0).
+ *   THREADING.  One mutex per handle, held for the length of a call.  The handle's blocks -- descriptors, labels, line
+ *   lengths, workgroup offsets, the host forms' text -- only grow and are guarded by an event across streams: a device-form
+ *   call returns while they are in use, and the next call (or lh_names_refresh, before it replaces the name table) waits
+ *   for that event before it rewrites them.  lh_names_destroy waits for it too. */
+typedef struct lh_names lh_names;
+struct lh_line_format;             /* the wire format's pieces: defined with lh_serialize below */
+int lh_names_create(lh_engine *e, int device, lh_names **out);
+int lh_names_refresh(lh_names *nm, uint32_t *count);
+int lh_names_destroy(lh_names *nm);
+
+#define LH_MAX_COLUMNS 128
+enum { LH_COL_F64 = 0, LH_COL_U64 = 1, LH_COL_U32 = 2, LH_COL_KEY = 3 };
+enum { LH_OP_VALUE = 0, LH_OP_RATIO = 1, LH_OP_SQRT_RATIO = 2, LH_OP_DIFF = 3 };
+enum { LH_LINES_SKIP_NAN = 1 };
+typedef struct lh_column {            /* 64 bytes */
+    const char *label;                /* Go format with exactly one %s ("%s_std"); "%%" is a literal % (as lh_serialize) */
+    const void *a;                    /* DEVICE memory; element of entry m at (char *)a + m * a_stride */
+    const void *b;                    /* likewise; NULL for LH_OP_VALUE */
+    const uint8_t *valid;             /* DEVICE, may be NULL: entry m's line is omitted when valid[m * valid_stride] == 0 */
+    uint64_t a_stride;                /* BYTES */
+    uint64_t b_stride;
+    uint64_t valid_stride;
+    uint8_t a_type;                   /* LH_COL_* */
+    uint8_t b_type;
+    uint8_t op;                       /* LH_OP_* */
+    uint8_t reserved0;                /* 0 */
+    uint32_t reserved1;               /* 0 */
+} lh_column;
+int lh_lines(lh_names *nm, uint32_t first, size_t n, const uint64_t *d_row_count, uint64_t row_count_stride,
+             const lh_column *cols, size_t ncols, const struct lh_line_format *fmt, uint32_t flags, void *stream,
+             char *out, size_t cap, size_t *len);
+int lh_lines_ids(lh_names *nm, const uint32_t *d_ids, uint64_t id_stride, size_t n, const uint64_t *d_row_count,
+                 uint64_t row_count_stride, const lh_column *cols, size_t ncols, const struct lh_line_format *fmt, uint32_t flags,
+                 void *stream, char *out, size_t cap, size_t *len);
+int lh_lines_device(lh_names *nm, uint32_t first, size_t n, const uint64_t *d_row_count, uint64_t row_count_stride,
+                    const lh_column *cols, size_t ncols, const struct lh_line_format *fmt, uint32_t flags, void *stream,
+                    char *d_out, size_t cap, uint64_t *d_len);
+int lh_lines_ids_device(lh_names *nm, const uint32_t *d_ids, uint64_t id_stride, size_t n, const uint64_t *d_row_count,
+                        uint64_t row_count_stride, const lh_column *cols, size_t ncols, const struct lh_line_format *fmt,
+                        uint32_t flags, void *stream, char *d_out, size_t cap, uint64_t *d_len);
 /* K4 -- multi-GPU merge of a snapshot across the ranks of an RCCL communicator (one process per GPU).
  * Ingest is data-parallel: every rank buckets its own slice of the stream for ALL names; the only
  * exchange is this integer SUM of the occupied window of the uint64 bucket matrix at the flip

@@ -26,6 +26,10 @@ TOP_ASCENDING = 1
 MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   # lh_movers* (k <= MAX_TOP)
 MOVERS_ASCENDING = 1
 MAX_ACROSS = 16        # lh_across*: snapshots of one call
+MAX_COLUMNS = 128      # lh_lines*
+COL_F64, COL_U64, COL_U32, COL_KEY = range(4)
+OP_VALUE, OP_RATIO, OP_SQRT_RATIO, OP_DIFF = range(4)
+LINES_SKIP_NAN = 1
 
 OK, EINVAL, ENOMEM, EDEVICE, ENODEVICE, EBUSY, ERANGE, ESTATE = range(8)
 
@@ -117,6 +121,14 @@ class LhMergeInfo(C.Structure):
 class LhLineFormat(C.Structure):
     _fields_ = [("prefix", C.c_char_p), ("sep", C.c_char_p), ("suffix", C.c_char_p),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LhColumn(C.Structure):
+    """lh_column (64 bytes): one column of an lh_lines* call."""
+    _fields_ = [("label", C.c_char_p), ("a", C.c_void_p), ("b", C.c_void_p), ("valid", C.c_void_p),
+                ("a_stride", C.c_uint64), ("b_stride", C.c_uint64), ("valid_stride", C.c_uint64),
+                ("a_type", C.c_uint8), ("b_type", C.c_uint8), ("op", C.c_uint8), ("reserved0", C.c_uint8),
+                ("reserved1", C.c_uint32)]
 
 
 FMT_UNDERSCORE_TO_DOT = 1
@@ -235,6 +247,17 @@ SIGNATURES = {
     "lh_count_le_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
     "lh_spread_ids": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_spread_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    "lh_names_refresh": (C.c_int, [_vp, _u32p]),
+    "lh_names_destroy": (C.c_int, [_vp]),
+    "lh_lines": (C.c_int, [_vp, C.c_uint32, _sz, _vp, C.c_uint64, C.POINTER(LhColumn), _sz, C.POINTER(LhLineFormat), C.c_uint32,
+                           _vp, _vp, _sz, _vp]),
+    "lh_lines_ids": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _vp, C.c_uint64, C.POINTER(LhColumn), _sz, C.POINTER(LhLineFormat),
+                               C.c_uint32, _vp, _vp, _sz, _vp]),
+    "lh_lines_device": (C.c_int, [_vp, C.c_uint32, _sz, _vp, C.c_uint64, C.POINTER(LhColumn), _sz, C.POINTER(LhLineFormat),
+                                  C.c_uint32, _vp, _vp, _sz, _vp]),
+    "lh_lines_ids_device": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _vp, C.c_uint64, C.POINTER(LhColumn), _sz,
+                                      C.POINTER(LhLineFormat), C.c_uint32, _vp, _vp, _sz, _vp]),
     "lh_snapshot_merge": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _u32p, _u32p]),
     "lh_snapshot_merge_info": (C.c_int, [_vp, C.POINTER(LhMergeInfo)]),
     "lh_set_rccl_library": (C.c_int, [C.c_char_p]),

@@ -479,6 +479,39 @@ class Snapshot:
             self.engine._decompress_table = self.engine.codec_tables()[1]
         return self.engine._decompress_table
 
+    def spread_lines(self, names: "Names", percentiles, prefix: str, sep: str, suffix: str, underscore_to_dot: bool = False,
+                     nmetrics: Optional[int] = None, first: int = 0) -> bytes:
+        """What statsd emits per name, as wire text formatted on the device: lh_spread_device into device tensors, then
+        Names.lines over them on the snapshot's stream -- nothing but the text comes back to the host.  Per name with samples
+        <name>_std = sqrt(m2 / count), then per percentile that has a bucket <name>_mean_<p> = sum_le / count_le,
+        <name>_upper_<p> = decompress(key), <name>_count_<p> = count_le and <name>_sum_<p> = sum_le.  `percentiles` is a
+        sequence of p (<p> is then 100 * p as %.10g prints it: 0.999 -> "99.9") or a mapping <p> text -> p."""
+        import torch
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        tags = list(percentiles.keys()) if hasattr(percentiles, "keys") else ["%.10g" % (100.0 * float(p)) for p in percentiles]
+        ps = [float(percentiles[t]) for t in tags] if hasattr(percentiles, "keys") else [float(p) for p in percentiles]
+        np_ = len(ps)
+        dev = torch.device("cuda", self.engine.device)
+        if nmetrics == 0:
+            return b""
+        t = dict(count=torch.empty(nmetrics, dtype=torch.int64, device=dev), m2=torch.empty(nmetrics, dtype=torch.float64, device=dev))
+        if np_:                                            # (lh_spread_device writes every element: nothing to clear)
+            shape = (nmetrics, np_)
+            t.update(pkeys=torch.empty(shape, dtype=torch.int16, device=dev), pvalid=torch.empty(shape, dtype=torch.uint8, device=dev),
+                     count_le=torch.empty(shape, dtype=torch.int64, device=dev), sum_le=torch.empty(shape, dtype=torch.float64, device=dev))
+        self._spread("lh_spread", (first, nmetrics), nmetrics, ps, t)
+        cols = [dict(label="%s_std", a=t["m2"], b=t["count"], op="sqrt_ratio")]
+        for i, tag in enumerate(tags):
+            tag = tag.replace("%", "%%")
+            v = t["pvalid"][:, i]
+            cols += [dict(label="%s_mean_" + tag, a=t["sum_le"][:, i], b=t["count_le"][:, i], op="ratio", valid=v),
+                     dict(label="%s_upper_" + tag, a=t["pkeys"][:, i], key=True, valid=v),
+                     dict(label="%s_count_" + tag, a=t["count_le"][:, i], valid=v),
+                     dict(label="%s_sum_" + tag, a=t["sum_le"][:, i], valid=v)]
+        return names.lines(cols, n=nmetrics, first=first, row_count=t["count"], prefix=prefix, sep=sep, suffix=suffix,
+                           underscore_to_dot=underscore_to_dot, stream=self.stream())
+
     # -- the k names that lead (a selection across names; what is ranked is what extract / count_le return) ---------------
     _TOP_BY = {"count": N.TOP_BY_COUNT, "sum": N.TOP_BY_SUM, "percentile": N.TOP_BY_PERCENTILE,
                "count_above": N.TOP_BY_COUNT_ABOVE}
@@ -692,6 +725,135 @@ class Snapshot:
         self.release()
 
 
+def _device_column(t, what, widths):
+    """A 1-D (possibly strided) torch device tensor whose (element width, "f" | "i") is in `widths` -> (address, byte stride,
+    element width, elements).  Host memory is refused: every data-shaped argument of lh_lines* is device memory."""
+    if not (hasattr(t, "data_ptr") and getattr(t, "is_cuda", False)):
+        raise ValueError(f"{what} is a torch device tensor (lh_lines* reads device memory only)")
+    if t.dim() != 1:
+        raise ValueError(f"{what} is 1-D (a strided view such as t[:, i] is fine)")
+    width = t.element_size()
+    if (width, "f" if t.is_floating_point() else "i") not in widths:
+        raise ValueError(f"{what} has an element type lh_lines* does not take")
+    return int(t.data_ptr()), int(t.stride(0)) * width if t.numel() > 1 else width, width, int(t.numel())
+
+
+class Names:
+    """A device copy of an engine's metric names (lh_names): what lh_lines* prints keys from.  Engine.device_names()."""
+
+    _OPS = {"value": N.OP_VALUE, "ratio": N.OP_RATIO, "sqrt_ratio": N.OP_SQRT_RATIO, "diff": N.OP_DIFF}
+
+    def __init__(self, engine: "Engine"):
+        h = C.c_void_p(0)
+        N.check(N.lib().lh_names_create(engine._h, engine.device, C.byref(h)), "lh_names_create")
+        self._h = h
+        self.engine = engine
+        self._buf = None
+        self.count = self.refresh()
+
+    def refresh(self) -> int:
+        """Appends the names interned since (lh_names_refresh) -> the number of names held."""
+        n = C.c_uint32(0)
+        N.check(N.lib().lh_names_refresh(self._h, C.byref(n)), "lh_names_refresh")
+        self.count = int(n.value)
+        return self.count
+
+    def _column(self, c: dict, n: int) -> N.LhColumn:
+        if set(c) - {"label", "a", "b", "op", "valid", "key"}:
+            raise ValueError("a column holds label, a and optionally b, op, valid, key")
+        op = c.get("op", "value")
+        if op not in self._OPS:
+            raise ValueError("op is one of " + ", ".join(self._OPS))
+        col = N.LhColumn()
+        col.label = c["label"].encode()
+        col.op = self._OPS[op]
+        for side in ("a", "b"):
+            t = c.get(side)
+            if t is None:
+                continue
+            key = side == "a" and bool(c.get("key"))
+            addr, stride, width, numel = _device_column(t, f"column {c['label']!r}: {side}",
+                                                        ((2, "i"),) if key else ((8, "f"), (8, "i"), (4, "i")))
+            if numel < n:
+                raise ValueError(f"column {c['label']!r}: {side} holds fewer than n elements")
+            kind = N.COL_KEY if key else N.COL_F64 if t.is_floating_point() else N.COL_U64 if width == 8 else N.COL_U32
+            setattr(col, side, addr)
+            setattr(col, side + "_stride", stride)
+            setattr(col, side + "_type", kind)
+        if c.get("key") and op != "value":
+            raise ValueError("key=True goes with op='value'")
+        if c.get("valid") is not None:
+            addr, stride, _, numel = _device_column(c["valid"], f"column {c['label']!r}: valid", ((1, "i"),))
+            if numel < n:
+                raise ValueError(f"column {c['label']!r}: valid holds fewer than n elements")
+            col.valid, col.valid_stride = addr, stride
+        return col
+
+    def lines(self, columns, n: Optional[int] = None, first: int = 0, ids=None, row_count=None, prefix: str = "", sep: str = " ",
+              suffix: str = "\n", underscore_to_dot: bool = False, skip_nan: bool = False, stream=None, out=None):
+        """One wire line per (entry, column), formatted on the device (lh_lines*): prefix key sep %f suffix with key =
+        label % name.  Each column is a dict: label (a Go format with one %s), a, optionally b, op ("value", "ratio" = a / b,
+        "sqrt_ratio" = sqrt(a / b), "diff" = a - b), valid (uint8: 0 omits the line) and key=True (a holds int16 bucket keys,
+        printed as their values).  a, b, valid, ids and row_count are 1-D torch DEVICE tensors, possibly strided views
+        (t[:, i] of an [n, np] tensor); the element type comes from the dtype (float64; 8- and 4-byte integers as unsigned).
+        Entry m's name is first + m, or ids[m] (4-byte integers; an id beyond the names held emits nothing); an entry whose
+        row_count is 0 emits nothing.  The work goes on `stream` (an int handle or a torch stream; usually
+        snapshot.stream()); None: the null stream.  Returns the text as bytes -- or, with out=(uint8 tensor, 8-byte length
+        tensor) on the device, takes the device form and returns `out`: the length always arrives, the text only if it
+        fits."""
+        L = N.lib()
+        id_addr = id_stride = 0
+        if ids is not None:
+            id_addr, id_stride, _, numel = _device_column(ids, "ids", ((4, "i"),))
+            n = numel if n is None else n
+            if numel < n:
+                raise ValueError("ids holds fewer than n elements")
+        elif n is None:
+            n = self.count - first
+        if n == 0 and out is None:                        # (an empty tensor has no address to hand over)
+            return b""
+        cols = (N.LhColumn * max(1, len(columns)))(*[self._column(c, n) for c in columns])
+        rc_addr = rc_stride = 0
+        if row_count is not None:
+            rc_addr, rc_stride, _, numel = _device_column(row_count, "row_count", ((8, "i"),))
+            if numel < n:
+                raise ValueError("row_count holds fewer than n elements")
+        fmt = N.LhLineFormat(prefix.encode(), sep.encode(), suffix.encode(), N.FMT_UNDERSCORE_TO_DOT if underscore_to_dot else 0, 0)
+        flags = N.LINES_SKIP_NAN if skip_nan else 0
+        rows = (id_addr, id_stride, n) if ids is not None else (first, n)
+        fn = "lh_lines_ids" if ids is not None else "lh_lines"
+        lead = (self._h, *rows, rc_addr, rc_stride, cols, len(columns), C.byref(fmt), flags, _stream_handle(stream))
+        if out is not None:
+            text, length = out
+            for t, what in ((text, "text"), (length, "length")):
+                if not (hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) and t.is_contiguous()):
+                    raise ValueError(f"device form: {what} is a contiguous torch device tensor")
+            if length.element_size() * int(length.numel()) < 8:
+                raise ValueError("device form: length holds 8 bytes")
+            N.check(getattr(L, fn + "_device")(*lead, _ptr(text), text.element_size() * int(text.numel()), _ptr(length)),
+                    fn + "_device")
+            return out
+        need = C.c_size_t(0)
+        if self._buf is None:
+            self._buf = C.create_string_buffer(1 << 20)
+        N.check(getattr(L, fn)(*lead, self._buf, len(self._buf), C.byref(need)), fn)
+        if need.value > len(self._buf):                 # size-then-call: the buffer only grows
+            self._buf = C.create_string_buffer(1 << max(20, int(need.value - 1).bit_length()))
+            N.check(getattr(L, fn)(*lead, self._buf, len(self._buf), C.byref(need)), fn)
+        return C.string_at(self._buf, need.value)
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            N.check(N.lib().lh_names_destroy(self._h), "lh_names_destroy")
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Engine:
     def __init__(self, device: int = 0, max_metrics: int = 1024, num_buffers: int = 2, num_lanes: int = 4,
                  lane_samples: int = 1 << 20, max_counters: int = 1024, cell_bits: Optional[int] = None):
@@ -712,6 +874,7 @@ class Engine:
         h = C.c_void_p(0)
         N.check(L.lh_create(C.byref(cfg), C.byref(h)), "lh_create")
         self._h = h
+        self.device = device
         self.max_metrics = max_metrics
         if widen_at:
             N.check(L.lh_set_option(h, N.OPT_WIDEN_AT_SAMPLES, widen_at), "lh_set_option")
@@ -736,6 +899,10 @@ class Engine:
         out = C.c_uint32(0)
         N.check(N.lib().lh_num_metrics(self._h, C.byref(out)), "lh_num_metrics")
         return int(out.value)
+
+    def device_names(self) -> "Names":
+        """A device copy of the names interned so far (lh_names_create), for Names.lines / Snapshot.spread_lines."""
+        return Names(self)
 
     def metric_name(self, metric_id: int) -> str:
         ln = C.c_size_t(0)
