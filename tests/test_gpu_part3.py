@@ -328,8 +328,10 @@ def test_threshold_fixture_through_the_hashed_scatter(native_lib, torch_cuda):
     import loghisto_amd
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
     import make_thresholds as mt
+    from tests import _adversarial_values as av
     x, _, _ = mt.read()
-    v = np.concatenate([x, -x, x[::-1]])
+    # ... and two and three ulp out, the doubles where 1 + |v| itself rounds, NaN payloads, infinities, the wrap region
+    v = np.concatenate([x, -x, x[::-1], av.extra_classes()])
     M = 9000
     ids = ((np.arange(v.size, dtype=np.uint64) * 7919) % M).astype(np.uint32)
     with loghisto_amd.Engine(max_metrics=M, num_buffers=2, num_lanes=1, lane_samples=1 << 16) as e:
