@@ -1,12 +1,8 @@
 // lh_fmt.h -- Go's %f for a float64 on the device (strconv.FormatFloat(v, 'f', 6, 64): the exact decimal expansion, 6
 // fractional digits, round-half-even on the exact value, "NaN" / "+Inf" / "-Inf"), and the workgroup scan the line kernels
-// lay their output out with.  For the units built beside the engine (lh_lines.hip).
-//
-// This text is lh_kernels_fmt.hip's (K6), which KEEPS ITS OWN COPY: that file is one of the sources the committed profiles
-// are stamped with (bench.tree_stamp), so it takes this header in the change that next regenerates them -- as lh_kernels.hip
-// keeps its pct_threshold beside lh_wave.h's.  Until then a fix to the formatter goes to both; tests/test_gpu_serialize.py
-// (test_format_f_matches_go_percent_f) holds K6's copy to the oracle and tests/test_gpu_lines.py holds this one, on the same
-// values.
+// lay their output out with.  The only copy: K6 (lh_kernels_fmt.hip) and lh_lines.hip both format with it, and
+// tests/test_gpu_serialize.py (test_format_f_matches_go_percent_f) and tests/test_gpu_lines.py hold it to the oracle
+// through either.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -87,8 +83,8 @@ __device__ __forceinline__ void put_digits(char *dst, uint64_t x, uint32_t nd)
 }
 
 // |v| >= 2^64: the value is the integer mant * 2^sh.  Decimal digits by repeated division by 1e9 (the rare path).
-// Returns the digit count; writes them when dst != nullptr.
-__device__ __noinline__ uint32_t big_digits(uint64_t bits, char *dst)
+// Returns the digit count; writes them when dst != nullptr.  (static: every unit that includes this has its own, out of line.)
+static __device__ __noinline__ uint32_t big_digits(uint64_t bits, char *dst)
 {
     const uint32_t eb = (uint32_t)(bits >> 52) & 0x7ffu;
     const uint64_t mant = (bits & 0xfffffffffffffull) | (1ull << 52);

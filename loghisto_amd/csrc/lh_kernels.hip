@@ -18,6 +18,7 @@
 #include "lh_kernels.h"
 #include "lh_codec.h"
 #include "lh_ids.h"
+#include "lh_wave.h"
 
 #include <algorithm>
 #include <atomic>
@@ -523,13 +524,6 @@ __device__ __forceinline__ uint64_t shfl_down_u64(uint64_t x, int d)
     hi = __shfl_down(hi, d, 64);
     return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t x, int src)
-{
-    uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-    lo = __shfl(lo, src, 64);
-    hi = __shfl(hi, src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ double shfl_f64(double x, int src)
 {
     return __longlong_as_double((long long)shfl_u64((uint64_t)__double_as_longlong(x), src));
@@ -701,91 +695,9 @@ __global__ __launch_bounds__(K2_BLOCK) void k_extract(const CELL *__restrict__ c
     }
 }
 
-// ---------------------------------------------------------------------------
-// Wave-level arithmetic that stays in the VALU (DPP): k_extract_wave's scans and reductions.  __shfl_up / __shfl_down
-// compile to ds_bpermute_b32 -- a round trip through the LDS crossbar each, two per 64-bit value -- and round 4's
-// wave kernel issued 216 of them per name.
-// ---------------------------------------------------------------------------
-#define LH_DPP32(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), (rows), 0xf, false))
-template <int CTRL, int ROWS> __device__ __forceinline__ uint64_t dpp_u64(uint64_t x)
-{
-    const uint32_t lo = LH_DPP32((uint32_t)x, CTRL, ROWS), hi = LH_DPP32((uint32_t)(x >> 32), CTRL, ROWS);
-    return ((uint64_t)hi << 32) | lo; // lanes without a source (or outside ROWS) get 0
-}
-// inclusive prefix sum over the 64 lanes: four steps inside the rows of 16 lanes (row_shr:1/2/4/8), then lane 15 of
-// rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3 (row_bcast:31)
-__device__ __forceinline__ uint64_t wave_scan_incl_u64(uint64_t x)
-{
-    x += dpp_u64<0x111, 0xf>(x);
-    x += dpp_u64<0x112, 0xf>(x);
-    x += dpp_u64<0x114, 0xf>(x);
-    x += dpp_u64<0x118, 0xf>(x);
-    x += dpp_u64<0x142, 0xa>(x);
-    x += dpp_u64<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t x)
-{
-    x += LH_DPP32(x, 0x111, 0xf);
-    x += LH_DPP32(x, 0x112, 0xf);
-    x += LH_DPP32(x, 0x114, 0xf);
-    x += LH_DPP32(x, 0x118, 0xf);
-    x += LH_DPP32(x, 0x142, 0xa);
-    x += LH_DPP32(x, 0x143, 0xc);
-    return x;
-}
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t x, uint32_t src) // src wave-uniform
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)src);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ double readlane_f64(double x, uint32_t src)
-{
-    return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), src));
-}
-// x of lane + D for the lanes whose lane + D is in the same row of 16 (what the others get does not matter to the caller)
-template <int D> __device__ __forceinline__ double row_down_f64(double x)
-{
-    return __longlong_as_double((long long)dpp_u64<0x100 + D, 0xf>((uint64_t)__double_as_longlong(x))); // row_shl:D
-}
-
-// metrics.go:413 as an INTEGER threshold: float64(sofar) / float64(total) >= p is monotone in sofar, so there is a
-// smallest prefix count T in [1, total] that reaches percentile p, and "the first bucket that reaches p" is the first
-// bin whose inclusive prefix is >= T (that bin is occupied: the prefix moves there).  One to three IEEE divides per
-// (name, percentile) -- by the lane that owns the percentile -- instead of one per cell.  ~0: no prefix reaches p
-// (p > 1 or NaN: the key is omitted, metrics.go:417).
-__device__ __forceinline__ bool pct_reached(uint64_t s, double ft, double p) { return (double)s / ft >= p; }
-__device__ inline uint64_t pct_threshold(double p, uint64_t total)
-{
-    if (!(1.0 >= p)) return ~0ull; // the largest quotient is float64(total) / float64(total) == 1
-    if (p <= 0.0) return 1;        // the first occupied bucket
-    const double ft = (double)total, est = p * ft;
-    uint64_t s = est >= 18446744073709549568.0 ? total : (uint64_t)est;
-    if ((double)s < est) s++; // ceil(p * total): the threshold itself unless a rounding went the other way
-    s = s < 1 ? 1 : (s > total ? total : s);
-    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s; // two divides: the usual case
-#pragma unroll 1
-    for (int it = 0; it < 4 && s > 1 && pct_reached(s - 1, ft, p); it++) s--;
-#pragma unroll 1
-    for (int it = 0; it < 4 && s < total && !pct_reached(s, ft, p); it++) s++;
-    if (pct_reached(s, ft, p) && (s == 1 || !pct_reached(s - 1, ft, p))) return s;
-    // not settled in four steps either way (totals beyond 2^53, where float64(s) moves in steps): bisection;
-    // reached(total) holds
-    uint64_t lo = 0, hi = total;
-#pragma unroll 1
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (pct_reached(mid, ft, p)) hi = mid; else lo = mid;
-    }
-    return hi;
-}
-
-// 16 bytes at an 8-byte-aligned address as ONE load (global_load_dwordx4; unaligned vector access is on for HSA)
-struct __attribute__((packed, aligned(8))) u64x2_a8 { uint64_t a, b; };
-struct __attribute__((packed, aligned(8))) f64x2_a8 { double a, b; };
-struct __attribute__((packed, aligned(4))) u32x4_a4 { uint32_t a, b, c, d; };
-
+// k_extract_wave: a wave per name.  Its scans and reductions stay in the VALU (lh_wave.h's DPP primitives), and a
+// percentile is the integer prefix count that reaches it (lh_wave.h's pct_threshold).
+//
 // What k_extract_wave does with a span it holds in registers (32-bit cells, a total below 2^32): pass 1 of
 // processHistograms, the prefix scan, the percentile search.
 __device__ __forceinline__ uint32_t ew_scan(uint32_t x) { return wave_scan_incl_u32(x); }
@@ -859,9 +771,9 @@ __device__ __forceinline__ void ew_reduce_and_search(const CT (&creg)[4][K2_PER_
 
     // ---- pass 2 (metrics.go:406-418): lane i < np owns percentile i; T = the prefix count that reaches it
     if (total && np) {
-        uint64_t T64 = ~0ull;
+        uint64_t T64 = PCT_NONE;
         if (lane < np) T64 = pct_threshold(pa.p[lane], (uint64_t)total);
-        const bool has = T64 != ~0ull; // (np <= 32: lanes 32 .. 63 hold no percentile)
+        const bool has = T64 != PCT_NONE; // (np <= 32: lanes 32 .. 63 hold no percentile)
         const CT T = (CT)T64;          // (a threshold that exists is <= total)
         // the step a percentile ends in: the first whose running total reaches its threshold (one compare per boundary for
         // all percentiles at once; a step then visits only its own)
@@ -993,7 +905,7 @@ __global__ __launch_bounds__(K2_BLOCK) void k_extract_wave(const CELL *__restric
     } else {
         // ---- wide span: every bin read here and again by the scan below
         uint64_t cnt = 0;
-        double sum4[K2_WAVES] = {0, 0, 0, 0};
+        double vsum[K2_WAVES] = {0, 0, 0, 0};
         uint32_t nb = 0;
         if (lo <= hi) {
             for (uint32_t base = lo; base <= hi; base += K2_BLOCK) {
@@ -1004,7 +916,7 @@ __global__ __launch_bounds__(K2_BLOCK) void k_extract_wave(const CELL *__restric
                         const uint64_t c = row[b];
                         if (c) {
                             cnt += c;
-                            sum4[v] += D[b] * (double)c;
+                            vsum[v] += D[b] * (double)c;
                             nb++;
                         }
                     }
@@ -1016,11 +928,11 @@ __global__ __launch_bounds__(K2_BLOCK) void k_extract_wave(const CELL *__restric
             cnt += shfl_down_u64(cnt, d);
             nb += __shfl_down(nb, d, 64);
 #pragma unroll
-            for (int v = 0; v < K2_WAVES; v++) sum4[v] += shfl_down_f64(sum4[v], d);
+            for (int v = 0; v < K2_WAVES; v++) vsum[v] += shfl_down_f64(vsum[v], d);
         }
         total = shfl_u64(cnt, 0);
 #pragma unroll
-        for (int v = 0; v < K2_WAVES; v++) tsum += shfl_f64(sum4[v], 0); // ((w0 + w1) + w2) + w3, as k_extract
+        for (int v = 0; v < K2_WAVES; v++) tsum += shfl_f64(vsum[v], 0); // ((w0 + w1) + w2) + w3, as k_extract
         tnb = __shfl(nb, 0, 64);
 
         // pass 2, 256 bins per step, as the in-register path does it (round 6; round 4's loop evaluated the quotient of
@@ -1029,9 +941,9 @@ __global__ __launch_bounds__(K2_BLOCK) void k_extract_wave(const CELL *__restric
         // the percentiles whose threshold falls inside it -- one 64-bit compare per lane and step -- and finds each one's
         // bin with a ballot and three compares.  Cells beyond hi are zero, so a 4-bin group that straddles hi needs no mask.
         if (total && np) {
-            uint64_t T64 = ~0ull;
+            uint64_t T64 = PCT_NONE;
             if (lane < np) T64 = pct_threshold(pa.p[lane], total);
-            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T64 != ~0ull); // percentiles without a bin yet (np <= 32)
+            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T64 != PCT_NONE); // percentiles without a bin yet (np <= 32)
             uint64_t carry = 0;
             for (uint32_t base = lo; base <= hi && todo; base += K2_TILE / K2_WAVES) {
                 const uint32_t b0 = base + lane * K2_PER_THREAD;

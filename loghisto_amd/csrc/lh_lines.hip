@@ -20,7 +20,7 @@
 //                   to HBM.  Nothing is written when the total exceeds cap.
 // line_value() is the one place a line's value is computed; both passes call it, so their bytes agree.  The descriptors
 // (64 bytes a column, up to 128 of them: more than the kernel-argument space) and the labels travel in the handle's device
-// block, through a pinned copy on the call's stream.  The formatter is lh_fmt.h (a copy of K6's: see there).
+// block, through a pinned copy on the call's stream.  The formatter is lh_fmt.h, the one K6 formats with.
 // tools/lines_bench.py measures it against lh_serialize over the same lines (profiles/lines.txt: 65 536 names x 15 keys, the
 // three kernels 84 us against K6's 71 us, 1.18 x per output byte; most of the difference is in the length pass).
 #include "../../include/loghisto_gpu.h"

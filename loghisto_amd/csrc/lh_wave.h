@@ -7,11 +7,9 @@
 //                     reads (row_of, row_span: the block's m-th, or -- the *_ids forms -- the one an id array names), a row's 4-bin group as one
 //                     load (load4_cells; load4_in inside a span; load4 with the bins' values), a group's count and weighted
 //                     sum (sum4, terms4) and the generator of the value table (k_value_table)
-// The scans' and the threshold's text is lh_kernels.hip's, which still carries its own copy for K2: that file is one of the
-// sources the committed profiles are stamped with (bench.tree_stamp), so it takes this header in the change that next
-// regenerates them.  Until then a fix to pct_threshold goes to both (tests/test_pct_threshold_model.py has the
-// arithmetic, tests/test_gpu_extract_thresholds.py and tests/test_gpu_spread.py hold both to the oracle).
-// Every unit that includes it is built with -ffp-contract=off (build.py's _COMMON).
+// The wave primitives, the threshold and the packed types are also K2's (lh_kernels.hip's k_extract_wave): the only copy
+// (tests/test_pct_threshold_model.py has the threshold's arithmetic, tests/test_gpu_extract_thresholds.py and
+// tests/test_gpu_spread.py hold it to the oracle).  Every unit that includes it is built with -ffp-contract=off (build.py's _COMMON).
 #pragma once
 
 #include "lh_codec.h"

@@ -7,6 +7,7 @@ summaries, the sweep, the read ceiling) and which are experiment records of EARL
 runs: they name the commit they were measured on and are exempt).  A kernel edit without a fresh `tools/round.sh profile`
 run shows up here, on the CPU box, and not only as a null `traffic` in the driver's line.  (Round 5's sweep was committed
 before two later kernel changes and still quoted as "final": VERDICT r5 weak #8.)"""
+import importlib.util
 import json
 import os
 
@@ -47,6 +48,21 @@ def test_manifest_lists_every_r06_file():
 def test_final_tree_evidence_carries_this_trees_stamp(name):
     assert _stamp_of(os.path.join(ROOT, "profiles", name)) == bench.tree_stamp(), \
         f"{name} was measured on other sources: run tools/round.sh profile + tools/collect_profiles.py r06"
+
+
+def test_unstamped_includes_of_the_stamped_sources_are_the_manifests():
+    """The stamp digests bench.STAMP_SOURCES; the csrc headers those include without being on the list (lh_cells.h, and
+    lh_wave.h / lh_fmt.h, which hold the only copy of K2's threshold and of K6's formatter) are held by their hashes in
+    the manifest, written by the same tools/collect_profiles.py run that records the stamp."""
+    spec = importlib.util.spec_from_file_location("collect_profiles", os.path.join(ROOT, "tools", "collect_profiles.py"))
+    collect = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(collect)
+    now = collect.unstamped_includes()
+    assert {"lh_cells.h", "lh_wave.h", "lh_fmt.h"} <= set(now), sorted(now)   # the walk itself: what the kernels include today
+    assert not set(now) & set(bench.STAMP_SOURCES)
+    assert _manifest().get("unstamped_includes") == now, \
+        "headers the stamped kernels include changed since the evidence was taken: " \
+        "run tools/round.sh profile + tools/collect_profiles.py r06"
 
 
 @pytest.mark.parametrize("path,kind", [(bench.K1_PMC, "k1"), (bench.C3_PMC, "c3"), (bench.C4_PMC, "c4"),

@@ -15,13 +15,20 @@
 #   c4_kernel_trace.txt / c4_pmc.json   the same for bench.py --workload c4 (65 536 names, one rank's 1.25e8-pair slice)
 #   first_calls.txt         tools/first_call.py: calls 0 .. 3 of fresh engines on wide, sorted and run-clustered streams
 # PMC passes are separate runs with no tracing domain mixed in.
+# The first step that fails ends the round (set -e -o pipefail: a pipeline fails with its producer, a { ...; } > file group
+# with its first failing command) and says where: nothing more is started on a GPU on which a step has just failed or hung.
+# Every step that uses the GPU runs under a limit of its own, about five to ten times what it took when this was last run
+# plus a cold start of python and torch (the whole round: 5.6 min; K1-only commands 3 - 8 s each, the C3 / C4 / 1e9-pair
+# commands under the tracer or a counter pass 8 - 22 s, a sweep 3 - 6 s, bench.py --full 131 s and 60 s, --workload c4 5 s).
+set -eE -o pipefail
+trap 'echo "profile_round.sh: line $LINENO failed with status $?, stopping" >&2' ERR
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/round; mkdir -p $OUT; cd $R
 STAMP=$(python -c "import bench; print(bench.tree_stamp())")
-{ echo "{\"tree_stamp\": \"$STAMP\"}"; loghisto_amd/build/read_ceiling --reps 20 2>&1; } > $OUT/read_ceiling.jsonl
+{ echo "{\"tree_stamp\": \"$STAMP\"}"; timeout -k 10 120 loghisto_amd/build/read_ceiling --reps 20 2>&1; } > $OUT/read_ceiling.jsonl
 cd /tmp; export TMPDIR=/tmp
 CMD="python $R/bench.py --full --workload c2 --no-secondary --steps 30 --warmup 5 --no-cpu-baseline --no-parity --latency-flips 0"
-rm -rf /tmp/pr_trace; rocprofv3 --kernel-trace -d /tmp/pr_trace -o t -- $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_under_trace.json
-$CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_unprofiled_after.json
+rm -rf /tmp/pr_trace; timeout -k 10 180 rocprofv3 --kernel-trace -d /tmp/pr_trace -o t -- $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_under_trace.json
+timeout -k 10 180 $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_unprofiled_after.json
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD"
   python $R/profiles/summarize_rocpd.py stats /tmp/pr_trace/t_results.db --min-ns 500000 | grep -E "^#|^kernel|k_ingest_single" | cut -c1-170
   python $R/profiles/summarize_rocpd.py list /tmp/pr_trace/t_results.db k_ingest_single --min-ns 500000 --skip 30
@@ -29,24 +36,24 @@ $CMD 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_unprofiled_after.json
 import json; j=json.loads(open('$OUT/$f.json').read()); r=j['roofline']; print('HIP events, $f run: avg_launch_ms %.4f frac %.4f ms_per_step %.4f' % (r['avg_launch_ms'], r['frac'], j['ms_per_step']))"; done; } > $OUT/kernel_trace.txt
 CMD2="python $R/bench.py --full --workload c2 --no-secondary --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
 rm -rf /tmp/pr_fetch /tmp/pr_write
-rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_fetch -o t -- $CMD2 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_write -o t -- $CMD2 > /dev/null 2>&1
+timeout -k 10 180 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_fetch -o t -- $CMD2 > /dev/null 2>&1
+timeout -k 10 180 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_write -o t -- $CMD2 > /dev/null 2>&1
 CMD3="python $R/bench.py --full --workload c3 --steps 3 --warmup 1 --no-cpu-baseline --no-parity --latency-flips 0"
 rm -rf /tmp/pr_c3t /tmp/pr_c3f /tmp/pr_c3w
-rocprofv3 --kernel-trace -d /tmp/pr_c3t -o t -- $CMD3 > $OUT/c3_under_trace.json 2>/dev/null
+timeout -k 10 240 rocprofv3 --kernel-trace -d /tmp/pr_c3t -o t -- $CMD3 > $OUT/c3_under_trace.json 2>/dev/null
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD3"; python $R/profiles/summarize_rocpd.py stats /tmp/pr_c3t/t_results.db | grep -E "^#|^kernel|lh::" | cut -c1-170; } > $OUT/c3_kernel_trace.txt
-rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_c3f -o t -- $CMD3 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_c3w -o t -- $CMD3 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_c3f -o t -- $CMD3 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_c3w -o t -- $CMD3 > /dev/null 2>&1
 CMD4="python $R/bench.py --full --workload c4 --steps 3 --warmup 1 --no-parity --latency-flips 0"
 rm -rf /tmp/pr_c4t /tmp/pr_c4f /tmp/pr_c4w
-rocprofv3 --kernel-trace -d /tmp/pr_c4t -o t -- $CMD4 > $OUT/c4_under_trace.json 2>/dev/null
+timeout -k 10 240 rocprofv3 --kernel-trace -d /tmp/pr_c4t -o t -- $CMD4 > $OUT/c4_under_trace.json 2>/dev/null
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD4"; python $R/profiles/summarize_rocpd.py stats /tmp/pr_c4t/t_results.db | grep -E "^#|^kernel|lh::" | cut -c1-170
   # the small merge / plan kernels launch by launch, in start order (10 - 60 x spreads): the run makes 4 SERIAL
   # steps (every phase drained: the kernel alone on the GPU) and then 4 PIPELINED ones (the kernel beside the next step's level 1,
   # which holds every CU's LDS: its workgroups wait for a CU)
   for k in k_merge_widths k_merge_prep k_plan_scan k_extract_wave; do python $R/profiles/summarize_rocpd.py list /tmp/pr_c4t/t_results.db $k | cut -c1-200; done; } > $OUT/c4_kernel_trace.txt
-rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_c4f -o t -- $CMD4 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_c4w -o t -- $CMD4 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_c4f -o t -- $CMD4 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_c4w -o t -- $CMD4 > /dev/null 2>&1
 python - <<PY
 import json, subprocess
 R="$R"
@@ -107,10 +114,10 @@ PY
 # 65 536 names, 1e9 pairs per call: bytes of every kernel of one call (tools/sweep.py), and its kernel split
 CMD5="python $R/tools/sweep.py --samples 1e9 --pairs 65536 --reps 3 --dists lognormal"
 rm -rf /tmp/pr_5t /tmp/pr_5f /tmp/pr_5w
-rocprofv3 --kernel-trace -d /tmp/pr_5t -o t -- $CMD5 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace -d /tmp/pr_5t -o t -- $CMD5 > /dev/null 2>&1
 { echo "# tree_stamp: $STAMP"; echo "# rocprofv3 --kernel-trace -- $CMD5"; python $R/profiles/summarize_rocpd.py stats /tmp/pr_5t/t_results.db | grep -E "^#|^kernel|lh::" | cut -c1-170; } > $OUT/c4_names_1e9_kernel_trace.txt
-rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_5f -o t -- $CMD5 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_5w -o t -- $CMD5 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE -d /tmp/pr_5f -o t -- $CMD5 > /dev/null 2>&1
+timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE -d /tmp/pr_5w -o t -- $CMD5 > /dev/null 2>&1
 python - <<PY
 import json, subprocess, sys
 R="$R"
@@ -141,25 +148,25 @@ PY
 # summaries measured on other kernel sources -- the ones just written are this tree's.
 cd $R
 for f in k1_pmc c3_pmc c4_pmc c4_names_1e9_pmc; do cp $OUT/$f.json $R/profiles/r06_$f.json; done
-python bench.py --full 2> $OUT/bench.err | grep "^{" | tail -1 > $OUT/bench.json
-python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $OUT/bench20.err | grep "^{" | tail -1 > $OUT/bench_steps20_warmup5.json
-python bench.py --full --workload c4 2> $OUT/c4_bench.err | grep "^{" | tail -1 > $OUT/c4_bench.json
+timeout -k 10 600 python bench.py --full 2> $OUT/bench.err | grep "^{" | tail -1 > $OUT/bench.json
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $OUT/bench20.err | grep "^{" | tail -1 > $OUT/bench_steps20_warmup5.json
+timeout -k 10 240 python bench.py --full --workload c4 2> $OUT/c4_bench.err | grep "^{" | tail -1 > $OUT/c4_bench.json
 # first calls of fresh engines and clustered streams (sweeps drop their first calls): per-call times of four calls each
 cd $R
 { echo "# tree_stamp: $STAMP"; echo "# tools/first_call.py <dists> <ids> 1e9 (NAMES=..., ONLY0=1): ms per call, calls 0 .. 3 of a fresh engine"
   for c in "65536 zipf lognormal,loguniform" "65536 sorted lognormal,loguniform" "65536 runs256 lognormal" "8192 sorted lognormal,loguniform" "1024 sorted lognormal"; do
-    set -- $c; echo "== names $1, ids $2"; NAMES=$1 ONLY0=1 timeout 300 python tools/first_call.py $3 $2 1e9 2>&1 | grep " call " | sed -e "s/ logw_opt 0//" -e "s/'records_level2'.*'region_overflows'/'region_overflows'/" | cut -c1-200
+    set -- $c; echo "== names $1, ids $2"; NAMES=$1 ONLY0=1 timeout -k 10 300 python tools/first_call.py $3 $2 1e9 2>&1 | grep " call " | sed -e "s/ logw_opt 0//" -e "s/'records_level2'.*'region_overflows'/'region_overflows'/" | cut -c1-200
   done; } > $OUT/first_calls.txt
 # LAST: the final kernels over the value distributions, each on its own survey, every sweep process behind its own
 # warm-up series (--warmup 40: K1 launches in the SAME process -- a warm-up in a process of its own left the next one cold)
 cd $R
 { echo "{\"tree_stamp\": \"$STAMP\"}"
-  python tools/sweep.py --warmup 40 --samples 1e9 --reps 5 2>/dev/null
-  python tools/sweep.py --warmup 40 --samples 1e9 --pairs 1024 --reps 4 --dists lognormal,constant,uniform,exponential,normal,loguniform,lognormal25,kvalues2,kvalues4,kvalues8,kvalues16,bimodal,signed_wide 2>/dev/null
-  python tools/sweep.py --warmup 40 --samples 1e9 --pairs 65536 --reps 4 --dists lognormal,constant,normal,kvalues2,kvalues8,bimodal,lognormal25,lognormal50,loguniform,signed_wide,thin_far_tail 2>/dev/null
-  for m in 8192 4096; do python tools/sweep.py --warmup 40 --samples 1e9 --pairs $m --reps 4 --dists lognormal,normal,lognormal25,lognormal50,loguniform,signed_wide,thin_far_tail 2>/dev/null; done
-  python tools/sweep.py --warmup 40 --samples 1e9 --pairs 65536 --reps 4 --ids sorted --dists lognormal 2>/dev/null
-  python tools/sweep.py --warmup 40 --samples 1e9 --pairs 1024 --reps 4 --ids sorted --dists lognormal 2>/dev/null
+  timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --reps 5 2>/dev/null
+  timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --pairs 1024 --reps 4 --dists lognormal,constant,uniform,exponential,normal,loguniform,lognormal25,kvalues2,kvalues4,kvalues8,kvalues16,bimodal,signed_wide 2>/dev/null
+  timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --pairs 65536 --reps 4 --dists lognormal,constant,normal,kvalues2,kvalues8,bimodal,lognormal25,lognormal50,loguniform,signed_wide,thin_far_tail 2>/dev/null
+  for m in 8192 4096; do timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --pairs $m --reps 4 --dists lognormal,normal,lognormal25,lognormal50,loguniform,signed_wide,thin_far_tail 2>/dev/null; done
+  timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --pairs 65536 --reps 4 --ids sorted --dists lognormal 2>/dev/null
+  timeout -k 10 300 python tools/sweep.py --warmup 40 --samples 1e9 --pairs 1024 --reps 4 --ids sorted --dists lognormal 2>/dev/null
 } | cut -c1-700 > $OUT/sweep_final.jsonl
 cat $OUT/c4_kernel_trace.txt | cut -c1-150
 ls -la $OUT; tail -c 1500 $OUT/bench.json; grep -E "k_ingest_single" $OUT/kernel_trace.txt | cut -c1-140; cat $OUT/c3_kernel_trace.txt | cut -c1-150; python -c "
