@@ -627,6 +627,79 @@ int lh_spread_ids(lh_snapshot *s, const uint32_t *ids, size_t n, const double *p
 int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const double *p, size_t np, uint64_t *d_count,
                          double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
                          double *d_sum_le);
+/* INTERVALS KEPT IN COMPACT FORM ON THE DEVICE: lh_keep, lh_kept_*.  lh_across* needs all K intervals alive as dense epoch
+ * buffers, and an engine has at most 16 of them (4 GiB each at 8 192 names).  An interval's OCCUPIED cells are small -- a few
+ * hundred (int16 key, uint64 count) pairs per name, RawMetricSet.Histograms (/root/reference/metrics.go:54-60) -- so a minute of
+ * 1 s intervals fits where two dense buffers do not.  lh_keep copies the occupied cells of rows [first, first + nmetrics) of a
+ * snapshot into device memory the handle owns; lh_kept_across* then gives lh_across*' outputs over a LIST of up to LH_MAX_KEPT
+ * handles without any dense buffer.  The sum is over time for ONE name: nothing is summed across names, no cell of a snapshot is
+ * written and no new statistic is defined -- every output is what lh_extract_rows would return for the cells atomic.AddUint64
+ * would have left had the samples arrived in one interval (metrics.go:278; the walks: metrics.go:336-418).
+ *   lh_keep           The handle's arrays are exactly what lh_buckets_all hands out for the same rows, in DEVICE memory:
+ *                     offsets[nrows + 1] from 0, keys ascending by bin (bin = (uint16)key ^ 0x8000), uint64 counts -- so
+ *                     lh_snapshot_add_buckets_csr_device(s2, first, nrows, d_offsets, d_keys, d_counts) restores the interval
+ *                     unchanged -- plus row_count[nrows], each row's sum of cells (wrapping).  Counted, prefix-summed and
+ *                     compacted on the device, on lh_snapshot_stream(s); only the two grand totals come back, to size ONE exact
+ *                     allocation.  Returns when the copy is complete: the snapshot may be released at once, and the handle
+ *                     depends on neither the snapshot nor the engine afterwards (it survives lh_destroy).  READ-ONLY on the
+ *                     snapshot: a narrow snapshot stays narrow.  A handle never changes after creation.  A block without an
+ *                     occupied cell gives a valid handle with cells == 0.  flags must be 0.
+ *                     LH_EINVAL: NULL s or out, flags != 0, nmetrics == 0.  LH_ERANGE: first + nmetrics beyond the snapshot's
+ *                     rows.  LH_ENOMEM: the allocation failed; *out is untouched and nothing is leaked.
+ *   lh_kept_release   frees the handle; waits first for enqueued work that still reads it: every lh_kept_across*_device call
+ *                     that listed it, on whichever streams (each such call chains one event behind the earlier ones), and
+ *                     whatever lh_kept_hold covered.
+ *   lh_kept_info_get  out->struct_size = sizeof(lh_kept_info) on entry.  cells: occupied cells held; samples: the sum of
+ *                     row_count (wrapping); bytes: the allocation, exactly (2 * nrows + 1) * 8 + cells * 10 -- the four arrays.
+ *   lh_kept_arrays    the four device arrays (any pointer may be NULL), valid until lh_kept_release; with cells == 0 the keys
+ *                     and counts arrays are empty.  Work of the caller's own that reads them is NOT guarded by itself:
+ *   lh_kept_hold      everything enqueued on `stream` (a hipStream_t of the handle's device; NULL: its null stream) up to now
+ *                     counts as a reader of the handle: lh_kept_release waits for it.  Call it right AFTER enqueueing work
+ *                     that reads lh_kept_arrays' pointers, lh_snapshot_add_buckets_csr_device on them for one.  LH_EINVAL:
+ *                     NULL k.
+ *   lh_kept_across, lh_kept_across_device, lh_kept_across_ids, lh_kept_across_ids_device
+ *                     lh_across* / lh_across_ids* over handles: the same outputs, definitions and error order, with
+ *                     C[b] = the sum over the listed handles of the name's cell b, taken in 64 bits.  Differences:
+ *                     1 <= nkept <= LH_MAX_KEPT; present_bits is uint64_t (bit i: kept[i] holds a cell of the name); `first` and
+ *                     ids are ABSOLUTE row numbers (metric ids), and [first, first + nmetrics) must lie inside EVERY handle's
+ *                     block [first_i, first_i + nrows_i), else LH_ERANGE; a host id outside some handle's block -> LH_ERANGE,
+ *                     nothing enqueued, nothing written; a DEVICE id outside some handle's block yields the empty entry and the
+ *                     kernel reads nothing for it (the stance of the *_ids_device forms above).  A handle may be listed more
+ *                     than once and counts that often.  nmetrics == 0 / n == 0 -> LH_OK before any handle is looked at.
+ *                     Handles on different devices -> LH_EINVAL.  Totals that wrap past 2^64: count wraps, the percentile
+ *                     outputs are unspecified (nothing faults).
+ *                     ORDERING: the work goes on `stream` (a hipStream_t of the handles' device; NULL: its null stream).  Host
+ *                     forms return with the results in the caller's arrays (pinned arrays by one copy each); device forms
+ *                     return after enqueueing, and the outputs and d_ids stay valid until the stream has passed the call.  p is
+ *                     a HOST array in all forms and travels by value, as does the list of handles.  sum is taken in one fixed
+ *                     order and does not depend on timing.  One set of staging blocks per DEVICE behind the unit's own mutex:
+ *                     calls take turns. */
+typedef struct lh_kept lh_kept;      /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
+#define LH_MAX_KEPT 64
+typedef struct lh_kept_info {
+    uint32_t struct_size;            /* sizeof(lh_kept_info) */
+    int32_t device;
+    uint32_t first, nrows;
+    uint64_t cells, samples, bytes;
+} lh_kept_info;
+int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_kept **out);
+int lh_kept_release(lh_kept *k);
+int lh_kept_info_get(const lh_kept *k, lh_kept_info *out);
+int lh_kept_arrays(const lh_kept *k, const uint64_t **d_offsets, const int16_t **d_keys, const uint64_t **d_counts,
+                   const uint64_t **d_row_count);
+int lh_kept_hold(lh_kept *k, void *stream);
+int lh_kept_across(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                   uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits,
+                   int16_t *pkeys, uint8_t *pvalid);
+int lh_kept_across_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                          uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
+                          uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
+int lh_kept_across_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np,
+                       uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits,
+                       int16_t *pkeys, uint8_t *pvalid);
+int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                              uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
+                              uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

@@ -146,6 +146,12 @@ int lh_tool_compare_switch(uint32_t wave_from_rows, uint32_t *previous);
 /* The same switch of lh_across* (default 1 024, lh_spread's, whose walks it shares; profiles/across.txt).  The two shapes agree
  * exactly in every integer output and to rounding in sum. */
 int lh_tool_across_switch(uint32_t wave_from_rows, uint32_t *previous);
+/* The same switch of lh_kept_across* (default 1 024; profiles/kept.txt has both shapes).  The two shapes walk a tile the same
+ * way: they agree exactly in every output, sum included. */
+int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous);
+/* *bins receives the width in bins of the LDS tile lh_kept_across* covers a row's union span with (tests put cells either
+ * side of a tile's edge).  NULL -> LH_EINVAL. */
+int lh_tool_kept_tile(uint32_t *bins);
 /* Device time of lh_top*'s two passes (HIP events on the snapshot's stream around each): one call with the arguments of
  * lh_top_device, its entries left in the unit's own block; returns when both times are known.  nmetrics >= 1. */
 int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,

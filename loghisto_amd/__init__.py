@@ -7,7 +7,7 @@ host-side mirror of that ABI; it contains no CPU compute path and raises if
 liblhgpu.so is not built.
 """
 from ._native import (LIB_PATH, MAX_PERCENTILES, NKEYS, NTHRESH, LhError, NativeLibraryError)
-from .engine import Engine, Names, Snapshot
+from .engine import Engine, Kept, Names, Snapshot
 
-__all__ = ["Engine", "Names", "Snapshot", "LhError", "NativeLibraryError", "LIB_PATH", "NKEYS", "NTHRESH",
+__all__ = ["Engine", "Kept", "Names", "Snapshot", "LhError", "NativeLibraryError", "LIB_PATH", "NKEYS", "NTHRESH",
            "MAX_PERCENTILES"]

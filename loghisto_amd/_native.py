@@ -26,6 +26,7 @@ TOP_ASCENDING = 1
 MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   # lh_movers* (k <= MAX_TOP)
 MOVERS_ASCENDING = 1
 MAX_ACROSS = 16        # lh_across*: snapshots of one call
+MAX_KEPT = 64          # lh_kept_across*: handles of one call
 MAX_COLUMNS = 128      # lh_lines*
 COL_F64, COL_U64, COL_U32, COL_KEY = range(4)
 OP_VALUE, OP_RATIO, OP_SQRT_RATIO, OP_DIFF = range(4)
@@ -131,6 +132,12 @@ class LhColumn(C.Structure):
                 ("reserved1", C.c_uint32)]
 
 
+class LhKeptInfo(C.Structure):
+    """lh_kept_info (40 bytes): what a kept interval holds."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("first", C.c_uint32), ("nrows", C.c_uint32),
+                ("cells", C.c_uint64), ("samples", C.c_uint64), ("bytes", C.c_uint64)]
+
+
 FMT_UNDERSCORE_TO_DOT = 1
 SER_AGGREGATES = 1
 FMT_SLOT = 336
@@ -172,6 +179,8 @@ TUNING_SIGNATURES = {
     "lh_tool_spread_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_compare_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_across_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_kept_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_kept_tile": (C.c_int, [_u32p]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
@@ -247,6 +256,15 @@ SIGNATURES = {
     "lh_count_le_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
     "lh_spread_ids": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_spread_ids_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_keep": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.POINTER(_vp)]),
+    "lh_kept_release": (C.c_int, [_vp]),
+    "lh_kept_info_get": (C.c_int, [_vp, C.POINTER(LhKeptInfo)]),
+    "lh_kept_arrays": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "lh_kept_hold": (C.c_int, [_vp, _vp]),
+    "lh_kept_across": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_across_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "lh_names_refresh": (C.c_int, [_vp, _u32p]),
     "lh_names_destroy": (C.c_int, [_vp]),

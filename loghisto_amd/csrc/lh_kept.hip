@@ -1,0 +1,753 @@
+// lh_kept.hip -- lh_keep / lh_kept_* (include/loghisto_gpu.h): an interval's occupied cells kept in COMPACT form in device
+// memory after its snapshot is gone, and lh_across' outputs over a list of up to 64 such copies -- p99 over the last minute
+// of 1 s intervals while no dense epoch buffer of them is alive.  A dense buffer is 4 GiB at 8 192 names; the occupied cells
+// of an interval are a few hundred (int16 key, uint64 count) pairs per name (RawMetricSet.Histograms, metrics.go:54-60).
+// With c_i[b] the cells of a name in kept[i]:
+//   C[b] = sum over i of c_i[b], in 64 bits -- the cell atomic.AddUint64 would have left had the samples arrived in one
+//          interval (metrics.go:278)
+//   count, sum, nbuckets, the percentile buckets: lh_across' definitions word for word (metrics.go:336-418), i.e. what
+//   lh_extract_rows returns for a snapshot that holds C.  present_bits: bit i set iff kept[i] holds a cell of the name.
+// Nothing is summed across names, no cell of a snapshot is written and no new statistic is defined.
+//
+// Built BESIDE the engine, on its public C ABI only (lh_beside.h, lh_wave.h), like lh_across.hip.
+//
+// THE HANDLE is one allocation of exactly  offsets[nrows + 1] | row_count[nrows] | counts[cells] | keys[cells]  (uint64,
+// uint64, uint64, int16): lh_buckets_all's CSR arrays of the same rows -- keys ascending by bin -- which
+// lh_snapshot_add_buckets_csr_device takes as they are, plus each row's sum of cells.  lh_keep makes it on the snapshot's
+// stream in three kernels: k_keep_count (a wave per row: the row's occupied cells and their sum), k_keep_scan (one
+// workgroup: the exclusive prefix of the former, the two grand totals), then -- the totals brought back, the allocation
+// made -- k_keep_fill (a wave per row again: the cells to their places).  It returns when the copy is complete; the handle
+// then depends on neither the snapshot nor the engine, and never changes.
+//
+// THE READER, k_kept_across, in two shapes switched by the rows of a call like the other readers:
+//   NW = 1    one WAVE per row, four rows per workgroup, a tile of its own each
+//   NW = 16   one WORKGROUP of 16 waves per row: the waves share the scatter (wave w takes handles w, w + 16, ...), wave 0
+//             walks the tile.  Same walk, same order: the two shapes agree bit for bit, sum included.
+// Lane i opens handle i: its row's segment [begin, end) of the CSR arrays, its row_count -- whose sum over the lanes is the
+// row's total, so every threshold (lh_wave.h's pct_threshold) is known BEFORE any cell is read -- and its first and last
+// bin.  The union span of the segments is then covered by TILES of KEPT_TILE bins of uint64 in LDS (8 KiB a tile; 32 KiB
+// static per workgroup in the wave shape).  Per tile: the start t0 is the least bin not yet taken, aligned down to 4 (empty
+// stretches between tiles cost nothing); every segment's entries inside [t0, t0 + KEPT_TILE) are one contiguous run --
+// found by a binary search per lane from the second tile on -- and are added into the tile with 64-bit LDS adds; then the
+// tile is walked in ascending bins, 256 per step, with lh_across' step: running prefix, nbuckets, the percentile bins and
+// the sum of D[b] * float64(C[b]) (per lane over the steps in ascending order, one DPP tree over the lanes at the end).
+// The walk puts zeros back where it read, so the next tile starts clean.  Integer cell sums do not depend on the order of
+// the adds and the float walk is fixed: no result depends on timing.
+//
+// THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
+// 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
+// a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
+// on the HOST for the previous one before rewriting it, or the unit would keep a pool of blocks.  By value there is nothing
+// to guard and two device-form calls on two streams never meet in a block of the unit's.
+//
+// WHAT IS GUARDED IS EACH HANDLE'S ALLOCATION, against lh_kept_release while enqueued work still reads it.  A device-form
+// call records ONE event behind its kernel (CallEvent, from a pool of the device's context), and every handle of its list
+// then points to that event and counts as a user of it.  A handle may be read on any number of streams, and an event holds
+// one record only; so before the record the call's stream is made to wait (on the device: hipStreamWaitEvent) for the event
+// each of its handles pointed to until now -- once per distinct event, which in the steady state of one list read again and
+// again is one wait.  The new event is thereby behind EVERY reader of the handle so far, on whichever stream, and
+// lh_kept_release has one event to wait for: the one the handle points to.  An event that no handle points to any more goes
+// back to the pool (the waits on it that are already enqueued keep the record they saw).  lh_kept_hold puts work of the
+// caller's own that reads lh_kept_arrays' pointers under the same guard.  Host forms return with their work complete.
+// Read-only: no store goes to a handle's arrays after lh_keep, to a cell, a span or any engine.
+#include "../../include/loghisto_gpu.h"
+#include "../../include/loghisto_gpu_tuning.h"
+#include "lh_beside.h"
+#include "lh_codec.h"
+#include "lh_wave.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <mutex>
+#include <new>
+#include <type_traits>
+
+namespace {
+
+using namespace lh; // (lh_wave.h)
+using namespace lh::beside;
+
+constexpr uint32_t KEPT_WAVE_FROM_DEFAULT = 1024; // lh_spread's default; profiles/kept.txt has both shapes
+constexpr uint32_t KEPT_TILE = 1024;              // bins of a tile: a lognormal name's union span fits one
+static_assert(KEPT_TILE % STEP == 0 && ROW_WAVES * KEPT_TILE * sizeof(u64) <= 65536, "whole steps; 64 KiB static LDS at most");
+static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
+static_assert(LH_MAX_KEPT == 64, "a handle per lane, their set in one 64-bit mask");
+
+struct KeptP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
+
+// one handle as the kernel sees it.  offsets at `block`, row_count = offsets + nrows + 1, counts = row_count + nrows, keys
+// behind counts.
+struct KeptRec {
+    u64 block; // its address: an integer, see gu64
+    u64 cells;
+    uint32_t first, nrows;
+};
+struct KeptList { // by value in the kernel arguments (1 544 bytes)
+    KeptRec h[LH_MAX_KEPT];
+    uint32_t n;
+};
+
+struct KeptOut {
+    u64 *count;
+    double *sum;
+    uint32_t *nbuckets;
+    u64 *present;
+    int16_t *pkeys;
+    uint8_t *pvalid;
+};
+
+__device__ __forceinline__ uint32_t occupied4(const u64 (&C)[4])
+{
+    return (C[0] ? 1u : 0u) + (C[1] ? 1u : 0u) + (C[2] ? 1u : 0u) + (C[3] ? 1u : 0u);
+}
+// A handle's arrays through pointers that say GLOBAL: their addresses travel as integers -- in the list, then from lane to
+// lane -- and a load through a generic pointer made of one would be a flat one, which every LDS wait then waits for too
+// (lh_across.hip's gcells), here in the loop of the tile's LDS adds.
+typedef const __attribute__((address_space(1))) u64 *gu64;
+typedef const __attribute__((address_space(1))) int16_t *gkeys;
+__device__ __forceinline__ uint32_t bin_of(int16_t key) { return key_to_bin((int)key); }
+
+// ---- lh_keep ----------------------------------------------------------------------------------------------------------
+// a wave per row of the block: nnz[m + 1] = the row's occupied cells, row_count[m] = their sum (wrapping)
+template <typename CELL>
+__global__ __launch_bounds__(ROW_BLOCK) void k_keep_count(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+                                                         size_t stride, uint32_t nrows, u64 *__restrict__ nnz,
+                                                         u64 *__restrict__ row_count)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    const Span sp = own_span(ranges, m);
+    u64 cnt = 0;
+    uint32_t occ = 0;
+    if (sp.any()) {
+        const CELL *row = cells + (size_t)m * stride;
+        for (uint32_t base = sp.base0(); base <= sp.hi; base += STEP) {
+            u64 c[4];
+            load4_cells(row, base + 4 * lane, sp.hi, c);
+            cnt += sum4(c);
+            occ += occupied4(c);
+        }
+    }
+    cnt = wave_scan_incl_u64(cnt);
+    occ = wave_scan_incl_u32(occ);
+    if (lane == 63) {
+        nnz[(size_t)m + 1] = occ;
+        row_count[m] = cnt;
+    }
+}
+
+// one workgroup: off[1 .. nrows] becomes its own inclusive prefix (off[0] = 0: the CSR offsets), totals = {cells, samples}
+__global__ __launch_bounds__(WG) void k_keep_scan(u64 *__restrict__ off, const u64 *__restrict__ row_count, uint32_t nrows,
+                                                  u64 *__restrict__ totals)
+{
+    __shared__ u64 s_w[WG_WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry = 0, samples = 0;
+    for (u64 base = 0; base < nrows; base += WG) { // uniform
+        const u64 i = base + threadIdx.x;
+        const bool in = i < nrows;
+        const u64 v = in ? off[i + 1] : 0;
+        samples += in ? row_count[i] : 0;
+        const u64 inc = wave_scan_incl_u64(v);
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        u64 below = 0, all = 0;
+        for (uint32_t k = 0; k < (uint32_t)WG_WAVES; k++) {
+            const u64 t = s_w[k];
+            below += k < wave ? t : 0;
+            all += t;
+        }
+        if (in) off[i + 1] = carry + below + inc;
+        carry += all;
+        __syncthreads();
+    }
+    samples = wave_scan_incl_u64(samples);
+    if (lane == 63) s_w[wave] = samples;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 all = 0;
+        for (uint32_t k = 0; k < (uint32_t)WG_WAVES; k++) all += s_w[k];
+        off[0] = 0;
+        totals[0] = carry;
+        totals[1] = all;
+    }
+}
+
+// a wave per row: the row's occupied cells to keys / counts[off[m] .. off[m + 1]), ascending by bin.  (Nothing is stored at
+// or beyond off[m + 1], whatever the cells hold now.)
+template <typename CELL>
+__global__ __launch_bounds__(ROW_BLOCK) void k_keep_fill(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
+                                                        size_t stride, uint32_t nrows, const u64 *__restrict__ off,
+                                                        int16_t *__restrict__ keys, u64 *__restrict__ counts)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    const Span sp = own_span(ranges, m);
+    if (!sp.any()) return;
+    u64 at = off[m];
+    const u64 lim = off[(size_t)m + 1];
+    const CELL *row = cells + (size_t)m * stride;
+    for (uint32_t base = sp.base0(); base <= sp.hi && at < lim; base += STEP) {
+        u64 c[4];
+        const uint32_t b0 = base + 4 * lane;
+        load4_cells(row, b0, sp.hi, c);
+        const uint32_t n = occupied4(c), inc = wave_scan_incl_u32(n);
+        u64 pos = at + (inc - n);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (c[k] && pos < lim) {
+                keys[pos] = (int16_t)bin_to_key(b0 + k);
+                counts[pos] = c[k];
+                pos++;
+            }
+        at += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+    }
+}
+
+// ---- the reader ---------------------------------------------------------------------------------------------------------
+// the bin, inside a step of 256, of the first inclusive prefix that reaches T (lh_across.hip's find_in_step)
+__device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
+{
+    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
+    const uint32_t f = reach ? (uint32_t)__builtin_ctzll(reach) : 63u;
+    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
+    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
+}
+// the tile's adds are complete and visible before anything behind this reads it (and the other way round)
+template <int NW> __device__ __forceinline__ void tile_sync()
+{
+    if constexpr (NW == 1) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // (a wave's LDS operations execute in order)
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __syncthreads();
+    }
+}
+
+// IDS: entry m reads row ids[m] (an absolute row number, as `first` is); otherwise row first + m.  A row outside the block
+// of ANY handle gives the empty entry, and nothing is read for it.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                          const double *__restrict__ D, const KeptP pa,
+                                                                          uint32_t np, const KeptOut o,
+                                                                          const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t m = NW == 1 ? blockIdx.x * ROW_WAVES + wave : blockIdx.x;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    u64 *tile = s_tile[NW == 1 ? wave : 0];
+    const uint32_t w = NW == 1 ? 0u : wave; // which of the NW scatterers of the tile this wave is
+    for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < KEPT_TILE; i += NW * 64) tile[i] = 0;
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    // ---- lane i opens handle i
+    u64 beg = 0, end = 0, rc = 0, keys = 0, counts = 0;
+    bool outside = false;
+    if (lane < s.n) {
+        const KeptRec h = s.h[lane];
+        const uint32_t lr = r - h.first;
+        if (r < h.first || lr >= h.nrows) {
+            outside = true;
+        } else {
+            const gu64 offsets = (gu64)h.block, row_count = offsets + (size_t)h.nrows + 1;
+            beg = offsets[lr];
+            end = offsets[(size_t)lr + 1];
+            rc = row_count[lr];
+            counts = h.block + 8 * (2 * (u64)h.nrows + 1);
+            keys = counts + 8 * h.cells;
+            if (end > h.cells || beg > end) beg = end = 0; // (never: lh_keep made them)
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(outside)) { // wave-uniform
+        beg = end = 0;
+        rc = 0;
+    }
+    uint32_t next = NO_BIN, last = 0; // the bin at the cursor / the segment's last bin
+    if (end > beg) {
+        next = bin_of(((gkeys)keys)[beg]);
+        last = bin_of(((gkeys)keys)[end - 1]);
+    }
+    const u64 total = readlane_u64(wave_scan_incl_u64(rc), 63);
+    const u64 present = __builtin_amdgcn_ballot_w64(end > beg);
+    const uint32_t hi = wave_max_u32(last);
+    u64 cur = beg;
+
+    double ps = 0.0;
+    uint32_t occ = 0, found = NO_BIN; // lane i < np: the bin of percentile i
+    if (total) {                       // uniform
+        u64 T = PCT_NONE, carry = 0;
+        if (lane < np) T = pct_threshold(pa.p[lane], total);
+        uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
+        tile_sync<NW>();                                                       // the tile is zero
+        for (uint32_t from = 0;;) { // (every wave of a workgroup takes the same turns: the state below is the same in all)
+            if (from) { // the first entry at or above `from`
+                u64 a = cur, b = end;
+                while (a < b) {
+                    const u64 mid = a + (b - a) / 2;
+                    if (bin_of(((gkeys)keys)[mid]) < from) a = mid + 1;
+                    else b = mid;
+                }
+                cur = a;
+                next = cur < end ? bin_of(((gkeys)keys)[cur]) : NO_BIN;
+            }
+            const uint32_t least = ~wave_max_u32(~next);
+            if (least == NO_BIN) break;
+            const uint32_t t0 = least & ~3u, tend = t0 + KEPT_TILE;
+            // ---- scatter: handle i's run inside the tile, 64 entries a turn
+            for (uint32_t i = w; i < s.n; i += NW) { // wave-uniform
+                u64 c = readlane_u64(cur, i);
+                const u64 e = readlane_u64(end, i);
+                const gkeys kp = (gkeys)readlane_u64(keys, i);
+                const gu64 cp = (gu64)readlane_u64(counts, i);
+                while (c < e) {
+                    const u64 idx = c + lane;
+                    bool in = false;
+                    if (idx < e) {
+                        const uint32_t at = bin_of(kp[idx]) - t0;
+                        if (at < KEPT_TILE) {
+                            in = true;
+                            atomicAdd(&tile[at], cp[idx]);
+                        }
+                    }
+                    const uint32_t took = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
+                    c += took;
+                    if (took < 64) break;
+                }
+            }
+            tile_sync<NW>();
+            // ---- walk, and zeros back
+            if (w == 0) {
+                const uint32_t wend = min(tend - 1, hi);
+                for (uint32_t base = t0; base <= wend; base += STEP) {
+                    const uint32_t b0 = base + 4 * lane, at = b0 - t0;
+                    u64 C[4];
+                    double d[4], t[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        C[k] = tile[at + k];
+                        tile[at + k] = 0;
+                    }
+                    d[0] = d[1] = d[2] = d[3] = 0.0;
+                    if (b0 <= hi) {
+                        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
+                        const f64x2_a8 d01 = dp[0], d23 = dp[1];
+                        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
+                    }
+                    const u64 tc = sum4(C);
+                    ps += terms4(C, d, t);
+                    occ += occupied4(C);
+                    const u64 inc = wave_scan_incl_u64(tc);
+                    const u64 upto = carry + readlane_u64(inc, 63);
+                    // (every open threshold is > carry: it would have ended in an earlier step otherwise)
+                    uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= upto) & todo;
+                    todo &= ~here;
+                    if (here) {
+                        u64 pre[4], sofar = carry + (inc - tc);
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            sofar += C[k];
+                            pre[k] = sofar;
+                        }
+                        for (; here; here &= here - 1) {
+                            const uint32_t i = (uint32_t)__builtin_ctz(here);
+                            const uint32_t idx = find_in_step(pre, readlane_u64(T, i));
+                            if (lane == i) found = base + idx;
+                        }
+                    }
+                    carry = upto;
+                }
+            }
+            tile_sync<NW>();
+            if (tend > hi) break; // nothing lies beyond
+            from = tend;
+        }
+    }
+    if (w != 0) return;
+    const double sum = readlane_f64(wave_scan_incl_f64(ps), 63);
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl_u32(occ), 63);
+    if (lane == 0) {
+        if (o.count) o.count[m] = total;
+        if (o.sum) o.sum[m] = total ? sum : 0.0;
+        if (o.nbuckets) o.nbuckets[m] = total ? nb : 0;
+        if (o.present) o.present[m] = total ? present : 0;
+    }
+    if (lane < np) {
+        const size_t at = (size_t)m * np + lane;
+        const bool ok = found != NO_BIN;
+        if (o.pkeys) o.pkeys[at] = ok ? (int16_t)bin_to_key(found) : (int16_t)0;
+        if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// behind a device-form call's kernel (or lh_kept_hold's caller's work); `users` handles point to it
+struct CallEvent {
+    hipEvent_t ev = nullptr;
+    size_t users = 0;
+    u64 waited_in = 0;         // the last hold() that made its stream wait for it
+    CallEvent *next = nullptr; // in the pool
+};
+// Per-device state of this unit (device_ctx<KeptCtx>).  `mu` is held for the length of a call -- lh_keep's and the host
+// forms' waits included -- and by lh_kept_release: it also guards the handles' events and their pool.
+struct KeptCtx {
+    std::mutex mu;
+    double *d_table = nullptr; // D[LH_NKEYS]
+    u64 *d_tmp = nullptr;      // lh_keep: offsets[nrows + 1] | row_count[nrows] | the two totals
+    size_t tmp_cap = 0;
+    u64 *h_totals = nullptr;   // pinned
+    size_t totals_cap = 0;
+    ResultBlocks res;          // host forms
+    IdBlocks ids;              // host form of lh_kept_across_ids
+    CallEvent *pool = nullptr; // events no handle points to
+    u64 holds = 0;
+};
+std::atomic<uint32_t> g_wave_from{KEPT_WAVE_FROM_DEFAULT};
+
+} // namespace
+
+struct lh_kept {
+    int device = -1;
+    uint32_t first = 0, nrows = 0;
+    u64 cells = 0, samples = 0, bytes = 0;
+    u64 *block = nullptr; // offsets | row_count | counts | keys
+    KeptCtx *cx = nullptr; // its device's
+    CallEvent *busy = nullptr; // behind every enqueued reader of the block so far, or null (under cx->mu)
+    const u64 *offsets() const { return block; }
+    const u64 *row_count() const { return block + (size_t)nrows + 1; }
+    const u64 *counts() const { return row_count() + nrows; }
+    const int16_t *keys() const { return reinterpret_cast<const int16_t *>(counts() + cells); }
+};
+
+namespace {
+
+typedef lh::beside::Source<KeptCtx> KeptSource;
+
+// (cx->mu held, the device current)
+int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
+{
+    KeptCtx *cx = q.cx;
+    const hipStream_t st = q.stream;
+    const size_t head = 2 * (size_t)nrows + 1; // offsets and row_count, in uint64
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, head + 2, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 2, 2);
+    if (rc) return rc;
+    u64 *off = cx->d_tmp, *row_count = off + nrows + 1, *totals = off + head;
+    const uint32_t *ranges = ranges_from(q, first);
+    const dim3 grid((nrows + ROW_WAVES - 1) / ROW_WAVES), block(ROW_BLOCK);
+    with_cells(q, first, [&](auto c) {
+        hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, row_count);
+    });
+    hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, row_count, nrows, totals);
+    LH_BESIDE_CHK(hipGetLastError());
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    const u64 cells = cx->h_totals[0];
+    if (cells > (u64)nrows * LH_NKEYS) return LH_EDEVICE; // (never)
+    k->first = first;
+    k->nrows = nrows;
+    k->cells = cells;
+    k->samples = cx->h_totals[1];
+    k->bytes = head * sizeof(u64) + cells * (sizeof(u64) + sizeof(int16_t));
+    LH_BESIDE_CHK(hipMalloc((void **)&k->block, (size_t)k->bytes));
+    LH_BESIDE_CHK(hipMemcpyAsync(k->block, off, head * sizeof(u64), hipMemcpyDeviceToDevice, st));
+    if (cells) {
+        u64 *counts = k->block + head;
+        int16_t *keys = reinterpret_cast<int16_t *>(counts + cells);
+        with_cells(q, first, [&](auto c) {
+            hipLaunchKernelGGL((k_keep_fill<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, keys, counts);
+        });
+        LH_BESIDE_CHK(hipGetLastError());
+    }
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    return LH_OK;
+}
+
+// (cx->mu held) one user less of `e`
+void unuse(KeptCtx *cx, CallEvent *e)
+{
+    if (e && --e->users == 0) {
+        e->next = cx->pool;
+        cx->pool = e;
+    }
+}
+
+// (cx->mu held, the device current) what is enqueued on `st` by now reads the blocks of kept[0 .. nkept): one event behind
+// it AND behind every earlier reader of these handles, to which they all point from here on.  After a failure the handles are
+// as they were, and the caller waits for `st` on the host.
+int hold(KeptCtx *cx, lh_kept *const *kept, size_t nkept, hipStream_t st)
+{
+    CallEvent *e = cx->pool;
+    if (e) {
+        cx->pool = e->next;
+    } else {
+        e = new (std::nothrow) CallEvent;
+        if (!e) return LH_ENOMEM;
+        const hipError_t err = hipEventCreateWithFlags(&e->ev, hipEventDisableTiming);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            delete e;
+            return err == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;
+        }
+    }
+    const u64 now = ++cx->holds;
+    hipError_t err = hipSuccess;
+    for (size_t i = 0; i < nkept && err == hipSuccess; i++) {
+        CallEvent *was = kept[i]->busy;
+        if (was && was->waited_in != now) {
+            was->waited_in = now;
+            err = hipStreamWaitEvent(st, was->ev, 0);
+        }
+    }
+    if (err == hipSuccess) err = hipEventRecord(e->ev, st);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        e->next = cx->pool;
+        cx->pool = e;
+        return LH_EDEVICE;
+    }
+    for (size_t i = 0; i < nkept; i++)
+        if (kept[i]->busy != e) { // (a handle listed twice: once)
+            unuse(cx, kept[i]->busy);
+            kept[i]->busy = e;
+            e->users++;
+        }
+    return LH_OK;
+}
+
+// every check that needs neither a handle nor a device.  With np == 0 the per-percentile outputs are ignored: they are
+// nulled here, and count for nothing.
+int check_args(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+               KeptOut &o)
+{
+    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
+    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return LH_EINVAL;
+    for (size_t i = 0; i < nkept; i++)
+        if (!kept[i]) return LH_EINVAL;
+    if (np > LH_MAX_PERCENTILES || (np && !p) || flags != 0) return LH_EINVAL;
+    if (np == 0) {
+        o.pkeys = nullptr;
+        o.pvalid = nullptr;
+    }
+    if (!o.count && !o.sum && !o.nbuckets && !o.present && !o.pkeys && !o.pvalid) return LH_EINVAL;
+    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.nbuckets, 4) ||
+        misaligned(o.present, 8) || misaligned(o.pkeys, 2))
+        return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    return LH_OK;
+}
+
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
+int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
+            const KeptOut &o, hipStream_t st)
+{
+    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    const uint32_t *ids = nullptr;
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    KeptP pa;
+    for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
+    KeptList s;
+    s.n = (uint32_t)nkept;
+    for (size_t i = 0; i < LH_MAX_KEPT; i++) {
+        const lh_kept *k = i < nkept ? kept[i] : nullptr;
+        s.h[i] = KeptRec{k ? (u64)(uintptr_t)k->block : 0, k ? k->cells : 0, k ? k->first : 0, k ? k->nrows : 0};
+    }
+    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
+    const double *D = cx->d_table;
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_across<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
+        else hipLaunchKernelGGL((k_kept_across<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+                void *stream, KeptOut o, bool device_form)
+{
+    int rc = check_args(kept, nkept, sel, nmetrics, p, np, flags, o);
+    if (rc) return rc;
+    if (nmetrics == 0) return LH_OK; // before any handle is looked at
+    // the rows every handle has: [lo, end)
+    u64 lo = 0, end = ~0ull;
+    for (size_t i = 0; i < nkept; i++) {
+        const u64 f = kept[i]->first, e = f + kept[i]->nrows;
+        lo = f > lo ? f : lo;
+        end = e < end ? e : end;
+    }
+    if (!sel.by_id) {
+        if (sel.first < lo || (u64)sel.first + nmetrics > end) return LH_ERANGE;
+    } else if (!sel.on_device) {
+        for (size_t m = 0; m < nmetrics; m++)
+            if (sel.ids[m] < lo || sel.ids[m] >= end) return LH_ERANGE;
+    }
+    const int device = kept[nkept - 1]->device;
+    for (size_t i = 0; i + 1 < nkept; i++)
+        if (kept[i]->device != device) return LH_EINVAL;
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(device));
+    if (device_form) {
+        rc = enqueue(cx, kept, nkept, sel, nmetrics, p, np, o, st);
+        if (rc) return rc;
+        rc = hold(cx, kept, nkept, st);
+        // what was enqueued reads handles that no event guards: wait here
+        if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+        return rc;
+    }
+    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays first, then the 4-byte one, keys, flags.
+    const size_t per_m = nmetrics, per_p = nmetrics * np;
+    const HostOut out[6] = {{o.count, per_m * 8}, {o.sum, per_m * 8},   {o.present, per_m * 8},
+                            {o.nbuckets, per_m * 4}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
+    rc = host_results(cx->res, st, out, [&](unsigned char *const(&dev)[6]) {
+        KeptOut d;
+        d.count = reinterpret_cast<u64 *>(dev[0]);
+        d.sum = reinterpret_cast<double *>(dev[1]);
+        d.present = reinterpret_cast<u64 *>(dev[2]);
+        d.nbuckets = reinterpret_cast<uint32_t *>(dev[3]);
+        d.pkeys = reinterpret_cast<int16_t *>(dev[4]);
+        d.pvalid = reinterpret_cast<uint8_t *>(dev[5]);
+        return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st);
+    });
+    if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_kept **out)
+{
+    if (!s || !out || flags != 0 || nmetrics == 0) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE;
+    KeptSource q;
+    int rc = source_cells(s, first, nmetrics, q);
+    if (!rc) rc = source_open(s, q);
+    if (rc) return rc;
+    lh_kept *k = new (std::nothrow) lh_kept;
+    if (!k) return LH_ENOMEM;
+    k->device = q.device;
+    k->cx = q.cx;
+    {
+        std::lock_guard<std::mutex> g(q.cx->mu);
+        rc = keep(q, first, (uint32_t)nmetrics, k);
+        if (rc) {
+            if (hipStreamSynchronize(q.stream) != hipSuccess) (void)hipGetLastError();
+            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+    }
+    if (rc) {
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return LH_OK;
+}
+
+int lh_kept_release(lh_kept *k)
+{
+    if (!k) return LH_EINVAL;
+    KeptCtx *cx = k->cx; // (lh_keep's: never null)
+    {
+        std::lock_guard<std::mutex> g(cx->mu);
+        (void)hipSetDevice(k->device);
+        if (k->busy) { // enqueued work may still read the block
+            (void)hipEventSynchronize(k->busy->ev);
+            unuse(cx, k->busy);
+        }
+        if (k->block) (void)hipFree(k->block);
+        (void)hipGetLastError();
+    }
+    delete k;
+    return LH_OK;
+}
+
+int lh_kept_hold(lh_kept *k, void *stream)
+{
+    if (!k) return LH_EINVAL;
+    KeptCtx *cx = k->cx;
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(k->device));
+    return hold(cx, &k, 1, static_cast<hipStream_t>(stream));
+}
+
+int lh_kept_info_get(const lh_kept *k, lh_kept_info *out)
+{
+    if (!k || !out || out->struct_size != sizeof(lh_kept_info)) return LH_EINVAL;
+    out->device = k->device;
+    out->first = k->first;
+    out->nrows = k->nrows;
+    out->cells = k->cells;
+    out->samples = k->samples;
+    out->bytes = k->bytes;
+    return LH_OK;
+}
+
+int lh_kept_arrays(const lh_kept *k, const uint64_t **d_offsets, const int16_t **d_keys, const uint64_t **d_counts,
+                   const uint64_t **d_row_count)
+{
+    if (!k) return LH_EINVAL;
+    if (d_offsets) *d_offsets = reinterpret_cast<const uint64_t *>(k->offsets());
+    if (d_keys) *d_keys = k->keys();
+    if (d_counts) *d_counts = reinterpret_cast<const uint64_t *>(k->counts());
+    if (d_row_count) *d_row_count = reinterpret_cast<const uint64_t *>(k->row_count());
+    return LH_OK;
+}
+
+int lh_kept_across(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+                   void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys,
+                   uint8_t *pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
+    return kept_across(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+}
+
+int lh_kept_across_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                          uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
+                          uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
+    return kept_across(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+}
+
+int lh_kept_across_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np, uint32_t flags,
+                       void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys,
+                       uint8_t *pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
+    return kept_across(kept, nkept, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+}
+
+int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                              uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
+                              uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
+    return kept_across(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+}
+
+int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous)
+{
+    switch_exchange(g_wave_from, wave_from_rows, KEPT_WAVE_FROM_DEFAULT, previous);
+    return LH_OK;
+}
+
+int lh_tool_kept_tile(uint32_t *bins)
+{
+    if (!bins) return LH_EINVAL;
+    *bins = KEPT_TILE;
+    return LH_OK;
+}
+
+} // extern "C"

@@ -692,6 +692,15 @@ class Snapshot:
             res["pvals"] = np.where(res["pvalid"] != 0, self._decompress_table()[bins], np.nan)
         return res
 
+    def keep(self, nmetrics: Optional[int] = None, first: int = 0) -> "Kept":
+        """The occupied cells of metrics [first, first+nmetrics) in compact form, in device memory of their own (lh_keep): a
+        Kept, which outlives this snapshot and the engine.  The snapshot is not changed."""
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
+        h = C.c_void_p(0)
+        N.check(N.lib().lh_keep(self._h, first, nmetrics, 0, C.byref(h)), "lh_keep")
+        return Kept(h, self._decompress_table())
+
     def merge_rccl(self, comm: int, nranks: int, rank: int, nrows: int, plan: str = "allreduce"):
         """K4 through the C ABI: RCCL merge on the snapshot's stream (comm = ncclComm_t as int).
         Returns the [first, last) rows that hold merged data on this rank."""
@@ -723,6 +732,114 @@ class Snapshot:
 
     def __exit__(self, *exc):
         self.release()
+
+
+class Kept:
+    """One interval's occupied cells of metrics [first, first + nrows), kept in compact form on the device (lh_kept):
+    Snapshot.keep().  It depends on neither its snapshot nor its engine, and never changes."""
+
+    _OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("nbuckets", 4, 0, np.uint32),
+            ("present_bits", 8, 0, np.uint64), ("pkeys", 2, 1, np.int16), ("pvalid", 1, 1, np.uint8))
+
+    def __init__(self, handle: C.c_void_p, decompress_table: np.ndarray):
+        self._h = handle
+        self._table = decompress_table
+        self.info = self._info()
+
+    def _info(self) -> dict:
+        ki = N.LhKeptInfo(struct_size=C.sizeof(N.LhKeptInfo))
+        N.check(N.lib().lh_kept_info_get(self._h, C.byref(ki)), "lh_kept_info_get")
+        return {k: int(getattr(ki, k)) for k, _ in N.LhKeptInfo._fields_ if k != "struct_size"}
+
+    def arrays(self):
+        """(offsets uint64[nrows + 1], keys int16[cells], counts uint64[cells], row_count uint64[nrows]) as torch device
+        tensors that VIEW the handle's memory (8-byte integers come as torch.int64): no copy, valid until close().
+        Exactly buckets_all() of the same rows, and each row's sum of cells."""
+        import torch
+        from .merge import _DeviceArray
+        ptrs = [C.c_void_p(0) for _ in range(4)]
+        N.check(N.lib().lh_kept_arrays(self._h, *[C.byref(p) for p in ptrs]), "lh_kept_arrays")
+        dev = torch.device("cuda", self.info["device"])
+        nrows, cells = self.info["nrows"], self.info["cells"]
+
+        def view(p, n, typestr, dtype):
+            if n == 0:
+                return torch.empty(0, dtype=dtype, device=dev)
+            return torch.as_tensor(_DeviceArray(int(p.value), (n,), typestr), device=dev)
+
+        return (view(ptrs[0], nrows + 1, "<i8", torch.int64), view(ptrs[1], cells, "<i2", torch.int16),
+                view(ptrs[2], cells, "<i8", torch.int64), view(ptrs[3], nrows, "<i8", torch.int64))
+
+    def add_to(self, snapshot: Snapshot):
+        """The kept cells added to `snapshot` (rows first .. first + nrows), on its stream: lh_snapshot_add_buckets_csr_device
+        with the handle's own arrays.  The handle may be closed at once: close() waits for the import (lh_kept_hold)."""
+        offsets, keys, counts, _ = self.arrays()
+        snapshot.add_buckets_csr(offsets, keys, counts, first=self.info["first"])
+        N.check(N.lib().lh_kept_hold(self._h, snapshot.stream()), "lh_kept_hold")
+
+    def across(self, earlier, percentiles, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Snapshot.across over kept intervals: dict(count, sum, avg, nbuckets, present_bits, pkeys, pvalid, pvals) for metrics
+        [first, first+nmetrics) -- or, with ids=, for the metrics `ids` in that order -- over list(earlier) + [self] taken
+        together (lh_kept_across*, at most N.MAX_KEPT handles; one may appear more than once and counts that often).  first
+        and ids are metric ids; every handle of the list must hold them.  nmetrics=None: up to the end of this handle's block.
+        present_bits is uint64.  out= as for Snapshot.across (present_bits 8 bytes); torch device tensors take the device form,
+        enqueued on `stream` (a torch stream or a raw handle; None: the null stream), and device ids go with them."""
+        L = N.lib()
+        kept = list(earlier) + [self]
+        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        np_ = int(p.size)
+        device_ids = None
+        if ids is not None:
+            keep, addr, nmetrics, device_ids = _id_list(ids)
+            fn, rows = "lh_kept_across_ids", (addr, nmetrics)
+        else:
+            if nmetrics is None:
+                nmetrics = self.info["first"] + self.info["nrows"] - first
+            fn, rows = "lh_kept_across", (first, nmetrics)
+        lead = (C.addressof(handles), len(kept), *rows, p.ctypes.data, np_, 0, _stream_handle(stream))
+        if device_ids and out is None:
+            raise ValueError("device ids go with an out= of device tensors")
+        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
+            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
+                                             for k, width, per_p, _ in self._OUT])
+            if device_ids is not None and device != device_ids:
+                raise ValueError("ids and out are both on the device or both on the host")
+            if device:
+                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
+                return dict(out)
+            N.check(getattr(L, fn)(*lead, *args), fn)
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
+                   if v is not None and (np_ or k not in ("pkeys", "pvalid"))}
+        else:
+            import torch
+            res = {}
+            for k, width, per_p, dt in self._OUT:      # (a row more than an empty call needs: the arrays have addresses)
+                n = max(nmetrics, 1) * (np_ if per_p else 1)
+                res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
+            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._OUT]), fn)
+            res = {k: v[:nmetrics * (np_ if per_p else 1)] for (k, _, per_p, _), v in zip(self._OUT, res.values())}
+        per_p = {k: c for k, _, c, _ in self._OUT}
+        res = {k: (v.reshape(nmetrics, np_) if per_p[k] else v.reshape(nmetrics)) for k, v in res.items()}
+        if "sum" in res and "count" in res:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res["avg"] = res["sum"] / res["count"].view(np.uint64).astype(np.float64)
+        if "pkeys" in res and "pvalid" in res:
+            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
+            res["pvals"] = np.where(res["pvalid"] != 0, self._table[bins], np.nan)
+        return res
+
+    def close(self):
+        """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
+        if self._h is not None and self._h.value:
+            N.check(N.lib().lh_kept_release(self._h), "lh_kept_release")
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _device_column(t, what, widths):
