@@ -156,3 +156,62 @@ def test_name_blocks_partition():
                 lo, hi = merge.name_blocks(nrows, r, world)
                 seen.extend(range(lo, hi))
             assert seen == list(range(nrows))
+
+
+def test_row_bits_at_the_class_boundaries():
+    """row_bits where world x rowmax is exactly 255 | 256 and 65 535 | 65 536: the classes are written out, not computed
+    by a second copy of the rule."""
+    import torch
+    from loghisto_amd import merge
+    for world, rowmax, bits in (
+            (1, 255, 8), (3, 85, 8), (5, 51, 8), (15, 17, 8), (255, 1, 8),                          # 255
+            (1, 256, 16), (2, 128, 16), (4, 64, 16), (8, 32, 16), (256, 1, 16),                     # 256
+            (1, 65535, 16), (3, 21845, 16), (5, 13107, 16), (255, 257, 16), (257, 255, 16),         # 65 535
+            (1, 65536, 32), (2, 32768, 32), (4, 16384, 32), (8, 8192, 32), (256, 256, 32),          # 65 536
+            (3, 86, 16), (3, 21846, 32), (4, 63, 8), (4, 16383, 16),                                # beside them
+            (2, 0xffffffff, 32), (1, 0, 8)):
+        assert merge.row_bits(torch.tensor([rowmax]), world, 1 << 20).tolist() == [bits], (world, rowmax)
+        assert merge.row_bits(torch.tensor([rowmax]), world).tolist() == [bits], (world, rowmax)
+
+
+def test_row_bits_at_the_table_of_the_merge_edges():
+    """The (nranks, c) pairs tests/_merge_edges_driver.py merges on the GPU, classes as the table states them."""
+    import torch
+    from loghisto_amd import merge
+    for world, cs, want in ((3, (85, 86, 21845, 21846), [8, 16, 16, 32]), (4, (63, 64, 16383, 16384), [8, 16, 16, 32])):
+        assert merge.row_bits(torch.tensor(cs), world, 1 << 20).tolist() == want
+        assert merge.row_bits(torch.tensor(cs), world).tolist() == want      # no sample count given: uint32 words
+
+
+def test_row_bits_at_the_wire_word_boundary():
+    """uint32 wire words iff the largest per-rank sample count < 0xffffffff and world x it < 2^32."""
+    import torch
+    from loghisto_amd import merge
+    rowmax = torch.tensor([1, 300, 70000])                  # 8, 16 and 32 bits at every world below
+    for world, largest, uint32_words in (
+            (4, (1 << 30) - 1, True),                       # 4 x (2^30 - 1) = 2^32 - 4
+            (4, 1 << 30, False),                            # 2^32
+            (3, 1431655765, True),                          # 3 x 1 431 655 765 = 2^32 - 1
+            (3, 1431655766, False),                         # 2^32 + 2
+            (2, (1 << 31) - 1, True), (2, 1 << 31, False),
+            (1, 0xfffffffe, True),
+            (1, 0xffffffff, False),                         # "unknown": the clipped count itself
+            (2, 0xffffffff, False), (4, 0xffffffff, False)):
+        got = merge.row_bits(rowmax, world, largest).tolist()
+        assert got == ([8, 16, 32] if uint32_words else [64, 64, 64]), (world, largest, got)
+
+
+def test_merge_edges_rows_are_what_they_claim():
+    """tests/_merge_edges_driver.py's crafted rows without a GPU: every boundary product is reached with the hot cell in
+    every field, every width stands at every class and lo % 4, the sample counts sit on the wire-word boundary, and the
+    reduce-scatter's owner blocks start beside narrow rows (oracle rows and numpy only)."""
+    from tests import _merge_edges_driver as d
+    for case in d.CASES:
+        for plan in ("allreduce", "reduce_scatter"):
+            for sc in d.scenarios(case):
+                X = d.expected(sc, plan)
+                d.self_check(case, sc, X)
+                if plan == "reduce_scatter" and case.startswith("B") and not sc.dirty:
+                    d.boundary_check(sc, X)
+                if plan == "reduce_scatter":
+                    assert X["brow"] == expected_blocks(X["words"], sc.nranks)
