@@ -35,7 +35,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
-#include "lh_wave.h"
+#include "lh_pct.h"
 
 #include <hip/hip_runtime.h>
 
@@ -45,13 +45,12 @@
 
 namespace {
 
-using namespace lh; // (lh_wave.h)
+using namespace lh; // (lh_wave.h, lh_pct.h)
 using namespace lh::beside;
 
 // Rows of a call from which a row gets a wave, not a workgroup: lh_spread's default, whose walks these are
 // (profiles/across.txt).
 constexpr uint32_t AC_WAVE_FROM_DEFAULT = 1024;
-static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
 static_assert(LH_MAX_ACROSS <= 32, "a snapshot per lane, their set in one 32-bit mask");
 
 constexpr uint32_t IN_FLIGHT = 8; // snapshots whose loads a lane has under way together
@@ -59,21 +58,13 @@ static_assert(LH_MAX_ACROSS % IN_FLIGHT == 0 && LH_MAX_ACROSS <= 64, "the lanes 
 
 enum { ALL_NARROW = 0, ALL_WIDE = 1, MIXED = 2 };
 
-struct AcrossP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
-
 struct AcrossSnaps { // by value in the kernel arguments (264 bytes)
     const void *cells[LH_MAX_ACROSS];      // row `first` of snapshot i, at the snapshot's own width
     const uint32_t *ranges[LH_MAX_ACROSS]; // the span of row `first`
     uint32_t n, narrow;                    // bit i of narrow: snapshot i has 4-byte cells
 };
 
-struct AcrossOut {
-    u64 *count;
-    double *sum;
-    uint32_t *nbuckets, *present;
-    int16_t *pkeys;
-    uint8_t *pvalid;
-};
+typedef ListOut<uint32_t> AcrossOut; // present_bits: a bit per snapshot
 
 // 16 bytes of a row as they lie in memory (4-byte aligned at least), through a pointer that says GLOBAL: an address taken out
 // of a lane is an integer, and a load through a generic pointer made of it would be a flat one, which every LDS wait then
@@ -164,36 +155,12 @@ __device__ __forceinline__ void sum_rows(const Rows &r, uint32_t n, uint32_t nar
         }
     }
 }
-// the value table's entries of bins b0 .. b0 + 3; a lane whose group starts beyond hi asks for nothing
-__device__ __forceinline__ void load4_values(const double *__restrict__ D, uint32_t b0, uint32_t hi, double (&d)[4])
-{
-    d[0] = d[1] = d[2] = d[3] = 0.0;
-    if (b0 <= hi) {
-        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
-        const f64x2_a8 d01 = dp[0], d23 = dp[1];
-        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
-    }
-}
-__device__ __forceinline__ uint32_t occupied4(const u64 (&C)[4])
-{
-    return (C[0] ? 1u : 0u) + (C[1] ? 1u : 0u) + (C[2] ? 1u : 0u) + (C[3] ? 1u : 0u);
-}
-// The bin, inside a step of 256, of the first inclusive prefix that reaches T (wave-uniform T).  pre[k]: the prefix at the
-// lane's bin k.  The caller knows that the step's last prefix reaches T; with a total that wrapped none may, and the answer
-// is then unspecified (lane 63's group).
-__device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
-{
-    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
-    const uint32_t f = reach ? (uint32_t)__builtin_ctzll(reach) : 63u;
-    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
-    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
-}
 
 // (Both kernels, IDS: entry m reads row ids[m] of every snapshot, `nrows` the rows of the shortest of them; m still indexes
 // the outputs.  Otherwise row m of the blocks; ids and nrows are not looked at.)
 template <int MODE, bool IDS>
 __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
-                                                          const double *__restrict__ D, const AcrossP pa, uint32_t np,
+                                                          const double *__restrict__ D, const PctArgs pa, uint32_t np,
                                                           const AcrossOut o, const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
@@ -203,7 +170,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, 
     u64 total = 0;
     double sum = 0.0;
     uint32_t nb = 0, present = 0, none = 0;
-    uint32_t found = NO_BIN; // lane i < np: the bin of percentile i
+    Open pct; // lane i < np: percentile i
     if (r.base0 != NO_BIN) { // wave-uniform
         u64 C[4];
         // ---- walk 1: count, sum, the occupied bins and who has a sample
@@ -225,32 +192,10 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, 
         }
         if (total) { // wave-uniform
             // ---- walk 2: up to the step the last threshold falls into
-            u64 T = PCT_NONE;
-            if (lane < np) T = pct_threshold(pa.p[lane], total);
-            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
-            u64 carry = 0;
-            for (uint32_t base = r.base0; base <= hi && todo; base += STEP) {
+            pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
+            for (uint32_t base = r.base0; base <= hi && pct.todo; base += STEP) {
                 sum_rows<MODE, false>(r, s.n, s.narrow, base + 4 * lane, C, none);
-                const u64 tc = sum4(C);
-                const u64 inc = wave_scan_incl_u64(tc);
-                const u64 end = carry + readlane_u64(inc, 63);
-                // (every open threshold is > carry: it would have ended in an earlier step otherwise)
-                uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= end) & todo;
-                todo &= ~here;
-                if (here) {
-                    u64 pre[4], sofar = carry + (inc - tc);
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        sofar += C[k];
-                        pre[k] = sofar;
-                    }
-                    for (; here; here &= here - 1) {
-                        const uint32_t i = (uint32_t)__builtin_ctz(here);
-                        const uint32_t idx = find_in_step(pre, readlane_u64(T, i));
-                        if (lane == i) found = base + idx;
-                    }
-                }
-                carry = end;
+                pct.step(C, sum4(C), base, lane);
             }
         } else {
             sum = 0.0;
@@ -264,17 +209,12 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_across_wave(const AcrossSnaps s, 
         if (o.nbuckets) o.nbuckets[m] = nb;
         if (o.present) o.present[m] = present;
     }
-    if (lane < np) {
-        const size_t at = (size_t)m * np + lane;
-        const bool ok = found != NO_BIN;
-        if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(found) : (int16_t)0;
-        if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
-    }
+    if (lane < np) store_pct(o.pkeys, o.pvalid, (size_t)m * np + lane, pct.found);
 }
 
 template <int MODE, bool IDS>
 __global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32_t nmetrics, size_t stride,
-                                                        const double *__restrict__ D, const AcrossP pa, uint32_t np,
+                                                        const double *__restrict__ D, const PctArgs pa, uint32_t np,
                                                         const AcrossOut o, const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
@@ -312,33 +252,7 @@ __global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32
         }
     }
     __syncthreads();
-    if (wave == 0) {
-        u64 v[4];
-        double w[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            const bool in = 4 * lane + k < nchunks;
-            v[k] = in ? s_cnt[4 * lane + k] : 0;
-            w[k] = in ? s_sum[4 * lane + k] : 0.0;
-        }
-        const u64 tv = (v[0] + v[1]) + (v[2] + v[3]);
-        const u64 inc = wave_scan_incl_u64(tv);
-        const double incs = wave_scan_incl_f64(((w[0] + w[1]) + w[2]) + w[3]);
-        const double up = __shfl_up(incs, 1, 64); // what the lanes below add up to
-        u64 ex = inc - tv;
-        double exs = lane ? up : 0.0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            s_cnt[4 * lane + k] = ex;
-            s_sum[4 * lane + k] = exs;
-            ex += v[k];
-            exs += w[k];
-        }
-        if (lane == 63) {
-            s_total = inc;
-            s_tsum = incs;
-        }
-    }
+    if (wave == 0) scan_chunks((lds_u64)s_cnt, (lds_f64)s_sum, nchunks, lane, (lds_u64)&s_total, (lds_f64)&s_tsum);
     __syncthreads();
     const u64 total = s_total;
     if (threadIdx.x == 0) {
@@ -357,29 +271,14 @@ __global__ __launch_bounds__(WG) void k_across_block(const AcrossSnaps s, uint32
         uint32_t bin = NO_BIN;
         const u64 T = total ? pct_threshold(pa.p[i], total) : PCT_NONE;
         if (T != PCT_NONE) {
-            // the last chunk with fewer than T samples below it (chunk 0 has none below: there is one)
-            uint32_t nlow = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++)
-                nlow += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(4 * lane + k < nchunks && s_cnt[4 * lane + k] < T));
-            const uint32_t ch = nlow - 1;
+            const uint32_t ch = chunk_of((lds_u64)s_cnt, nchunks, lane, T);
             u64 C[4], pre[4];
             sum_rows<MODE, false>(r, s.n, s.narrow, base0 + ch * STEP + 4 * lane, C, none);
             const u64 tc = sum4(C);
-            u64 sofar = s_cnt[ch] + (wave_scan_incl_u64(tc) - tc);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                sofar += C[k];
-                pre[k] = sofar;
-            }
+            prefix4(C, s_cnt[ch], tc, wave_scan_incl_u64(tc), pre);
             bin = base0 + ch * STEP + find_in_step(pre, T);
         }
-        if (lane == 0) {
-            const size_t at = (size_t)m * np + i;
-            const bool ok = bin != NO_BIN;
-            if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(bin) : (int16_t)0;
-            if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
-        }
+        if (lane == 0) store_pct(o.pkeys, o.pvalid, (size_t)m * np + i, bin);
     }
 }
 
@@ -394,28 +293,6 @@ struct AcrossCtx {
     IdBlocks ids;              // host form of lh_across_ids
 };
 std::atomic<uint32_t> g_wave_from{AC_WAVE_FROM_DEFAULT};
-
-// every check that needs neither a snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
-// nulled here, and count for nothing.
-int check_args(lh_snapshot *const *snaps, size_t nsnaps, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
-               uint32_t flags, AcrossOut &o)
-{
-    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
-    if (!snaps || misaligned(snaps, alignof(lh_snapshot *)) || nsnaps == 0 || nsnaps > LH_MAX_ACROSS) return LH_EINVAL;
-    for (size_t i = 0; i < nsnaps; i++)
-        if (!snaps[i]) return LH_EINVAL;
-    if (np > LH_MAX_PERCENTILES || (np && !p) || flags != 0) return LH_EINVAL;
-    if (np == 0) {
-        o.pkeys = nullptr;
-        o.pvalid = nullptr;
-    }
-    if (!o.count && !o.sum && !o.nbuckets && !o.present && !o.pkeys && !o.pvalid) return LH_EINVAL;
-    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.nbuckets, 4) ||
-        misaligned(o.present, 4) || misaligned(o.pkeys, 2))
-        return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    return LH_OK;
-}
 
 typedef lh::beside::Source<AcrossCtx> Source;
 
@@ -435,8 +312,7 @@ int enqueue(const Source *q, size_t nsnaps, const RowSel &sel, size_t nmetrics, 
     const uint32_t first = sel.first;
     uint32_t nrows = last.nrows; // what an id is guarded against: the rows of the shortest snapshot
     for (size_t i = 0; i < nsnaps; i++) nrows = q[i].nrows < nrows ? q[i].nrows : nrows;
-    AcrossP pa;
-    for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
+    const PctArgs pa = pct_args(p, np);
     AcrossSnaps s;
     s.n = (uint32_t)nsnaps;
     s.narrow = 0;
@@ -470,7 +346,7 @@ int enqueue(const Source *q, size_t nsnaps, const RowSel &sel, size_t nmetrics, 
 int across(lh_snapshot *const *snaps, size_t nsnaps, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
            AcrossOut o, bool device_form)
 {
-    int rc = check_args(snaps, nsnaps, sel, nmetrics, p, np, flags, o);
+    int rc = check_list_args(snaps, nsnaps, LH_MAX_ACROSS, sel, nmetrics, p, np, flags, o);
     if (rc) return rc;
     Source q[LH_MAX_ACROSS];
     rc = list_cells(snaps, nsnaps, sel, nmetrics, q);
@@ -482,20 +358,9 @@ int across(lh_snapshot *const *snaps, size_t nsnaps, const RowSel &sel, size_t n
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(q, nsnaps, sel, nmetrics, p, np, o);
 
-    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, the 4-byte ones, the keys, the flags.
-    const size_t per_m = nmetrics, per_p = nmetrics * np;
-    const HostOut out[6] = {{o.count, per_m * 8}, {o.sum, per_m * 8},   {o.nbuckets, per_m * 4},
-                            {o.present, per_m * 4}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
-    rc = host_results(cx->res, q[nsnaps - 1].stream, out, [&](unsigned char *const(&dev)[6]) {
-        AcrossOut d;
-        d.count = reinterpret_cast<u64 *>(dev[0]);
-        d.sum = reinterpret_cast<double *>(dev[1]);
-        d.nbuckets = reinterpret_cast<uint32_t *>(dev[2]);
-        d.present = reinterpret_cast<uint32_t *>(dev[3]);
-        d.pkeys = reinterpret_cast<int16_t *>(dev[4]);
-        d.pvalid = reinterpret_cast<uint8_t *>(dev[5]);
-        return enqueue(q, nsnaps, sel, nmetrics, p, np, d);
-    });
+    // host form: results to HBM, then back to the caller's arrays
+    rc = list_host_results(cx->res, q[nsnaps - 1].stream, o, nmetrics, np,
+                             [&](const AcrossOut &d) { return enqueue(q, nsnaps, sel, nmetrics, p, np, d); });
     return settle_ids(rc, sel, q[nsnaps - 1].stream);
 }
 

@@ -9,7 +9,8 @@
 //   lh_extract_rows returns for a snapshot that holds C.  present_bits: bit i set iff kept[i] holds a cell of the name.
 // Nothing is summed across names, no cell of a snapshot is written and no new statistic is defined.
 //
-// Built BESIDE the engine, on its public C ABI only (lh_beside.h, lh_wave.h), like lh_across.hip.
+// Built BESIDE the engine, on its public C ABI only (lh_beside.h, lh_wave.h), like lh_across.hip, whose out record, argument
+// check and find_in_step it shares (lh_pct.h).
 //
 // THE HANDLE is one allocation of exactly  offsets[nrows + 1] | row_count[nrows] | counts[cells] | keys[cells]  (uint64,
 // uint64, uint64, int16): lh_buckets_all's CSR arrays of the same rows -- keys ascending by bin -- which
@@ -54,7 +55,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
-#include "lh_wave.h"
+#include "lh_pct.h"
 
 #include <hip/hip_runtime.h>
 
@@ -65,16 +66,13 @@
 
 namespace {
 
-using namespace lh; // (lh_wave.h)
+using namespace lh; // (lh_wave.h, lh_pct.h)
 using namespace lh::beside;
 
 constexpr uint32_t KEPT_WAVE_FROM_DEFAULT = 1024; // lh_spread's default; profiles/kept.txt has both shapes
 constexpr uint32_t KEPT_TILE = 1024;              // bins of a tile: a lognormal name's union span fits one
 static_assert(KEPT_TILE % STEP == 0 && ROW_WAVES * KEPT_TILE * sizeof(u64) <= 65536, "whole steps; 64 KiB static LDS at most");
-static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
 static_assert(LH_MAX_KEPT == 64, "a handle per lane, their set in one 64-bit mask");
-
-struct KeptP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
 
 // one handle as the kernel sees it.  offsets at `block`, row_count = offsets + nrows + 1, counts = row_count + nrows, keys
 // behind counts.
@@ -88,19 +86,8 @@ struct KeptList { // by value in the kernel arguments (1 544 bytes)
     uint32_t n;
 };
 
-struct KeptOut {
-    u64 *count;
-    double *sum;
-    uint32_t *nbuckets;
-    u64 *present;
-    int16_t *pkeys;
-    uint8_t *pvalid;
-};
+typedef ListOut<u64> KeptOut; // present_bits: a bit per handle
 
-__device__ __forceinline__ uint32_t occupied4(const u64 (&C)[4])
-{
-    return (C[0] ? 1u : 0u) + (C[1] ? 1u : 0u) + (C[2] ? 1u : 0u) + (C[3] ? 1u : 0u);
-}
 // A handle's arrays through pointers that say GLOBAL: their addresses travel as integers -- in the list, then from lane to
 // lane -- and a load through a generic pointer made of one would be a flat one, which every LDS wait then waits for too
 // (lh_across.hip's gcells), here in the loop of the tile's LDS adds.
@@ -206,14 +193,6 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_keep_fill(const CELL *__restrict_
 }
 
 // ---- the reader ---------------------------------------------------------------------------------------------------------
-// the bin, inside a step of 256, of the first inclusive prefix that reaches T (lh_across.hip's find_in_step)
-__device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
-{
-    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
-    const uint32_t f = reach ? (uint32_t)__builtin_ctzll(reach) : 63u;
-    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
-    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
-}
 // the tile's adds are complete and visible before anything behind this reads it (and the other way round)
 template <int NW> __device__ __forceinline__ void tile_sync()
 {
@@ -229,7 +208,7 @@ template <int NW> __device__ __forceinline__ void tile_sync()
 // of ANY handle gives the empty entry, and nothing is read for it.
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const KeptList s, uint32_t nmetrics, uint32_t first,
-                                                                          const double *__restrict__ D, const KeptP pa,
+                                                                          const double *__restrict__ D, const PctArgs pa,
                                                                           uint32_t np, const KeptOut o,
                                                                           const uint32_t *__restrict__ ids)
 {
@@ -277,11 +256,10 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
     u64 cur = beg;
 
     double ps = 0.0;
-    uint32_t occ = 0, found = NO_BIN; // lane i < np: the bin of percentile i
+    uint32_t occ = 0;
+    Open pct; // lane i < np: percentile i
     if (total) {                       // uniform
-        u64 T = PCT_NONE, carry = 0;
-        if (lane < np) T = pct_threshold(pa.p[lane], total);
-        uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
+        pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
         tile_sync<NW>();                                                       // the tile is zero
         for (uint32_t from = 0;;) { // (every wave of a workgroup takes the same turns: the state below is the same in all)
             if (from) { // the first entry at or above `from`
@@ -331,34 +309,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
                         C[k] = tile[at + k];
                         tile[at + k] = 0;
                     }
-                    d[0] = d[1] = d[2] = d[3] = 0.0;
-                    if (b0 <= hi) {
-                        const f64x2_a8 *dp = reinterpret_cast<const f64x2_a8 *>(D + b0);
-                        const f64x2_a8 d01 = dp[0], d23 = dp[1];
-                        d[0] = d01.a; d[1] = d01.b; d[2] = d23.a; d[3] = d23.b;
-                    }
+                    load4_values(D, b0, hi, d);
                     const u64 tc = sum4(C);
                     ps += terms4(C, d, t);
                     occ += occupied4(C);
-                    const u64 inc = wave_scan_incl_u64(tc);
-                    const u64 upto = carry + readlane_u64(inc, 63);
-                    // (every open threshold is > carry: it would have ended in an earlier step otherwise)
-                    uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= upto) & todo;
-                    todo &= ~here;
-                    if (here) {
-                        u64 pre[4], sofar = carry + (inc - tc);
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            sofar += C[k];
-                            pre[k] = sofar;
-                        }
-                        for (; here; here &= here - 1) {
-                            const uint32_t i = (uint32_t)__builtin_ctz(here);
-                            const uint32_t idx = find_in_step(pre, readlane_u64(T, i));
-                            if (lane == i) found = base + idx;
-                        }
-                    }
-                    carry = upto;
+                    pct.step(C, tc, base, lane);
                 }
             }
             tile_sync<NW>();
@@ -376,10 +331,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
         if (o.present) o.present[m] = total ? present : 0;
     }
     if (lane < np) {
-        const size_t at = (size_t)m * np + lane;
-        const bool ok = found != NO_BIN;
-        if (o.pkeys) o.pkeys[at] = ok ? (int16_t)bin_to_key(found) : (int16_t)0;
-        if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+        store_pct(o.pkeys, o.pvalid, (size_t)m * np + lane, pct.found);
     }
 }
 
@@ -518,28 +470,6 @@ int hold(KeptCtx *cx, lh_kept *const *kept, size_t nkept, hipStream_t st)
     return LH_OK;
 }
 
-// every check that needs neither a handle nor a device.  With np == 0 the per-percentile outputs are ignored: they are
-// nulled here, and count for nothing.
-int check_args(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
-               KeptOut &o)
-{
-    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
-    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return LH_EINVAL;
-    for (size_t i = 0; i < nkept; i++)
-        if (!kept[i]) return LH_EINVAL;
-    if (np > LH_MAX_PERCENTILES || (np && !p) || flags != 0) return LH_EINVAL;
-    if (np == 0) {
-        o.pkeys = nullptr;
-        o.pvalid = nullptr;
-    }
-    if (!o.count && !o.sum && !o.nbuckets && !o.present && !o.pkeys && !o.pvalid) return LH_EINVAL;
-    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.nbuckets, 4) ||
-        misaligned(o.present, 8) || misaligned(o.pkeys, 2))
-        return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    return LH_OK;
-}
-
 // (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
 int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
             const KeptOut &o, hipStream_t st)
@@ -548,8 +478,7 @@ int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, 
     const uint32_t *ids = nullptr;
     if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
     if (rc) return rc;
-    KeptP pa;
-    for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
+    const PctArgs pa = pct_args(p, np);
     KeptList s;
     s.n = (uint32_t)nkept;
     for (size_t i = 0; i < LH_MAX_KEPT; i++) {
@@ -573,7 +502,7 @@ int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, 
 int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
                 void *stream, KeptOut o, bool device_form)
 {
-    int rc = check_args(kept, nkept, sel, nmetrics, p, np, flags, o);
+    int rc = check_list_args(kept, nkept, LH_MAX_KEPT, sel, nmetrics, p, np, flags, o);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any handle is looked at
     // the rows every handle has: [lo, end)
@@ -605,20 +534,9 @@ int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nm
         if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
         return rc;
     }
-    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays first, then the 4-byte one, keys, flags.
-    const size_t per_m = nmetrics, per_p = nmetrics * np;
-    const HostOut out[6] = {{o.count, per_m * 8}, {o.sum, per_m * 8},   {o.present, per_m * 8},
-                            {o.nbuckets, per_m * 4}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
-    rc = host_results(cx->res, st, out, [&](unsigned char *const(&dev)[6]) {
-        KeptOut d;
-        d.count = reinterpret_cast<u64 *>(dev[0]);
-        d.sum = reinterpret_cast<double *>(dev[1]);
-        d.present = reinterpret_cast<u64 *>(dev[2]);
-        d.nbuckets = reinterpret_cast<uint32_t *>(dev[3]);
-        d.pkeys = reinterpret_cast<int16_t *>(dev[4]);
-        d.pvalid = reinterpret_cast<uint8_t *>(dev[5]);
-        return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st);
-    });
+    // host form: results to HBM, then back to the caller's arrays
+    rc = list_host_results(cx->res, st, o, nmetrics, np,
+                           [&](const KeptOut &d) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st); });
     if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
     return rc;
 }

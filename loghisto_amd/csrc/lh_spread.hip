@@ -24,7 +24,8 @@
 //                   threshold falls into.  For calls of few rows, which may span all 65 536 bins.
 // Each row takes two walks.  Walk 1 gives count and sum, hence the mean and the thresholds T = the smallest prefix count
 // that reaches p (pct_threshold, lh_wave.h: tests/test_pct_threshold_model.py has the arithmetic).  Walk 2 re-reads the window
-// (L2-resident at typical spans) for m2 and, in the steps a threshold falls into, the key, count_le and sum_le.
+// (L2-resident at typical spans) for m2 and, in the steps a threshold falls into, the key, count_le and sum_le.  The walk's
+// state, the chunk scan and lookup and the key's store are lh_pct.h's.
 // Every floating-point sum is taken in a fixed order (per lane over the steps in ascending order, then one DPP tree over
 // the lanes; chunk totals in ascending order), so a result does not depend on timing -- but the two shapes associate
 // differently and agree to rounding only.
@@ -32,7 +33,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
-#include "lh_wave.h"
+#include "lh_pct.h"
 
 #include <hip/hip_runtime.h>
 
@@ -43,7 +44,7 @@
 
 namespace {
 
-using namespace lh; // (lh_wave.h)
+using namespace lh; // (lh_wave.h, lh_pct.h)
 using namespace lh::beside;
 
 // Rows of a call from which a row gets a wave, not a workgroup.  profiles/spread.txt has both shapes either side: over
@@ -51,9 +52,6 @@ using namespace lh::beside;
 // from 1 024 on (16.4 against 23.5); over one full-span row the workgroup is four to five times faster -- so few rows,
 // which may be wide, get workgroups.
 constexpr uint32_t SP_WAVE_FROM_DEFAULT = 1024;
-static_assert(LH_MAX_PERCENTILES <= 32, "a percentile per lane, their set in one 32-bit mask");
-
-struct SpreadP { double p[LH_MAX_PERCENTILES]; }; // by value in the kernel arguments (256 bytes)
 
 struct SpreadOut {
     u64 *count;
@@ -76,10 +74,12 @@ __device__ __forceinline__ double central4(const u64 (&c)[4], const double (&d)[
     return (q[0] + q[1]) + (q[2] + q[3]);
 }
 
+// lh_pct.h's find_in_step with what this unit adds, in one piece as it was (on top of locate_in_step the two kernels come out
+// reordered, and without that function's guard for an empty ballot, which this text never had).
 // One step of 256 bins in which threshold T is reached (wave-uniform T; `before` counts / `sbefore` sums everything below
 // the step).  pre[k]: inclusive prefix count at the lane's bin k; t[k]: the bins' terms; incs: inclusive scan over the lanes
 // of the terms' sums.  Returns the index of the bin inside the step, the prefix count and the prefix sum there.
-__device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], const double (&t)[4], double incs, double sbefore, u64 T,
+__device__ __forceinline__ uint32_t sums_in_step(const u64 (&pre)[4], const double (&t)[4], double incs, double sbefore, u64 T,
                                                  u64 &cle, double &sle)
 {
     // the first lane whose last bin reaches T (lane 63's does), and how many of its bins stay below
@@ -102,7 +102,7 @@ __device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], const doub
 template <typename CELL, bool IDS>
 __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                           uint32_t nmetrics, size_t stride, const double *__restrict__ D,
-                                                          const SpreadP pa, uint32_t np, const SpreadOut o,
+                                                          const PctArgs pa, uint32_t np, const SpreadOut o,
                                                           const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restric
     const uint32_t hi = sp.hi;
     u64 total = 0, r_cle = 0;
     double sum = 0.0, m2 = 0.0, r_sle = 0.0;
-    uint32_t found = 0xffffffffu; // lane i < np: the bin of percentile i
+    Open pct; // lane i < np: percentile i
     if (sp.any()) {               // wave-uniform; an empty row costs two loads and its stores
         const CELL *__restrict__ row = cells + (size_t)r * stride;
         const uint32_t base0 = sp.base0();
@@ -136,45 +136,33 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restric
         if (total) { // wave-uniform
             // ---- walk 2: the centred moment; the steps the thresholds fall into
             const double mean = sum / (double)total;
-            u64 T = PCT_NONE;
-            if (lane < np) T = pct_threshold(pa.p[lane], total);
-            uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(T != PCT_NONE); // percentiles without a bin yet
-            u64 carry = 0;
+            pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
             double run = 0.0, q = 0.0; // the lane's terms of the steps so far; its share of m2
             load4(row, D, base0 + 4 * lane, hi, c, d);
             for (uint32_t base = base0; base <= hi; base += STEP) {
                 load4(row, D, base + STEP + 4 * lane, hi, nc, nd);
                 q += central4(c, d, mean);
                 const double ts = terms4(c, d, t);
-                if (todo) { // wave-uniform
+                if (pct.todo) { // wave-uniform
                     const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
-                    const u64 inc = wave_scan_incl_u64(tc);
-                    const u64 end = carry + readlane_u64(inc, 63);
-                    // (every open threshold is > carry: it would have ended in an earlier step otherwise)
-                    uint32_t here = (uint32_t)__builtin_amdgcn_ballot_w64(T <= end) & todo;
-                    todo &= ~here;
+                    uint32_t here = pct.ending(tc);
                     if (here) {
-                        u64 pre[4], sofar = carry + (inc - tc);
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            sofar += c[k];
-                            pre[k] = sofar;
-                        }
+                        u64 pre[4];
+                        pct.prefixes(c, tc, pre);
                         const double sbefore = readlane_f64(wave_scan_incl_f64(run), 63);
                         const double incs = wave_scan_incl_f64(ts);
                         for (; here; here &= here - 1) {
                             const uint32_t i = (uint32_t)__builtin_ctz(here);
                             u64 cle;
                             double sle;
-                            const uint32_t idx = find_in_step(pre, t, incs, sbefore, readlane_u64(T, i), cle, sle);
+                            const uint32_t idx = sums_in_step(pre, t, incs, sbefore, pct.threshold(i), cle, sle);
                             if (lane == i) {
-                                found = base + idx;
+                                pct.found = base + idx;
                                 r_cle = cle;
                                 r_sle = sle;
                             }
                         }
                     }
-                    carry = end;
                 }
                 run += ts;
 #pragma unroll
@@ -192,9 +180,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restric
     }
     if (lane < np) {
         const size_t at = (size_t)m * np + lane;
-        const bool ok = found != 0xffffffffu;
-        if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(found) : (int16_t)0;
-        if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+        store_pct(o.pkeys, o.pvalid, at, pct.found);
         if (o.count_le) o.count_le[at] = r_cle;
         if (o.sum_le) o.sum_le[at] = r_sle;
     }
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_spread_wave(const CELL *__restric
 template <typename CELL, bool IDS>
 __global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
                                                         uint32_t nmetrics, size_t stride, const double *__restrict__ D,
-                                                        const SpreadP pa, uint32_t np, const SpreadOut o,
+                                                        const PctArgs pa, uint32_t np, const SpreadOut o,
                                                         const uint32_t *__restrict__ ids, uint32_t nrows)
 {
     __shared__ u64 s_cnt[CHUNKS];    // the chunks' counts, then their exclusive prefix
@@ -238,33 +224,7 @@ __global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ ce
         }
     }
     __syncthreads();
-    if (wave == 0) {
-        u64 v[4];
-        double w[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            const bool in = 4 * lane + k < nchunks;
-            v[k] = in ? s_cnt[4 * lane + k] : 0;
-            w[k] = in ? s_sum[4 * lane + k] : 0.0;
-        }
-        const u64 tv = (v[0] + v[1]) + (v[2] + v[3]);
-        const u64 inc = wave_scan_incl_u64(tv);
-        const double incs = wave_scan_incl_f64(((w[0] + w[1]) + w[2]) + w[3]);
-        const double up = __shfl_up(incs, 1, 64); // what the lanes below add up to
-        u64 ex = inc - tv;
-        double exs = lane ? up : 0.0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            s_cnt[4 * lane + k] = ex;
-            s_sum[4 * lane + k] = exs;
-            ex += v[k];
-            exs += w[k];
-        }
-        if (lane == 63) {
-            s_total = inc;
-            s_tsum = incs;
-        }
-    }
+    if (wave == 0) scan_chunks((lds_u64)s_cnt, (lds_f64)s_sum, nchunks, lane, (lds_u64)&s_total, (lds_f64)&s_tsum);
     __syncthreads();
     const u64 total = s_total;
     if (total == 0) { // workgroup-uniform: an empty row, or a span over nothing but zeros
@@ -304,30 +264,24 @@ __global__ __launch_bounds__(WG) void k_spread_block(const CELL *__restrict__ ce
         u64 cle = 0;
         double sle = 0.0;
         if (T != PCT_NONE) {
-            // the last chunk with fewer than T samples below it (chunk 0 has none below; T <= total)
-            uint32_t nlow = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++)
-                nlow += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(4 * lane + k < nchunks && s_cnt[4 * lane + k] < T));
-            const uint32_t ch = nlow - 1;
+            const uint32_t ch = chunk_of((lds_u64)s_cnt, nchunks, lane, T);
             u64 c[4], pre[4];
             double d[4], t[4];
             load4(row, D, base0 + ch * STEP + 4 * lane, hi, c, d);
             const double ts = terms4(c, d, t);
             const u64 tc = (c[0] + c[1]) + (c[2] + c[3]);
+            // (prefix4, lh_pct.h, written out: through the helper this kernel measures 1 % slower, profiles/pct_walk_isa.txt)
             u64 sofar = s_cnt[ch] + (wave_scan_incl_u64(tc) - tc);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 sofar += c[k];
                 pre[k] = sofar;
             }
-            bin = base0 + ch * STEP + find_in_step(pre, t, wave_scan_incl_f64(ts), s_sum[ch], T, cle, sle);
+            bin = base0 + ch * STEP + sums_in_step(pre, t, wave_scan_incl_f64(ts), s_sum[ch], T, cle, sle);
         }
         if (lane == 0) {
             const size_t at = (size_t)m * np + i;
-            const bool ok = bin != 0xffffffffu;
-            if (o.pkeys) o.pkeys[at] = ok ? (int16_t)lh::bin_to_key(bin) : (int16_t)0;
-            if (o.pvalid) o.pvalid[at] = ok ? 1 : 0;
+            store_pct(o.pkeys, o.pvalid, at, bin);
             if (o.count_le) o.count_le[at] = cle;
             if (o.sum_le) o.sum_le[at] = sle;
         }
@@ -384,8 +338,7 @@ int enqueue(const Source &q, const RowSel &sel, size_t nmetrics, const double *p
     int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<SpreadCtx>);
     if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, q.stream, ids);
     if (rc) return rc;
-    SpreadP pa;
-    for (size_t i = 0; i < LH_MAX_PERCENTILES; i++) pa.p[i] = i < np ? p[i] : 0.0;
+    const PctArgs pa = pct_args(p, np);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const uint32_t *ranges = ranges_from(q, sel.first);
     const double *D = cx->d_table;

@@ -112,6 +112,8 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict_
                 const u64 inc = wave_scan_incl_u64(tc);
                 const u64 end = carry + readlane_u64(inc, 63);
                 if (T <= end) { // wave-uniform: it is in this step
+                    // (find_in_step, lh_pct.h, written out: through the helper this kernel's code comes out reordered and two
+                    // instructions longer, profiles/pct_walk_isa.txt)
                     const u64 p0 = carry + (inc - tc) + c[0], p1 = p0 + c[1], p2 = p1 + c[2], p3 = p2 + c[3];
                     // the first lane whose last bin reaches T (lane 63's does), and how many of its bins stay below
                     const uint32_t f = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(p3 >= T));
