@@ -673,7 +673,24 @@ int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const 
  *                     return after enqueueing, and the outputs and d_ids stay valid until the stream has passed the call.  p is
  *                     a HOST array in all forms and travels by value, as does the list of handles.  sum is taken in one fixed
  *                     order and does not depend on timing.  One set of staging blocks per DEVICE behind the unit's own mutex:
- *                     calls take turns. */
+ *                     calls take turns.
+ *   lh_kept_merge     CONSOLIDATION: one new handle of rows [first, first + nmetrics) out of 1 .. LH_MAX_KEPT handles -- sixty
+ *                     1 s handles into one of a minute, sixty of those into one of an hour; lh_kept_across* takes any mix.
+ *                     *out holds exactly what lh_keep would return for a snapshot whose cells are C[b] = the sum over the
+ *                     listed handles of the name's cell b in 64 bits, wrapping (the cell atomic.AddUint64 would have left had
+ *                     the samples arrived in one interval, metrics.go:278; the pairs of RawMetricSet.Histograms,
+ *                     metrics.go:54-60): per row the union of the handles' bins ascending by bin, a bin whose sum wraps to 0
+ *                     not listed (it is not an occupied cell), row_count[m] the wrapping sum of the row's cells, samples the
+ *                     sum of those; the same single allocation, layout and bytes.  A handle listed twice counts twice;
+ *                     nkept == 1 is a slice, or a copy.  Nothing is summed across names; no snapshot, engine or listed handle
+ *                     is written.  The work goes on `stream` (a hipStream_t of the handles' device; NULL: its null stream) and
+ *                     is complete on return, like lh_keep's (the allocation's size is known only after the count pass); the
+ *                     new handle depends on none of the listed ones.  The rows of the call choose between the reader's two
+ *                     kernel shapes, which give identical bytes.  flags must be 0.  Checked on the host, in this order, before
+ *                     any handle is looked at -- LH_EINVAL: NULL or misaligned list, a NULL entry, nkept == 0 or
+ *                     > LH_MAX_KEPT, flags != 0, NULL out, nmetrics == 0; LH_ERANGE: nmetrics > 0xffffffff -- then LH_EINVAL:
+ *                     handles on different devices; LH_ERANGE: [first, first + nmetrics) not inside EVERY handle's block
+ *                     (lh_kept_across' rule).  LH_ENOMEM: the allocation failed.  *out is untouched on any failure. */
 typedef struct lh_kept lh_kept;      /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
 #define LH_MAX_KEPT 64
 typedef struct lh_kept_info {
@@ -700,6 +717,8 @@ int lh_kept_across_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, 
 int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
                               uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
+int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream,
+                  lh_kept **out);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

@@ -265,6 +265,7 @@ SIGNATURES = {
     "lh_kept_across_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_merge": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
     "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "lh_names_refresh": (C.c_int, [_vp, _u32p]),
     "lh_names_destroy": (C.c_int, [_vp]),

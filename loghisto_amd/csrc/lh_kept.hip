@@ -35,6 +35,19 @@
 // The walk puts zeros back where it read, so the next tile starts clean.  Integer cell sums do not depend on the order of
 // the adds and the float walk is fixed: no result depends on timing.
 //
+// THE MERGE, lh_kept_merge: up to 64 handles rolled up into ONE new handle of rows [first, first + nmetrics) -- 60 x 1 s into a
+// minute, 60 minutes into an hour -- that holds exactly what lh_keep would return for a snapshot whose cells are C: per row
+// the union of the handles' bins ascending by bin, each with its 64-bit wrapping sum, a sum that wrapped to 0 not listed (not
+// an occupied cell); row_count[m] the wrapping sum of the row's cells, which is the wrapping sum of the handles' own
+// row_count entries, so no cell is read for it.  lh_keep's three steps with the reader's row walk in the outer two:
+// k_merge_count, k_keep_scan as it is, the totals brought back and the allocation made, k_merge_fill (each step's non-zero
+// cells to off[m] plus a running position, from a wave scan of occupied4 as in k_keep_fill; not launched without a cell).
+// The open and the turns over the tiles are ONE device function (Row, turns) that takes the walk's step: the reader's is
+// lh_across', the count pass's counts the non-zero cells, the fill pass's places them.  Both passes have the reader's two
+// shapes, switched by the rows of the call through the same switch, and give identical bytes.  Synchronous like lh_keep, on
+// the caller's stream, under the unit's mutex from the first look at a handle to the end (no lh_kept_release frees an input
+// under it); it only reads its inputs, so it records no event on them, and the new handle depends on none of them.
+//
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
 // a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
@@ -204,6 +217,128 @@ template <int NW> __device__ __forceinline__ void tile_sync()
     }
 }
 
+// ---- a row of a list of handles: the open and the turns, once for the reader and for lh_kept_merge's two passes ----------
+// Lane i's view of handle i's segment of the row: the cursor and the end in its CSR arrays, the addresses of those (as
+// integers: they travel from lane to lane), its row_count entry, the bin at the cursor.  hi: the last bin of the union.
+struct Row {
+    u64 cur = 0, end = 0, rc = 0, keys = 0, counts = 0;
+    uint32_t next = NO_BIN, hi = 0;
+    bool outside = false;
+    // (lane < the list's n)  row r of handle h; a row outside its block marks the whole entry empty (settle)
+    __device__ __forceinline__ void open(const KeptRec h, uint32_t r)
+    {
+        const uint32_t lr = r - h.first;
+        if (r < h.first || lr >= h.nrows) {
+            outside = true;
+        } else {
+            const gu64 offsets = (gu64)h.block, row_count = offsets + (size_t)h.nrows + 1;
+            cur = offsets[lr];
+            end = offsets[(size_t)lr + 1];
+            rc = row_count[lr];
+            counts = h.block + 8 * (2 * (u64)h.nrows + 1);
+            keys = counts + 8 * h.cells;
+            if (end > h.cells || cur > end) cur = end = 0; // (never: lh_keep made them)
+        }
+    }
+    // (the whole wave)  A row outside the block of ANY handle is empty in all; the first and the last bin of each segment
+    __device__ __forceinline__ void settle()
+    {
+        if (__builtin_amdgcn_ballot_w64(outside)) { // wave-uniform
+            cur = end = 0;
+            rc = 0;
+        }
+        uint32_t last = 0;
+        if (end > cur) {
+            next = bin_of(((gkeys)keys)[cur]);
+            last = bin_of(((gkeys)keys)[end - 1]);
+        }
+        hi = wave_max_u32(last);
+    }
+};
+
+// The turns over a row's tiles (the tile is zero on entry, and again on return): the start of each, the scatter of every
+// handle's run inside it, then -- wave 0 of the NW that share the tile -- the ascending walk, 256 bins a step, which hands
+// step(C, base) the lane's four summed cells of bins base + 4 * lane .. + 3 and puts zeros back.  Every wave of a workgroup
+// takes the same turns: the state below is the same in all.  w: which of the NW scatterers this wave is; n: the handles.
+template <int NW, class Step>
+__device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t lane, uint32_t w, Step step)
+{
+    tile_sync<NW>(); // the tile is zero
+    for (uint32_t from = 0;;) {
+        if (from) { // the first entry at or above `from`
+            u64 a = row.cur, b = row.end;
+            while (a < b) {
+                const u64 mid = a + (b - a) / 2;
+                if (bin_of(((gkeys)row.keys)[mid]) < from) a = mid + 1;
+                else b = mid;
+            }
+            row.cur = a;
+            row.next = row.cur < row.end ? bin_of(((gkeys)row.keys)[row.cur]) : NO_BIN;
+        }
+        const uint32_t least = ~wave_max_u32(~row.next);
+        if (least == NO_BIN) break;
+        const uint32_t t0 = least & ~3u, tend = t0 + KEPT_TILE;
+        // ---- scatter: handle i's run inside the tile, 64 entries a turn
+        for (uint32_t i = w; i < n; i += NW) { // wave-uniform
+            u64 c = readlane_u64(row.cur, i);
+            const u64 e = readlane_u64(row.end, i);
+            const gkeys kp = (gkeys)readlane_u64(row.keys, i);
+            const gu64 cp = (gu64)readlane_u64(row.counts, i);
+            while (c < e) {
+                const u64 idx = c + lane;
+                bool in = false;
+                if (idx < e) {
+                    const uint32_t at = bin_of(kp[idx]) - t0;
+                    if (at < KEPT_TILE) {
+                        in = true;
+                        atomicAdd(&tile[at], cp[idx]);
+                    }
+                }
+                const uint32_t took = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
+                c += took;
+                if (took < 64) break;
+            }
+        }
+        tile_sync<NW>();
+        // ---- walk, and zeros back
+        if (w == 0) {
+            const uint32_t wend = min(tend - 1, row.hi);
+            for (uint32_t base = t0; base <= wend; base += STEP) {
+                const uint32_t at = base + 4 * lane - t0;
+                u64 C[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    C[k] = tile[at + k];
+                    tile[at + k] = 0;
+                }
+                step(C, base);
+            }
+        }
+        tile_sync<NW>();
+        if (tend > row.hi) break; // nothing lies beyond
+        from = tend;
+    }
+}
+
+// the tile (of the kernel's s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE]), the scatterer and the entry of a call that this wave
+// works on, for the two shapes
+template <int NW> struct Seat {
+    uint32_t lane, w, m;
+    u64 *tile;
+    __device__ __forceinline__ Seat(u64 (*s_tile)[KEPT_TILE])
+    {
+        const uint32_t wave = threadIdx.x >> 6;
+        lane = threadIdx.x & 63;
+        w = NW == 1 ? 0u : wave;
+        m = NW == 1 ? blockIdx.x * ROW_WAVES + wave : blockIdx.x;
+        tile = s_tile[NW == 1 ? wave : 0];
+    }
+    __device__ __forceinline__ void clear() const
+    {
+        for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < KEPT_TILE; i += NW * 64) tile[i] = 0;
+    }
+};
+
 // IDS: entry m reads row ids[m] (an absolute row number, as `first` is); otherwise row first + m.  A row outside the block
 // of ANY handle gives the empty entry, and nothing is read for it.
 template <bool IDS, int NW>
@@ -213,115 +348,36 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
                                                                           const uint32_t *__restrict__ ids)
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t m = NW == 1 ? blockIdx.x * ROW_WAVES + wave : blockIdx.x;
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
     if (m >= nmetrics) return; // uniform for all that share a tile
-    u64 *tile = s_tile[NW == 1 ? wave : 0];
-    const uint32_t w = NW == 1 ? 0u : wave; // which of the NW scatterers of the tile this wave is
-    for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < KEPT_TILE; i += NW * 64) tile[i] = 0;
+    at.clear();
 
     uint32_t r;
     if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
     else r = first + m;
-    // ---- lane i opens handle i
-    u64 beg = 0, end = 0, rc = 0, keys = 0, counts = 0;
-    bool outside = false;
-    if (lane < s.n) {
-        const KeptRec h = s.h[lane];
-        const uint32_t lr = r - h.first;
-        if (r < h.first || lr >= h.nrows) {
-            outside = true;
-        } else {
-            const gu64 offsets = (gu64)h.block, row_count = offsets + (size_t)h.nrows + 1;
-            beg = offsets[lr];
-            end = offsets[(size_t)lr + 1];
-            rc = row_count[lr];
-            counts = h.block + 8 * (2 * (u64)h.nrows + 1);
-            keys = counts + 8 * h.cells;
-            if (end > h.cells || beg > end) beg = end = 0; // (never: lh_keep made them)
-        }
-    }
-    if (__builtin_amdgcn_ballot_w64(outside)) { // wave-uniform
-        beg = end = 0;
-        rc = 0;
-    }
-    uint32_t next = NO_BIN, last = 0; // the bin at the cursor / the segment's last bin
-    if (end > beg) {
-        next = bin_of(((gkeys)keys)[beg]);
-        last = bin_of(((gkeys)keys)[end - 1]);
-    }
-    const u64 total = readlane_u64(wave_scan_incl_u64(rc), 63);
-    const u64 present = __builtin_amdgcn_ballot_w64(end > beg);
-    const uint32_t hi = wave_max_u32(last);
-    u64 cur = beg;
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], r);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    const u64 present = __builtin_amdgcn_ballot_w64(row.end > row.cur);
+    const uint32_t hi = row.hi;
 
     double ps = 0.0;
     uint32_t occ = 0;
     Open pct; // lane i < np: percentile i
     if (total) {                       // uniform
         pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
-        tile_sync<NW>();                                                       // the tile is zero
-        for (uint32_t from = 0;;) { // (every wave of a workgroup takes the same turns: the state below is the same in all)
-            if (from) { // the first entry at or above `from`
-                u64 a = cur, b = end;
-                while (a < b) {
-                    const u64 mid = a + (b - a) / 2;
-                    if (bin_of(((gkeys)keys)[mid]) < from) a = mid + 1;
-                    else b = mid;
-                }
-                cur = a;
-                next = cur < end ? bin_of(((gkeys)keys)[cur]) : NO_BIN;
-            }
-            const uint32_t least = ~wave_max_u32(~next);
-            if (least == NO_BIN) break;
-            const uint32_t t0 = least & ~3u, tend = t0 + KEPT_TILE;
-            // ---- scatter: handle i's run inside the tile, 64 entries a turn
-            for (uint32_t i = w; i < s.n; i += NW) { // wave-uniform
-                u64 c = readlane_u64(cur, i);
-                const u64 e = readlane_u64(end, i);
-                const gkeys kp = (gkeys)readlane_u64(keys, i);
-                const gu64 cp = (gu64)readlane_u64(counts, i);
-                while (c < e) {
-                    const u64 idx = c + lane;
-                    bool in = false;
-                    if (idx < e) {
-                        const uint32_t at = bin_of(kp[idx]) - t0;
-                        if (at < KEPT_TILE) {
-                            in = true;
-                            atomicAdd(&tile[at], cp[idx]);
-                        }
-                    }
-                    const uint32_t took = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
-                    c += took;
-                    if (took < 64) break;
-                }
-            }
-            tile_sync<NW>();
-            // ---- walk, and zeros back
-            if (w == 0) {
-                const uint32_t wend = min(tend - 1, hi);
-                for (uint32_t base = t0; base <= wend; base += STEP) {
-                    const uint32_t b0 = base + 4 * lane, at = b0 - t0;
-                    u64 C[4];
-                    double d[4], t[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        C[k] = tile[at + k];
-                        tile[at + k] = 0;
-                    }
-                    load4_values(D, b0, hi, d);
-                    const u64 tc = sum4(C);
-                    ps += terms4(C, d, t);
-                    occ += occupied4(C);
-                    pct.step(C, tc, base, lane);
-                }
-            }
-            tile_sync<NW>();
-            if (tend > hi) break; // nothing lies beyond
-            from = tend;
-        }
+        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+            double d[4], t[4];
+            load4_values(D, base + 4 * lane, hi, d);
+            const u64 tc = sum4(C);
+            ps += terms4(C, d, t);
+            occ += occupied4(C);
+            pct.step(C, tc, base, lane);
+        });
     }
-    if (w != 0) return;
+    if (at.w != 0) return;
     const double sum = readlane_f64(wave_scan_incl_f64(ps), 63);
     const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl_u32(occ), 63);
     if (lane == 0) {
@@ -333,6 +389,65 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
     if (lane < np) {
         store_pct(o.pkeys, o.pvalid, (size_t)m * np + lane, pct.found);
     }
+}
+
+// ---- lh_kept_merge ----------------------------------------------------------------------------------------------------------
+// The two passes around k_keep_scan, rows [first, first + nrows) of every handle of the list (the host checked that each
+// holds them), in the reader's two shapes.  count: nnz[m + 1] = the non-zero cells of the union -- a sum that wrapped to 0 is
+// none --, row_count[m] = the wrapping sum of the handles' own row_count entries (which is the wrapping sum of the cells).
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_count(const KeptList s, uint32_t nrows, uint32_t first,
+                                                                          u64 *__restrict__ nnz, u64 *__restrict__ row_count)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nrows) return; // uniform for all that share a tile
+    at.clear();
+    Row row;
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    uint32_t occ = 0;
+    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t) { occ += occupied4(C); });
+    if (at.w != 0) return;
+    occ = wave_scan_incl_u32(occ);
+    if (lane == 63) {
+        nnz[(size_t)m + 1] = occ;
+        row_count[m] = total;
+    }
+}
+
+// fill: the same turns; each step's non-zero cells to keys / counts[off[m] .. off[m + 1]), ascending by bin, as k_keep_fill
+// places them.  (Nothing is stored at or beyond off[m + 1].)
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const KeptList s, uint32_t nrows, uint32_t first,
+                                                                         const u64 *__restrict__ off, int16_t *__restrict__ keys,
+                                                                         u64 *__restrict__ counts)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nrows) return; // uniform for all that share a tile
+    u64 to = off[m];
+    const u64 lim = off[(size_t)m + 1];
+    if (to >= lim) return; // (the same)
+    at.clear();
+    Row row;
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        const uint32_t b0 = base + 4 * lane, n = occupied4(C), inc = wave_scan_incl_u32(n);
+        u64 pos = to + (inc - n);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (C[k] && pos < lim) {
+                keys[pos] = (int16_t)bin_to_key(b0 + k);
+                counts[pos] = C[k];
+                pos++;
+            }
+        to += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+    });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -378,21 +493,19 @@ namespace {
 
 typedef lh::beside::Source<KeptCtx> KeptSource;
 
-// (cx->mu held, the device current)
-int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
+// (cx->mu held, the device current)  The making of a handle of rows [first, first + nrows) on `st`, for lh_keep and
+// lh_kept_merge: count(off, row_count) enqueues the pass that leaves nnz in off[1 ..] and the rows' sums; then the scan, the
+// totals brought back, the allocation; fill(off, keys, counts) enqueues the pass that places the cells -- unless there are
+// none.  Returns when the handle is complete.  After a failure the caller waits for `st` and frees k->block.
+template <class Count, class Fill>
+int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k, Count count, Fill fill)
 {
-    KeptCtx *cx = q.cx;
-    const hipStream_t st = q.stream;
     const size_t head = 2 * (size_t)nrows + 1; // offsets and row_count, in uint64
     int rc = grow_device(cx->d_tmp, cx->tmp_cap, head + 2, 4096);
     if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 2, 2);
     if (rc) return rc;
     u64 *off = cx->d_tmp, *row_count = off + nrows + 1, *totals = off + head;
-    const uint32_t *ranges = ranges_from(q, first);
-    const dim3 grid((nrows + ROW_WAVES - 1) / ROW_WAVES), block(ROW_BLOCK);
-    with_cells(q, first, [&](auto c) {
-        hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, row_count);
-    });
+    count(off, row_count);
     hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, row_count, nrows, totals);
     LH_BESIDE_CHK(hipGetLastError());
     LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
@@ -408,14 +521,61 @@ int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
     LH_BESIDE_CHK(hipMemcpyAsync(k->block, off, head * sizeof(u64), hipMemcpyDeviceToDevice, st));
     if (cells) {
         u64 *counts = k->block + head;
-        int16_t *keys = reinterpret_cast<int16_t *>(counts + cells);
-        with_cells(q, first, [&](auto c) {
-            hipLaunchKernelGGL((k_keep_fill<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, keys, counts);
-        });
+        fill(off, reinterpret_cast<int16_t *>(counts + cells), counts);
         LH_BESIDE_CHK(hipGetLastError());
     }
     LH_BESIDE_CHK(hipStreamSynchronize(st));
     return LH_OK;
+}
+
+// (cx->mu held, the device current)  lh_keep: from the snapshot's cells, on its stream, a wave per row
+int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
+{
+    const hipStream_t st = q.stream;
+    const uint32_t *ranges = ranges_from(q, first);
+    const dim3 grid((nrows + ROW_WAVES - 1) / ROW_WAVES), block(ROW_BLOCK);
+    return make(
+        q.cx, st, first, nrows, k,
+        [&](u64 *off, u64 *row_count) {
+            with_cells(q, first, [&](auto c) {
+                hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, row_count);
+            });
+        },
+        [&](const u64 *off, int16_t *keys, u64 *counts) {
+            with_cells(q, first, [&](auto c) {
+                hipLaunchKernelGGL((k_keep_fill<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, keys, counts);
+            });
+        });
+}
+
+// the list as the kernels take it
+KeptList list_of(lh_kept *const *kept, size_t nkept)
+{
+    KeptList s;
+    s.n = (uint32_t)nkept;
+    for (size_t i = 0; i < LH_MAX_KEPT; i++) {
+        const lh_kept *k = i < nkept ? kept[i] : nullptr;
+        s.h[i] = KeptRec{k ? (u64)(uintptr_t)k->block : 0, k ? k->cells : 0, k ? k->first : 0, k ? k->nrows : 0};
+    }
+    return s;
+}
+
+// (cx->mu held, the device current)  lh_kept_merge: from the handles' own arrays, on the caller's stream, in the shape the
+// reader would take for as many rows
+int merge(KeptCtx *cx, lh_kept *const *kept, size_t nkept, uint32_t first, uint32_t nrows, hipStream_t st, lh_kept *k)
+{
+    const KeptList s = list_of(kept, nkept);
+    const RowShape sh = row_shape(nrows, g_wave_from.load(std::memory_order_relaxed));
+    return make(
+        cx, st, first, nrows, k,
+        [&](u64 *off, u64 *row_count) {
+            if (sh.wave) hipLaunchKernelGGL((k_merge_count<1>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
+            else hipLaunchKernelGGL((k_merge_count<WG_WAVES>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
+        },
+        [&](const u64 *off, int16_t *keys, u64 *counts) {
+            if (sh.wave) hipLaunchKernelGGL((k_merge_fill<1>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
+            else hipLaunchKernelGGL((k_merge_fill<WG_WAVES>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
+        });
 }
 
 // (cx->mu held) one user less of `e`
@@ -479,12 +639,7 @@ int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, 
     if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
     if (rc) return rc;
     const PctArgs pa = pct_args(p, np);
-    KeptList s;
-    s.n = (uint32_t)nkept;
-    for (size_t i = 0; i < LH_MAX_KEPT; i++) {
-        const lh_kept *k = i < nkept ? kept[i] : nullptr;
-        s.h[i] = KeptRec{k ? (u64)(uintptr_t)k->block : 0, k ? k->cells : 0, k ? k->first : 0, k ? k->nrows : 0};
-    }
+    const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const double *D = cx->d_table;
     const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
@@ -562,6 +717,44 @@ int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_
         rc = keep(q, first, (uint32_t)nmetrics, k);
         if (rc) {
             if (hipStreamSynchronize(q.stream) != hipSuccess) (void)hipGetLastError();
+            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+    }
+    if (rc) {
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return LH_OK;
+}
+
+int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream, lh_kept **out)
+{
+    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return LH_EINVAL;
+    for (size_t i = 0; i < nkept; i++)
+        if (!kept[i]) return LH_EINVAL;
+    if (flags != 0 || !out || nmetrics == 0) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE;
+    // ---- from here on the handles are looked at
+    const int device = kept[nkept - 1]->device;
+    for (size_t i = 0; i + 1 < nkept; i++)
+        if (kept[i]->device != device) return LH_EINVAL;
+    for (size_t i = 0; i < nkept; i++) // the block lies inside every handle's: lh_kept_across' rule
+        if (first < kept[i]->first || (u64)first + nmetrics > (u64)kept[i]->first + kept[i]->nrows) return LH_ERANGE;
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE;
+    lh_kept *k = new (std::nothrow) lh_kept;
+    if (!k) return LH_ENOMEM;
+    k->device = device;
+    k->cx = cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    { // the mutex for the whole call: no lh_kept_release frees an input under it (it only reads them: no hold)
+        std::lock_guard<std::mutex> g(cx->mu);
+        rc = hipSetDevice(device) == hipSuccess ? merge(cx, kept, nkept, first, (uint32_t)nmetrics, st, k) : LH_EDEVICE;
+        if (rc) {
+            (void)hipGetLastError();
+            if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
             if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
         }
     }

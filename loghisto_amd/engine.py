@@ -829,6 +829,23 @@ class Kept:
             res["pvals"] = np.where(res["pvalid"] != 0, self._table[bins], np.nan)
         return res
 
+    def merge(self, earlier=(), nmetrics: Optional[int] = None, first: Optional[int] = None, stream=None) -> "Kept":
+        """list(earlier) + [self] rolled up into ONE new Kept of metrics [first, first+nmetrics) (lh_kept_merge): per metric the
+        union of the handles' bins with their counts summed in 64 bits -- what Snapshot.keep would give had the samples arrived
+        in one interval.  A handle listed twice counts twice; every handle of the list must hold the block.  first=None: this
+        handle's first; nmetrics=None: up to the end of this handle's block.  The work goes on `stream` (a torch stream or a
+        raw handle; None: the null stream) and is complete on return; the new handle depends on none of the listed ones."""
+        kept = list(earlier) + [self]
+        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
+        if first is None:
+            first = self.info["first"]
+        if nmetrics is None:
+            nmetrics = self.info["first"] + self.info["nrows"] - first
+        h = C.c_void_p(0)
+        N.check(N.lib().lh_kept_merge(C.addressof(handles), len(kept), first, nmetrics, 0, _stream_handle(stream), C.byref(h)),
+                "lh_kept_merge")
+        return Kept(h, self._table)
+
     def close(self):
         """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
         if self._h is not None and self._h.value:
