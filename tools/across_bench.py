@@ -12,48 +12,26 @@ slowly moving scale) stay alive as K snapshots.  Reported, with the nine default
 Medians of --reps calls after --warmup, with the spread (min .. max).  One thing is asserted: the old route's fastest run
 is slower than the host form's slowest.  No other number is fixed in advance; the two ratios are recorded.  The results of the old route and of both shapes are compared before anything is written.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after
-a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/across_bench.py [--names 8192] [--k 8] [--pairs 2e7] [--reps 25] [--warmup 5] [--out profiles/across.txt]"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
-SHAPES = (("wave", 1), ("workgroup", 1 << 30))
+TOOL = "across_bench"
 MARK = "# ==== measured: tools/across_bench.py"
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"across_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
 
 
 def merge_listings(listings, M):
@@ -89,21 +67,16 @@ def main():
     assert 1 <= K <= N.MAX_ACROSS
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [MARK, f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/across_bench.py --names {M} --k {K} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             f"# {K} intervals of one engine of 32-bit cells (Zipf(1.0) names, lognormal values, each interval 2 % higher); us are "
-             "medians (min .. max) of the timed calls;", "# device forms: HIP events on the last snapshot's stream around the call(s); "
-             "host form and the old route: wall time"]
-
-    def row(name, ts, extra=""):
-        m, lo, hi = med(ts)
-        lines.append(f"{name:<78} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    rep = kit.Report(width=78)
+    row = rep.row
+    rep.lines += [MARK, *kit.header(TOOL, f"--names {M} --k {K} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  f"# {K} intervals of one engine of 32-bit cells (Zipf(1.0) names, lognormal values, each interval 2 % higher); us are "
+                  "medians (min .. max) of the timed calls;", "# device forms: HIP events on the last snapshot's stream around the call(s); "
+                  "host form and the old route: wall time"]
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=K + 2, num_lanes=1, lane_samples=1 << 16, cell_bits=32)
     snaps = []
-    with limit(420, "ingest"):
+    with kit.limit(420, "ingest", TOOL):
         for i in range(K):
             ids = bench.zipf_ids(n, M, 4000 + i)
             data = bench.make_samples(n, "lognormal", seed=40 + i)
@@ -116,54 +89,31 @@ def main():
     last = snaps[-1]
     xs = torch.cuda.ExternalStream(last.stream())
     widths = [s.device_cells()[2] for s in snaps]
-    lines.append(f"# {M} names, {K} snapshots of {n:g} samples each, cells of {widths} bytes")
+    rep.note(f"# {M} names, {K} snapshots of {n:g} samples each, cells of {widths} bytes")
     kinds = dict(count=torch.int64, sum=torch.float64, nbuckets=torch.int32, present_bits=torch.int32, pkeys=torch.int16,
                  pvalid=torch.uint8)
 
-    def timed_events(what, call):
-        with limit(120, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                call()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+    def events(what, call):
+        return kit.timed_events(xs, call, a.reps, a.warmup, what, 120, TOOL)
 
-    def timed_wall(what, call, reps, warmup=2, before=None, after=None):
-        with limit(420, what):
-            ts = []
-            for r in range(warmup + reps):
-                ctx = before() if before else None
-                t0 = time.perf_counter()
-                out = call(ctx) if before else call()
-                dt = (time.perf_counter() - t0) * 1e3
-                if after:
-                    out = after(ctx, out)
-                if r >= warmup:
-                    ts.append(dt)
-        return ts, out
+    def wall(what, call, reps, warmup=2, before=None, after=None):
+        return kit.timed_wall(call, reps, warmup, what, 420, TOOL, before, after)
 
     # ---- lh_across: the device form in both shapes, the host form
     prev = C.c_uint32(0)
     t, res = {}, {}
-    for shape, wave_from in SHAPES:
-        assert L.lh_tool_across_switch(wave_from, C.byref(prev)) == 0
+    for shape, _ in kit.shapes(L.lh_tool_across_switch):
         out = {k: torch.zeros((M, len(PCTS)) if k in ("pkeys", "pvalid") else (M,), dtype=d, device="cuda") for k, d in kinds.items()}
-        ts = timed_events(f"across {shape}", lambda: last.across(snaps[:-1], PCTS, M, out=out))
+        ts = events(f"across {shape}", lambda: last.across(snaps[:-1], PCTS, M, out=out))
         res[shape] = {k: v.cpu().numpy() for k, v in out.items()}
         t[shape] = row(f"across device form, {M} names x {K} snapshots, np = 9, a {shape} per row", ts)
-    assert L.lh_tool_across_switch(0, C.byref(prev)) == 0 and L.lh_tool_across_switch(0, C.byref(prev)) == 0   # prev: the default
+    assert L.lh_tool_across_switch(0, C.byref(prev)) == 0      # prev: the default (the shapes' loop has put it back)
     for k in ("count", "nbuckets", "present_bits", "pkeys", "pvalid"):
         assert np.array_equal(res["wave"][k], res["workgroup"][k]), k
     assert np.allclose(res["wave"]["sum"], res["workgroup"]["sum"], rtol=1e-9, atol=0)
     assert int(res["wave"]["count"].view(np.uint64).sum()) == K * n
     default = "wave" if M >= prev.value else "workgroup"
-    ts, host = timed_wall("across host form", lambda: last.across(snaps[:-1], PCTS, M), a.reps)
+    ts, host = wall("across host form", lambda: last.across(snaps[:-1], PCTS, M), a.reps)
     t["host"] = row(f"across host form (wall, with the derived arrays), {M} names x {K} snapshots, np = 9", ts)
     host_ts = ts
     assert np.array_equal(host["count"], res[default]["count"].view(np.uint64)) and np.array_equal(host["pkeys"], res[default]["pkeys"])
@@ -179,10 +129,10 @@ def main():
         spare.release()
         return out
 
-    ts, (old, ncells) = timed_wall("old route", old_route, a.host_reps, 1, before=eng.flip, after=release)
+    ts, (old, ncells) = wall("old route", old_route, a.host_reps, 1, before=eng.flip, after=release)
     old_ts = ts
     t["old"] = row(f"old route (wall): {K} x buckets_all + host merge + add_buckets_csr + extract_compact", ts)
-    lines.append(f"#   the old route moves {ncells} merged cells back to the device after pulling every snapshot's occupied cells out")
+    rep.note(f"#   the old route moves {ncells} merged cells back to the device after pulling every snapshot's occupied cells out")
     assert np.array_equal(old["count"], host["count"]) and np.array_equal(old["nbuckets"], host["nbuckets"])
     assert np.array_equal(old["pkeys"], host["pkeys"])
     assert np.allclose(old["sum"], host["sum"], rtol=1e-9, atol=0)
@@ -197,28 +147,19 @@ def main():
             s.spread(PCTS, M, out=sout)
 
     assert all(s.stream() == last.stream() for s in snaps)
-    t["spread"] = row(f"{K} x spread device form, one snapshot each, {M} names, np = 9 (for scale)", timed_events("K x spread", k_spreads))
+    t["spread"] = row(f"{K} x spread device form, one snapshot each, {M} names, np = 9 (for scale)", events("K x spread", k_spreads))
 
     # the acceptance: lh_across beats the old route by more than the run-to-run spread of either
     assert min(old_ts) > max(host_ts), (min(old_ts), max(host_ts))
-    lines.append(f"# old route / across host form: {t['old'] / t['host']:.1f} x      across device form ({default}) / {K} x spread: "
-                 f"{t[default] / t['spread']:.2f}")
-    print(lines[-1], flush=True)
+    rep.note(f"# old route / across host form: {t['old'] / t['host']:.1f} x      across device form ({default}) / {K} x spread: "
+             f"{t[default] / t['spread']:.2f}")
+    print(rep.lines[-1], flush=True)
     for s in snaps:
         s.release()
     eng.close()
 
     # the compile-time resource table at the top of the file stays; the measured part is replaced
-    head = []
-    if os.path.exists(a.out):
-        with open(a.out) as f:
-            for ln in f.read().splitlines():
-                if ln.startswith(MARK):
-                    break
-                head.append(ln)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(head + lines) + "\n")
+    rep.write(a.out, mark=MARK)
     return 0
 
 

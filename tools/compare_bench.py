@@ -9,42 +9,23 @@ reads in the shape the same switch value gives lh_spread, with the ratio; the ho
 256 .. 16 384 names, which is where a switch default would come from; and one name whose rows are filled over the full key
 range.  Medians of --reps calls after --warmup, with the spread (min .. max).  No number is fixed in advance.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after a
-step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started on
+the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/compare_bench.py [--names 65536] [--pairs 6e7] [--reps 25] [--warmup 5] [--out profiles/compare.txt]"""
 import argparse
-import contextlib
-import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
-SHAPES = (("wave", 1), ("workgroup", 1 << 30))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"compare_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
+TOOL = "compare_bench"
 
 
 def main():
@@ -59,21 +40,16 @@ def main():
     M, n = a.names, int(a.pairs)
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/compare_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# two intervals of one engine (Zipf(1.0) names, lognormal values, the second interval 10 % higher); us are medians "
-             "(min .. max) of the timed calls;", "# device forms: HIP events on cur's stream around the call(s); host form: wall time"]
-
-    def row(name, ts, extra=""):
-        m, lo, hi = statistics.median(ts), min(ts), max(ts)
-        lines.append(f"{name:<66} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    rep = kit.Report(width=66)
+    row = rep.row
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# two intervals of one engine (Zipf(1.0) names, lognormal values, the second interval 10 % higher); us are medians "
+                  "(min .. max) of the timed calls;", "# device forms: HIP events on cur's stream around the call(s); host form: wall time"]
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=3, num_lanes=1, lane_samples=1 << 16)
     snaps = []
     for k, scale in enumerate((1.0, 1.1)):
-        with limit(300, f"interval {k}"):
+        with kit.limit(300, f"interval {k}", TOOL):
             ids = bench.zipf_ids(n, M, 4000 + k)
             data = bench.make_samples(n, "lognormal", seed=40 + k)
             data.mul_(scale * torch.exp(3e-5 * ids.to(torch.float64)))
@@ -88,27 +64,16 @@ def main():
             torch.cuda.empty_cache()
     base, cur = snaps
     xs = torch.cuda.ExternalStream(cur.stream())
-    lines.append(f"# {M} names, {n:g} samples per interval, cells of {base.device_cells()[2]} and {cur.device_cells()[2]} bytes")
+    rep.note(f"# {M} names, {n:g} samples per interval, cells of {base.device_cells()[2]} and {cur.device_cells()[2]} bytes")
     kinds = dict(count_a=torch.int64, count_b=torch.int64, ks=torch.float64, key=torch.int16, below_a=torch.int64,
                  below_b=torch.int64, w1=torch.float64, shift=torch.float64)
 
-    def timed_events(what, call):
-        with limit(120, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                call()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+    def events(what, call):
+        return kit.timed_events(xs, call, a.reps, a.warmup, what, 120, TOOL)
 
     def compare_device(what, c, b, nmetrics):
         out = {k: torch.zeros((nmetrics,), dtype=t, device="cuda") for k, t in kinds.items()}
-        ts = timed_events(what, lambda: c.compare(b, nmetrics, out=out))
+        ts = events(what, lambda: c.compare(b, nmetrics, out=out))
         return ts, {k: v.cpu().numpy() for k, v in out.items()}
 
     def spread_reads(what, c, b, nmetrics):
@@ -120,25 +85,21 @@ def main():
             b.spread([], nmetrics, out=outs[0])
             c.spread([], nmetrics, out=outs[1])
         assert b.stream() == c.stream()
-        ts = timed_events(what, call)
+        ts = events(what, call)
         return ts, [o["count"].cpu().numpy().view(np.uint64) for o in outs]
 
     def both(c, b, nmetrics, indent=""):
         """lh_compare_device and the two spread reads in each shape, alternating; the integer outputs of the shapes agree"""
-        prev = C.c_uint32(0)
         res = {}
-        for shape, wave_from in SHAPES:
-            assert L.lh_tool_compare_switch(wave_from, C.byref(prev)) == 0
-            assert L.lh_tool_spread_switch(wave_from, C.byref(prev)) == 0
+        for shape, _ in kit.shapes(lambda w, prev: L.lh_tool_compare_switch(w, prev) or L.lh_tool_spread_switch(w, prev)):
             tc, res[shape] = compare_device(f"compare {shape} {nmetrics}", c, b, nmetrics)
             tr, counts = spread_reads(f"spread {shape} {nmetrics}", c, b, nmetrics)
             assert np.array_equal(counts[0], res[shape]["count_a"].view(np.uint64))
             assert np.array_equal(counts[1], res[shape]["count_b"].view(np.uint64))
             mc = row(f"{indent}compare device form, {nmetrics} names, a {shape} per row", tc)
             mr = row(f"{indent}  two moment-only spread reads, {nmetrics} names, a {shape} per row", tr)
-            lines.append(f"{indent}  ratio compare / two spread reads: {mc / mr:.2f}")
-            print(lines[-1], flush=True)
-        assert L.lh_tool_compare_switch(0, C.byref(prev)) == 0 and L.lh_tool_spread_switch(0, C.byref(prev)) == 0
+            rep.note(f"{indent}  ratio compare / two spread reads: {mc / mr:.2f}")
+            print(rep.lines[-1], flush=True)
         for k in ("count_a", "count_b", "ks", "key", "below_a", "below_b"):
             assert res["wave"][k].tobytes() == res["workgroup"][k].tobytes(), k
         for k in ("w1", "shift"):                               # the shapes associate the sums differently
@@ -148,19 +109,13 @@ def main():
     full = both(cur, base, M)
     assert int(full["count_a"].view(np.uint64).sum()) == n and int(full["count_b"].view(np.uint64).sum()) == n
     ok = ~np.isnan(full["shift"])
-    lines.append(f"# names with samples in both intervals: {int(ok.sum())}; median shift {np.median(full['shift'][ok]):.2f} buckets "
-                 f"(a scale of 1.1 is 100 ln 1.1 = 9.53 buckets where 1 + v ~ v), median ks {np.median(full['ks'][ok]):.4f}")
-    with limit(300, "host form"):
-        ts = []
-        for r in range(2 + a.reps):
-            t0 = time.perf_counter()
-            host = cur.compare(base, M)
-            if r >= 2:
-                ts.append((time.perf_counter() - t0) * 1e3)
+    rep.note(f"# names with samples in both intervals: {int(ok.sum())}; median shift {np.median(full['shift'][ok]):.2f} buckets "
+             f"(a scale of 1.1 is 100 ln 1.1 = 9.53 buckets where 1 + v ~ v), median ks {np.median(full['ks'][ok]):.4f}")
+    ts, host = kit.timed_wall(lambda: cur.compare(base, M), a.reps, 2, "host form", 300, TOOL)
     row(f"compare host form (wall, pinned results), {M} names", ts)
     for k in ("count_a", "count_b", "ks", "key", "below_a", "below_b"):
         assert host[k].tobytes() == full[k].tobytes(), k
-    lines.append("# both kernel shapes over the first names (Zipf: the widest windows):")
+    rep.note("# both kernel shapes over the first names (Zipf: the widest windows):")
     for k in (256, 1024, 2048, 4096, 16384):
         if k < M:
             part = both(cur, base, k, indent="  ")
@@ -170,23 +125,21 @@ def main():
     eng.close()
 
     # ---- one name, both rows filled over the full key range (64-bit cells; 512 KiB each)
-    with limit(120, "one full row"):
+    with kit.limit(120, "one full row", TOOL):     # (two snapshots of one engine: not benchkit.full_row_snapshot)
         one = loghisto_amd.Engine(device=0, max_metrics=1, num_buffers=3, num_lanes=1, lane_samples=1 << 16)
         base, cur = one.flip(), one.flip()
         keys = np.arange(-32768, 32768, dtype=np.int16)
         base.add_buckets(np.zeros(keys.size, dtype=np.uint32), keys, np.full(keys.size, 3, dtype=np.uint64))
         cur.add_buckets(np.zeros(keys.size, dtype=np.uint32), keys, (1 + np.arange(keys.size) % 5).astype(np.uint64))
         xs = torch.cuda.ExternalStream(cur.stream())
-    lines.append("# one name, all 65 536 cells occupied on both sides, device form:")
+    rep.note("# one name, all 65 536 cells occupied on both sides, device form:")
     got = both(cur, base, 1, indent="  ")
     assert int(got["count_a"][0]) == 3 * 65536 and int(got["count_b"][0]) == int((1 + np.arange(65536) % 5).sum())
     base.release()
     cur.release()
     one.close()
 
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.write(a.out)
     return 0
 
 

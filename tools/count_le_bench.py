@@ -11,46 +11,24 @@ spread (min .. max).  TWO conditions, both relative and taken in this run:
   host form at nb = 9   <= 2 x extract_compact's wall median
   device form at nb = 9 <=     extract_compact's wall median
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU
-after a step that hung).
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is
+started on the GPU after a step that hung).
 usage: python tools/count_le_bench.py [--names 65536] [--pairs 1.25e8] [--reps 25] [--warmup 5] [--out profiles/count_le.txt]"""
 import argparse
-import contextlib
-import ctypes as C
 import os
-import signal
 import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-import loghisto_amd  # noqa: E402
+import benchkit as kit  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
+TOOL = "count_le_bench"
+
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"count_le_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
 
 
 def main():
@@ -66,139 +44,87 @@ def main():
     M, n = a.names, int(a.pairs)
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/count_le_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
-             "(min .. max) of the timed calls;", "# device form: HIP events on the snapshot's stream around the call; "
-             "host form, extract_compact and buckets_all: wall time"]
+    rep = kit.Report(width=58)
+    row = rep.row
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
+                  "(min .. max) of the timed calls;", "# device form: HIP events on the snapshot's stream around the call; "
+                  "host form, extract_compact and buckets_all: wall time"]
 
-    def row(name, ts, extra=""):
-        m, lo, hi = med(ts)
-        lines.append(f"{name:<58} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    def quantiles(data):
+        return torch.quantile(data[:1_000_000], torch.linspace(0.02, 0.999, 64, dtype=torch.float64, device=data.device)).cpu().numpy()
 
-    with limit(240, "inputs"):
-        ids = bench.zipf_ids(n, M, 4000)
-        data = bench.make_samples(n, "lognormal", seed=40)
-        data.mul_(torch.exp(3e-5 * ids.to(torch.float64)))
-        q = torch.quantile(data[:1_000_000], torch.linspace(0.02, 0.999, 64, dtype=torch.float64, device=data.device)).cpu().numpy()
-        bi, bd = bench.OwnBuffer(ids), bench.OwnBuffer(data)
-        ids, data = bi.tensor, bd.tensor
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize()
+    eng, snap, q = kit.c4_slice(M, n, TOOL, look=quantiles)
     bounds = {1: q[31:32].copy(), 9: q[3::7][:9].copy(), 64: q.copy()}        # thresholds inside the stream's own range
-    eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-    with limit(240, "ingest"):
-        eng.submit_pairs_device(ids, data, n)
-        snap = eng.flip()
-        torch.cuda.synchronize()
-    bi.free()
-    bd.free()
-    del ids, data
-    torch.cuda.empty_cache()
     xs = torch.cuda.ExternalStream(snap.stream())
     cells = snap.device_cells()
-    lines.append(f"# S: {M} names, {n:g} samples, cells of {cells[2]} bytes")
+    rep.note(f"# S: {M} names, {n:g} samples, cells of {cells[2]} bytes")
 
-    call_ms = []          # wall time of the last timed_device's calls themselves (the device form returns after enqueueing)
+    call_ms = []          # wall time of the last count_le_device's calls themselves (the device form returns after enqueueing)
 
-    def timed_device(what, b, nmetrics, reps=None, warmup=None):
-        reps, warmup = a.reps if reps is None else reps, a.warmup if warmup is None else warmup
-        nb = b.shape[-1]
-        with limit(120, what):
-            cum = torch.zeros((nmetrics, nb), dtype=torch.int64, device="cuda")
-            total = torch.zeros((nmetrics,), dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            ts = []
-            call_ms.clear()
-            for r in range(warmup + reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                t0 = time.perf_counter()
-                snap.count_le(b, nmetrics, out=(cum, total))
-                t1 = time.perf_counter()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= warmup:
-                    ts.append(e0.elapsed_time(e1))
-                    call_ms.append((t1 - t0) * 1e3)
+    def count_le_device(what, b, nmetrics):
+        cum = torch.zeros((nmetrics, b.shape[-1]), dtype=torch.int64, device="cuda")
+        total = torch.zeros((nmetrics,), dtype=torch.int64, device="cuda")
+        ts, call_ms[:] = kit.timed_events(xs, lambda: snap.count_le(b, nmetrics, out=(cum, total)), a.reps, a.warmup, what, 120, TOOL,
+                                          wall=True)
         return ts, cum, total
 
-    def timed_wall(what, call, reps, warmup=2):
-        with limit(240, what):
-            ts = []
-            for r in range(warmup + reps):
-                t0 = time.perf_counter()
-                out = call()
-                if r >= warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-        return ts, out
+    def wall(what, call, reps, warmup=2):
+        return kit.timed_wall(call, reps, warmup, what, 240, TOOL)
 
     # ---- the whole snapshot
     dev = {}
     for nb in (1, 9, 64):
-        ts, cum, total = timed_device(f"device nb={nb}", bounds[nb], M)
+        ts, cum, total = count_le_device(f"device nb={nb}", bounds[nb], M)
         dev[nb] = row(f"count_le device form, {M} names, nb = {nb} shared", ts,
                       f"  calling thread inside the call {statistics.median(call_ms) * 1e3:.1f} us")
         if nb == 9:
             d_cum9, d_total9 = cum.cpu().numpy().view(np.uint64), total.cpu().numpy().view(np.uint64)
     per = np.sort(np.stack([bounds[9][2] * (1.0 + 1e-5 * np.arange(M)), bounds[9][6] * (1.0 + 1e-5 * np.arange(M))], axis=1), axis=1)
-    row(f"count_le device form, {M} names, nb = 2 per metric", timed_device("device per-metric", per, M)[0],
+    row(f"count_le device form, {M} names, nb = 2 per metric", count_le_device("device per-metric", per, M)[0],
         f"  of which the calling thread is inside the call (copies {per.nbytes:,d} B of bounds) {statistics.median(call_ms) * 1e3:.1f} us")
-    ts, host9 = timed_wall("host nb=9", lambda: snap.count_le(bounds[9], M), a.reps)
+    ts, host9 = wall("host nb=9", lambda: snap.count_le(bounds[9], M), a.reps)
     host_ms = row(f"count_le host form (wall), {M} names, nb = 9 shared", ts)
     assert np.array_equal(host9["cum"], d_cum9) and np.array_equal(host9["total"], d_total9)
     assert int(host9["total"].sum()) == n and np.all(host9["cum"][:, -1] <= host9["total"])
-    ts, ex = timed_wall("extract_compact", lambda: snap.extract_compact(PCTS, M), a.reps)
+    ts, ex = wall("extract_compact", lambda: snap.extract_compact(PCTS, M), a.reps)
     ex_ms = row(f"extract_compact (wall), {M} names, 9 percentiles", ts)
     assert np.array_equal(ex["count"], host9["total"])
-    ts, S = timed_wall("buckets_all", lambda: snap.buckets_all(M), a.host_reps, 1)
+    ts, S = wall("buckets_all", lambda: snap.buckets_all(M), a.host_reps, 1)
     row(f"buckets_all (wall), {M} names, {S[1].size:,d} occupied cells", ts)
 
     # ---- where a row gets a wave and where a workgroup: the first names of S (Zipf: the widest windows) in both shapes
-    prev = C.c_uint32(0)
-    lines.append("# both kernel shapes, device form, nb = 9 shared, over the first names of S:")
+    rep.note("# both kernel shapes, device form, nb = 9 shared, over the first names of S:")
     for k in (256, 1024, 2048, 4096, 16384):
         if k > M:
             continue
         t = {}
-        for shape, wave_from in (("wave", 1), ("workgroup", 1 << 30)):
-            assert L.lh_tool_count_le_switch(wave_from, C.byref(prev)) == 0
-            ts, cum, _ = timed_device(f"{shape} {k}", bounds[9], k)
+        for shape, _ in kit.shapes(L.lh_tool_count_le_switch):
+            ts, cum, _ = count_le_device(f"{shape} {k}", bounds[9], k)
             assert np.array_equal(cum.cpu().numpy().view(np.uint64), d_cum9[:k])
             t[shape] = row(f"  {k:>6} names, a {shape} per row", ts)
-    assert L.lh_tool_count_le_switch(0, C.byref(prev)) == 0
     snap.release()
     eng.close()
 
     # ---- one name, its row filled over the full key range (64-bit cells; 512 KiB)
-    with limit(120, "one full row"):
-        one = loghisto_amd.Engine(device=0, max_metrics=1, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-        snap = one.flip()
-        keys = np.arange(-32768, 32768, dtype=np.int16)
-        snap.add_buckets(np.zeros(keys.size, dtype=np.uint32), keys, np.full(keys.size, 3, dtype=np.uint64))
-        xs = torch.cuda.ExternalStream(snap.stream())
-    lines.append("# one name, all 65 536 cells occupied, device form, nb = 9:")
+    one, snap = kit.full_row_snapshot(TOOL)
+    xs = torch.cuda.ExternalStream(snap.stream())
+    rep.note("# one name, all 65 536 cells occupied, device form, nb = 9:")
     b1 = np.array([-1e100, -1e3, -1.0, 0.0, 1.0, 1e3, 1e9, 1e100, np.inf])
-    for shape, wave_from in (("workgroup (default)", 0), ("wave", 1)):
-        assert L.lh_tool_count_le_switch(wave_from, C.byref(prev)) == 0
-        ts, cum, total = timed_device(f"one row {shape}", b1, 1)
+    for shape, _ in kit.shapes(L.lh_tool_count_le_switch, (("workgroup (default)", 0), ("wave", 1))):
+        ts, cum, total = count_le_device(f"one row {shape}", b1, 1)
         assert int(total[0]) == 3 * 65536 and int(cum[0, -1]) == 3 * 65536 and int(cum[0, 3]) == 3 * 32769
         row(f"  1 name, full span, a {shape} per row", ts)
-    assert L.lh_tool_count_le_switch(0, C.byref(prev)) == 0
     snap.release()
     one.close()
 
     c1, c2 = host_ms <= 2 * ex_ms, dev[9] <= ex_ms
-    lines.append(f"# condition 1: host form nb = 9 ({host_ms * 1e3:.1f} us) <= 2 x extract_compact wall ({ex_ms * 1e3:.1f} us): "
-                 f"{'MET' if c1 else 'NOT MET'}; ratio {host_ms / ex_ms:.2f}")
-    lines.append(f"# condition 2: device form nb = 9 ({dev[9] * 1e3:.1f} us) <= extract_compact wall ({ex_ms * 1e3:.1f} us): "
-                 f"{'MET' if c2 else 'NOT MET'}; ratio {dev[9] / ex_ms:.2f}")
-    print("\n".join(lines[-2:]), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.note(f"# condition 1: host form nb = 9 ({host_ms * 1e3:.1f} us) <= 2 x extract_compact wall ({ex_ms * 1e3:.1f} us): "
+             f"{'MET' if c1 else 'NOT MET'}; ratio {host_ms / ex_ms:.2f}")
+    rep.note(f"# condition 2: device form nb = 9 ({dev[9] * 1e3:.1f} us) <= extract_compact wall ({ex_ms * 1e3:.1f} us): "
+             f"{'MET' if c2 else 'NOT MET'}; ratio {dev[9] / ex_ms:.2f}")
+    print("\n".join(rep.lines[-2:]), flush=True)
+    rep.write(a.out)
     return 0
 
 

@@ -16,52 +16,32 @@ cells: what is left is the indirection).
 earlier build: that this change did not slow the shared kernels.  Its rows are APPENDED to the file.
 Medians of --reps calls after --warmup, with the spread (min .. max).
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after
-a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/ids_bench.py [--names 8192] [--pairs 1e7] [--reps 25] [--warmup 5] [--out profiles/ids.txt]"""
 import argparse
-import contextlib
 import os
-import signal
 import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
 BOUNDS = [10.0, 100.0, 1000.0]
 CALLS = 8                                                   # device-form calls between two events: the time is per call
+TOOL = "ids_bench"
 MARK = "# ==== measured: tools/ids_bench.py"
 BASE_MARK = "# ==== base forms only: tools/ids_bench.py --base-only"
 INT_OUT = dict(across=("count", "nbuckets", "present_bits", "pkeys", "pvalid"), count_le=("cum", "total"),
                spread=("count", "pkeys", "pvalid", "count_le"))
 FLOAT_OUT = dict(across=("sum",), count_le=(), spread=("sum", "m2", "sum_le"))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"ids_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
 
 
 def main():
@@ -83,21 +63,16 @@ def main():
     assert M >= 2048
     torch.cuda.set_device(0)
     mark = BASE_MARK if a.base_only else MARK
-    lines = [mark + (f" --lib {a.lib}" if a.lib else ""), f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/ids_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup} --host-reps {a.host_reps}: "
-             f"{torch.cuda.get_device_name(0)}",
-             "# two intervals of one engine of 32-bit cells (Zipf(1.0) names, lognormal values); us are medians (min .. max) of the "
-             "timed calls;", f"# device forms: HIP events on the snapshot's stream around {CALLS} calls, per call; host forms and routes: wall time"]
-
-    def row(name, ts, extra=""):
-        m, lo, hi = med(ts)
-        lines.append(f"{name:<92} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    rep = kit.Report(width=92)
+    row = rep.row
+    rep.lines += [mark + (f" --lib {a.lib}" if a.lib else ""),
+                  *kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup} --host-reps {a.host_reps}", torch),
+                  "# two intervals of one engine of 32-bit cells (Zipf(1.0) names, lognormal values); us are medians (min .. max) of the "
+                  "timed calls;", f"# device forms: HIP events on the snapshot's stream around {CALLS} calls, per call; host forms and routes: wall time"]
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=4, num_lanes=1, lane_samples=1 << 16, cell_bits=32)
     snaps = []
-    with limit(300, "ingest"):
+    with kit.limit(300, "ingest", TOOL):
         for i in range(2):
             ids = bench.zipf_ids(n, M, 4000 + i)
             data = bench.make_samples(n, "lognormal", seed=40 + i)
@@ -108,35 +83,16 @@ def main():
         torch.cuda.empty_cache()
     first, last = snaps
     xs = torch.cuda.ExternalStream(last.stream())
-    lines.append(f"# {M} names, 2 snapshots of {n:g} samples each, cells of {[s.device_cells()[2] for s in snaps]} bytes; across: both "
-                 f"snapshots, np = 9; count_le: the later one, {len(BOUNDS)} shared bounds; spread: the later one, np = 9")
+    rep.note(f"# {M} names, 2 snapshots of {n:g} samples each, cells of {[s.device_cells()[2] for s in snaps]} bytes; across: both "
+             f"snapshots, np = 9; count_le: the later one, {len(BOUNDS)} shared bounds; spread: the later one, np = 9")
     B = np.array(BOUNDS)
     np_ = len(PCTS)
 
-    def timed_events(what, call):
-        with limit(120, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                for _ in range(CALLS):
-                    call()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1) / CALLS)
-        return ts
+    def events(what, call):
+        return kit.timed_events(xs, call, a.reps, a.warmup, what, 120, TOOL, calls=CALLS)
 
-    def timed_wall(what, call, reps, warmup=2):
-        with limit(300, what):
-            ts = []
-            for r in range(warmup + reps):
-                t0 = time.perf_counter()
-                out = call()
-                if r >= warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-        return ts, out
+    def wall(what, call, reps, warmup=2):
+        return kit.timed_wall(call, reps, warmup, what, 300, TOOL)
 
     def device_out(unit, k):
         """the device form's output tensors for k entries"""
@@ -179,8 +135,8 @@ def main():
         for unit in units:
             for k in (M, 1024, 20):
                 out = device_out(unit, k)
-                ts = timed_events(f"{unit} base {k}", lambda: base(unit, k, 0, out))
-                row(f"{unit} base device form, rows [0, {k})", ts, f"   {med(ts)[0] * 1e3 / k:8.4f} us per row")
+                ts = events(f"{unit} base {k}", lambda: base(unit, k, 0, out))
+                row(f"{unit} base device form, rows [0, {k})", ts, f"   {kit.med(ts)[0] * 1e3 / k:8.4f} us per row")
     else:
         rng = np.random.default_rng(2024)
         for k in (20, 1024):
@@ -189,9 +145,9 @@ def main():
             idx = ids.astype(np.int64)
             for unit in units:
                 out = device_out(unit, k)
-                ts = timed_events(f"{unit}_ids device {k}", lambda: by_id(unit, d_ids, out))
-                t_dev = row(f"{unit}_ids device form, {k} ids of {M} names", ts, f"   {med(ts)[0] * 1e3 / k:8.4f} us per id")
-                ids_ts, got = timed_wall(f"{unit}_ids host {k}", lambda: by_id(unit, ids), a.host_reps)
+                ts = events(f"{unit}_ids device {k}", lambda: by_id(unit, d_ids, out))
+                t_dev = row(f"{unit}_ids device form, {k} ids of {M} names", ts, f"   {kit.med(ts)[0] * 1e3 / k:8.4f} us per id")
+                ids_ts, got = wall(f"{unit}_ids host {k}", lambda: by_id(unit, ids), a.host_reps)
                 row(f"{unit}_ids host form (wall), {k} ids of {M} names", ids_ts)
                 dev = ({f: v.cpu().numpy() for f, v in out.items()} if isinstance(out, dict)
                        else dict(cum=out[0].cpu().numpy(), total=out[1].cpu().numpy()))
@@ -201,9 +157,9 @@ def main():
                 def one_by_one():
                     return [base(unit, 1, int(r)) for r in ids]
 
-                r1_ts, rows1 = timed_wall(f"{unit} one-row calls {k}", one_by_one, a.host_reps if k <= 64 else 3, 1)
+                r1_ts, rows1 = wall(f"{unit} one-row calls {k}", one_by_one, a.host_reps if k <= 64 else 3, 1)
                 row(f"route 1 (wall): {k} one-row calls of {unit}'s host form", r1_ts)
-                r2_ts, whole = timed_wall(f"{unit} whole range", lambda: base(unit, M), a.host_reps)
+                r2_ts, whole = wall(f"{unit} whole range", lambda: base(unit, M), a.host_reps)
                 row(f"route 2 (wall): one call of {unit}'s host form over all {M} names", r2_ts)
                 same(unit, got, whole, idx, False, (unit, k, "whole range"))
                 for m, one in enumerate(rows1):                      # a one-row call takes the workgroup form, as k < 1 024 entries do
@@ -214,45 +170,39 @@ def main():
                     if not (max(ids_ts) < min(r1_ts) and max(ids_ts) < min(r2_ts)):   # asserted once everything is on file
                         missed.append(f"{unit}, 20 ids: the id-list host form's slowest call ({max(ids_ts) * 1e3:.1f} us) is not below "
                                       f"the fastest call of route 1 ({min(r1_ts) * 1e3:.1f} us) and of route 2 ({min(r2_ts) * 1e3:.1f} us)")
-                    lines.append(f"#   {unit}, 20 ids: the faster of today's routes is {best[0]} at {statistics.median(best[1]) * 1e3:.1f} us; "
-                                 f"the id-list host form takes {statistics.median(ids_ts) * 1e3:.1f} us "
-                                 f"({statistics.median(best[1]) / statistics.median(ids_ts):.1f} x), slowest call {max(ids_ts) * 1e3:.1f} "
-                                 f"against the routes' fastest {min(min(r1_ts), min(r2_ts)) * 1e3:.1f}")
-                    print(lines[-1], flush=True)
+                    rep.note(f"#   {unit}, 20 ids: the faster of today's routes is {best[0]} at {statistics.median(best[1]) * 1e3:.1f} us; "
+                             f"the id-list host form takes {statistics.median(ids_ts) * 1e3:.1f} us "
+                             f"({statistics.median(best[1]) / statistics.median(ids_ts):.1f} x), slowest call {max(ids_ts) * 1e3:.1f} "
+                             f"against the routes' fastest {min(min(r1_ts), min(r2_ts)) * 1e3:.1f}")
+                    print(rep.lines[-1], flush=True)
                 else:
                     # the indirection alone: rows [0, 1 024) by the base form, and the same rows as a shuffled id list
                     bout = device_out(unit, k)
-                    ts = timed_events(f"{unit} base contiguous {k}", lambda: base(unit, k, 0, bout))
+                    ts = events(f"{unit} base contiguous {k}", lambda: base(unit, k, 0, bout))
                     t_base = row(f"{unit} base device form, rows [0, {k}) (same kernel shape)", ts,
-                                 f"   {med(ts)[0] * 1e3 / k:8.4f} us per row")
+                                 f"   {kit.med(ts)[0] * 1e3 / k:8.4f} us per row")
                     perm = rng.permutation(k).astype(np.uint32)
                     d_perm = torch.from_numpy(perm.view(np.int32)).cuda()
                     pout = device_out(unit, k)
-                    ts = timed_events(f"{unit}_ids shuffled contiguous {k}", lambda: by_id(unit, d_perm, pout))
+                    ts = events(f"{unit}_ids shuffled contiguous {k}", lambda: by_id(unit, d_perm, pout))
                     t_perm = row(f"{unit}_ids device form, rows [0, {k}) as a shuffled id list", ts,
-                                 f"   {med(ts)[0] * 1e3 / k:8.4f} us per id")
+                                 f"   {kit.med(ts)[0] * 1e3 / k:8.4f} us per id")
                     b0, p0 = (bout, pout) if isinstance(bout, dict) else (dict(cum=bout[0], total=bout[1]), dict(cum=pout[0], total=pout[1]))
                     for f in INT_OUT[unit] + FLOAT_OUT[unit]:
                         assert p0[f].cpu().numpy().tobytes() == np.ascontiguousarray(b0[f].cpu().numpy()[perm.astype(np.int64)]).tobytes(), (unit, f)
-                    lines.append(f"#   {unit}, {k} rows: id list / contiguous = {t_perm / t_base:.3f} on the same rows; the drawn ids "
-                                 f"(lighter rows: Zipf names beyond the first {k}) take {t_dev / t_base:.3f} of it")
-                    print(lines[-1], flush=True)
+                    rep.note(f"#   {unit}, {k} rows: id list / contiguous = {t_perm / t_base:.3f} on the same rows; the drawn ids "
+                             f"(lighter rows: Zipf names beyond the first {k}) take {t_dev / t_base:.3f} of it")
+                    print(rep.lines[-1], flush=True)
     for s in snaps:
         s.release()
     eng.close()
 
     # the compile-time resource table at the top of the file stays; the measured part is replaced, base-only runs are appended
-    head = []
-    if os.path.exists(a.out):
+    if a.base_only and os.path.exists(a.out):               # (appended: everything the file holds stays, MARK's part too)
         with open(a.out) as f:
-            for ln in f.read().splitlines():
-                if ln.startswith(MARK) and not a.base_only:
-                    break
-                head.append(ln)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    lines += ["# MISSED: " + m for m in missed]
-    with open(a.out, "w") as f:
-        f.write("\n".join(head + lines) + "\n")
+            rep.lines[:0] = f.read().splitlines()
+    rep.lines += ["# MISSED: " + m for m in missed]
+    rep.write(a.out, mark=None if a.base_only else MARK)
     assert not missed, missed
     return 0
 

@@ -7,14 +7,11 @@ forms; beside them (a) submit_pairs_device of the pairs that produced S and (b) 
 Medians of --reps calls after --warmup, with the spread (min .. max).  THE timing condition: CSR device, K = 1, takes less
 device time than (a).
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU
-after a step that hung).
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is
+started on the GPU after a step that hung).
 usage: python tools/import_bench.py [--names 65536] [--pairs 1.25e8] [--reps 25] [--warmup 5] [--out profiles/import_cells.txt]"""
 import argparse
-import contextlib
 import os
-import signal
-import statistics
 import sys
 import time
 
@@ -22,27 +19,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
+from benchkit import limit, med  # noqa: E402
 
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"import_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
+TOOL = "import_bench"
 
 
 def main():
@@ -57,31 +38,24 @@ def main():
     a = ap.parse_args()
     M, n = a.names, int(a.pairs)
     torch.cuda.set_device(0)
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/import_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# S = cells of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); ms are medians "
-             "(min .. max) of the timed calls;", "# device forms: HIP events on the snapshot's stream around the call "
-             "(validation pre-pass, its read-back and the add); host forms and buckets_all: wall time"]
+    rep = kit.Report(width=34)
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# S = cells of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); ms are medians "
+                  "(min .. max) of the timed calls;", "# device forms: HIP events on the snapshot's stream around the call "
+                  "(validation pre-pass, its read-back and the add); host forms and buckets_all: wall time"]
 
-    def row(name, cells, nbytes, ts, extra=""):
+    def row(name, cells, nbytes, ts, extra=""):           # (its own columns: cells, bytes in, ms and cells/s)
         m, lo, hi = med(ts)
-        lines.append(f"{name:<34} cells {cells:>11,d}  bytes in {nbytes:>13,d}  ms {m:8.3f} ({lo:.3f} .. {hi:.3f})  "
-                     f"{cells / (m * 1e-3):.3e} cells/s{extra}")
-        print(lines[-1], flush=True)
+        rep.note(f"{name:<34} cells {cells:>11,d}  bytes in {nbytes:>13,d}  ms {m:8.3f} ({lo:.3f} .. {hi:.3f})  "
+                 f"{cells / (m * 1e-3):.3e} cells/s{extra}", echo=True)
 
-    with limit(240, "inputs"):
-        ids = bench.zipf_ids(n, M, 4000)
-        data = bench.make_samples(n, "lognormal", seed=40)
-        data.mul_(torch.exp(3e-5 * ids.to(torch.float64)))
-        bi, bd = bench.OwnBuffer(ids), bench.OwnBuffer(data)
-        ids, data = bi.tensor, bd.tensor
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize()
+    bi, bd, _ = kit.c4_inputs(M, n, TOOL)
+    ids, data = bi.tensor, bd.tensor
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
     stream = torch.cuda.Stream()
 
     # (a) the parent's path: the samples through submit_pairs_device; the last interval becomes S
-    with limit(240, "submit_pairs_device"):
+    with limit(240, "submit_pairs_device", TOOL):
         ts = []
         S = None
         for r in range(a.warmup + a.reps):
@@ -122,9 +96,10 @@ def main():
     d_ids8, d_keys8, d_counts8 = d_ids.repeat(K), d_keys.repeat(K), d_counts.repeat(K)    # S eight times over, source-major
     torch.cuda.synchronize()
 
-    def timed_device(what, call, reps, warmup, times_s):
-        """Every call adds into ONE empty snapshot: the first (untimed) call moves it to its wide store."""
-        with limit(240, what):
+    def timed_adds(what, call, reps, warmup, times_s):
+        """Every call adds into ONE empty snapshot: the first (untimed) call moves it to its wide store.  (Not
+        benchkit.timed_events: the step takes and checks the snapshot too, and the first call's own time is reported.)"""
+        with limit(240, what, TOOL):
             snap = eng.flip()
             xs = torch.cuda.ExternalStream(snap.stream())
             ts, first = [], None
@@ -144,15 +119,15 @@ def main():
             torch.cuda.synchronize()
         return ts, first
 
-    ts_csr, first_csr = timed_device("csr device", lambda s: s.add_buckets_csr(d_off, d_keys, d_counts), a.reps, a.warmup, 1)
+    ts_csr, first_csr = timed_adds("csr device", lambda s: s.add_buckets_csr(d_off, d_keys, d_counts), a.reps, a.warmup, 1)
     row("CSR device, K = 1", cells, cells * 10 + (M + 1) * 8, ts_csr, f"  first call on the narrow snapshot {first_csr:.3f} ms")
-    ts_coo, _ = timed_device("coo device", lambda s: s.add_buckets(d_ids, d_keys, d_counts), a.reps, a.warmup, 1)
+    ts_coo, _ = timed_adds("coo device", lambda s: s.add_buckets(d_ids, d_keys, d_counts), a.reps, a.warmup, 1)
     row("COO device, K = 1", cells, cells * 14, ts_coo)
-    ts_coo8, _ = timed_device("coo device x8", lambda s: s.add_buckets(d_ids8, d_keys8, d_counts8), a.reps, a.warmup, K)
+    ts_coo8, _ = timed_adds("coo device x8", lambda s: s.add_buckets(d_ids8, d_keys8, d_counts8), a.reps, a.warmup, K)
     row("COO device, K = 8 (S eight times)", cells * K, cells * K * 14, ts_coo8)
 
-    def timed_host(what, call):
-        with limit(240, what):
+    def timed_host(what, call):                             # (not benchkit.timed_wall: the step takes and checks the snapshot too)
+        with limit(240, what, TOOL):
             snap = eng.flip()
             ts = []
             for r in range(1 + a.host_reps):
@@ -171,15 +146,13 @@ def main():
     c, lo, hi = med(ts_csr)
     k1, k8 = med(ts_coo)[0], med(ts_coo8)[0]
     ok = hi < ingest_ms[1]                      # beyond the run-to-run spread: the slowest import against the fastest ingest
-    lines.append(f"# condition: CSR device K = 1 ({c:.3f} ms, max {hi:.3f}) < submit_pairs_device of the same interval "
-                 f"({ingest_ms[0]:.3f} ms, min {ingest_ms[1]:.3f}): {'MET' if c < ingest_ms[0] else 'NOT MET'}"
-                 f"{' (also max < min)' if ok else ''}; ratio {ingest_ms[0] / c:.2f} x")
-    lines.append(f"# CSR device / buckets_all wall: {c / med(tb)[0]:.3f};  COO K = 8 / K = 1: {k8 / k1:.2f} x "
-                 f"({'more' if k8 > 8 * k1 else 'not more'} than 8 x)")
-    print("\n".join(lines[-2:]), flush=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.note(f"# condition: CSR device K = 1 ({c:.3f} ms, max {hi:.3f}) < submit_pairs_device of the same interval "
+             f"({ingest_ms[0]:.3f} ms, min {ingest_ms[1]:.3f}): {'MET' if c < ingest_ms[0] else 'NOT MET'}"
+             f"{' (also max < min)' if ok else ''}; ratio {ingest_ms[0] / c:.2f} x")
+    rep.note(f"# CSR device / buckets_all wall: {c / med(tb)[0]:.3f};  COO K = 8 / K = 1: {k8 / k1:.2f} x "
+             f"({'more' if k8 > 8 * k1 else 'not more'} than 8 x)")
+    print("\n".join(rep.lines[-2:]), flush=True)
+    rep.write(a.out)
     return 0 if c < ingest_ms[0] else 1
 
 

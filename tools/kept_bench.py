@@ -15,14 +15,12 @@ Per name count: K intervals of one engine of 32-bit cells (Zipf names, lognormal
 Medians of the timed calls with the spread (min .. max).  No number is fixed in advance; the integer results of the new and
 the old route are compared before anything is written.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after
-a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/kept_bench.py [--names 1024,65536] [--k 60] [--pairs 2e6,2e7] [--reps 15] [--out profiles/kept.txt]"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
 import statistics
 import sys
 import time
@@ -32,45 +30,27 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
-SHAPES = (("wave", 1), ("workgroup", 1 << 30))
+TOOL = "kept_bench"
 NIDS = 20
 
 
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"kept_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def run(torch, a, M, n, lines):
+def run(torch, a, M, n, rep):
     L = N.lib()
     K = a.k
     dense_too = M <= 8192                                    # 16 dense buffers fit
     live = min(K, 14)                                        # an engine has at most 16 buffers: 14 live snapshots, the spare, ingest
 
-    def row(name, ts, extra=""):
-        m, lo, hi = statistics.median(ts), min(ts), max(ts)
-        lines.append(f"{name:<96} us {m * 1e3:11.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    row = rep.row
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=16 if dense_too else 3, num_lanes=1,
                               lane_samples=1 << 16, cell_bits=32)
     kept, snaps, keep_ms = [], [], []
-    with limit(600, "ingest and keep"):
+    with kit.limit(600, "ingest and keep", TOOL):
         ids = bench.zipf_ids(n, M, 4000)
         data = bench.make_samples(n, "lognormal", seed=40)
         for i in range(K):
@@ -90,10 +70,10 @@ def run(torch, a, M, n, lines):
         torch.cuda.empty_cache()
     info = [k.info for k in kept]
     dense = M * loghisto_amd.Snapshot.row_stride() * width
-    lines.append(f"# {M} names, {K} intervals of {n:g} samples each, cells of {width} bytes: a dense buffer is {dense / 2**20:.0f} MiB; a kept "
-                 f"interval holds {statistics.median(i['cells'] for i in info):.0f} cells in {statistics.median(i['bytes'] for i in info) / 2**20:.2f} MiB "
-                 f"(median; {sum(i['bytes'] for i in info) / 2**20:.1f} MiB for all {K}), 1 / {dense / statistics.median(i['bytes'] for i in info):.0f} of it")
-    print(lines[-1], flush=True)
+    rep.note(f"# {M} names, {K} intervals of {n:g} samples each, cells of {width} bytes: a dense buffer is {dense / 2**20:.0f} MiB; a kept "
+             f"interval holds {statistics.median(i['cells'] for i in info):.0f} cells in {statistics.median(i['bytes'] for i in info) / 2**20:.2f} MiB "
+             f"(median; {sum(i['bytes'] for i in info) / 2**20:.1f} MiB for all {K}), 1 / {dense / statistics.median(i['bytes'] for i in info):.0f} of it")
+    print(rep.lines[-1], flush=True)
     row(f"lh_keep (wall), {M} names, one interval (the first call allocates the unit's blocks: left out)", keep_ms[1:])
     assert all(i["samples"] == n for i in info)
 
@@ -104,58 +84,38 @@ def run(torch, a, M, n, lines):
     def outs(rows):
         return {k: torch.zeros((rows, len(PCTS)) if k in ("pkeys", "pvalid") else (rows,), dtype=d, device="cuda") for k, d in kinds.items()}
 
-    def timed_events(what, call, stream):
-        with limit(180, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                call()
-                e1.record(stream)
-                stream.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+    def events(what, call, stream):
+        return kit.timed_events(stream, call, a.reps, a.warmup, what, 180, TOOL)
 
-    def timed_wall(what, call, reps, warmup, before=None, after=None):
-        with limit(420, what):
-            ts = []
-            for r in range(warmup + reps):
-                ctx = before() if before else None
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = call(ctx) if before else call()
-                dt = (time.perf_counter() - t0) * 1e3
-                if after:
-                    after(ctx)
-                if r >= warmup:
-                    ts.append(dt)
-        return ts, out
+    def wall(what, call, reps, warmup, before=None, after=None):
+        return kit.timed_wall(call, reps, warmup, what, 420, TOOL, before, after, sync=torch.cuda.synchronize)
+
+    def release(spare, out):
+        spare.release()
+        return out
 
     rng = np.random.default_rng(20)
     ids20 = np.sort(rng.choice(min(M, 2000), NIDS, replace=False)).astype(np.uint32)   # busy names: the head of the Zipf order
     d_ids20 = torch.from_numpy(ids20.astype(np.int32)).cuda()
     prev = C.c_uint32(0)
     res, t = {}, {}
-    for shape, wave_from in SHAPES:
-        assert L.lh_tool_kept_switch(wave_from, C.byref(prev)) == 0
+    for shape, _ in kit.shapes(L.lh_tool_kept_switch):
         out = outs(M)
-        ts = timed_events(f"kept across {shape}", lambda: kept[-1].across(kept[:-1], PCTS, M, out=out, stream=st), st)
+        ts = events(f"kept across {shape}", lambda: kept[-1].across(kept[:-1], PCTS, M, out=out, stream=st), st)
         res[shape] = {k: v.cpu().numpy() for k, v in out.items()}
         t[shape] = row(f"lh_kept_across_device, {M} names x {K} handles, np = 9, a {shape} per row", ts)
         out20 = outs(NIDS)
-        ts = timed_events(f"kept across ids {shape}", lambda: kept[-1].across(kept[:-1], PCTS, ids=d_ids20, out=out20, stream=st), st)
+        ts = events(f"kept across ids {shape}", lambda: kept[-1].across(kept[:-1], PCTS, ids=d_ids20, out=out20, stream=st), st)
         res[shape + "20"] = {k: v.cpu().numpy() for k, v in out20.items()}
         t[shape + "20"] = row(f"lh_kept_across_ids_device, {NIDS} ids x {K} handles, np = 9, a {shape} per row", ts)
-    assert L.lh_tool_kept_switch(0, C.byref(prev)) == 0 and L.lh_tool_kept_switch(0, C.byref(prev)) == 0   # prev: the default
+    assert L.lh_tool_kept_switch(0, C.byref(prev)) == 0         # prev: the default (the shapes' loop has put it back)
     for k in kinds:
         assert res["wave"][k].tobytes() == res["workgroup"][k].tobytes(), k
         assert res["wave20"][k].tobytes() == res["workgroup20"][k].tobytes() == res["wave"][k][ids20].tobytes(), k
     assert int(res["wave"]["count"].view(np.uint64).sum()) == K * n
-    ts, host = timed_wall("kept across host form", lambda: kept[-1].across(kept[:-1], PCTS, M), a.reps, 2)
+    ts, host = wall("kept across host form", lambda: kept[-1].across(kept[:-1], PCTS, M), a.reps, 2)
     t["host"] = row(f"lh_kept_across host form (wall, with the derived arrays), {M} names x {K} handles, np = 9", ts)
-    ts, host20 = timed_wall("kept across ids host form", lambda: kept[-1].across(kept[:-1], PCTS, ids=ids20), a.reps, 2)
+    ts, host20 = wall("kept across ids host form", lambda: kept[-1].across(kept[:-1], PCTS, ids=ids20), a.reps, 2)
     t["host20"] = row(f"lh_kept_across_ids host form (wall), {NIDS} ids x {K} handles, np = 9", ts)
     assert host["count"].tobytes() == res["wave"]["count"].tobytes() and host["pkeys"].tobytes() == res["wave"]["pkeys"].tobytes()
 
@@ -171,9 +131,9 @@ def run(torch, a, M, n, lines):
             k.add_to(spare)
         return spare.across_ids(ids20, [], PCTS)
 
-    ts, old = timed_wall("old route", old_route, a.host_reps, 1, before=eng.flip, after=lambda s: s.release())
+    ts, old = wall("old route", old_route, a.host_reps, 1, before=eng.flip, after=release)
     t["old"] = row(f"old route (wall): {K} x add_buckets_csr_device into a spare snapshot + extract_rows_compact, {M} names", ts)
-    ts, old20 = timed_wall("old route, 20 ids", old_route20, a.host_reps, 1, before=eng.flip, after=lambda s: s.release())
+    ts, old20 = wall("old route, 20 ids", old_route20, a.host_reps, 1, before=eng.flip, after=release)
     t["old20"] = row(f"old route (wall): {K} x add_buckets_csr_device into a spare snapshot + lh_across_ids there, {NIDS} ids", ts)
     assert np.array_equal(old["count"], host["count"]) and np.array_equal(old["nbuckets"], host["nbuckets"])
     assert np.array_equal(old["pkeys"], host["pkeys"]) and np.allclose(old["sum"], host["sum"], rtol=1e-9, atol=0)
@@ -184,19 +144,19 @@ def run(torch, a, M, n, lines):
         xs = torch.cuda.ExternalStream(last.stream())
         ak = dict(kinds, present_bits=torch.int32)
         aout = {k: torch.zeros((M, len(PCTS)) if k in ("pkeys", "pvalid") else (M,), dtype=d, device="cuda") for k, d in ak.items()}
-        ts = timed_events("across", lambda: last.across(snaps[:-1], PCTS, M, out=aout), xs)
+        ts = events("across", lambda: last.across(snaps[:-1], PCTS, M, out=aout), xs)
         t["across"] = row(f"lh_across_device over the last {live} LIVE snapshots (of 16 dense buffers), {M} names, np = 9", ts)
         kout = outs(M)
-        ts = timed_events("kept across 16", lambda: kept[-1].across(kept[-live:-1], PCTS, M, out=kout, stream=st), st)
+        ts = events("kept across 16", lambda: kept[-1].across(kept[-live:-1], PCTS, M, out=kout, stream=st), st)
         t["kept16"] = row(f"lh_kept_across_device over the same {live} intervals' handles, {M} names, np = 9", ts)
         for k in ("count", "nbuckets", "pkeys", "pvalid"):
             assert aout[k].cpu().numpy().tobytes() == kout[k].cpu().numpy().tobytes(), k
     else:
-        lines.append(f"# lh_across over 14 live snapshots is not measured at {M} names: 16 dense buffers of {dense / 2**30:.0f} GiB do not fit")
+        rep.note(f"# lh_across over 14 live snapshots is not measured at {M} names: 16 dense buffers of {dense / 2**30:.0f} GiB do not fit")
     default = "wave" if M >= prev.value else "workgroup"
-    lines.append(f"# {M} names: old route / lh_kept_across host form: {t['old'] / t['host']:.2f} x;  {NIDS} ids: {t['old20'] / t['host20']:.2f} x"
-                 f"   (device form, default shape '{default}': {t[default] * 1e3:.0f} us for all names)")
-    print(lines[-1], flush=True)
+    rep.note(f"# {M} names: old route / lh_kept_across host form: {t['old'] / t['host']:.2f} x;  {NIDS} ids: {t['old20'] / t['host20']:.2f} x"
+             f"   (device form, default shape '{default}': {t[default] * 1e3:.0f} us for all names)")
+    print(rep.lines[-1], flush=True)
     for s in snaps:
         s.release()
     for k in kept:
@@ -219,15 +179,14 @@ def main():
     names, pairs = [int(x) for x in a.names.split(",")], [int(float(x)) for x in a.pairs.split(",")]
     assert len(names) == len(pairs) and 2 <= a.k <= N.MAX_KEPT
     torch.cuda.set_device(0)
-    lines = [f"# tools/kept_bench.py --names {a.names} --k {a.k} --pairs {a.pairs} --reps {a.reps} --warmup {a.warmup}: "
-             f"{torch.cuda.get_device_name(0)}", f"# tree_stamp: {bench.tree_stamp()}",
-             "# Zipf(1.0) names, lognormal values, each interval 0.5 % higher; us are medians (min .. max) of the timed calls;",
-             "# device forms: HIP events on the caller's stream around the call; host forms, lh_keep and the old route: wall time"]
+    rep = kit.Report(width=96, digits=11)
+    stamp, command = kit.header(TOOL, f"--names {a.names} --k {a.k} --pairs {a.pairs} --reps {a.reps} --warmup {a.warmup}", torch)
+    rep.lines += [command, stamp,
+                  "# Zipf(1.0) names, lognormal values, each interval 0.5 % higher; us are medians (min .. max) of the timed calls;",
+                  "# device forms: HIP events on the caller's stream around the call; host forms, lh_keep and the old route: wall time"]
     for M, n in zip(names, pairs):
-        run(torch, a, M, n, lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        run(torch, a, M, n, rep)
+    rep.write(a.out)
     return 0
 
 

@@ -14,64 +14,42 @@ Medians of the timed calls with the spread (min .. max).  No number is fixed in 
 merged handle's arrays are compared byte for byte between the two shapes and with the old route's handle, and the integer
 results of the two reads with each other.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after
-a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/kept_merge_bench.py [--names 1024,65536] [--k 60] [--pairs 2e6,2e7] [--reps 15] [--out profiles/kept_merge.txt]
                                         [--across LABEL=FILE ...]   (tools/kept_bench.py outputs of the same session, e.g. of the
                                         parent commit and of this tree: their lh_kept_across_device lines are copied in)"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
-SHAPES = (("wave", 1), ("workgroup", 1 << 30))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"kept_merge_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
+TOOL = "kept_merge_bench"
 
 
 def listing(k):
     return [t.cpu().numpy().tobytes() for t in k.arrays()]
 
 
-def run(torch, a, M, n, lines):
+def run(torch, a, M, n, rep):
     L = N.lib()
     K = a.k
 
-    def row(name, ts, extra=""):
-        m, lo, hi = statistics.median(ts), min(ts), max(ts)
-        lines.append(f"{name:<100} us {m * 1e3:11.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    row = rep.row
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=3, num_lanes=1, lane_samples=1 << 16, cell_bits=32)
     kept = []
-    with limit(600, "ingest and keep"):
+    with kit.limit(600, "ingest and keep", TOOL):
         ids = bench.zipf_ids(n, M, 4000)
         data = bench.make_samples(n, "lognormal", seed=40)
         for i in range(K):
@@ -83,46 +61,29 @@ def run(torch, a, M, n, lines):
         torch.cuda.empty_cache()
     assert all(k.info["samples"] == n for k in kept)
 
-    def timed_wall(what, call, reps, warmup, before=None, after=None, done=None):
-        with limit(420, what):
-            ts, out = [], None
-            for r in range(warmup + reps):
-                ctx = before() if before else None
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                new = call(ctx) if before else call()
-                dt = (time.perf_counter() - t0) * 1e3
-                if after:
-                    after(ctx)
-                if out is not None and done:
-                    done(out)
-                out = new
-                if r >= warmup:
-                    ts.append(dt)
-        return ts, out
+    def wall(what, call, reps, warmup, before=None):
+        """Every call makes a kept handle: the one of the call before is closed (untimed) once the next is made; the last is returned."""
+        held = []
 
-    def timed_events(what, call, stream):
-        with limit(180, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                call()
-                e1.record(stream)
-                stream.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+        def after(spare, new):
+            if spare:
+                spare.release()
+            if held:
+                held.pop().close()
+            held.append(new)
+            return new
+        return kit.timed_wall(call, reps, warmup, what, 420, TOOL, before, after, sync=torch.cuda.synchronize)
+
+    def events(what, call, stream):
+        return kit.timed_events(stream, call, a.reps, a.warmup, what, 180, TOOL)
 
     # ---- the merge, in both shapes
     prev = C.c_uint32(0)
     t, one = {}, {}
-    for shape, wave_from in SHAPES:
-        assert L.lh_tool_kept_switch(wave_from, C.byref(prev)) == 0
-        ts, one[shape] = timed_wall(f"merge {shape}", lambda: kept[-1].merge(kept[:-1]), a.reps, a.warmup, done=lambda k: k.close())
+    for shape, _ in kit.shapes(L.lh_tool_kept_switch):
+        ts, one[shape] = wall(f"merge {shape}", lambda: kept[-1].merge(kept[:-1]), a.reps, a.warmup)
         t["merge " + shape] = row(f"lh_kept_merge (wall), {M} names x {K} handles, a {shape} per row", ts)
-    assert L.lh_tool_kept_switch(0, C.byref(prev)) == 0 and L.lh_tool_kept_switch(0, C.byref(prev)) == 0   # prev: the default
+    assert L.lh_tool_kept_switch(0, C.byref(prev)) == 0         # prev: the default (the shapes' loop has put it back)
     default = "wave" if M >= prev.value else "workgroup"
     merged = one["wave"]
     assert listing(merged) == listing(one["workgroup"]) and merged.info == one["workgroup"].info
@@ -135,7 +96,7 @@ def run(torch, a, M, n, lines):
             k.add_to(spare)
         return spare.keep(M)
 
-    ts, old = timed_wall("old route", old_route, a.host_reps, 1, before=eng.flip, after=lambda s: s.release(), done=lambda k: k.close())
+    ts, old = wall("old route", old_route, a.host_reps, 1, before=eng.flip)
     t["old"] = row(f"old route (wall): {K} x add_buckets_csr_device into a live snapshot + lh_keep there, {M} names", ts)
     assert listing(old) == listing(merged) and old.info == merged.info
     old.close()
@@ -145,14 +106,12 @@ def run(torch, a, M, n, lines):
     kinds = dict(count=torch.int64, sum=torch.float64, nbuckets=torch.int32, present_bits=torch.int64, pkeys=torch.int16,
                  pvalid=torch.uint8)
     res = {}
-    for shape, wave_from in SHAPES:
-        assert L.lh_tool_kept_switch(wave_from, C.byref(prev)) == 0
+    for shape, _ in kit.shapes(L.lh_tool_kept_switch):
         for what, last, earlier in (("the ONE merged handle", merged, []), (f"the {K} handles", kept[-1], kept[:-1])):
             out = {k: torch.zeros((M, len(PCTS)) if k in ("pkeys", "pvalid") else (M,), dtype=d, device="cuda") for k, d in kinds.items()}
-            ts = timed_events(f"across {what} {shape}", lambda: last.across(earlier, PCTS, M, out=out, stream=st), st)
+            ts = events(f"across {what} {shape}", lambda: last.across(earlier, PCTS, M, out=out, stream=st), st)
             res[shape, what] = {k: v.cpu().numpy() for k, v in out.items()}
             t[shape, what] = row(f"lh_kept_across_device over {what}, {M} names, np = 9, a {shape} per row", ts)
-    assert L.lh_tool_kept_switch(0, C.byref(prev)) == 0
     first = res["wave", "the ONE merged handle"]
     for key, r in res.items():
         for k in ("count", "nbuckets", "pkeys", "pvalid"):
@@ -160,13 +119,13 @@ def run(torch, a, M, n, lines):
     assert int(first["count"].view(np.uint64).sum()) == K * n
 
     total = sum(k.info["bytes"] for k in kept)
-    lines.append(f"# {M} names: the merged handle holds {merged.info['cells']} cells in {merged.info['bytes'] / 2**20:.2f} MiB; the {K} "
-                 f"handles hold {sum(k.info['cells'] for k in kept)} in {total / 2**20:.1f} MiB ({total / merged.info['bytes']:.1f} x)")
-    lines.append(f"# {M} names: old route / lh_kept_merge (default shape '{default}'): {t['old'] / t['merge ' + default]:.1f} x;  "
-                 f"lh_kept_across_device over the {K} / over the merged one (default shape): "
-                 f"{t[default, f'the {K} handles'] / t[default, 'the ONE merged handle']:.1f} x;  merge, wave / workgroup: "
-                 f"{t['merge wave'] / t['merge workgroup']:.2f}")
-    print("\n".join(lines[-2:]), flush=True)
+    rep.note(f"# {M} names: the merged handle holds {merged.info['cells']} cells in {merged.info['bytes'] / 2**20:.2f} MiB; the {K} "
+             f"handles hold {sum(k.info['cells'] for k in kept)} in {total / 2**20:.1f} MiB ({total / merged.info['bytes']:.1f} x)")
+    rep.note(f"# {M} names: old route / lh_kept_merge (default shape '{default}'): {t['old'] / t['merge ' + default]:.1f} x;  "
+             f"lh_kept_across_device over the {K} / over the merged one (default shape): "
+             f"{t[default, f'the {K} handles'] / t[default, 'the ONE merged handle']:.1f} x;  merge, wave / workgroup: "
+             f"{t['merge wave'] / t['merge workgroup']:.2f}")
+    print("\n".join(rep.lines[-2:]), flush=True)
     merged.close()
     for k in kept:
         k.close()
@@ -190,20 +149,19 @@ def main():
     names, pairs = [int(x) for x in a.names.split(",")], [int(float(x)) for x in a.pairs.split(",")]
     assert len(names) == len(pairs) and 2 <= a.k <= N.MAX_KEPT
     torch.cuda.set_device(0)
-    lines = [f"# tools/kept_merge_bench.py --names {a.names} --k {a.k} --pairs {a.pairs} --reps {a.reps} --warmup {a.warmup}: "
-             f"{torch.cuda.get_device_name(0)}", f"# tree_stamp: {bench.tree_stamp()}",
-             "# Zipf(1.0) names, lognormal values, each interval 0.5 % higher; us are medians (min .. max) of the timed calls;",
-             "# lh_kept_merge and the old route: wall time; lh_kept_across_device: HIP events on the caller's stream around the call"]
+    rep = kit.Report(width=100, digits=11)
+    stamp, command = kit.header(TOOL, f"--names {a.names} --k {a.k} --pairs {a.pairs} --reps {a.reps} --warmup {a.warmup}", torch)
+    rep.lines += [command, stamp,
+                  "# Zipf(1.0) names, lognormal values, each interval 0.5 % higher; us are medians (min .. max) of the timed calls;",
+                  "# lh_kept_merge and the old route: wall time; lh_kept_across_device: HIP events on the caller's stream around the call"]
     for M, n in zip(names, pairs):
-        run(torch, a, M, n, lines)
+        run(torch, a, M, n, rep)
     if a.across:                                             # the reader before and after a change to it, same session
-        lines.append("# --across: lh_kept_across_device as tools/kept_bench.py measured it in the same session, by library")
+        rep.note("# --across: lh_kept_across_device as tools/kept_bench.py measured it in the same session, by library")
     for spec in a.across:
         label, path = spec.split("=", 1)
-        lines += [f"# [{label}] {x.rstrip()}" for x in open(path) if x.startswith("lh_kept_across_device,")]
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        rep.lines += [f"# [{label}] {x.rstrip()}" for x in open(path) if x.startswith("lh_kept_across_device,")]
+    rep.write(a.out)
     return 0
 
 

@@ -13,14 +13,11 @@ reported: the same lines, the same bytes.  Each is timed two ways:
   wall     the host form, the copy of the text included.
 Medians of --reps calls after --warmup, with the spread (min .. max).  No number is fixed in advance.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after a
-step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started on
+the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/lines_bench.py [--names 65536] [--pairs 2e7] [--reps 25] [--warmup 5] [--out profiles/lines.txt]"""
 import argparse
-import contextlib
 import os
-import signal
-import statistics
 import sys
 import time
 
@@ -28,27 +25,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 import oracle  # noqa: E402
 
 PCT = dict(oracle.DEFAULT_PERCENTILES)                       # metrics.go:145-155
+TOOL = "lines_bench"
 WIRE = dict(prefix="cockroach.box-1_a.", sep=" ", suffix=" 1411104988\n", underscore_to_dot=True)
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"lines_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
 
 
 def main():
@@ -62,19 +45,18 @@ def main():
     a = ap.parse_args()
     M, n = a.names, int(a.pairs)
     torch.cuda.set_device(0)
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/lines_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# us are medians (min .. max) of the timed calls; device: HIP events on the snapshot's stream around the call; wall: "
-             "the host form, text copied to the host"]
+    rep = kit.Report(width=84)
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# us are medians (min .. max) of the timed calls; device: HIP events on the snapshot's stream around the call; wall: "
+                  "the host form, text copied to the host"]
 
-    def row(name, ts, nlines=0, nbytes=0):
-        m, lo, hi = statistics.median(ts), min(ts), max(ts)
+    def row(name, ts, nlines=0, nbytes=0):               # (its own columns: ts in us, lines/us and GB/s)
+        m, lo, hi = kit.med(ts)
         rate = f"   {nlines / m:8.1f} lines/us {nbytes / m / 1e3:7.2f} GB/s" if nlines else ""
-        lines.append(f"{name:<84} us {m:10.1f} ({lo:.1f} .. {hi:.1f}){rate}")
-        print(lines[-1], flush=True)
+        rep.note(f"{name:<84} us {m:10.1f} ({lo:.1f} .. {hi:.1f}){rate}", echo=True)
         return m
 
-    with limit(240, "ingest"):
+    with kit.limit(240, "ingest", TOOL):
         rng = np.random.default_rng(30)
         ids = torch.from_numpy(rng.integers(0, M, n).astype(np.int32)).cuda()
         vals = torch.from_numpy(rng.lognormal(11.5, 1.0, n)).cuda()
@@ -88,9 +70,9 @@ def main():
         torch.cuda.synchronize()
     xs = torch.cuda.ExternalStream(snap.stream())
 
-    def device_span(what, call):
+    def device_span(what, call):                          # (not benchkit.timed_events: us, and it waits for the closing event alone)
         ts = []
-        with limit(300, what):
+        with kit.limit(300, what, TOOL):
             for r in range(a.warmup + a.reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(xs)
@@ -101,9 +83,9 @@ def main():
                     ts.append(e0.elapsed_time(e1) * 1e3)
         return ts
 
-    def wall(what, call, reps=a.reps, warmup=a.warmup):
+    def wall(what, call, reps=a.reps, warmup=a.warmup):   # (not benchkit.timed_wall: us, as this tool's rows take them)
         ts, out = [], None
-        with limit(600, what):
+        with kit.limit(600, what, TOOL):
             for r in range(warmup + reps):
                 t0 = time.perf_counter()
                 out = call()
@@ -116,14 +98,14 @@ def main():
     serialize = lambda: snap.serialize(PCT, aggregates=True, **WIRE)       # noqa: E731
     text = serialize()
     nl, nb = text.count(b"\n"), len(text)
-    lines.append(f"# S: {M} names, {n:g} samples; {nl} lines, {nb} bytes ({nb / nl:.1f} a line), the same for both")
+    rep.note(f"# S: {M} names, {n:g} samples; {nl} lines, {nb} bytes ({nb / nl:.1f} a line), the same for both")
     t_ser_dev = row("lh_serialize, 15 keys: device span (extract + K6 + text copy)", device_span("serialize span", serialize), nl, nb)
     t_ext_dev = row("  of which lh_extract_rows_view alone (same names, same percentiles)",
                     device_span("extract span", lambda: snap.extract_view(ps, M)))
     t_ser_wall = row("lh_serialize, 15 keys: host form, wall", wall("serialize wall", serialize)[0], nl, nb)
 
     # ---- lh_lines over the same 15 values a name, as device columns
-    with limit(120, "columns"):
+    with kit.limit(120, "columns", TOOL):
         st = snap.extract(ps, M)
         lc, ls = eng.lifetime(M)
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()   # noqa: E731
@@ -147,9 +129,9 @@ def main():
     t_lin_dev = row("lh_lines_device, 15 columns: device span (descriptor copy + 3 kernels)", device_span("lines span", device_form),
                     nl, nb)
     t_lin_wall = row("lh_lines, 15 columns: host form, wall", wall("lines wall", host_form)[0], nl, nb)
-    lines.append(f"# per output byte, lh_lines / lh_serialize: device span {t_lin_dev / t_ser_dev:.4f} x "
-                 f"({t_lin_dev / max(t_ser_dev - t_ext_dev, 1e-9):.4f} x with the extract's own span taken off lh_serialize's), "
-                 f"wall {t_lin_wall / t_ser_wall:.2f} x  (equal bytes: the ratio of the times)")
+    rep.note(f"# per output byte, lh_lines / lh_serialize: device span {t_lin_dev / t_ser_dev:.4f} x "
+             f"({t_lin_dev / max(t_ser_dev - t_ext_dev, 1e-9):.4f} x with the extract's own span taken off lh_serialize's), "
+             f"wall {t_lin_wall / t_ser_wall:.2f} x  (equal bytes: the ratio of the times)")
 
     # ---- the case the feature exists for: statsd's keys for every name
     tags = ["%.10g" % (100.0 * p) for p in ps]
@@ -171,21 +153,19 @@ def main():
     on_device = lambda: snap.spread_lines(names, ps, **WIRE)       # noqa: E731
     stext = on_device()
     sl, sb = stext.count(b"\n"), len(stext)
-    lines.append(f"# spread_lines: {M} names x (std + 4 keys x {len(ps)} percentiles): {sl} lines, {sb} bytes")
+    rep.note(f"# spread_lines: {M} names x (std + 4 keys x {len(ps)} percentiles): {sl} lines, {sb} bytes")
     ts, htext = wall("spread on the host", on_the_host, reps=3, warmup=1)
     same = htext == stext      # (Python's %f rounds the exact value half-even as Go's does; reported, not assumed)
     t_host = row("Snapshot.spread + one Python format per key, wall (3 calls)", ts, sl, sb)
     t_dev = row("Snapshot.spread_lines (lh_spread_device + lh_lines), wall", wall("spread_lines", on_device)[0], sl, sb)
-    lines.append(f"# spread_lines: host route / device route = {t_host / t_dev:.0f} x; the two texts are "
-                 f"{'equal byte for byte' if same else 'NOT equal'}")
+    rep.note(f"# spread_lines: host route / device route = {t_host / t_dev:.0f} x; the two texts are "
+             f"{'equal byte for byte' if same else 'NOT equal'}")
     assert same, "spread_lines and the host's text differ"
 
     snap.release()
     names.close()
     eng.close()
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.write(a.out)
     return 0
 
 

@@ -8,44 +8,27 @@ stream around the call), its two passes through lh_tool_movers_passes_ms, the ho
 Medians of --reps calls after --warmup, with the spread (min .. max).  No number is fixed in advance.  The ids of the device
 form, the host form and the baseline must agree.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU after a
-step that hung), and the first failed check ends the run.  The file's lines before MARK (the compile-time resource table)
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started on
+the GPU after a step that hung), and the first failed check ends the run.  The file's lines before MARK (the compile-time resource table)
 are kept.
 usage: python tools/movers_bench.py [--names 65536] [--pairs 6e7] [--reps 25] [--warmup 5] [--k 20] [--out profiles/movers.txt]"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import benchkit as kit  # noqa: E402
 import loghisto_amd  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 MARK = "# ==== measured: tools/movers_bench.py"
+TOOL = "movers_bench"
 BYS = (("ks", None), ("w1", None), ("shift", None), ("percentile", 0.99))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"movers_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
 
 
 def main():
@@ -61,22 +44,16 @@ def main():
     M, n, K = a.names, int(a.pairs), a.k
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [MARK, f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/movers_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup} --k {K}: "
-             f"{torch.cuda.get_device_name(0)}",
-             "# two intervals of one engine (Zipf(1.0) names, lognormal values, the second interval 10 % higher); us are medians "
-             "(min .. max) of the timed calls;", "# device forms and passes: HIP events on cur's stream; host form and baseline: wall time"]
-
-    def row(name, ts, extra=""):
-        m, lo, hi = statistics.median(ts), min(ts), max(ts)
-        lines.append(f"{name:<72} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    rep = kit.Report(width=72)
+    row = rep.row
+    rep.lines += [MARK, *kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup} --k {K}", torch),
+                  "# two intervals of one engine (Zipf(1.0) names, lognormal values, the second interval 10 % higher); us are medians "
+                  "(min .. max) of the timed calls;", "# device forms and passes: HIP events on cur's stream; host form and baseline: wall time"]
 
     eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=3, num_lanes=1, lane_samples=1 << 16)
     snaps = []
     for k, scale in enumerate((1.0, 1.1)):
-        with limit(300, f"interval {k}"):
+        with kit.limit(300, f"interval {k}", TOOL):
             ids = bench.zipf_ids(n, M, 4000 + k)
             data = bench.make_samples(n, "lognormal", seed=40 + k)
             data.mul_(scale * torch.exp(3e-5 * ids.to(torch.float64)))
@@ -91,31 +68,13 @@ def main():
             torch.cuda.empty_cache()
     base, cur = snaps
     xs = torch.cuda.ExternalStream(cur.stream())
-    lines.append(f"# {M} names, {n:g} samples per interval, cells of {base.device_cells()[2]} and {cur.device_cells()[2]} bytes")
+    rep.note(f"# {M} names, {n:g} samples per interval, cells of {base.device_cells()[2]} and {cur.device_cells()[2]} bytes")
 
-    def timed_events(what, call):
-        with limit(120, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                call()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+    def events(what, call):
+        return kit.timed_events(xs, call, a.reps, a.warmup, what, 120, TOOL)
 
-    def timed_wall(what, call, seconds=300):
-        with limit(seconds, what):
-            ts, res = [], None
-            for r in range(2 + a.reps):
-                t0 = time.perf_counter()
-                res = call()
-                if r >= 2:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-        return ts, res
+    def wall(what, call):
+        return kit.timed_wall(call, a.reps, 2, what, 300, TOOL)
 
     select_over_score = {}
 
@@ -124,12 +83,12 @@ def main():
         cnt = torch.zeros((1,), dtype=torch.int32, device="cuda")
         for by, arg in BYS:
             name = by if arg is None else f"{by} p={arg}"
-            ts = timed_events(f"movers {name} {nmetrics}", lambda: cur.movers(base, K, by, arg, False, nmetrics, out=(ent, cnt)))
+            ts = events(f"movers {name} {nmetrics}", lambda: cur.movers(base, K, by, arg, False, nmetrics, out=(ent, cnt)))
             row(f"{indent}movers device form by {name}, k = {K}, {nmetrics} names", ts)
             dev = ent.cpu().numpy().view(N.MOVER_ENTRY)[:int(cnt.cpu()[0])].copy()
             sc, se = [], []
             s_ms, e_ms = C.c_float(0), C.c_float(0)
-            with limit(120, f"passes {name} {nmetrics}"):
+            with kit.limit(120, f"passes {name} {nmetrics}", TOOL):
                 for r in range(a.warmup + a.reps):
                     rc = L.lh_tool_movers_passes_ms(base._h, cur._h, 0, nmetrics, N.MOVERS_BY_KS + [b for b, _ in BYS].index(by), arg or 0.0,
                                                     K, 0, C.byref(s_ms), C.byref(e_ms))
@@ -140,7 +99,7 @@ def main():
             ms = row(f"{indent}  score pass", sc)
             me = row(f"{indent}  select pass (one workgroup)", se)
             select_over_score[(nmetrics, name)] = me / ms
-            ts, host = timed_wall(f"movers host {name} {nmetrics}", lambda: cur.movers(base, K, by, arg, False, nmetrics))
+            ts, host = wall(f"movers host {name} {nmetrics}", lambda: cur.movers(base, K, by, arg, False, nmetrics))
             row(f"{indent}  movers host form (wall)", ts)
             assert host.tobytes() == dev.tobytes(), (by, nmetrics)
             if by == "ks":
@@ -156,34 +115,26 @@ def main():
                     part = ok[ks[ok] >= kth]
                     return part[np.lexsort((part, -ks[part]))][:kk]
                 today.out = {"ks": torch.zeros((nmetrics,), dtype=torch.float64).pin_memory().numpy()}
-                ts, ids = timed_wall(f"baseline {nmetrics}", today)
+                ts, ids = wall(f"baseline {nmetrics}", today)
                 row(f"{indent}  baseline: compare host form for ks (pinned), argpartition + sort (wall)", ts)
-                lines.append(f"{indent}  the baseline copies {nmetrics * 8} bytes back, lh_movers {K * 32 + 8}")
-                print(lines[-1], flush=True)
+                rep.note(f"{indent}  the baseline copies {nmetrics * 8} bytes back, lh_movers {K * 32 + 8}")
+                print(rep.lines[-1], flush=True)
                 assert ids.tolist() == host["id"].tolist(), (ids[:5], host["id"][:5])
 
     one_size(M)
     if M > 1024:
-        lines.append("# the first 1 024 names (Zipf: the widest windows):")
+        rep.note("# the first 1 024 names (Zipf: the widest windows):")
         one_size(1024, indent="  ")
     worst = max((v, k) for k, v in select_over_score.items() if k[0] == M)
-    lines.append(f"# select pass / score pass at {M} names: at most {worst[0]:.2f} (by {worst[1][1]})" +
-                 (": the one-workgroup select costs more than the score pass -- a histogram pass over several workgroups is the "
+    rep.note(f"# select pass / score pass at {M} names: at most {worst[0]:.2f} (by {worst[1][1]})" +
+             (": the one-workgroup select costs more than the score pass -- a histogram pass over several workgroups is the "
                   "next lever (not built here)" if worst[0] > 1 else ""))
-    print(lines[-1], flush=True)
+    print(rep.lines[-1], flush=True)
     for s in snaps:
         s.release()
     eng.close()
 
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    head = []
-    if os.path.exists(a.out):
-        for ln in open(a.out).read().splitlines():
-            if ln.startswith(MARK):
-                break
-            head.append(ln)
-    with open(a.out, "w") as f:
-        f.write("\n".join(head + lines) + "\n")
+    rep.write(a.out, mark=MARK)
     return 0
 
 

@@ -9,48 +9,24 @@ read of the same windows: the floor; extract_compact with the nine default perce
 256 .. 16 384 names of S, which is where the default switch comes from; and one name whose row is filled over the full key
 range, in both shapes.  Medians of --reps calls after --warmup, with the spread (min .. max).  No number is fixed in advance.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU
-after a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/spread_bench.py [--names 65536] [--pairs 1.25e8] [--reps 25] [--warmup 5] [--out profiles/spread.txt]"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-import loghisto_amd  # noqa: E402
+import benchkit as kit  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
 PSETS = {0: [], 1: [0.9], 9: PCTS}
-SHAPES = (("wave", 1), ("workgroup", 1 << 30))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"spread_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
+TOOL = "spread_bench"
 
 
 def numpy_route(snap, M, D, P):
@@ -97,78 +73,41 @@ def main():
     M, n = a.names, int(a.pairs)
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/spread_bench.py --names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
-             "(min .. max) of the timed calls;", "# device forms: HIP events on the snapshot's stream around the call; "
-             "host form, extract_compact and the numpy route: wall time"]
+    rep = kit.Report(width=62)
+    row = rep.row
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
+                  "(min .. max) of the timed calls;", "# device forms: HIP events on the snapshot's stream around the call; "
+                  "host form, extract_compact and the numpy route: wall time"]
 
-    def row(name, ts, extra=""):
-        m, lo, hi = med(ts)
-        lines.append(f"{name:<62} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
+    def quantiles(data):
+        return torch.quantile(data[:1_000_000], torch.linspace(0.02, 0.999, 64, dtype=torch.float64, device=data.device)).cpu().numpy()
 
-    with limit(240, "inputs"):
-        ids = bench.zipf_ids(n, M, 4000)
-        data = bench.make_samples(n, "lognormal", seed=40)
-        data.mul_(torch.exp(3e-5 * ids.to(torch.float64)))
-        q = torch.quantile(data[:1_000_000], torch.linspace(0.02, 0.999, 64, dtype=torch.float64, device=data.device)).cpu().numpy()
-        bi, bd = bench.OwnBuffer(ids), bench.OwnBuffer(data)
-        ids, data = bi.tensor, bd.tensor
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize()
+    eng, snap, q = kit.c4_slice(M, n, TOOL, look=quantiles)
     bounds = {1: q[31:32].copy(), 9: q[3::7][:9].copy()}
-    eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-    with limit(240, "ingest"):
-        eng.submit_pairs_device(ids, data, n)
-        snap = eng.flip()
-        torch.cuda.synchronize()
-    bi.free()
-    bd.free()
-    del ids, data
-    torch.cuda.empty_cache()
     xs = torch.cuda.ExternalStream(snap.stream())
     cells = snap.device_cells()
     D = eng.codec_tables()[1]
-    lines.append(f"# S: {M} names, {n:g} samples, cells of {cells[2]} bytes")
+    rep.note(f"# S: {M} names, {n:g} samples, cells of {cells[2]} bytes")
     kinds = dict(count=torch.int64, sum=torch.float64, m2=torch.float64, pkeys=torch.int16, pvalid=torch.uint8,
                  count_le=torch.int64, sum_le=torch.float64)
 
-    def timed_events(what, call):
-        with limit(120, what):
-            torch.cuda.synchronize()
-            ts = []
-            for r in range(a.warmup + a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(xs)
-                call()
-                e1.record(xs)
-                xs.synchronize()
-                if r >= a.warmup:
-                    ts.append(e0.elapsed_time(e1))
-        return ts
+    def events(what, call):
+        return kit.timed_events(xs, call, a.reps, a.warmup, what, 120, TOOL)
 
     def spread_device(what, P, nmetrics):
         out = {k: torch.zeros((nmetrics,) if k in ("count", "sum", "m2") else (nmetrics, len(P)), dtype=t, device="cuda")
                for k, t in kinds.items() if P or k in ("count", "sum", "m2")}
-        ts = timed_events(what, lambda: snap.spread(P, nmetrics, out=out))
+        ts = events(what, lambda: snap.spread(P, nmetrics, out=out))
         return ts, {k: v.cpu().numpy() for k, v in out.items()}
 
     def count_le_device(what, b, nmetrics):
         cum = torch.zeros((nmetrics, b.size), dtype=torch.int64, device="cuda")
         total = torch.zeros((nmetrics,), dtype=torch.int64, device="cuda")
-        return timed_events(what, lambda: snap.count_le(b, nmetrics, out=(cum, total))), total.cpu().numpy().view(np.uint64)
+        return events(what, lambda: snap.count_le(b, nmetrics, out=(cum, total))), total.cpu().numpy().view(np.uint64)
 
-    def timed_wall(what, call, reps, warmup=2):
-        with limit(300, what):
-            ts = []
-            for r in range(warmup + reps):
-                t0 = time.perf_counter()
-                out = call()
-                if r >= warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-        return ts, out
+    def wall(what, call, reps, warmup=2):
+        return kit.timed_wall(call, reps, warmup, what, 300, TOOL)
 
     def same_integers(x, y, what):
         for k in ("count", "pkeys", "pvalid", "count_le"):
@@ -176,14 +115,11 @@ def main():
                 assert np.array_equal(x[k].view(np.uint8), np.ascontiguousarray(y[k]).view(np.uint8)), (what, k)
 
     # ---- the whole snapshot, both shapes
-    prev = C.c_uint32(0)
     t, res = {}, {}
-    for shape, wave_from in SHAPES:
-        assert L.lh_tool_spread_switch(wave_from, C.byref(prev)) == 0
+    for shape, _ in kit.shapes(L.lh_tool_spread_switch):
         for k, P in PSETS.items():
             ts, res[shape, k] = spread_device(f"{shape} np={k}", P, M)
             t[shape, k] = row(f"spread device form, {M} names, np = {k}, a {shape} per row", ts)
-    assert L.lh_tool_spread_switch(0, C.byref(prev)) == 0
     for k in PSETS:
         same_integers(res["wave", k], res["workgroup", k], f"shapes np={k}")
         for f in ("sum", "m2", "sum_le"):                      # the shapes associate the sums differently
@@ -194,23 +130,25 @@ def main():
         ts, total = count_le_device(f"count_le nb={nb}", bounds[nb], M)
         row(f"count_le device form, {M} names, nb = {nb} (one read: the floor)", ts)
         assert np.array_equal(total, res["wave", 9]["count"].view(np.uint64))
-    ts, ex = timed_wall("extract_compact", lambda: snap.extract_compact(PCTS, M), a.reps)
+    ts, ex = wall("extract_compact", lambda: snap.extract_compact(PCTS, M), a.reps)
     row(f"extract_compact (wall), {M} names, 9 percentiles", ts)
     assert np.array_equal(ex["count"], res["wave", 9]["count"].view(np.uint64))
     assert np.array_equal(ex["pkeys"], res["wave", 9]["pkeys"])
-    ts, host = timed_wall("host np=9", lambda: snap.spread(PCTS, M), a.reps)
+    ts, host = wall("host np=9", lambda: snap.spread(PCTS, M), a.reps)
     row(f"spread host form (wall, with the derived arrays), {M} names, np = 9", ts)
     pinned = {k: torch.zeros((M,) if k in ("count", "sum", "m2") else (M, 9), dtype=t, pin_memory=True).numpy()
               for k, t in kinds.items()}
     pp = np.array(PCTS)
     args = [pinned[k].ctypes.data for k in ("count", "sum", "m2", "pkeys", "pvalid", "count_le", "sum_le")]
-    ts, rc = timed_wall("host C call", lambda: L.lh_spread(snap._h, 0, M, pp.ctypes.data, 9, *args), a.reps)
+    ts, rc = wall("host C call", lambda: L.lh_spread(snap._h, 0, M, pp.ctypes.data, 9, *args), a.reps)
     assert rc == 0
     row(f"lh_spread into the caller's pinned arrays (wall), {M} names, np = 9", ts)
     same_integers(pinned, host, "C call")
+    prev = C.c_uint32(0)
+    assert L.lh_tool_spread_switch(0, C.byref(prev)) == 0      # prev: the default (the shapes' loop has put it back)
     default = "wave" if M >= prev.value else "workgroup"
     same_integers(res[default, 9], host, "host form")
-    ts, ref = timed_wall("numpy route", lambda: numpy_route(snap, M, D, PCTS), a.host_reps, 1)
+    ts, ref = wall("numpy route", lambda: numpy_route(snap, M, D, PCTS), a.host_reps, 1)
     row(f"buckets_all + numpy (wall): the route this replaces, {M} names, np = 9", ts)
     assert np.array_equal(ref["count"], host["count"]) and np.array_equal(ref["count_le"], host["count_le"])
     assert np.allclose(ref["sum"], host["sum"], rtol=1e-9, atol=1e-9 * float(np.abs(host["sum"]).sum())) and np.allclose(ref["m2"], host["m2"], rtol=1e-6)
@@ -218,42 +156,32 @@ def main():
     assert np.allclose(ref["sum_le"], host["sum_le"], rtol=1e-9, atol=1e-9 * float(np.abs(host["sum"]).sum()))
 
     # ---- where a row gets a wave and where a workgroup: the first names of S (Zipf: the widest windows) in both shapes
-    lines.append("# both kernel shapes, device form, np = 9, over the first names of S:")
+    rep.note("# both kernel shapes, device form, np = 9, over the first names of S:")
     for k in (256, 1024, 2048, 4096, 16384):
         if k > M:
             continue
-        for shape, wave_from in SHAPES:
-            assert L.lh_tool_spread_switch(wave_from, C.byref(prev)) == 0
+        for shape, _ in kit.shapes(L.lh_tool_spread_switch):
             ts, got = spread_device(f"{shape} {k}", PCTS, k)
             same_integers(got, {f: v[:k] for f, v in res["wave", 9].items()}, f"{shape} {k}")
             row(f"  {k:>6} names, a {shape} per row", ts)
-    assert L.lh_tool_spread_switch(0, C.byref(prev)) == 0
     snap.release()
     eng.close()
 
     # ---- one name, its row filled over the full key range (64-bit cells; 512 KiB)
-    with limit(120, "one full row"):
-        one = loghisto_amd.Engine(device=0, max_metrics=1, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-        snap = one.flip()
-        keys = np.arange(-32768, 32768, dtype=np.int16)
-        snap.add_buckets(np.zeros(keys.size, dtype=np.uint32), keys, np.full(keys.size, 3, dtype=np.uint64))
-        xs = torch.cuda.ExternalStream(snap.stream())
-    lines.append("# one name, all 65 536 cells occupied, device form:")
+    one, snap = kit.full_row_snapshot(TOOL)
+    xs = torch.cuda.ExternalStream(snap.stream())
+    rep.note("# one name, all 65 536 cells occupied, device form:")
     for k, P in PSETS.items():
-        for shape, wave_from in SHAPES:
-            assert L.lh_tool_spread_switch(wave_from, C.byref(prev)) == 0
+        for shape, _ in kit.shapes(L.lh_tool_spread_switch):
             ts, got = spread_device(f"one row {shape}", P, 1)
             assert int(got["count"][0]) == 3 * 65536 and (k != 9 or int(got["count_le"][0, -1]) == 3 * 65536)
             row(f"  1 name, full span, np = {k}, a {shape} per row", ts)
         ts, _ = count_le_device("one row count_le", np.array([0.0] * max(k, 1)), 1)
         row(f"  1 name, full span, count_le nb = {max(k, 1)} (default shape)", ts)
-    assert L.lh_tool_spread_switch(0, C.byref(prev)) == 0
     snap.release()
     one.close()
 
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.write(a.out)
     return 0
 
 

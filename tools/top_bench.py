@@ -10,48 +10,25 @@ name whose row is filled over the full key range: what the single wave shape cos
 today's route before its time is reported.  Medians of --reps calls after --warmup, with the spread (min .. max).  No number
 is fixed in advance.
 
-One process; every step runs under a limit of its own (an alarm that ends the process: nothing is started on the GPU
-after a step that hung), and the first failed check ends the run.
+One process; every step runs under a limit of its own (tools/benchkit.py's alarm, which ends the process: nothing is started
+on the GPU after a step that hung), and the first failed check ends the run.
 usage: python tools/top_bench.py [--names 65536] [--pairs 1.25e8] [--k 100] [--reps 25] [--warmup 5] [--out profiles/top.txt]"""
 import argparse
-import contextlib
 import ctypes as C
 import os
-import signal
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-import loghisto_amd  # noqa: E402
+import benchkit as kit  # noqa: E402
 from loghisto_amd import _native as N  # noqa: E402
 
 PCTS = [0.0, .5, .75, .9, .95, .99, .999, .9999, 1.0]       # metrics.go:145-155
 BYS = (("count", N.TOP_BY_COUNT, 0.0), ("sum", N.TOP_BY_SUM, 0.0), ("percentile 0.99", N.TOP_BY_PERCENTILE, 0.99),
        ("count above 250", N.TOP_BY_COUNT_ABOVE, 250.0))
-
-
-@contextlib.contextmanager
-def limit(seconds, what):
-    def expired(*_):
-        sys.stderr.write(f"top_bench: step '{what}' passed its limit of {seconds} s; ending\n")
-        sys.stderr.flush()
-        os._exit(124)
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-def med(ts):
-    return statistics.median(ts), min(ts), max(ts)
+TOOL = "top_bench"
 
 
 def leaders(score, count, k):
@@ -83,41 +60,19 @@ def main():
     M, n, K = a.names, int(a.pairs), a.k
     torch.cuda.set_device(0)
     L = N.lib()
-    lines = [f"# tree_stamp: {bench.tree_stamp()}",
-             f"# tools/top_bench.py --names {M} --pairs {n:g} --k {K} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}",
-             "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
-             "(min .. max) of the timed calls;", "# score / select pass: HIP events on the snapshot's stream around each kernel; "
-             "host form and today's route: wall time"]
-
-    def row(name, ts, extra=""):
-        m, lo, hi = med(ts)
-        lines.append(f"{name:<72} us {m * 1e3:10.1f} ({lo * 1e3:.1f} .. {hi * 1e3:.1f}){extra}")
-        print(lines[-1], flush=True)
-        return m
-
-    with limit(240, "inputs"):
-        ids = bench.zipf_ids(n, M, 4000)
-        data = bench.make_samples(n, "lognormal", seed=40)
-        data.mul_(torch.exp(3e-5 * ids.to(torch.float64)))
-        bi, bd = bench.OwnBuffer(ids), bench.OwnBuffer(data)
-        ids, data = bi.tensor, bd.tensor
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize()
-    eng = loghisto_amd.Engine(device=0, max_metrics=M, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-    with limit(240, "ingest"):
-        eng.submit_pairs_device(ids, data, n)
-        snap = eng.flip()
-        torch.cuda.synchronize()
-    bi.free()
-    bd.free()
-    del ids, data
-    torch.cuda.empty_cache()
-    lines.append(f"# S: {M} names, {n:g} samples, cells of {snap.device_cells()[2]} bytes; k = {K}")
+    rep = kit.Report(width=72)
+    row = rep.row
+    rep.lines += [*kit.header(TOOL, f"--names {M} --pairs {n:g} --k {K} --reps {a.reps} --warmup {a.warmup}", torch),
+                  "# S = snapshot of config 4's one-rank slice (Zipf(1.0) names, lognormal values: bench.py's stream); us are medians "
+                  "(min .. max) of the timed calls;", "# score / select pass: HIP events on the snapshot's stream around each kernel; "
+                  "host form and today's route: wall time"]
+    eng, snap, _ = kit.c4_slice(M, n, TOOL)
+    rep.note(f"# S: {M} names, {n:g} samples, cells of {snap.device_cells()[2]} bytes; k = {K}")
 
     def passes(s, what, by, arg, nmetrics, k=K):
         sc, se = C.c_float(0), C.c_float(0)
         score, select = [], []
-        with limit(120, what):
+        with kit.limit(120, what, TOOL):
             for r in range(a.warmup + a.reps):
                 rc = L.lh_tool_top_passes_ms(s._h, 0, nmetrics, by, arg, k, 0, C.byref(sc), C.byref(se))
                 assert rc == 0, rc
@@ -126,15 +81,8 @@ def main():
                     select.append(se.value)
         return score, select
 
-    def timed_wall(what, call, reps, warmup=2):
-        with limit(300, what):
-            ts = []
-            for r in range(warmup + reps):
-                t0 = time.perf_counter()
-                out = call()
-                if r >= warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-        return ts, out
+    def wall(what, call, reps, warmup=2):
+        return kit.timed_wall(call, reps, warmup, what, 300, TOOL)
 
     out = np.zeros(K, dtype=N.TOP_ENTRY)
     n_out = C.c_size_t(0)
@@ -156,15 +104,15 @@ def main():
 
     share = {}
     for nmetrics in sorted({M, min(M, 1024)}, reverse=True):
-        lines.append(f"# the first {nmetrics} names of S:")
+        rep.note(f"# the first {nmetrics} names of S:")
         for name, by, arg in BYS:
             sc, se = passes(snap, f"passes {name} {nmetrics}", by, arg, nmetrics)
             a_sc = row(f"  {nmetrics:>6} names, by {name}: score pass", sc)
             a_se = row(f"  {nmetrics:>6} names, by {name}: select pass", se)
             share[nmetrics, name] = (a_sc, a_se)
-            ts, got = timed_wall(f"host {name}", lambda: host_form(by, arg, nmetrics), a.reps)
+            ts, got = wall(f"host {name}", lambda: host_form(by, arg, nmetrics), a.reps)
             row(f"  {nmetrics:>6} names, by {name}: lh_top host form, round trip (wall)", ts)
-            ts, want = timed_wall(f"today {name}", lambda: today(by, arg, nmetrics), a.reps)
+            ts, want = wall(f"today {name}", lambda: today(by, arg, nmetrics), a.reps)
             what = "lh_count_le" if by == N.TOP_BY_COUNT_ABOVE else "extract_compact (9 percentiles)"
             row(f"  {nmetrics:>6} names, by {name}: today, {what} + argpartition (wall)", ts)
             if by != N.TOP_BY_SUM:       # (lh_stats.sum and this unit's sum associate differently: equal to rounding only)
@@ -175,12 +123,8 @@ def main():
     eng.close()
 
     # ---- one name, its row filled over the full key range (64-bit cells; 512 KiB): the single wave shape's worst case
-    with limit(120, "one full row"):
-        one = loghisto_amd.Engine(device=0, max_metrics=1, num_buffers=2, num_lanes=1, lane_samples=1 << 16)
-        snap1 = one.flip()
-        keys = np.arange(-32768, 32768, dtype=np.int16)
-        snap1.add_buckets(np.zeros(keys.size, dtype=np.uint32), keys, np.full(keys.size, 3, dtype=np.uint64))
-    lines.append("# one name, all 65 536 cells occupied (a wave walks 256 steps per walk):")
+    one, snap1 = kit.full_row_snapshot(TOOL)
+    rep.note("# one name, all 65 536 cells occupied (a wave walks 256 steps per walk):")
     for name, by, arg in BYS:
         sc, se = passes(snap1, f"one row {name}", by, arg, 1, 1)
         row(f"  1 name, full span, by {name}: score pass", sc)
@@ -190,11 +134,9 @@ def main():
     snap1.release()
     one.close()
     big = [f"{name}: score {s * 1e3:.1f} us, select {e * 1e3:.1f} us" for (nm, name), (s, e) in share.items() if nm == M]
-    lines.append(f"# at {M} names the larger share of the device time -- " + "; ".join(big))
+    rep.note(f"# at {M} names the larger share of the device time -- " + "; ".join(big))
 
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.write(a.out)
     return 0
 
 
