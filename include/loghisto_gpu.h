@@ -432,7 +432,8 @@ int lh_top_device(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, 
 /* How a name's distribution in one snapshot differs from its distribution in another: "which names changed against the
  * previous interval", "does the canary's latency match the baseline's", "did the deploy shift p-anything" -- answered on the
  * device, where both intervals already are (num_buffers >= 3 keeps the previous snapshot alive across a flip;
- * lh_snapshot_add_buckets* puts a stored baseline into a snapshot), instead of pulling both intervals' cells to the host with
+ * lh_snapshot_add_buckets* puts a stored baseline into a snapshot; lh_kept_compare* below compares intervals kept in compact
+ * form without one), instead of pulling both intervals' cells to the host with
  * lh_buckets_all.  One more bucket walk of the kind percentile() does (/root/reference/metrics.go:389-418), over two rows at
  * once.  For metric first + m, with a[j] the cells of `base` and b[j] the cells of `cur` in ascending bin order (ascending bin
  * is ascending value), A_j and B_j their inclusive prefix counts and na, nb the totals:
@@ -719,6 +720,44 @@ int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
 int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream,
                   lh_kept **out);
+/* DISTRIBUTION SHIFT BETWEEN KEPT INTERVALS: lh_compare* over handles, so that the baseline -- the same minute an hour ago, the
+ * interval before the deploy, yesterday's roll-up -- need not be alive as a dense snapshot, nor be poured back into one.  With
+ *   a[j] = the sum over the `base` list of the name's cell j, b[j] = the same sum over the `cur` list, both in 64 bits
+ * (lh_kept_across' C[b], once per side), every output is lh_compare's, word for word, for two snapshots that hold those cells:
+ * count_a / count_b (the wrapping sums of the handles' row_count entries), the argmax of X_j in exact 128-bit integers with the
+ * lowest bin among equals (ks_key, ks_below_a, ks_below_b), ks as the fixed function of the two prefixes, w1 and shift over every
+ * bin from the lowest to the highest occupied one of the two sides (empty bins between them included, as inside lh_compare's
+ * union span), NaN with key and prefixes 0 for a name without samples on a side, exact zeros for identical normalised
+ * distributions, wrapped totals unspecified (nothing faults).  The totals are known before a cell is read, so a row is walked
+ * once, over its occupied stretches only; w1 and shift are taken in one fixed order, the same in both kernel shapes (which
+ * agree bit for bit), and differ from lh_compare's in the last bits only.
+ *   1 <= nbase, 1 <= ncur, nbase + ncur <= LH_MAX_KEPT: ONE handle per lane of a wave, and the two lists travel by value in the
+ *   kernel's arguments.  Longer windows go through lh_kept_merge first.  A handle may appear more than once in a list and
+ *   counts that often; a handle may appear in both lists; identical lists give exact zeros for every non-empty name.
+ *   `first` and ids are ABSOLUTE row numbers, as for lh_kept_across*.  Any output may be NULL, but not all.  flags must be 0.
+ *   Checked on the host, in this order, before any handle is looked at -- LH_EINVAL: (ids forms: NULL ids with n > 0,
+ *   misaligned ids,) a NULL or misaligned list, nbase == 0, ncur == 0, nbase + ncur > LH_MAX_KEPT, a NULL entry, flags != 0,
+ *   all outputs NULL, an output not aligned to its element; LH_ERANGE: nmetrics > 0xffffffff; nmetrics == 0 / n == 0 -> LH_OK,
+ *   nothing looked at -- then LH_EINVAL: handles of the two lists on different devices; LH_ERANGE, nothing enqueued and nothing
+ *   written: [first, first + nmetrics), or a HOST id, outside the block of ANY handle of either list.  A DEVICE id outside some
+ *   handle's block yields the entry of two empty sides (counts 0, NaN, key and prefixes 0); nothing is read for it.
+ *   ORDERING and staging as for lh_kept_across*: the work goes on `stream`; host forms return with the results in the caller's
+ *   arrays (pinned arrays by one copy each); device forms return after enqueueing, with ALL handles of both lists guarded
+ *   against lh_kept_release until the stream has passed the call.  READ-ONLY. */
+int lh_kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                    uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                    uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift);
+int lh_kept_compare_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                           size_t nmetrics, uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b,
+                           double *d_ks, int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1,
+                           double *d_shift);
+int lh_kept_compare_ids(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *ids, size_t n,
+                        uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                        uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift);
+int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *d_ids,
+                               size_t n, uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
+                               int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1,
+                               double *d_shift);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

@@ -152,6 +152,9 @@ int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous);
 /* *bins receives the width in bins of the LDS tile lh_kept_across* covers a row's union span with (tests put cells either
  * side of a tile's edge).  NULL -> LH_EINVAL. */
 int lh_tool_kept_tile(uint32_t *bins);
+/* The same for lh_kept_compare*, whose rows have TWO such tiles (one per side) and whose width is a constant of its own
+ * (profiles/kept_compare.txt has both widths measured).  lh_tool_kept_switch switches its two shapes too. */
+int lh_tool_kept_compare_tile(uint32_t *bins);
 /* Device time of lh_top*'s two passes (HIP events on the snapshot's stream around each): one call with the arguments of
  * lh_top_device, its entries left in the unit's own block; returns when both times are known.  nmetrics >= 1. */
 int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags,

@@ -181,6 +181,7 @@ TUNING_SIGNATURES = {
     "lh_tool_across_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_kept_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_kept_tile": (C.c_int, [_u32p]),
+    "lh_tool_kept_compare_tile": (C.c_int, [_u32p]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
@@ -266,6 +267,10 @@ SIGNATURES = {
     "lh_kept_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_merge": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_compare": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_compare_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_compare_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_compare_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "lh_names_refresh": (C.c_int, [_vp, _u32p]),
     "lh_names_destroy": (C.c_int, [_vp]),

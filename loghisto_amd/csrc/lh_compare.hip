@@ -50,34 +50,7 @@ using namespace lh::beside;
 // tools/compare_bench.py has been run (profiles/compare.txt).
 constexpr uint32_t CP_WAVE_FROM_DEFAULT = 1024;
 
-struct CompareOut {
-    u64 *count_a, *count_b;
-    double *ks;
-    int16_t *ks_key;
-    u64 *below_a, *below_b;
-    double *w1, *shift;
-};
-
-// one lane writes a name's results; bin == NO_BIN: the two normalised distributions are identical
-__device__ __forceinline__ void store_row(const CompareOut &o, uint32_t m, u64 na, u64 nb, uint32_t bin, u64 a, u64 b, double w1,
-                                          double shift)
-{
-    double ks = 0.0;
-    if (na == 0 || nb == 0) {
-        ks = w1 = shift = __builtin_nan("");
-        bin = NO_BIN;
-    }
-    if (bin == NO_BIN) a = b = 0;
-    else ks = fabs((double)a / (double)na - (double)b / (double)nb);
-    if (o.count_a) o.count_a[m] = na;
-    if (o.count_b) o.count_b[m] = nb;
-    if (o.ks) o.ks[m] = ks;
-    if (o.ks_key) o.ks_key[m] = bin == NO_BIN ? (int16_t)0 : (int16_t)lh::bin_to_key(bin);
-    if (o.below_a) o.below_a[m] = a;
-    if (o.below_b) o.below_b[m] = b;
-    if (o.w1) o.w1[m] = w1;
-    if (o.shift) o.shift[m] = shift;
-}
+// (CompareOut, a name's eight results, and store_row, the lane that writes them: lh_pair.h)
 
 template <typename CA, typename CB>
 __global__ __launch_bounds__(ROW_BLOCK) void k_compare_wave(const CA *__restrict__ cells_a, const uint32_t *__restrict__ ranges_a,

@@ -48,6 +48,20 @@
 // the caller's stream, under the unit's mutex from the first look at a handle to the end (no lh_kept_release frees an input
 // under it); it only reads its inputs, so it records no event on them, and the new handle depends on none of them.
 //
+// THE COMPARE, lh_kept_compare*: lh_compare's outputs (lh_compare.hip's header has X, ks, w1 and shift) for a[j] = the sum over
+// the `base` list of the name's cell j and b[j] = the same over the `cur` list -- a kept baseline against a kept interval
+// with no dense buffer alive.  Up to 64 handles in the two lists together, which travel as ONE list (base first) with the
+// number of base handles beside it: lane i opens handle i as in the reader, na / nb are the wrapping sums of row_count over
+// the lanes of each side, so the scale (lh_pair.h's make_scale) is known before a cell is read and the row is walked ONCE,
+// where lh_compare walks it twice.  k_kept_compare has the reader's two shapes behind the same switch and takes the same
+// turns with TWO tiles a row, one per side (KEPT_COMPARE_TILE bins each): handle i scatters into its side's tile, the walk
+// hands the step both sides' four cells and k_compare_wave's walk 2 follows (two wave scans, take4).  The tiles cover occupied
+// stretches only, and X is constant where no cell is: for the g bins between the end of the last step walked and the start
+// of the next tile's first, lane 0 adds g x the term once, just before that step (one product, one add).  Every bin from
+// the lowest to the highest occupied one thereby counts exactly once; bins beyond the last occupied one have A = na and
+// B = nb and add an exact 0.  Wave 0 alone walks in both shapes, so they agree bit for bit, sums included.  Device forms put
+// ALL handles of both lists under one hold.
+//
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
 // a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
@@ -68,6 +82,7 @@
 #include "../../include/loghisto_gpu_tuning.h"
 #include "lh_beside.h"
 #include "lh_codec.h"
+#include "lh_pair.h"
 #include "lh_pct.h"
 
 #include <hip/hip_runtime.h>
@@ -86,6 +101,15 @@ constexpr uint32_t KEPT_WAVE_FROM_DEFAULT = 1024; // lh_spread's default; profil
 constexpr uint32_t KEPT_TILE = 1024;              // bins of a tile: a lognormal name's union span fits one
 static_assert(KEPT_TILE % STEP == 0 && ROW_WAVES * KEPT_TILE * sizeof(u64) <= 65536, "whole steps; 64 KiB static LDS at most");
 static_assert(LH_MAX_KEPT == 64, "a handle per lane, their set in one 64-bit mask");
+// bins of each of the compare's two tiles (one per side): half the reader's width, 32 KiB static in the wave shape.  At the
+// reader's width that shape holds the 64 KiB a kernel may have static and measures a quarter slower at 65 536 names, while the
+// workgroup shape (calls of fewer than 1 024 rows) measures up to a third faster: profiles/kept_compare.txt has both widths.
+#ifndef LH_KEPT_COMPARE_TILE
+#define LH_KEPT_COMPARE_TILE 512
+#endif
+constexpr uint32_t KEPT_COMPARE_TILE = LH_KEPT_COMPARE_TILE;
+static_assert(KEPT_COMPARE_TILE % STEP == 0 && KEPT_COMPARE_TILE >= STEP && ROW_WAVES * 2 * KEPT_COMPARE_TILE * sizeof(u64) <= 65536,
+              "whole steps; 64 KiB static LDS at most");
 
 // one handle as the kernel sees it.  offsets at `block`, row_count = offsets + nrows + 1, counts = row_count + nrows, keys
 // behind counts.
@@ -260,8 +284,11 @@ struct Row {
 // handle's run inside it, then -- wave 0 of the NW that share the tile -- the ascending walk, 256 bins a step, which hands
 // step(C, base) the lane's four summed cells of bins base + 4 * lane .. + 3 and puts zeros back.  Every wave of a workgroup
 // takes the same turns: the state below is the same in all.  w: which of the NW scatterers this wave is; n: the handles.
-template <int NW, class Step>
-__device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t lane, uint32_t w, Step step)
+// With SIDES == 2 (the compare) the row has two tiles of TILE bins, the second right behind the first: handles 0 .. n0 - 1
+// add into the first and the others into the second, the walk hands step(A, B, base) the lane's four cells of each and
+// puts zeros back in both.  Between two tiles no step is taken: `base` jumps.
+template <int NW, int SIDES, uint32_t TILE, class Step>
+__device__ __forceinline__ void turns_of(Row &row, uint32_t n, uint32_t n0, u64 *tile, uint32_t lane, uint32_t w, Step step)
 {
     tile_sync<NW>(); // the tile is zero
     for (uint32_t from = 0;;) {
@@ -277,21 +304,23 @@ __device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t 
         }
         const uint32_t least = ~wave_max_u32(~row.next);
         if (least == NO_BIN) break;
-        const uint32_t t0 = least & ~3u, tend = t0 + KEPT_TILE;
+        const uint32_t t0 = least & ~3u, tend = t0 + TILE;
         // ---- scatter: handle i's run inside the tile, 64 entries a turn
         for (uint32_t i = w; i < n; i += NW) { // wave-uniform
             u64 c = readlane_u64(row.cur, i);
             const u64 e = readlane_u64(row.end, i);
             const gkeys kp = (gkeys)readlane_u64(row.keys, i);
             const gu64 cp = (gu64)readlane_u64(row.counts, i);
+            u64 *to = tile;
+            if constexpr (SIDES == 2) to = i < n0 ? tile : tile + TILE;
             while (c < e) {
                 const u64 idx = c + lane;
                 bool in = false;
                 if (idx < e) {
                     const uint32_t at = bin_of(kp[idx]) - t0;
-                    if (at < KEPT_TILE) {
+                    if (at < TILE) {
                         in = true;
-                        atomicAdd(&tile[at], cp[idx]);
+                        atomicAdd(&to[at], cp[idx]);
                     }
                 }
                 const uint32_t took = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
@@ -311,7 +340,17 @@ __device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t 
                     C[k] = tile[at + k];
                     tile[at + k] = 0;
                 }
-                step(C, base);
+                if constexpr (SIDES == 2) {
+                    u64 B[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        B[k] = tile[TILE + at + k];
+                        tile[TILE + at + k] = 0;
+                    }
+                    step(C, B, base);
+                } else {
+                    step(C, base);
+                }
             }
         }
         tile_sync<NW>();
@@ -319,13 +358,19 @@ __device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t 
         from = tend;
     }
 }
+// the one-sided turns of the reader and of lh_kept_merge's two passes
+template <int NW, class Step>
+__device__ __forceinline__ void turns(Row &row, uint32_t n, u64 *tile, uint32_t lane, uint32_t w, Step step)
+{
+    turns_of<NW, 1, KEPT_TILE>(row, n, n, tile, lane, w, step);
+}
 
 // the tile (of the kernel's s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE]), the scatterer and the entry of a call that this wave
-// works on, for the two shapes
-template <int NW> struct Seat {
+// works on, for the two shapes.  WORDS: what a row has in LDS (the compare's two tiles are one such block).
+template <int NW, uint32_t WORDS = KEPT_TILE> struct Seat {
     uint32_t lane, w, m;
     u64 *tile;
-    __device__ __forceinline__ Seat(u64 (*s_tile)[KEPT_TILE])
+    __device__ __forceinline__ Seat(u64 (*s_tile)[WORDS])
     {
         const uint32_t wave = threadIdx.x >> 6;
         lane = threadIdx.x & 63;
@@ -335,7 +380,7 @@ template <int NW> struct Seat {
     }
     __device__ __forceinline__ void clear() const
     {
-        for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < KEPT_TILE; i += NW * 64) tile[i] = 0;
+        for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < WORDS; i += NW * 64) tile[i] = 0;
     }
 };
 
@@ -448,6 +493,63 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const K
             }
         to += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
     });
+}
+
+// ---- lh_kept_compare ----------------------------------------------------------------------------------------------------------
+// Handles 0 .. nbase - 1 of the list are `base`, the others `cur`; rows as in k_kept_across.  One walk: k_compare_wave's walk 2
+// over the steps the tiles cover, and for the bins between two tiles -- X is constant there -- their number times the term,
+// added by lane 0 just before the step behind them.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const KeptList s, uint32_t nbase, uint32_t nmetrics,
+                                                                           uint32_t first, const CompareOut o,
+                                                                           const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share the tiles
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], r);
+    row.settle();
+    const u64 na = readlane_u64(wave_scan_incl_u64(lane < nbase ? row.rc : 0), 63);
+    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < nbase ? 0 : row.rc), 63);
+
+    Best b;
+    best_init(b);
+    if (na && nb) { // uniform
+        const Scale sc = make_scale(na, nb);
+        u64 ca = 0, cb = 0;        // what lies below the step
+        uint32_t behind = NO_BIN;  // the bin behind the last step taken (NO_BIN: none yet)
+        turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nbase, at.tile, lane, at.w,
+                                           [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+            if (behind != NO_BIN && base > behind && lane == 0) { // bins [behind, base) lie in no tile: the prefixes stay ca, cb
+                const u128 xa = (u128)ca * sc.nb, xb = (u128)cb * sc.na;
+                const bool up = xa >= xb;
+                const u128 x = up ? xa - xb : xb - xa;
+                const double t = (double)(base - behind) * ((double)(u64)(x >> sc.sh) / sc.den);
+                b.w += t;
+                b.s += up ? t : -t;
+            }
+            const u64 ta = sum4(A), tb = sum4(B);
+            const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+            take4(b, sc, base + 4 * lane, ca + (ia - ta), cb + (ib - tb), A, B);
+            ca += readlane_u64(ia, 63);
+            cb += readlane_u64(ib, 63);
+            behind = base + STEP;
+        });
+    }
+    if (at.w != 0) return;
+    u128 x;
+    uint32_t bin;
+    u64 ba, bb;
+    wave_best(b, x, bin, ba, bb);
+    const double w1 = readlane_f64(wave_scan_incl_f64(b.w), 63), shift = readlane_f64(wave_scan_incl_f64(b.s), 63);
+    if (lane == 0) store_row(o, m, na, nb, bin, ba, bb, w1, shift);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -696,6 +798,99 @@ int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nm
     return rc;
 }
 
+// ---- lh_kept_compare*
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`;
+// all[0 .. nbase) is the base list, all[nbase .. n) the cur list
+int enqueue_compare(KeptCtx *cx, lh_kept *const *all, size_t n, size_t nbase, const RowSel &sel, size_t nmetrics,
+                    const CompareOut &o, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    const KeptList s = list_of(all, n);
+    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nbase;
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_compare<IDS, 1>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o, ids);
+        else hipLaunchKernelGGL((k_kept_compare<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o, ids);
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const RowSel &sel, size_t nmetrics,
+                 uint32_t flags, void *stream, const CompareOut &o, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device
+    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
+    if (!base || !cur || misaligned(base, alignof(lh_kept *)) || misaligned(cur, alignof(lh_kept *))) return LH_EINVAL;
+    if (nbase == 0 || ncur == 0 || nbase > LH_MAX_KEPT || ncur > LH_MAX_KEPT || nbase + ncur > LH_MAX_KEPT) return LH_EINVAL;
+    lh_kept *all[LH_MAX_KEPT]; // one list, base first: a handle per lane
+    const size_t n = nbase + ncur;
+    for (size_t i = 0; i < n; i++) {
+        all[i] = i < nbase ? base[i] : cur[i - nbase];
+        if (!all[i]) return LH_EINVAL;
+    }
+    if (flags != 0) return LH_EINVAL;
+    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
+    if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
+        misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
+        return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    // ---- the rows every handle of either list has: [lo, end)
+    const int device = all[n - 1]->device;
+    for (size_t i = 0; i + 1 < n; i++)
+        if (all[i]->device != device) return LH_EINVAL;
+    u64 lo = 0, end = ~0ull;
+    for (size_t i = 0; i < n; i++) {
+        const u64 f = all[i]->first, e = f + all[i]->nrows;
+        lo = f > lo ? f : lo;
+        end = e < end ? e : end;
+    }
+    if (!sel.by_id) {
+        if (sel.first < lo || (u64)sel.first + nmetrics > end) return LH_ERANGE;
+    } else if (!sel.on_device) {
+        for (size_t m = 0; m < nmetrics; m++)
+            if (sel.ids[m] < lo || sel.ids[m] >= end) return LH_ERANGE;
+    }
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(device));
+    int rc;
+    if (device_form) {
+        rc = enqueue_compare(cx, all, n, nbase, sel, nmetrics, o, st);
+        if (rc) return rc;
+        rc = hold(cx, all, n, st); // the handles of BOTH lists
+        // what was enqueued reads handles that no event guards: wait here
+        if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+        return rc;
+    }
+    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys (lh_compare's blocks).
+    const size_t n8 = nmetrics * 8;
+    const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
+                            {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
+    rc = host_results(cx->res, st, out, [&](unsigned char *const(&dev)[8]) {
+        CompareOut d;
+        d.count_a = reinterpret_cast<u64 *>(dev[0]);
+        d.count_b = reinterpret_cast<u64 *>(dev[1]);
+        d.ks = reinterpret_cast<double *>(dev[2]);
+        d.below_a = reinterpret_cast<u64 *>(dev[3]);
+        d.below_b = reinterpret_cast<u64 *>(dev[4]);
+        d.w1 = reinterpret_cast<double *>(dev[5]);
+        d.shift = reinterpret_cast<double *>(dev[6]);
+        d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
+        return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
+    });
+    if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -846,6 +1041,49 @@ int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
 {
     const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
     return kept_across(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+}
+
+int lh_kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                    uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                    uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
+                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+    return kept_compare(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream, o, false);
+}
+
+int lh_kept_compare_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                           uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
+                           int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
+                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
+    return kept_compare(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream, o, true);
+}
+
+int lh_kept_compare_ids(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *ids, size_t n,
+                        uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                        uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
+                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+    return kept_compare(base, nbase, cur, ncur, rows_by_id(ids, false), n, flags, stream, o, false);
+}
+
+int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *d_ids,
+                               size_t n, uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
+                               int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
+                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
+    return kept_compare(base, nbase, cur, ncur, rows_by_id(d_ids, true), n, flags, stream, o, true);
+}
+
+int lh_tool_kept_compare_tile(uint32_t *bins)
+{
+    if (!bins) return LH_EINVAL;
+    *bins = KEPT_COMPARE_TILE;
+    return LH_OK;
 }
 
 int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous)

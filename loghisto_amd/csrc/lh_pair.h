@@ -1,5 +1,7 @@
 // lh_pair.h -- the device side of the units that walk TWO rows at once, a name in one snapshot against the same name in
-// another (lh_compare.hip, lh_movers.hip): what the walk is scaled by (Scale), a lane's state of it (Best), a lane's four
+// another (lh_compare.hip, lh_movers.hip), or in one list of kept intervals against another (lh_kept.hip's k_kept_compare):
+// what the walk is scaled by (Scale), a lane's state of it (Best), a name's results and the lane that stores them (CompareOut,
+// store_row), a lane's four
 // bins (take4) and the wave's largest X at its lowest bin (wave_best, without LDS: DPP max-reductions, lh_wave.h's wave_max_u32, over the
 // 32-bit words of X from the top).  lh_compare.hip's header says what X, ks, w1 and shift are; a unit that wants the bits of
 // k_compare_wave's sums calls these in its order: the steps in ascending order per lane, then one DPP tree over the lanes.
@@ -44,6 +46,34 @@ __device__ __forceinline__ void best_init(Best &r)
     r.bin = NO_BIN;
     r.a = r.b = 0;
     r.w = r.s = 0.0;
+}
+// A name's eight results, each null when not asked for (lh_compare*'s and lh_kept_compare*'s outputs)
+struct CompareOut {
+    u64 *count_a, *count_b;
+    double *ks;
+    int16_t *ks_key;
+    u64 *below_a, *below_b;
+    double *w1, *shift;
+};
+// one lane writes a name's results; bin == NO_BIN: the two normalised distributions are identical
+__device__ __forceinline__ void store_row(const CompareOut &o, uint32_t m, u64 na, u64 nb, uint32_t bin, u64 a, u64 b, double w1,
+                                          double shift)
+{
+    double ks = 0.0;
+    if (na == 0 || nb == 0) {
+        ks = w1 = shift = __builtin_nan("");
+        bin = NO_BIN;
+    }
+    if (bin == NO_BIN) a = b = 0;
+    else ks = fabs((double)a / (double)na - (double)b / (double)nb);
+    if (o.count_a) o.count_a[m] = na;
+    if (o.count_b) o.count_b[m] = nb;
+    if (o.ks) o.ks[m] = ks;
+    if (o.ks_key) o.ks_key[m] = bin == NO_BIN ? (int16_t)0 : (int16_t)bin_to_key(bin);
+    if (o.below_a) o.below_a[m] = a;
+    if (o.below_b) o.below_b[m] = b;
+    if (o.w1) o.w1[m] = w1;
+    if (o.shift) o.shift[m] = shift;
 }
 // the lane's four bins bin0 .. bin0 + 3; pa / pb: the prefixes below them
 __device__ __forceinline__ void take4(Best &r, const Scale &sc, uint32_t bin0, u64 pa, u64 pb, const u64 (&a)[4], const u64 (&b)[4])

@@ -846,6 +846,54 @@ class Kept:
                 "lh_kept_merge")
         return Kept(h, self._table)
 
+    def compare(self, base, nmetrics: Optional[int] = None, first: int = 0, earlier=(), ids=None, stream=None, out=None):
+        """Snapshot.compare over kept intervals (lh_kept_compare*): how metrics [first, first+nmetrics) -- or, with ids=, the
+        metrics `ids` in that order -- of list(earlier) + [self] taken together differ from the same names of `base`, a Kept or
+        a sequence of them taken together.  The same dict: count_a / count_b (base / here), ks, key, below_a, below_b,
+        ks_value, w1, shift, with NaN for a name that is empty on either side.  At most N.MAX_KEPT handles in the two lists
+        together; one may appear more than once, and in both lists.  first and ids are metric ids; every handle must hold
+        them.  nmetrics=None: up to the end of this handle's block.  out= as for Snapshot.compare; torch device tensors take
+        the device form, enqueued on `stream` (a torch stream or a raw handle; None: the null stream), and device ids go with
+        them.  Every handle may be closed right afterwards: close() waits."""
+        L = N.lib()
+        spec = Snapshot._COMPARE_OUT
+        lists = []
+        for kept in (([base] if isinstance(base, Kept) else list(base)), list(earlier) + [self]):
+            lists.append((C.c_void_p * max(len(kept), 1))(*[k._h.value for k in kept]))
+            lists.append(len(kept))
+        device_ids = None
+        if ids is not None:
+            keep, addr, nmetrics, device_ids = _id_list(ids)
+            fn, rows = "lh_kept_compare_ids", (addr, nmetrics)
+        else:
+            if nmetrics is None:
+                nmetrics = self.info["first"] + self.info["nrows"] - first
+            fn, rows = "lh_kept_compare", (first, nmetrics)
+        lead = (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3], *rows, 0, _stream_handle(stream))
+        if device_ids and out is None:
+            raise ValueError("device ids go with an out= of device tensors")
+        if out is not None:
+            args, device = _out_arrays(out, [(k, width, nmetrics) for k, width, _ in spec])
+            if device_ids is not None and device != device_ids:
+                raise ValueError("ids and out are both on the device or both on the host")
+            if device:
+                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
+                return dict(out)
+            N.check(getattr(L, fn)(*lead, *args), fn)
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()).reshape(nmetrics)
+                   for k, v in out.items() if v is not None}
+        else:
+            import torch
+            res = {}
+            for k, width, dt in spec:                  # (an element more than an empty call needs: the arrays have addresses)
+                res[k] = torch.zeros((max(nmetrics, 1) * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
+            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data for k, _, _ in spec]), fn)
+            res = {k: v[:nmetrics] for k, v in res.items()}
+        if "key" in res:
+            value = self._table[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
+            res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
+        return res
+
     def close(self):
         """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
         if self._h is not None and self._h.value:
