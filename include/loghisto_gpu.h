@@ -758,6 +758,69 @@ int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *cons
                                size_t n, uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
                                int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1,
                                double *d_shift);
+/* COUNTS AT OR BELOW VALUES, SPREAD AND TRIMMED SUMS OVER KEPT INTERVALS: lh_count_le* and lh_spread* over handles, the two
+ * per-name readers whose natural windows -- the last hour's SLO ratio and `le` buckets, the last minute's std / mean_90 / sum_90 /
+ * upper_90 -- exist only as handles.  With C[b] = the sum over the listed handles of the name's cell b, in 64 bits wrapping
+ * (lh_kept_across' C; a handle listed twice counts twice), every output is, word for word, what lh_count_le / lh_spread return
+ * for a snapshot whose cells are C (the walks: metrics.go:342-346 and 389-418): no dense buffer is alive or
+ * filled, nothing is summed across names, no new statistic is defined, and no handle, snapshot or engine is written.  The outputs
+ * are per-name columns in device memory in the device forms, which lh_lines* turns into wire lines as they are.
+ *   lh_kept_count_le, lh_kept_count_le_device, lh_kept_count_le_ids, lh_kept_count_le_ids_device
+ *                     cum[m * nb + j] = the sum of C[b] over the bins whose key is <= the key of bounds[j]; total[m] = the
+ *                     wrapping sum of the handles' row_count entries (no cell is read for it).  The bound-to-key rule, +-Inf,
+ *                     -0.0 and the saturation beyond the int16 key range are lh_count_le's; counts are exact uint64 sums that
+ *                     wrap past 2^64.  bounds is ONE HOST array of nb doubles shared by all names, which travels by value beside
+ *                     the list of handles.  flags must be 0: LH_LE_PER_METRIC is NOT supported here and returns LH_EINVAL -- a
+ *                     row of bounds per name would need a block in device memory guarded across streams, which is why the
+ *                     list itself travels by value.  One walk of the row, over its occupied stretches only.
+ *                     Checked on the host before any handle is looked at -- LH_EINVAL: (ids forms: NULL ids with n > 0,
+ *                     misaligned ids,) a NULL or misaligned list, nkept == 0 or > LH_MAX_KEPT, a NULL entry, nb == 0 or
+ *                     nb > LH_MAX_BOUNDS, NULL bounds, both outputs NULL (either one may be), flags != 0, arrays not 8-byte
+ *                     aligned, a NaN bound, a decreasing row of bounds (equal neighbours are allowed; -0.0 == 0.0); then
+ *                     LH_ERANGE: nmetrics > 0xffffffff.  (The bounds being one shared row, every cause of LH_EINVAL comes before
+ *                     that LH_ERANGE.)
+ *   lh_kept_spread, lh_kept_spread_device, lh_kept_spread_ids, lh_kept_spread_ids_device
+ *                     count, sum, m2 and, per p[i], pkeys, pvalid, count_le, sum_le: lh_spread's definitions -- m2 the CENTRED
+ *                     second moment about sum / float64(count), taken in a second walk; the percentile's bucket the first bin
+ *                     whose inclusive prefix reaches T (metrics.go:413); D[] bit for bit lh_codec_tables'.  count is the wrapping
+ *                     sum of the handles' row_count entries, so the thresholds are known before a cell is read.  count == 0:
+ *                     every output of the name is 0.  np <= LH_MAX_PERCENTILES; np == 0 is allowed: moments only, the four
+ *                     per-percentile outputs are ignored.  Any output may be NULL, but not all.  flags must be 0.  Totals that
+ *                     wrap past 2^64: count wraps, the other outputs are unspecified (nothing faults).  Every floating-point sum
+ *                     is taken in ONE fixed order, the same in both kernel shapes, which therefore agree BIT FOR BIT on every
+ *                     output (lh_spread's own two shapes agree to rounding only); sum, m2 and sum_le differ from lh_spread's on
+ *                     a snapshot of the same cells in the last bits only.
+ *                     Checked on the host before any handle is looked at -- LH_EINVAL: (ids forms as above,) a NULL or
+ *                     misaligned list, nkept == 0 or > LH_MAX_KEPT, a NULL entry, flags != 0, np too large, np > 0 with NULL p,
+ *                     all outputs NULL, arrays not aligned to their element size; then LH_ERANGE: nmetrics > 0xffffffff.
+ *   Both families, as lh_kept_across*: nmetrics == 0 / n == 0 -> LH_OK before any handle is looked at, nothing written; then
+ *   LH_ERANGE, nothing enqueued and nothing written, unless [first, first + nmetrics) -- `first` and ids are ABSOLUTE row numbers
+ *   -- or every HOST id lies inside EVERY handle's block; LH_EINVAL for handles on different devices.  A DEVICE id outside some
+ *   handle's block yields the empty entry (all zeros), and nothing is read for it.  ORDERING and staging as for lh_kept_across*:
+ *   the work goes on `stream` (a hipStream_t of the handles' device; NULL: its null stream); host forms return with the results
+ *   in the caller's arrays (pinned arrays by one copy each, others through a pinned block of the library's); device forms return
+ *   after enqueueing, with ALL listed handles under one hold, so that lh_kept_release waits for the call.  bounds and p are HOST
+ *   arrays in all forms.  The rows of a call choose between the reader's two kernel shapes (lh_tool_kept_switch). */
+int lh_kept_count_le(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
+                     uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_count_le_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
+                            uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_count_le_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *bounds, size_t nb,
+                         uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_count_le_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *bounds,
+                                size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_spread(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                   uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid,
+                   uint64_t *count_le, double *sum_le);
+int lh_kept_spread_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                          uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
+                          uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le);
+int lh_kept_spread_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np,
+                       uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid,
+                       uint64_t *count_le, double *sum_le);
+int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                              uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
+                              uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

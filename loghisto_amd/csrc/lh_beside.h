@@ -220,6 +220,13 @@ inline RowSel rows_from(uint32_t first) { return RowSel{first, nullptr, false, f
 inline RowSel rows_by_id(const uint32_t *ids, bool on_device) { return RowSel{0, ids, true, on_device}; }
 // the *_ids forms' own causes of LH_EINVAL, decided before anything else (so that they win over the early LH_ERANGE)
 inline bool bad_ids(const RowSel &sel, size_t n) { return sel.by_id && ((!sel.ids && n > 0) || misaligned(sel.ids, 4)); }
+// a row of lh_count_le*'s bounds that no call takes: a NaN, or a decreasing pair (-0.0 == 0.0; equal neighbours are allowed)
+inline bool bad_bounds(const double *b, size_t nb)
+{
+    for (size_t j = 0; j < nb; j++)
+        if (b[j] != b[j] || (j && b[j] < b[j - 1])) return true;
+    return false;
+}
 // LH_ERANGE for rows a snapshot of `nrows` rows does not have: the end of the block, or the first id of a host list at or
 // beyond nrows.  (A device list is not looked at.)  n <= 2^32 - 1: the units' argument checks came first.
 inline int rows_in(const RowSel &sel, size_t n, uint32_t nrows)

@@ -195,11 +195,8 @@ int check_args(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double 
     if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32): not a row of bounds is read
     const size_t rows = (flags & LH_LE_PER_METRIC) ? nmetrics : 1;
-    for (size_t r = 0; r < rows; r++) {
-        const double *b = bounds + r * nb;
-        for (size_t j = 0; j < nb; j++)
-            if (b[j] != b[j] || (j && b[j] < b[j - 1])) return LH_EINVAL; // NaN / a decreasing row (-0.0 == 0.0)
-    }
+    for (size_t r = 0; r < rows; r++)
+        if (bad_bounds(bounds + r * nb, nb)) return LH_EINVAL; // NaN / a decreasing row (-0.0 == 0.0)
     return LH_OK;
 }
 

@@ -1,5 +1,5 @@
 // lh_kept.hip -- lh_keep / lh_kept_* (include/loghisto_gpu.h): an interval's occupied cells kept in COMPACT form in device
-// memory after its snapshot is gone, and lh_across' outputs over a list of up to 64 such copies -- p99 over the last minute
+// memory after its snapshot is gone, and lh_across' (further down: lh_compare's, lh_count_le's, lh_spread's) outputs over a list of up to 64 such copies -- p99 over the last minute
 // of 1 s intervals while no dense epoch buffer of them is alive.  A dense buffer is 4 GiB at 8 192 names; the occupied cells
 // of an interval are a few hundred (int16 key, uint64 count) pairs per name (RawMetricSet.Histograms, metrics.go:54-60).
 // With c_i[b] the cells of a name in kept[i]:
@@ -61,6 +61,24 @@
 // the lowest to the highest occupied one thereby counts exactly once; bins beyond the last occupied one have A = na and
 // B = nb and add an exact 0.  Wave 0 alone walks in both shapes, so they agree bit for bit, sums included.  Device forms put
 // ALL handles of both lists under one hold.
+//
+// THE TWO OTHER PER-NAME READERS, lh_kept_count_le* and lh_kept_spread*: lh_count_le's and lh_spread's outputs, word for word, for
+// a snapshot whose cells are C -- the last hour's SLO ratio and `le` buckets, the last minute's std and trimmed sums, with no
+// dense buffer alive.  Both take the reader's Row and turns as they are, in its two shapes behind the same switch.
+//   k_kept_count_le  ONE turn with k_count_le_wave's step: lane j owns bound j (E = le_take, lh_wave.h), and the prefix is
+//                    fetched from the lane that owns the bound's bin only in a step some pending bound falls into.  `base` jumps
+//                    between tiles: a pending bound whose E is at or below the step's base lies before the first tile or in a
+//                    stretch no tile covers and takes the running carry; one beyond the last step takes everything.  total is
+//                    the wrapping sum of the row_count entries.  The bounds are one row shared by all names and travel by value
+//                    beside the list (512 + 1 544 bytes); a row per name (LH_LE_PER_METRIC) would need a guarded device block
+//                    -- see the next paragraph -- and is refused.  Integer sums only: the shapes agree exactly.
+//   k_kept_spread    TWO turns over the same row (the opened Row is kept and taken again; the tile is zero on return).  The
+//                    count comes from row_count, so the thresholds are known before a cell is read.  Walk 1: sum.  Walk 2:
+//                    k_spread_wave's -- m2 about sum / float64(count) and, in the steps a threshold falls into, key, count_le
+//                    and sum_le (central4 and sums_in_step, which lh_pct.h now holds for both units), with the unit's d_table.
+//                    Wave 0 alone walks in both shapes, per lane over the steps in ascending order, then one DPP tree over the
+//                    lanes: the two shapes agree BIT FOR BIT, floating-point outputs included (lh_spread's own two shapes
+//                    associate differently and agree to rounding only).
 //
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
@@ -552,6 +570,155 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const
     if (lane == 0) store_row(o, m, na, nb, bin, ba, bb, w1, shift);
 }
 
+// ---- lh_kept_count_le ---------------------------------------------------------------------------------------------------------
+// the bounds, shared by all names, by value in the kernel arguments (512 bytes beside the list's 1 544)
+struct KeptBounds { double b[LH_MAX_BOUNDS]; };
+
+// Rows as in k_kept_across.  One turn over the row with k_count_le_wave's step: lane j owns bound j, which takes in the first
+// E = le_take(bounds[j]) bins, and the prefix at bin E - 1 is fetched from the lane that owns it only in a step some pending
+// bound falls into.  `base` jumps between tiles: a pending bound whose E is at or below the step's base lies before the first
+// tile or in a stretch no tile covers, and takes the running carry; one beyond the last step takes everything.  total is the
+// wrapping sum of the handles' row_count entries: no cell is read for it (and the row is walked whatever it is: cells whose
+// sum wraps to 0 still count towards cum).  Integer sums only: the two shapes agree exactly.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                            const KeptBounds sb, uint32_t nb, u64 *__restrict__ cum,
+                                                                            u64 *__restrict__ total,
+                                                                            const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], r);
+    row.settle();
+    const u64 tot = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+
+    uint32_t E = 0;
+    if (lane < nb) E = le_take(sb.b[lane]);
+    bool pend = lane < nb && E > 0; // a bound that takes in no bin: 0
+    u64 res = 0, carry = 0;
+    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        if (pend && E <= base) { // every bin it takes in lies below this step: what the steps so far hold
+            res = carry;
+            pend = false;
+        }
+        const u64 t = sum4(C);
+        const u64 inc = wave_scan_incl_u64(t);
+        // (every pending E is > base now)
+        const bool in = pend && E <= base + STEP;
+        if (__builtin_amdgcn_ballot_w64(in)) { // wave-uniform
+            const uint32_t idx = in ? E - 1 - base : 0, f = idx >> 2, k = idx & 3;
+            const u64 p0 = carry + (inc - t) + C[0], p1 = p0 + C[1], p2 = p1 + C[2], p3 = p2 + C[3];
+            const u64 v0 = shfl_u64(p0, f), v1 = shfl_u64(p1, f), v2 = shfl_u64(p2, f), v3 = shfl_u64(p3, f);
+            if (in) {
+                res = k == 0 ? v0 : k == 1 ? v1 : k == 2 ? v2 : v3;
+                pend = false;
+            }
+        }
+        carry += readlane_u64(inc, 63);
+    });
+    if (at.w != 0) return;
+    if (pend) res = carry; // beyond the last step: everything
+    if (cum && lane < nb) cum[(size_t)m * nb + lane] = res;
+    if (total && lane == 0) total[m] = tot;
+}
+
+// ---- lh_kept_spread -----------------------------------------------------------------------------------------------------------
+// Rows as in k_kept_across.  lh_spread's two walks as TWO turns over the same row (the turns advance the cursors: the opened
+// Row is kept and taken again; the tile is zero on return).  The count is the sum of the row_count entries, so the thresholds
+// are known before a cell is read.  Walk 1: sum.  Walk 2: k_spread_wave's -- the centred moment about sum / float64(count) and,
+// in the steps a threshold falls into, the key, count_le and sum_le (lh_pct.h's central4, sums_in_step).  Wave 0 alone walks
+// in both shapes, per lane over the steps in ascending order, then one DPP tree over the lanes: the shapes agree bit for bit.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                          const double *__restrict__ D, const PctArgs pa,
+                                                                          uint32_t np, const SpreadOut o,
+                                                                          const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], r);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    const uint32_t hi = row.hi;
+
+    double sum = 0.0, m2 = 0.0, r_sle = 0.0;
+    u64 r_cle = 0;
+    Open pct; // lane i < np: percentile i
+    if (total) { // uniform
+        const Row opened = row;
+        // ---- walk 1: the sum
+        double ps = 0.0;
+        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+            double d[4], t[4];
+            load4_values(D, base + 4 * lane, hi, d);
+            ps += terms4(C, d, t);
+        });
+        sum = readlane_f64(wave_scan_incl_f64(ps), 63); // (wave 0's: the others walk nothing, here and below)
+        // ---- walk 2: the centred moment; the steps the thresholds fall into
+        const double mean = sum / (double)total;
+        pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
+        double run = 0.0, q = 0.0; // the lane's terms of the steps so far; its share of m2
+        row = opened;
+        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+            double d[4], t[4];
+            load4_values(D, base + 4 * lane, hi, d);
+            q += central4(C, d, mean);
+            const double ts = terms4(C, d, t);
+            if (pct.todo) { // wave-uniform
+                const u64 tc = sum4(C);
+                uint32_t here = pct.ending(tc);
+                if (here) {
+                    u64 pre[4];
+                    pct.prefixes(C, tc, pre);
+                    const double sbefore = readlane_f64(wave_scan_incl_f64(run), 63);
+                    const double incs = wave_scan_incl_f64(ts);
+                    for (; here; here &= here - 1) {
+                        const uint32_t i = (uint32_t)__builtin_ctz(here);
+                        u64 cle;
+                        double sle;
+                        const uint32_t idx = sums_in_step(pre, t, incs, sbefore, pct.threshold(i), cle, sle);
+                        if (lane == i) {
+                            pct.found = base + idx;
+                            r_cle = cle;
+                            r_sle = sle;
+                        }
+                    }
+                }
+            }
+            run += ts;
+        });
+        m2 = readlane_f64(wave_scan_incl_f64(q), 63);
+    }
+    if (at.w != 0) return;
+    if (lane == 0) {
+        if (o.count) o.count[m] = total;
+        if (o.sum) o.sum[m] = sum;
+        if (o.m2) o.m2[m] = m2;
+    }
+    if (lane < np) {
+        const size_t to = (size_t)m * np + lane;
+        store_pct(o.pkeys, o.pvalid, to, pct.found);
+        if (o.count_le) o.count_le[to] = r_cle;
+        if (o.sum_le) o.sum_le[to] = r_sle;
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // behind a device-form call's kernel (or lh_kept_hold's caller's work); `users` handles point to it
 struct CallEvent {
@@ -732,6 +899,58 @@ int hold(KeptCtx *cx, lh_kept *const *kept, size_t nkept, hipStream_t st)
     return LH_OK;
 }
 
+// ---- what the readers of a list share behind their own argument checks --------------------------------------------------------
+// The two checks that look at the handles.  LH_ERANGE unless every row asked for lies inside EVERY handle's block: the rows
+// they all have are [lo, end).  (A device id list is not looked at: the kernels give a row outside a block the empty entry.)
+int rows_in_all(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics)
+{
+    u64 lo = 0, end = ~0ull;
+    for (size_t i = 0; i < nkept; i++) {
+        const u64 f = kept[i]->first, e = f + kept[i]->nrows;
+        lo = f > lo ? f : lo;
+        end = e < end ? e : end;
+    }
+    if (!sel.by_id) {
+        if (sel.first < lo || (u64)sel.first + nmetrics > end) return LH_ERANGE;
+    } else if (!sel.on_device) {
+        for (size_t m = 0; m < nmetrics; m++)
+            if (sel.ids[m] < lo || sel.ids[m] >= end) return LH_ERANGE;
+    }
+    return LH_OK;
+}
+// LH_EINVAL unless all handles are on one device, which *device then names
+int one_device(lh_kept *const *kept, size_t nkept, int *device)
+{
+    *device = kept[nkept - 1]->device;
+    for (size_t i = 0; i + 1 < nkept; i++)
+        if (kept[i]->device != *device) return LH_EINVAL;
+    return LH_OK;
+}
+// The way of a call from there on: the unit's context on the handles' device, its mutex for the length of the call, the
+// device made current.  A device form's work -- direct(cx, st) enqueues it on the caller's stream -- goes under ONE hold of
+// all listed handles; a host form's -- through(cx, st) brings the results back to the caller's arrays and waits -- leaves
+// nothing of the call under way, after a failure either.
+template <class Direct, class Through>
+int run(lh_kept *const *kept, size_t nkept, int device, void *stream, bool device_form, Direct direct, Through through)
+{
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(device));
+    int rc;
+    if (device_form) {
+        rc = direct(cx, st);
+        if (rc) return rc;
+        rc = hold(cx, kept, nkept, st);
+        // what was enqueued reads handles that no event guards: wait here
+        if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+        return rc;
+    }
+    rc = through(cx, st);
+    if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
+    return rc;
+}
 // (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
 int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
             const KeptOut &o, hipStream_t st)
@@ -762,40 +981,126 @@ int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nm
     int rc = check_list_args(kept, nkept, LH_MAX_KEPT, sel, nmetrics, p, np, flags, o);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any handle is looked at
-    // the rows every handle has: [lo, end)
-    u64 lo = 0, end = ~0ull;
-    for (size_t i = 0; i < nkept; i++) {
-        const u64 f = kept[i]->first, e = f + kept[i]->nrows;
-        lo = f > lo ? f : lo;
-        end = e < end ? e : end;
-    }
-    if (!sel.by_id) {
-        if (sel.first < lo || (u64)sel.first + nmetrics > end) return LH_ERANGE;
-    } else if (!sel.on_device) {
-        for (size_t m = 0; m < nmetrics; m++)
-            if (sel.ids[m] < lo || sel.ids[m] >= end) return LH_ERANGE;
-    }
-    const int device = kept[nkept - 1]->device;
-    for (size_t i = 0; i + 1 < nkept; i++)
-        if (kept[i]->device != device) return LH_EINVAL;
-    KeptCtx *cx = device_ctx<KeptCtx>(device);
-    if (!cx) return LH_EDEVICE;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> g(cx->mu);
-    LH_BESIDE_CHK(hipSetDevice(device));
-    if (device_form) {
-        rc = enqueue(cx, kept, nkept, sel, nmetrics, p, np, o, st);
-        if (rc) return rc;
-        rc = hold(cx, kept, nkept, st);
-        // what was enqueued reads handles that no event guards: wait here
-        if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-        return rc;
-    }
-    // host form: results to HBM, then back to the caller's arrays
-    rc = list_host_results(cx->res, st, o, nmetrics, np,
-                           [&](const KeptOut &d) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st); });
-    if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
-    return rc;
+    int device = -1;
+    rc = rows_in_all(kept, nkept, sel, nmetrics);
+    if (!rc) rc = one_device(kept, nkept, &device);
+    if (rc) return rc;
+    return run(
+        kept, nkept, device, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, o, st); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            return list_host_results(cx->res, st, o, nmetrics, np,
+                                     [&](const KeptOut &d) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st); });
+        });
+}
+
+// ---- lh_kept_count_le*
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
+int enqueue_count_le(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *bounds,
+                     size_t nb, u64 *d_cum, u64 *d_total, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    KeptBounds sb;
+    for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_count_le<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, sb, NB, d_cum, d_total, ids);
+        else hipLaunchKernelGGL((k_kept_count_le<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, sb, NB, d_cum, d_total, ids);
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+// a list of 1 .. LH_MAX_KEPT handles, none of them NULL (LH_EINVAL), as check_list_args has it
+bool bad_list(lh_kept *const *kept, size_t nkept)
+{
+    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return true;
+    for (size_t i = 0; i < nkept; i++)
+        if (!kept[i]) return true;
+    return false;
+}
+
+int kept_count_le(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb,
+                  uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: lh_count_le's, with the list in the snapshot's place.  The bounds
+    // are one shared row (LH_LE_PER_METRIC is refused with every other flag), so every cause of LH_EINVAL comes first.
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept)) return LH_EINVAL;
+    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
+    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
+    if (bad_bounds(bounds, nb)) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    int device = -1;
+    int rc = rows_in_all(kept, nkept, sel, nmetrics);
+    if (!rc) rc = one_device(kept, nkept, &device);
+    if (rc) return rc;
+    u64 *c = reinterpret_cast<u64 *>(cum), *t = reinterpret_cast<u64 *>(total);
+    return run(
+        kept, nkept, device, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return enqueue_count_le(cx, kept, nkept, sel, nmetrics, bounds, nb, c, t, st); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            const HostOut out[2] = {{cum, nmetrics * nb * sizeof(u64)}, {total, nmetrics * sizeof(u64)}};
+            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) {
+                return enqueue_count_le(cx, kept, nkept, sel, nmetrics, bounds, nb, reinterpret_cast<u64 *>(dev[0]),
+                                        reinterpret_cast<u64 *>(dev[1]), st);
+            });
+        });
+}
+
+// ---- lh_kept_spread*
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
+int enqueue_spread(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
+                   const SpreadOut &o, hipStream_t st)
+{
+    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    const uint32_t *ids = nullptr;
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    const PctArgs pa = pct_args(p, np);
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
+    const double *D = cx->d_table;
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    const auto launch = [&](auto by_id) {
+        constexpr bool IDS = decltype(by_id)::value;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_spread<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
+        else hipLaunchKernelGGL((k_kept_spread<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
+    };
+    if (sel.by_id) launch(std::true_type());
+    else launch(std::false_type());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+
+int kept_spread(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+                void *stream, SpreadOut o, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: lh_spread's, with the list in the snapshot's place
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept) || flags != 0) return LH_EINVAL;
+    int rc = check_spread_args(p, np, o);
+    if (rc) return rc;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    int device = -1;
+    rc = rows_in_all(kept, nkept, sel, nmetrics);
+    if (!rc) rc = one_device(kept, nkept, &device);
+    if (rc) return rc;
+    return run(
+        kept, nkept, device, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return enqueue_spread(cx, kept, nkept, sel, nmetrics, p, np, o, st); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            return spread_host_results(cx->res, st, o, nmetrics, np, [&](const SpreadOut &d) {
+                return enqueue_spread(cx, kept, nkept, sel, nmetrics, p, np, d, st);
+            });
+        });
 }
 
 // ---- lh_kept_compare*
@@ -841,54 +1146,32 @@ int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t
         return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    // ---- the rows every handle of either list has: [lo, end)
-    const int device = all[n - 1]->device;
-    for (size_t i = 0; i + 1 < n; i++)
-        if (all[i]->device != device) return LH_EINVAL;
-    u64 lo = 0, end = ~0ull;
-    for (size_t i = 0; i < n; i++) {
-        const u64 f = all[i]->first, e = f + all[i]->nrows;
-        lo = f > lo ? f : lo;
-        end = e < end ? e : end;
-    }
-    if (!sel.by_id) {
-        if (sel.first < lo || (u64)sel.first + nmetrics > end) return LH_ERANGE;
-    } else if (!sel.on_device) {
-        for (size_t m = 0; m < nmetrics; m++)
-            if (sel.ids[m] < lo || sel.ids[m] >= end) return LH_ERANGE;
-    }
-    KeptCtx *cx = device_ctx<KeptCtx>(device);
-    if (!cx) return LH_EDEVICE;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> g(cx->mu);
-    LH_BESIDE_CHK(hipSetDevice(device));
-    int rc;
-    if (device_form) {
-        rc = enqueue_compare(cx, all, n, nbase, sel, nmetrics, o, st);
-        if (rc) return rc;
-        rc = hold(cx, all, n, st); // the handles of BOTH lists
-        // what was enqueued reads handles that no event guards: wait here
-        if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-        return rc;
-    }
-    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys (lh_compare's blocks).
-    const size_t n8 = nmetrics * 8;
-    const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
-                            {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
-    rc = host_results(cx->res, st, out, [&](unsigned char *const(&dev)[8]) {
-        CompareOut d;
-        d.count_a = reinterpret_cast<u64 *>(dev[0]);
-        d.count_b = reinterpret_cast<u64 *>(dev[1]);
-        d.ks = reinterpret_cast<double *>(dev[2]);
-        d.below_a = reinterpret_cast<u64 *>(dev[3]);
-        d.below_b = reinterpret_cast<u64 *>(dev[4]);
-        d.w1 = reinterpret_cast<double *>(dev[5]);
-        d.shift = reinterpret_cast<double *>(dev[6]);
-        d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
-        return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
-    });
-    if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
-    return rc;
+    // ---- the handles are looked at: one device, and the rows every handle of either list has
+    int device = -1;
+    int rc = one_device(all, n, &device);
+    if (!rc) rc = rows_in_all(all, n, sel, nmetrics);
+    if (rc) return rc;
+    return run(
+        all, n, device, stream, device_form, // (a device form's hold: the handles of BOTH lists)
+        [&](KeptCtx *cx, hipStream_t st) { return enqueue_compare(cx, all, n, nbase, sel, nmetrics, o, st); },
+        [&](KeptCtx *cx, hipStream_t st) {
+            // results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys (lh_compare's blocks).
+            const size_t n8 = nmetrics * 8;
+            const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
+                                    {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
+            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[8]) {
+                CompareOut d;
+                d.count_a = reinterpret_cast<u64 *>(dev[0]);
+                d.count_b = reinterpret_cast<u64 *>(dev[1]);
+                d.ks = reinterpret_cast<double *>(dev[2]);
+                d.below_a = reinterpret_cast<u64 *>(dev[3]);
+                d.below_b = reinterpret_cast<u64 *>(dev[4]);
+                d.w1 = reinterpret_cast<double *>(dev[5]);
+                d.shift = reinterpret_cast<double *>(dev[6]);
+                d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
+                return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
+            });
+        });
 }
 
 } // namespace
@@ -1077,6 +1360,64 @@ int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *cons
     const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
                           reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
     return kept_compare(base, nbase, cur, ncur, rows_by_id(d_ids, true), n, flags, stream, o, true);
+}
+
+int lh_kept_count_le(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
+                     uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_count_le(kept, nkept, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_count_le_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
+                            uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_count_le(kept, nkept, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_count_le_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *bounds, size_t nb,
+                         uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_count_le(kept, nkept, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_count_le_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *bounds, size_t nb,
+                                uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_count_le(kept, nkept, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_spread(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
+                   void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le,
+                   double *sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
+    return kept_spread(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+}
+
+int lh_kept_spread_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
+                          uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
+                          uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
+                         d_sum_le};
+    return kept_spread(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+}
+
+int lh_kept_spread_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np, uint32_t flags,
+                       void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le,
+                       double *sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
+    return kept_spread(kept, nkept, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+}
+
+int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
+                              uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
+                              uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
+                         d_sum_le};
+    return kept_spread(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
 }
 
 int lh_tool_kept_compare_tile(uint32_t *bins)

@@ -4,16 +4,19 @@
 //   PctArgs, pct_args         the percentiles, by value in the kernel arguments, and the host loop that fills them
 //   occupied4, load4_values   a 4-bin group's occupied bins; its entries of the value table alone
 //   prefix4, locate_in_step, find_in_step   the prefixes at a lane's four bins; where, inside a step of 256, they reach T
+//   central4, sums_in_step, SpreadOut       the spread readers' walk 2: a group's centred terms, the search that also returns
+//                                           count_le and sum_le, and their out record
 //   Open                      the open thresholds of a wave that walks a row in ascending steps (a percentile per lane)
 //   scan_chunks, chunk_of     the workgroup shape: wave 0's scan of the chunk totals in LDS, the chunk a threshold falls into
 //   store_pct                 a percentile's key and flag
 // Three pieces keep a text of their own, each with a comment at the place (profiles/pct_walk_isa.txt has the figures):
-// lh_spread.hip's search, which also returns count_le and sum_le (sums_in_step), k_spread_block's pre[4] (through prefix4
+// the spread readers' search, which also returns count_le and sum_le (sums_in_step, below), k_spread_block's pre[4] (through prefix4
 // that kernel measures 1 % slower) and k_top_score's search (through find_in_step its code comes out reordered).  And K2's
 // copy of the step (lh_kernels.hip's k_extract_wave, pass 2): that file and every header it includes are what the committed
 // profiles are stamped with, so it cannot include this one.  A change to the step goes to those four too, by hand.
 // The host side is in this header as well, behind the device part: the out record (ListOut), its way through host_results
-// and the argument check of the two readers of a LIST of sources, lh_across.hip (snapshots) and lh_kept.hip (kept intervals).
+// and the argument check of the two readers of a LIST of sources, lh_across.hip (snapshots) and lh_kept.hip (kept intervals);
+// the same two for the spread readers (check_spread_args, spread_host_results).
 #pragma once
 
 #include "lh_beside.h"
@@ -74,6 +77,42 @@ __device__ __forceinline__ uint32_t find_in_step(const u64 (&pre)[4], u64 T)
 {
     const InStep h = locate_in_step(pre, T);
     return 4 * h.lane + (uint32_t)__builtin_amdgcn_readlane((int)h.below, (int)h.lane);
+}
+
+// float64(count) * (value - mean)^2 of a lane's four bins (an empty cell adds +0)
+__device__ __forceinline__ double central4(const u64 (&c)[4], const double (&d)[4], double mean)
+{
+    double q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const double dev = d[k] - mean;
+        q[k] = (double)c[k] * (dev * dev);
+    }
+    return (q[0] + q[1]) + (q[2] + q[3]);
+}
+
+// find_in_step with what the spread readers add (lh_spread.hip's two kernels, lh_kept.hip's k_kept_spread), in one piece as it
+// was in lh_spread.hip (on top of locate_in_step that unit's kernels come out reordered, and without that function's guard for
+// an empty ballot, which this text never had).
+// One step of 256 bins in which threshold T is reached (wave-uniform T; `before` counts / `sbefore` sums everything below
+// the step).  pre[k]: inclusive prefix count at the lane's bin k; t[k]: the bins' terms; incs: inclusive scan over the lanes
+// of the terms' sums.  Returns the index of the bin inside the step, the prefix count and the prefix sum there.
+__device__ __forceinline__ uint32_t sums_in_step(const u64 (&pre)[4], const double (&t)[4], double incs, double sbefore, u64 T,
+                                                 u64 &cle, double &sle)
+{
+    // the first lane whose last bin reaches T (lane 63's does), and how many of its bins stay below
+    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
+    const uint32_t f = (uint32_t)__builtin_ctzll(reach);
+    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
+    const u64 csel = below == 0 ? pre[0] : below == 1 ? pre[1] : below == 2 ? pre[2] : pre[3];
+    double psel = t[0];
+    if (below >= 1) psel += t[1];
+    if (below >= 2) psel += t[2];
+    if (below >= 3) psel += t[3];
+    const double lanes_below = readlane_f64(incs, f ? f - 1 : 0);
+    cle = readlane_u64(csel, f);
+    sle = (sbefore + (f ? lanes_below : 0.0)) + readlane_f64(psel, f);
+    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
 }
 
 // The thresholds of a row that a wave walks in ascending steps of 256 bins: lane i < np owns percentile i, the smallest
@@ -177,6 +216,16 @@ __device__ __forceinline__ void store_pct(int16_t *pkeys, uint8_t *pvalid, size_
     if (pvalid) pvalid[at] = ok ? 1 : 0;
 }
 
+// the seven outputs of the spread readers (lh_spread*, lh_kept_spread*), each null when not asked for
+struct SpreadOut {
+    u64 *count;
+    double *sum, *m2;
+    int16_t *pkeys;
+    uint8_t *pvalid;
+    u64 *count_le;
+    double *sum_le;
+};
+
 // ---- host side: the readers of a list of sources ------------------------------------------------------------------------
 namespace beside {
 
@@ -237,6 +286,45 @@ int check_list_args(H *const *list, size_t n, size_t most, const RowSel &sel, si
         return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     return LH_OK;
+}
+
+// ---- the spread readers (lh_spread.hip over a snapshot, lh_kept.hip over kept intervals) ---------------------------------------
+// Their checks of the percentiles and the seven outputs, which need neither a source nor a device (LH_EINVAL, or LH_OK).  With
+// np == 0 the per-percentile outputs are ignored: they are nulled here, and count for nothing.
+inline int check_spread_args(const double *p, size_t np, SpreadOut &o)
+{
+    if (np > LH_MAX_PERCENTILES || (np && !p)) return LH_EINVAL;
+    if (np == 0) {
+        o.pkeys = nullptr;
+        o.pvalid = nullptr;
+        o.count_le = nullptr;
+        o.sum_le = nullptr;
+    }
+    if (!o.count && !o.sum && !o.m2 && !o.pkeys && !o.pvalid && !o.count_le && !o.sum_le) return LH_EINVAL;
+    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.m2, 8) ||
+        misaligned(o.pkeys, 2) || misaligned(o.count_le, 8) || misaligned(o.sum_le, 8))
+        return LH_EINVAL;
+    return LH_OK;
+}
+// (the context's mutex held)  Their host form: `enqueue(d)` puts the work that fills d -- o's arrays, in HBM -- on `st`.  The
+// 8-byte arrays, then the keys, then the flags.
+template <class Enqueue>
+int spread_host_results(ResultBlocks &rb, hipStream_t st, const SpreadOut &o, size_t nmetrics, size_t np, Enqueue enqueue)
+{
+    const size_t per_m = nmetrics, per_p = nmetrics * np;
+    const HostOut out[7] = {{o.count, per_m * 8},    {o.sum, per_m * 8},    {o.m2, per_m * 8},   {o.count_le, per_p * 8},
+                            {o.sum_le, per_p * 8}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
+    return host_results(rb, st, out, [&](unsigned char *const(&dev)[7]) {
+        SpreadOut d;
+        d.count = reinterpret_cast<u64 *>(dev[0]);
+        d.sum = reinterpret_cast<double *>(dev[1]);
+        d.m2 = reinterpret_cast<double *>(dev[2]);
+        d.count_le = reinterpret_cast<u64 *>(dev[3]);
+        d.sum_le = reinterpret_cast<double *>(dev[4]);
+        d.pkeys = reinterpret_cast<int16_t *>(dev[5]);
+        d.pvalid = reinterpret_cast<uint8_t *>(dev[6]);
+        return enqueue(d);
+    });
 }
 
 } // namespace beside

@@ -53,49 +53,7 @@ using namespace lh::beside;
 // which may be wide, get workgroups.
 constexpr uint32_t SP_WAVE_FROM_DEFAULT = 1024;
 
-struct SpreadOut {
-    u64 *count;
-    double *sum, *m2;
-    int16_t *pkeys;
-    uint8_t *pvalid;
-    u64 *count_le;
-    double *sum_le;
-};
-
-// float64(count) * (value - mean)^2 of a lane's four bins (an empty cell adds +0)
-__device__ __forceinline__ double central4(const u64 (&c)[4], const double (&d)[4], double mean)
-{
-    double q[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double dev = d[k] - mean;
-        q[k] = (double)c[k] * (dev * dev);
-    }
-    return (q[0] + q[1]) + (q[2] + q[3]);
-}
-
-// lh_pct.h's find_in_step with what this unit adds, in one piece as it was (on top of locate_in_step the two kernels come out
-// reordered, and without that function's guard for an empty ballot, which this text never had).
-// One step of 256 bins in which threshold T is reached (wave-uniform T; `before` counts / `sbefore` sums everything below
-// the step).  pre[k]: inclusive prefix count at the lane's bin k; t[k]: the bins' terms; incs: inclusive scan over the lanes
-// of the terms' sums.  Returns the index of the bin inside the step, the prefix count and the prefix sum there.
-__device__ __forceinline__ uint32_t sums_in_step(const u64 (&pre)[4], const double (&t)[4], double incs, double sbefore, u64 T,
-                                                 u64 &cle, double &sle)
-{
-    // the first lane whose last bin reaches T (lane 63's does), and how many of its bins stay below
-    const unsigned long long reach = __builtin_amdgcn_ballot_w64(pre[3] >= T);
-    const uint32_t f = (uint32_t)__builtin_ctzll(reach);
-    const uint32_t below = (pre[0] < T ? 1u : 0u) + (pre[1] < T ? 1u : 0u) + (pre[2] < T ? 1u : 0u);
-    const u64 csel = below == 0 ? pre[0] : below == 1 ? pre[1] : below == 2 ? pre[2] : pre[3];
-    double psel = t[0];
-    if (below >= 1) psel += t[1];
-    if (below >= 2) psel += t[2];
-    if (below >= 3) psel += t[3];
-    const double lanes_below = readlane_f64(incs, f ? f - 1 : 0);
-    cle = readlane_u64(csel, f);
-    sle = (sbefore + (f ? lanes_below : 0.0)) + readlane_f64(psel, f);
-    return 4 * f + (uint32_t)__builtin_amdgcn_readlane((int)below, (int)f);
-}
+// (SpreadOut, central4 and sums_in_step are lh_pct.h's: lh_kept.hip's k_kept_spread takes the same walk 2.)
 
 // (Both kernels, IDS: entry m reads row ids[m] of the snapshot -- lh::row_of, whose guard against `nrows` leaves an empty span;
 // m still indexes the outputs.  Otherwise row m of the block; ids and nrows are not looked at.)
@@ -308,22 +266,12 @@ struct SpreadCtx {
 };
 std::atomic<uint32_t> g_wave_from{SP_WAVE_FROM_DEFAULT};
 
-// every check that needs neither the snapshot nor a device.  With np == 0 the per-percentile outputs are ignored: they are
-// nulled here, and count for nothing.
+// every check that needs neither the snapshot nor a device (the percentiles' and the outputs': lh_pct.h's check_spread_args)
 int check_args(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *p, size_t np, SpreadOut &o)
 {
-    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
-    if (!s || np > LH_MAX_PERCENTILES || (np && !p)) return LH_EINVAL;
-    if (np == 0) {
-        o.pkeys = nullptr;
-        o.pvalid = nullptr;
-        o.count_le = nullptr;
-        o.sum_le = nullptr;
-    }
-    if (!o.count && !o.sum && !o.m2 && !o.pkeys && !o.pvalid && !o.count_le && !o.sum_le) return LH_EINVAL;
-    if ((np && misaligned(p, 8)) || misaligned(o.count, 8) || misaligned(o.sum, 8) || misaligned(o.m2, 8) ||
-        misaligned(o.pkeys, 2) || misaligned(o.count_le, 8) || misaligned(o.sum_le, 8))
-        return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || !s) return LH_EINVAL;
+    const int rc = check_spread_args(p, np, o);
+    if (rc) return rc;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     return LH_OK;
 }
@@ -375,21 +323,8 @@ int spread(lh_snapshot *s, const RowSel &sel, size_t nmetrics, const double *p, 
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(q, sel, nmetrics, p, np, o);
 
-    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys, then the flags.
-    const size_t per_m = nmetrics, per_p = nmetrics * np;
-    const HostOut out[7] = {{o.count, per_m * 8},    {o.sum, per_m * 8},    {o.m2, per_m * 8},   {o.count_le, per_p * 8},
-                            {o.sum_le, per_p * 8}, {o.pkeys, per_p * 2}, {o.pvalid, per_p}};
-    rc = host_results(cx->res, q.stream, out, [&](unsigned char *const(&dev)[7]) {
-        SpreadOut d;
-        d.count = reinterpret_cast<u64 *>(dev[0]);
-        d.sum = reinterpret_cast<double *>(dev[1]);
-        d.m2 = reinterpret_cast<double *>(dev[2]);
-        d.count_le = reinterpret_cast<u64 *>(dev[3]);
-        d.sum_le = reinterpret_cast<double *>(dev[4]);
-        d.pkeys = reinterpret_cast<int16_t *>(dev[5]);
-        d.pvalid = reinterpret_cast<uint8_t *>(dev[6]);
-        return enqueue(q, sel, nmetrics, p, np, d);
-    });
+    // host form: results to HBM, then back to the caller's arrays
+    rc = spread_host_results(cx->res, q.stream, o, nmetrics, np, [&](const SpreadOut &d) { return enqueue(q, sel, nmetrics, p, np, d); });
     return settle_ids(rc, sel, q.stream);
 }
 

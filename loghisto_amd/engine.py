@@ -73,6 +73,51 @@ def _id_list(ids):
     return a, int(a.ctypes.data), int(a.size), False
 
 
+_SPREAD_OUT = (("count", 8, 0), ("sum", 8, 0), ("m2", 8, 0), ("pkeys", 2, 1), ("pvalid", 1, 1), ("count_le", 8, 1), ("sum_le", 8, 1))
+
+
+def _spread_call(fn, lead, nmetrics, np_, out, device_ids, table):
+    """Snapshot.spread* and Kept.spread: library call `fn` (host form) or fn + "_device" with `lead`, every argument ahead of
+    the seven outputs, for nmetrics names and np_ percentiles -> the dict with the derived fields.  device_ids: whether an id
+    list lies on the device, which the outputs then do too (None: there is none); table(): decompress() by bin."""
+    L = N.lib()
+    if device_ids and out is None:
+        raise ValueError("device ids go with an out= of device tensors")
+    if out is not None:                                # (without percentiles the per-percentile arrays are not measured)
+        args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
+                                         for k, width, per_p in _SPREAD_OUT])
+        if device_ids is not None and device != device_ids:
+            raise ValueError("ids and out are both on the device or both on the host")
+        if device:
+            N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
+            return dict(out)
+        N.check(getattr(L, fn)(*lead, *args), fn)
+        res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
+               if v is not None and (np_ or k in ("count", "sum", "m2"))}
+    else:
+        import torch
+        kinds = dict(count=(torch.int64, np.uint64), sum=(torch.float64, np.float64), m2=(torch.float64, np.float64),
+                     pkeys=(torch.int16, np.int16), pvalid=(torch.uint8, np.uint8), count_le=(torch.int64, np.uint64),
+                     sum_le=(torch.float64, np.float64))
+        res = {}
+        for k, _, per_p in _SPREAD_OUT:                # (a row more than an empty call needs: the arrays have addresses)
+            shape = (max(nmetrics, 1), np_) if per_p else (max(nmetrics, 1),)
+            res[k] = torch.zeros(shape, dtype=kinds[k][0], pin_memory=True).numpy().view(kinds[k][1])
+        N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in _SPREAD_OUT]), fn)
+        res = {k: v[:nmetrics] for k, v in res.items()}
+    res = {k: (v.reshape(nmetrics, np_) if dict((a, c) for a, _, c in _SPREAD_OUT)[k] else v.reshape(nmetrics))
+           for k, v in res.items()}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if "m2" in res and "count" in res:
+            res["std"] = np.sqrt(res["m2"] / res["count"].view(np.uint64).astype(np.float64))
+        if "sum_le" in res and "count_le" in res:
+            res["mean_le"] = res["sum_le"] / res["count_le"].view(np.uint64).astype(np.float64)
+    if "pkeys" in res and "pvalid" in res:
+        bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
+        res["upper"] = np.where(res["pvalid"] != 0, table()[bins], np.nan)
+    return res
+
+
 class Snapshot:
     """One interval's cells, stolen at the epoch flip (metrics.go:460-463)."""
 
@@ -403,8 +448,7 @@ class Snapshot:
         return dict(cum=cum, total=total)
 
     # -- spread and percentile-trimmed sums (the weighted walk of metrics.go:342-346, cut where percentile() cuts) --------
-    _SPREAD_OUT = (("count", 8, 0), ("sum", 8, 0), ("m2", 8, 0), ("pkeys", 2, 1), ("pvalid", 1, 1), ("count_le", 8, 1),
-                   ("sum_le", 8, 1))
+    _SPREAD_OUT = _SPREAD_OUT
 
     def spread(self, percentiles, nmetrics: Optional[int] = None, first: int = 0, out=None):
         """dict(count, sum, m2, std, pkeys, pvalid, count_le, sum_le, mean_le, upper) for metrics [first, first+nmetrics)
@@ -433,45 +477,9 @@ class Snapshot:
     def _spread(self, fn, rows, nmetrics, percentiles, out, device_ids=None):
         """spread / spread_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments.
         device_ids: whether an id list lies on the device, which the outputs then do too (None: there is none)."""
-        L = N.lib()
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
-        np_ = int(p.size)
-        if device_ids and out is None:
-            raise ValueError("device ids go with an out= of device tensors")
-        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
-            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
-                                             for k, width, per_p in self._SPREAD_OUT])
-            if device_ids is not None and device != device_ids:
-                raise ValueError("ids and out are both on the device or both on the host")
-            if device:
-                N.check(getattr(L, fn + "_device")(self._h, *rows, p.ctypes.data, np_, *args), fn + "_device")
-                return dict(out)
-            N.check(getattr(L, fn)(self._h, *rows, p.ctypes.data, np_, *args), fn)
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
-                   if v is not None and (np_ or k in ("count", "sum", "m2"))}
-        else:
-            import torch
-            kinds = dict(count=(torch.int64, np.uint64), sum=(torch.float64, np.float64), m2=(torch.float64, np.float64),
-                         pkeys=(torch.int16, np.int16), pvalid=(torch.uint8, np.uint8), count_le=(torch.int64, np.uint64),
-                         sum_le=(torch.float64, np.float64))
-            res = {}
-            for k, _, per_p in self._SPREAD_OUT:       # (a row more than an empty call needs: the arrays have addresses)
-                shape = (max(nmetrics, 1), np_) if per_p else (max(nmetrics, 1),)
-                res[k] = torch.zeros(shape, dtype=kinds[k][0], pin_memory=True).numpy().view(kinds[k][1])
-            N.check(getattr(L, fn)(self._h, *rows, p.ctypes.data, np_,
-                                   *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in self._SPREAD_OUT]), fn)
-            res = {k: v[:nmetrics] for k, v in res.items()}
-        res = {k: (v.reshape(nmetrics, np_) if dict((a, c) for a, _, c in self._SPREAD_OUT)[k] else v.reshape(nmetrics))
-               for k, v in res.items()}
-        with np.errstate(divide="ignore", invalid="ignore"):
-            if "m2" in res and "count" in res:
-                res["std"] = np.sqrt(res["m2"] / res["count"].view(np.uint64).astype(np.float64))
-            if "sum_le" in res and "count_le" in res:
-                res["mean_le"] = res["sum_le"] / res["count_le"].view(np.uint64).astype(np.float64)
-        if "pkeys" in res and "pvalid" in res:
-            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
-            res["upper"] = np.where(res["pvalid"] != 0, self._decompress_table()[bins], np.nan)
-        return res
+        return _spread_call(fn, (self._h, *rows, p.ctypes.data, int(p.size)), nmetrics, int(p.size), out, device_ids,
+                            self._decompress_table)
 
     def _decompress_table(self) -> np.ndarray:
         """decompress() by bin (the engine's codec_tables), fetched once per engine."""
@@ -893,6 +901,63 @@ class Kept:
             value = self._table[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
             res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
         return res
+
+    def _list_rows(self, earlier, fn, nmetrics, first, ids):
+        """The leading arguments of a reader over list(earlier) + [self]: -> (what keeps the arrays alive, library call, (list,
+        nkept, rows ...), nmetrics, device ids? or None).  nmetrics=None: up to the end of this handle's block."""
+        kept = list(earlier) + [self]
+        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
+        if ids is not None:
+            keep, addr, nmetrics, device_ids = _id_list(ids)
+            return (handles, keep), fn + "_ids", (C.addressof(handles), len(kept), addr, nmetrics), nmetrics, device_ids
+        if nmetrics is None:
+            nmetrics = self.info["first"] + self.info["nrows"] - first
+        return (handles,), fn, (C.addressof(handles), len(kept), first, nmetrics), nmetrics, None
+
+    def count_le(self, bounds, earlier=(), nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Snapshot.count_le over kept intervals (lh_kept_count_le*): dict(cum=uint64[nmetrics, nb], total=uint64[nmetrics]) for
+        metrics [first, first+nmetrics) -- or, with ids=, for the metrics `ids` in that order -- over list(earlier) + [self] taken
+        together: cum[m, j] = the samples whose bucket key is <= the key of bound j, total[m] = all of them, both exact and
+        wrapping past 2^64.  `bounds` is 1-D, non-decreasing and shared by all names (a row per name is not supported over
+        handles).  first and ids are metric ids; every handle must hold them.  out= a dict with cum and / or total, as for
+        Kept.across: torch device tensors take the device form, enqueued on `stream` (a torch stream or a raw handle; None: the
+        null stream), and device ids go with them; every handle may be closed right afterwards: close() waits."""
+        L = N.lib()
+        b = np.ascontiguousarray(bounds, dtype=np.float64)
+        if b.ndim != 1:
+            raise ValueError("bounds over kept intervals are 1-D: one row shared by all names")
+        nb = int(b.size)
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(earlier, "lh_kept_count_le", nmetrics, first, ids)
+        lead = (*rows, b.ctypes.data, nb, 0, _stream_handle(stream))
+        if device_ids and out is None:
+            raise ValueError("device ids go with an out= of device tensors")
+        if out is not None:
+            args, device = _out_arrays(out, [("cum", 8, nmetrics * nb), ("total", 8, nmetrics)])
+            if device_ids is not None and device != device_ids:
+                raise ValueError("ids and out are both on the device or both on the host")
+            if device:
+                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
+                return dict(out)
+            N.check(getattr(L, fn)(*lead, *args), fn)
+            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items() if v is not None}
+        else:
+            import torch
+            res = {k: torch.zeros((max(n, 1),), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)[:n]
+                   for k, n in (("cum", nmetrics * nb), ("total", nmetrics))}
+            N.check(getattr(L, fn)(*lead, res["cum"].ctypes.data, res["total"].ctypes.data), fn)
+        return {k: (v.reshape(nmetrics, nb) if k == "cum" else v.reshape(nmetrics)) for k, v in res.items()}
+
+    def spread(self, percentiles, earlier=(), nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Snapshot.spread over kept intervals (lh_kept_spread*): the same dict -- count, sum, m2, std, pkeys, pvalid, count_le,
+        sum_le, mean_le, upper -- for metrics [first, first+nmetrics) -- or, with ids=, for the metrics `ids` in that order --
+        over list(earlier) + [self] taken together.  `percentiles` may be empty: moments only.  first and ids are metric ids;
+        every handle must hold them.  out= as for Snapshot.spread; torch device tensors take the device form, enqueued on
+        `stream` (a torch stream or a raw handle; None: the null stream), nothing is derived, and device ids go with them;
+        every handle may be closed right afterwards: close() waits."""
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(earlier, "lh_kept_spread", nmetrics, first, ids)
+        lead = (*rows, p.ctypes.data, int(p.size), 0, _stream_handle(stream))
+        return _spread_call(fn, lead, nmetrics, int(p.size), out, device_ids, lambda: self._table)
 
     def close(self):
         """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
