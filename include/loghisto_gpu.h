@@ -821,6 +821,56 @@ int lh_kept_spread_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, 
 int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
                               uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
                               uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le);
+/* THE K NAMES THAT LEAD, AND THE K THAT MOVED MOST, OVER KEPT INTERVALS: lh_top* and lh_movers* over handles, the two readers that
+ * SELECT across names, for the windows that exist only as handles -- "which 20 of my 65 536 endpoints have the worst p99 over the
+ * last minute", "whose distribution moved most against the same minute an hour ago" -- so that k entries travel instead of the
+ * per-name readers' arrays over every name, and no dense buffer is filled.  With C[b] = the sum over the list of the name's cell b,
+ * in 64 bits wrapping (lh_kept_across' C; a handle listed twice counts twice), nothing is summed across names and no new statistic
+ * is defined: every ranked value is one an lh_kept_* reader above returns for the same lists.  lh_top_entry, lh_mover_entry,
+ * LH_TOP_*, LH_MOVERS_* and LH_MAX_TOP are lh_top's and lh_movers'.
+ *   lh_kept_top, lh_kept_top_device
+ *                     lh_top's CANDIDATES, SCORE, ORDER and FIELDS, word for word, for a snapshot whose cells are C.  count is the
+ *                     wrapping sum of the handles' row_count entries (no cell is read for it), and a row is a candidate iff that
+ *                     count != 0.  sum is BIT-EQUAL to lh_kept_across' sum for the same list and row (the same step in the same
+ *                     order, in both kernel shapes).  LH_TOP_BY_PERCENTILE ranks the bin of the bucket lh_kept_across selects for
+ *                     p = arg, and pkey is its pkeys entry.  LH_TOP_BY_COUNT_ABOVE ranks count minus lh_kept_count_le's cum at
+ *                     bounds = {arg}: the same bound-to-key rule, +-Inf and saturation.  A name whose total wraps past 2^64 has
+ *                     count and its candidate status as defined; its other fields and its rank are unspecified (nothing faults).
+ *   lh_kept_movers, lh_kept_movers_device
+ *                     lh_movers' definitions for a[j] / b[j] = C over the `base` / `cur` list (lh_kept_compare's two sides).
+ *                     CANDIDATES: the rows with count_a != 0 and count_b != 0.  The LH_MOVERS_BY_KS, _BY_W1 and _BY_SHIFT scores
+ *                     are BIT-EQUAL to lh_kept_compare's ks, w1 and shift for the same lists (its walk; its two shapes agree bit
+ *                     for bit, so these do), and for BY_KS key is its ks_key.  LH_MOVERS_BY_PERCENTILE:
+ *                     score = (double)((int64)bin_cur - (int64)bin_base), each bin the one lh_kept_across selects for p = arg over
+ *                     that side's list; key / key_base are the two pkeys.  1 <= nbase, 1 <= ncur, nbase + ncur <= LH_MAX_KEPT, as
+ *                     for lh_kept_compare; longer windows go through lh_kept_merge first.  Identical lists give score 0 for every
+ *                     candidate, and the lowest ids win.  Wrapped totals: unspecified (nothing faults).
+ *   There are no _ids forms: the candidates of a selection are a range.  `first` is an ABSOLUTE row number, and ids are absolute.
+ *   ORDER OF THE CHECKS.  On the host, before any handle is looked at -- LH_EINVAL: a NULL or misaligned list; a wrong list length
+ *   (top: nkept == 0 or > LH_MAX_KEPT; movers: nbase == 0, ncur == 0 or nbase + ncur > LH_MAX_KEPT); a NULL entry; unknown `by`;
+ *   unknown flag bits (LH_TOP_ASCENDING / LH_MOVERS_ASCENDING are the known ones); lh_top's / lh_movers' rules for arg (NaN for
+ *   BY_PERCENTILE and BY_COUNT_ABOVE, outside [0, 1] for BY_PERCENTILE); k == 0 or k > LH_MAX_TOP; NULL out or n_out, out not
+ *   8-byte aligned, n_out not aligned to its type (size_t in the host forms, uint32_t in the device forms); then LH_ERANGE:
+ *   nmetrics > 0xffffffff.  nmetrics == 0: the host forms write *n_out = 0 and return LH_OK before any handle is looked at; the
+ *   device forms look at the handles' devices only (LH_EINVAL for more than one), zero d_n_out on `stream` and return LH_OK.
+ *   Then the handles are looked at -- LH_EINVAL: handles on different devices; LH_ERANGE, nothing enqueued and nothing written:
+ *   [first, first + nmetrics) not inside EVERY handle's block (both lists).  Entries at and beyond n_out are never written.
+ *   ORDERING, staging and lifetime: the work goes on `stream` (a hipStream_t of the handles' device; NULL: its null stream): a
+ *   score pass over every row in one of the reader's two kernel shapes (lh_tool_kept_switch; identical bytes), then lh_top's exact
+ *   radix select and sort in one workgroup.  Host forms return with the first n_out entries in `out`; entries and n_out come back
+ *   in one copy through a pinned block of the library's, whatever memory `out` is.  Device forms take device memory for both and
+ *   return after enqueueing, with ALL listed handles (both lists) under ONE hold, so that lh_kept_release waits for the call; the
+ *   unit's records block is guarded by an event, so a call on another stream waits for it on the device.  READ-ONLY: no handle,
+ *   snapshot or engine is written.  One records block per DEVICE behind the unit's own mutex: calls take turns. */
+int lh_kept_top(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                uint32_t flags, void *stream, lh_top_entry *out, size_t *n_out);
+int lh_kept_top_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                       uint32_t flags, void *stream, lh_top_entry *d_out, uint32_t *d_n_out);
+int lh_kept_movers(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                   uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_mover_entry *out, size_t *n_out);
+int lh_kept_movers_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                          size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                          lh_mover_entry *d_out, uint32_t *d_n_out);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

@@ -163,6 +163,14 @@ int lh_tool_top_passes_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, uint3
  * the unit's own block; returns when both times are known.  nmetrics >= 1. */
 int lh_tool_movers_passes_ms(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics, uint32_t by, double arg,
                              size_t k, uint32_t flags, float *score_ms, float *select_ms);
+/* The same for lh_kept_top*'s and lh_kept_movers*'s two passes, on `stream`: one call with the arguments of lh_kept_top /
+ * lh_kept_movers up to `stream`, its entries left in the unit's own block; returns when both times are known.  nmetrics >= 1.
+ * lh_tool_kept_switch switches the score passes' two shapes. */
+int lh_tool_kept_top_passes_ms(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg,
+                               size_t k, uint32_t flags, void *stream, float *score_ms, float *select_ms);
+int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                                  size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                  float *score_ms, float *select_ms);
 
 #ifdef __cplusplus
 }

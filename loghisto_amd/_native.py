@@ -186,6 +186,10 @@ TUNING_SIGNATURES = {
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                            C.POINTER(C.c_float)]),
+    "lh_tool_kept_top_passes_ms": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp,
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_kept_movers_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 # name -> (restype, argtypes): every symbol include/loghisto_gpu.h declares.
@@ -279,6 +283,10 @@ SIGNATURES = {
     "lh_kept_spread_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_top": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_top_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_movers": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_movers_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "lh_names_refresh": (C.c_int, [_vp, _u32p]),
     "lh_names_destroy": (C.c_int, [_vp]),

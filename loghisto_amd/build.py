@@ -32,7 +32,7 @@ _UNITS = [
     ("lh_compare.hip", ["--offload-arch=gfx950"]), # lh_compare*: per-name distribution shift between two snapshots; public ABI only
     ("lh_movers.hip", ["--offload-arch=gfx950"]),  # lh_movers*: the k names whose distribution moved most between two snapshots; public ABI only
     ("lh_across.hip", ["--offload-arch=gfx950"]),  # lh_across*: stats and percentiles of a name over up to 16 snapshots at once; public ABI only
-    ("lh_kept.hip", ["--offload-arch=gfx950"]),    # lh_keep, lh_kept_*: intervals kept in compact form on the device; lh_across', lh_compare's, lh_count_le's and lh_spread's outputs over up to 64 of them; public ABI only
+    ("lh_kept.hip", ["--offload-arch=gfx950"]),    # lh_keep, lh_kept_*: intervals kept in compact form on the device; lh_across', lh_compare's, lh_count_le's, lh_spread's, lh_top's and lh_movers' outputs over up to 64 of them; public ABI only
     ("lh_lines.hip", ["--offload-arch=gfx950"]),   # lh_names_*, lh_lines*: wire lines for any per-name device columns, formatted on the device; public ABI only
     ("lh_engine.cc", []),
     ("lh_dispatch.cc", []),         # the mixed ingest's path choice: pure functions (tests/test_dispatch.py)

@@ -80,6 +80,23 @@
 //                    lanes: the two shapes agree BIT FOR BIT, floating-point outputs included (lh_spread's own two shapes
 //                    associate differently and agree to rounding only).
 //
+// THE TWO SELECTING READERS, lh_kept_top* and lh_kept_movers*: lh_top's and lh_movers' selections -- the k names of a range that lead,
+// or that moved most between two lists -- for a snapshot whose cells are C, so that k entries travel and no dense buffer is filled.
+// Two score kernels in front of lh_select.h's k_select, whose records (TopRecords, MoversRecords) and Emit functors that header
+// now holds for lh_top.hip / lh_movers.hip and this unit alike.  Every ranked value is one the per-name readers above return:
+//   k_kept_top_score     the reader's Row and ONE turn: count from row_count (a candidate iff != 0), so the percentile's threshold and
+//                        the bound's take are known before a cell is read; sum by k_kept_across' step in its order (BIT-EQUAL to
+//                        its sum); BY_PERCENTILE: lane 0 owns the one threshold of Open, k_kept_across' search and bin;
+//                        BY_COUNT_ABOVE: the cells at or beyond le_take(arg), bins being absolute (count minus k_kept_count_le's cum).
+//   k_kept_movers_score  k_kept_compare's open, totals, turns, take4, gap product and wave_best through ONE device function
+//                        (compare_turns): ks, w1 and shift are BIT-EQUAL to lh_kept_compare's.  BY_PERCENTILE: one joint turn that
+//                        carries both prefixes and finds each side's first bin reaching its own threshold; the turns are not left
+//                        early (the tiles come back zeroed), the step does nothing once both are found.
+// Both in the reader's two shapes behind the same switch, wave 0 alone walking: identical bytes.  KeptCtx has ONE SelectState (calls
+// take turns under its mutex), its records block always sized for the movers' five fields; device forms put ALL listed handles
+// under one hold, and the records block is guarded by SelectState's event.  Out of scope: a BY_COUNT pass that skips the cell walk,
+// a multi-workgroup select, _ids forms, more than 64 handles a call (lh_kept_merge first).
+//
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
 // a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
@@ -102,6 +119,7 @@
 #include "lh_codec.h"
 #include "lh_pair.h"
 #include "lh_pct.h"
+#include "lh_select.h"
 
 #include <hip/hip_runtime.h>
 
@@ -517,6 +535,33 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const K
 // Handles 0 .. nbase - 1 of the list are `base`, the others `cur`; rows as in k_kept_across.  One walk: k_compare_wave's walk 2
 // over the steps the tiles cover, and for the bins between two tiles -- X is constant there -- their number times the term,
 // added by lane 0 just before the step behind them.
+// (na and nb both non-zero)  The walk itself, for k_kept_compare and for k_kept_movers_score, whose three distances are thereby
+// the same bits: the turns over the opened row's two tiles with the step above, into the lane's b (best_init'ed by the caller).
+template <int NW>
+__device__ __forceinline__ void compare_turns(Row &row, uint32_t n, uint32_t nbase, u64 *tile, uint32_t lane, uint32_t w, u64 na,
+                                              u64 nb, Best &b)
+{
+    const Scale sc = make_scale(na, nb);
+    u64 ca = 0, cb = 0;        // what lies below the step
+    uint32_t behind = NO_BIN;  // the bin behind the last step taken (NO_BIN: none yet)
+    turns_of<NW, 2, KEPT_COMPARE_TILE>(row, n, nbase, tile, lane, w, [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+        if (behind != NO_BIN && base > behind && lane == 0) { // bins [behind, base) lie in no tile: the prefixes stay ca, cb
+            const u128 xa = (u128)ca * sc.nb, xb = (u128)cb * sc.na;
+            const bool up = xa >= xb;
+            const u128 x = up ? xa - xb : xb - xa;
+            const double t = (double)(base - behind) * ((double)(u64)(x >> sc.sh) / sc.den);
+            b.w += t;
+            b.s += up ? t : -t;
+        }
+        const u64 ta = sum4(A), tb = sum4(B);
+        const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+        take4(b, sc, base + 4 * lane, ca + (ia - ta), cb + (ib - tb), A, B);
+        ca += readlane_u64(ia, 63);
+        cb += readlane_u64(ib, 63);
+        behind = base + STEP;
+    });
+}
+
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const KeptList s, uint32_t nbase, uint32_t nmetrics,
                                                                            uint32_t first, const CompareOut o,
@@ -539,28 +584,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const
 
     Best b;
     best_init(b);
-    if (na && nb) { // uniform
-        const Scale sc = make_scale(na, nb);
-        u64 ca = 0, cb = 0;        // what lies below the step
-        uint32_t behind = NO_BIN;  // the bin behind the last step taken (NO_BIN: none yet)
-        turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nbase, at.tile, lane, at.w,
-                                           [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
-            if (behind != NO_BIN && base > behind && lane == 0) { // bins [behind, base) lie in no tile: the prefixes stay ca, cb
-                const u128 xa = (u128)ca * sc.nb, xb = (u128)cb * sc.na;
-                const bool up = xa >= xb;
-                const u128 x = up ? xa - xb : xb - xa;
-                const double t = (double)(base - behind) * ((double)(u64)(x >> sc.sh) / sc.den);
-                b.w += t;
-                b.s += up ? t : -t;
-            }
-            const u64 ta = sum4(A), tb = sum4(B);
-            const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
-            take4(b, sc, base + 4 * lane, ca + (ia - ta), cb + (ib - tb), A, B);
-            ca += readlane_u64(ia, 63);
-            cb += readlane_u64(ib, 63);
-            behind = base + STEP;
-        });
-    }
+    if (na && nb) compare_turns<NW>(row, s.n, nbase, at.tile, lane, at.w, na, nb, b); // uniform
     if (at.w != 0) return;
     u128 x;
     uint32_t bin;
@@ -568,6 +592,162 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const
     wave_best(b, x, bin, ba, bb);
     const double w1 = readlane_f64(wave_scan_incl_f64(b.w), 63), shift = readlane_f64(wave_scan_incl_f64(b.s), 63);
     if (lane == 0) store_row(o, m, na, nb, bin, ba, bb, w1, shift);
+}
+
+// ---- lh_kept_top / lh_kept_movers: the score passes in front of lh_select.h's k_select ---------------------------------------------
+// Rows first + m (the host refused a range outside any handle's block; such a row would still be the empty entry).  ONE turn over
+// the row: the total comes from row_count, so the percentile's threshold and the bound's take are known before a cell is read.
+// The sum by k_kept_across' step in its order (the same bits); BY_PERCENTILE: lane 0 owns the one threshold of lh_pct.h's Open,
+// k_kept_across' search; BY_COUNT_ABOVE: the cells of the bins at or beyond the take -- bins are absolute, so a take before the
+// first tile takes every cell, one in a stretch no tile covers the cells of the tiles behind it, one beyond the last step none:
+// count minus what k_kept_count_le returns for the bound.  Wave 0 alone walks; its lane 0 writes the row's record (TopRecords,
+// the key complemented for LH_TOP_ASCENDING: `flip`).
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                             const double *__restrict__ D, uint32_t by, double arg,
+                                                                             u64 flip, const TopRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    const uint32_t hi = row.hi;
+
+    double ps = 0.0;
+    u64 ab = 0;
+    Open pct; // lane 0: the percentile
+    if (total) { // uniform
+        const bool want_pct = by == LH_TOP_BY_PERCENTILE, want_above = by == LH_TOP_BY_COUNT_ABOVE; // uniform
+        const uint32_t take = want_above ? le_take(arg) : 0u;
+        pct.open(want_pct && lane == 0 ? pct_threshold(arg, total) : PCT_NONE);
+        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+            double d[4], t[4];
+            load4_values(D, base + 4 * lane, hi, d);
+            const u64 tc = sum4(C);
+            ps += terms4(C, d, t);
+            if (want_pct) pct.step(C, tc, base, lane);
+            if (want_above) {
+                const uint32_t b0 = base + 4 * lane;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) ab += b0 + k >= take ? C[k] : 0;
+            }
+        });
+    }
+    if (at.w != 0) return;
+    const double sum = total ? readlane_f64(wave_scan_incl_f64(ps), 63) : 0.0;
+    const u64 above = readlane_u64(wave_scan_incl_u64(ab), 63);
+    if (lane == 0) {
+        uint32_t found = pct.found;
+        if (found == NO_BIN) found = total ? hi : 0u; // (a total that wrapped: some bin of the row)
+        u64 key, aux = 0;
+        if (by == LH_TOP_BY_COUNT) {
+            key = total;
+        } else if (by == LH_TOP_BY_SUM) {
+            key = order_key_f64(sum);
+        } else if (by == LH_TOP_BY_PERCENTILE) {
+            key = found;
+            aux = total ? (u64)(uint16_t)(int16_t)bin_to_key(found) : 0;
+        } else {
+            key = above;
+            aux = above;
+        }
+        r.key[m] = key ^ flip;
+        r.count[m] = total;
+        r.sum[m] = sum;
+        r.aux[m] = aux;
+    }
+}
+
+// Handles 0 .. nbase - 1 of the list are `base`, the others `cur`, as in k_kept_compare, whose open, totals and -- for the three
+// distances -- walk, wave_best and sums these are (compare_turns): the scores are the bits lh_kept_compare returns.
+// BY_PERCENTILE: ONE joint turn that carries both prefixes and finds, on each side, the first bin whose inclusive prefix reaches
+// that side's threshold (k_kept_across' search, find_in_step); the turns are not left early -- the tiles must come back zeroed --
+// so once both bins are found the step does nothing, and the turns only put zeros back.  Lane 0 of wave 0 writes the row's record
+// (MoversRecords).
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(const KeptList s, uint32_t nbase, uint32_t nmetrics,
+                                                                                uint32_t first, uint32_t by, double arg, u64 flip,
+                                                                                const MoversRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share the tiles
+    at.clear();
+
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    const u64 na = readlane_u64(wave_scan_incl_u64(lane < nbase ? row.rc : 0), 63);
+    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < nbase ? 0 : row.rc), 63);
+    const bool is_cand = na != 0 && nb != 0; // uniform
+
+    double score = 0.0;
+    uint32_t keys = 0; // key << 16 | key_base
+    if (by != LH_MOVERS_BY_PERCENTILE) { // uniform
+        Best b;
+        best_init(b);
+        if (is_cand) compare_turns<NW>(row, s.n, nbase, at.tile, lane, at.w, na, nb, b);
+        if (at.w != 0) return;
+        u128 x;
+        uint32_t bin;
+        u64 ba, bb;
+        wave_best(b, x, bin, ba, bb);
+        const double w1 = readlane_f64(wave_scan_incl_f64(b.w), 63), shift = readlane_f64(wave_scan_incl_f64(b.s), 63);
+        if (by == LH_MOVERS_BY_KS) { // (store_row's: an X of 0 everywhere is a distance of 0 at key 0)
+            if (is_cand && bin != NO_BIN) {
+                score = fabs((double)ba / (double)na - (double)bb / (double)nb);
+                keys = (uint32_t)(uint16_t)(int16_t)bin_to_key(bin) << 16;
+            }
+        } else {
+            score = by == LH_MOVERS_BY_W1 ? w1 : shift;
+        }
+    } else {
+        uint32_t fa = NO_BIN, fb = NO_BIN;
+        if (is_cand) {
+            // (the host keeps arg in [0, 1]: 1 <= T <= total)
+            const u64 Ta = readlane_u64(pct_threshold(arg, na), 0), Tb = readlane_u64(pct_threshold(arg, nb), 0);
+            u64 ca = 0, cb = 0; // what lies below the step
+            turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nbase, at.tile, lane, at.w,
+                                               [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+                if (fa != NO_BIN && fb != NO_BIN) return; // uniform: both found
+                const u64 ta = sum4(A), tb = sum4(B);
+                const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
+                const u64 ea = ca + readlane_u64(ia, 63), eb = cb + readlane_u64(ib, 63);
+                if (fa == NO_BIN && Ta <= ea) { // uniform: it is in this step
+                    u64 pre[4];
+                    prefix4(A, ca, ta, ia, pre);
+                    fa = base + find_in_step(pre, Ta);
+                }
+                if (fb == NO_BIN && Tb <= eb) {
+                    u64 pre[4];
+                    prefix4(B, cb, tb, ib, pre);
+                    fb = base + find_in_step(pre, Tb);
+                }
+                ca = ea;
+                cb = eb;
+            });
+            if (fa == NO_BIN) fa = row.hi; // (totals that wrapped: some bin of the row)
+            if (fb == NO_BIN) fb = row.hi;
+            score = (double)((long long)fb - (long long)fa);
+            keys = (uint32_t)(uint16_t)(int16_t)bin_to_key(fb) << 16 | (uint32_t)(uint16_t)(int16_t)bin_to_key(fa);
+        }
+        if (at.w != 0) return;
+    }
+    if (lane == 0) {
+        if (!is_cand) score = 0.0;
+        r.key[m] = order_key_f64(score) ^ flip;
+        r.cand[m] = is_cand ? MOVER_CANDIDATE | keys : 0;
+        r.count_a[m] = na;
+        r.count_b[m] = nb;
+        r.score[m] = (u64)__double_as_longlong(score);
+    }
 }
 
 // ---- lh_kept_count_le ---------------------------------------------------------------------------------------------------------
@@ -740,6 +920,8 @@ struct KeptCtx {
     IdBlocks ids;              // host form of lh_kept_across_ids
     CallEvent *pool = nullptr; // events no handle points to
     u64 holds = 0;
+    SelectState sel;           // lh_kept_top* / lh_kept_movers*: ONE records block, sized for the kind with more fields (calls take
+                               // turns under mu), its guard, and the host forms' landing block
 };
 std::atomic<uint32_t> g_wave_from{KEPT_WAVE_FROM_DEFAULT};
 
@@ -1174,9 +1356,203 @@ int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t
         });
 }
 
+// ---- lh_kept_top* / lh_kept_movers*: lh_select.h's host side around this unit's score passes -----------------------------------
+// What a selecting call is given beside its list(s); `all` is one list (movers: base first), nbase == 0 for lh_kept_top*.
+struct SelectCall {
+    lh_kept *all[LH_MAX_KEPT];
+    size_t n = 0, nbase = 0;
+    uint32_t first = 0, by = 0, flags = 0;
+    size_t nmetrics = 0, k = 0;
+    double arg = 0.0;
+    bool movers = false;
+};
+
+// (cx->mu held, the device current) both passes over rows [first, first + nmetrics) on `st`.  ev[0 .. 2] (may be null): events to
+// record before the score pass, between the passes and behind the select pass (lh_tool_kept_*_passes_ms).  The records block
+// is always asked for with the movers' five fields: a block a top call made also serves a movers call of as many rows.
+template <class Entry> int enqueue_select(KeptCtx *cx, const SelectCall &c, hipStream_t st, Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev)
+{
+    u64 *base = nullptr;
+    size_t npad = 0;
+    int rc = c.movers ? LH_OK : ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    if (!rc) rc = select_records(cx->sel, st, c.nmetrics, MOVERS_FIELDS, base, npad);
+    if (rc) return rc;
+    const KeptList s = list_of(c.all, c.n);
+    const uint32_t M = (uint32_t)c.nmetrics;
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[0], st));
+    if constexpr (std::is_same<Entry, lh_top_entry>::value) {
+        const TopRecords r = top_records(base, npad);
+        const u64 flip = (c.flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;
+        const double *D = cx->d_table;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_top_score<1>), sh.grid, sh.block, 0, st, s, M, c.first, D, c.by, c.arg, flip, r);
+        else hipLaunchKernelGGL((k_kept_top_score<WG_WAVES>), sh.grid, sh.block, 0, st, s, M, c.first, D, c.by, c.arg, flip, r);
+        LH_BESIDE_CHK(hipGetLastError());
+        return select_pass(cx->sel, st, r.key, r.count, M, c.k, TopEmit{r, c.first, c.by, d_out}, d_n_out, ev);
+    } else {
+        const MoversRecords r = movers_records(base, npad);
+        const u64 flip = (c.flags & LH_MOVERS_ASCENDING) ? ~0ull : 0ull;
+        const uint32_t NB = (uint32_t)c.nbase;
+        if (sh.wave) hipLaunchKernelGGL((k_kept_movers_score<1>), sh.grid, sh.block, 0, st, s, NB, M, c.first, c.by, c.arg, flip, r);
+        else hipLaunchKernelGGL((k_kept_movers_score<WG_WAVES>), sh.grid, sh.block, 0, st, s, NB, M, c.first, c.by, c.arg, flip, r);
+        LH_BESIDE_CHK(hipGetLastError());
+        return select_pass(cx->sel, st, r.key, r.cand, M, c.k, MoversEmit{r, c.first, d_out}, d_n_out, ev);
+    }
+}
+
+// Every check that needs neither a handle nor a device, in the documented order: the list(s), `by`, the flags, lh_top's /
+// lh_movers' rules for arg, then select_check_args (k, out, n_out, and the early LH_ERANGE behind every LH_EINVAL).  Fills c.
+int check_select(SelectCall &c, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                 uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out, uintptr_t n_out_align)
+{
+    if (c.movers) {
+        if (!base || !cur || misaligned(base, alignof(lh_kept *)) || misaligned(cur, alignof(lh_kept *))) return LH_EINVAL;
+        if (nbase == 0 || ncur == 0 || nbase > LH_MAX_KEPT || ncur > LH_MAX_KEPT || nbase + ncur > LH_MAX_KEPT) return LH_EINVAL;
+    } else {
+        if (!cur || misaligned(cur, alignof(lh_kept *)) || ncur == 0 || ncur > LH_MAX_KEPT) return LH_EINVAL;
+    }
+    c.nbase = nbase;
+    c.n = nbase + ncur;
+    for (size_t i = 0; i < c.n; i++) {
+        c.all[i] = i < nbase ? base[i] : cur[i - nbase];
+        if (!c.all[i]) return LH_EINVAL;
+    }
+    if (c.movers) {
+        if (by > LH_MOVERS_BY_PERCENTILE || (flags & ~(uint32_t)LH_MOVERS_ASCENDING)) return LH_EINVAL;
+        if (by == LH_MOVERS_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL; // NaN too: no bucket to rank by
+    } else {
+        if (by > LH_TOP_BY_COUNT_ABOVE || (flags & ~(uint32_t)LH_TOP_ASCENDING)) return LH_EINVAL;
+        if (by == LH_TOP_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL;
+        if (by == LH_TOP_BY_COUNT_ABOVE && arg != arg) return LH_EINVAL;
+    }
+    c.first = first;
+    c.nmetrics = nmetrics;
+    c.by = by;
+    c.arg = arg;
+    c.k = k;
+    c.flags = flags;
+    return select_check_args(nmetrics, k, out, n_out, n_out_align);
+}
+
+// the two checks that look at the handles: one device (LH_EINVAL), then the rows every handle has (LH_ERANGE)
+int open_select(const SelectCall &c, int *device)
+{
+    const int rc = one_device(c.all, c.n, device);
+    return rc ? rc : rows_in_all(c.all, c.n, rows_from(c.first), c.nmetrics);
+}
+
+template <class Entry>
+int kept_select(bool movers, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                uint32_t by, double arg, size_t k, uint32_t flags, void *stream, Entry *out, size_t *n_out)
+{
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, out, n_out, alignof(size_t));
+    if (rc) return rc;
+    if (nmetrics == 0) { // before any handle is looked at
+        *n_out = 0;
+        return LH_OK;
+    }
+    int device = -1;
+    rc = open_select(c, &device);
+    if (rc) return rc;
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, device, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+        return select_host_form(cx->sel, st, k, out, n_out, [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+            return enqueue_select(cx, c, st, d_out, d_n_out, ev);
+        });
+    });
+}
+
+template <class Entry>
+int kept_select_device(bool movers, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                       size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, Entry *d_out,
+                       uint32_t *d_n_out)
+{
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, d_out, d_n_out, alignof(uint32_t));
+    if (rc) return rc;
+    int device = -1;
+    if (nmetrics == 0) { // the handles' devices alone are looked at: that is where d_n_out is zeroed
+        rc = one_device(c.all, c.n, &device);
+        if (rc) return rc;
+        LH_BESIDE_CHK(hipSetDevice(device));
+        LH_BESIDE_CHK(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream)));
+        return LH_OK;
+    }
+    rc = open_select(c, &device);
+    if (rc) return rc;
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, device, stream, true, // (one hold: the handles of BOTH lists)
+               [&](KeptCtx *cx, hipStream_t st) { return enqueue_select(cx, c, st, d_out, d_n_out, (hipEvent_t *)nullptr); }, never);
+}
+
+template <class Entry>
+int kept_select_passes_ms(bool movers, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                          size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, float *score_ms,
+                          float *select_ms)
+{
+    alignas(8) unsigned char own[8] = {0}; // (the results stay in the unit's own block)
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, own, own, 1);
+    if (rc) return rc;
+    if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
+    int device = -1;
+    rc = open_select(c, &device);
+    if (rc) return rc;
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, device, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+        return select_passes_ms<Entry>(cx->sel, st, k, score_ms, select_ms, [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
+            return enqueue_select(cx, c, st, d_out, d_n_out, ev);
+        });
+    });
+}
+
 } // namespace
 
 extern "C" {
+
+int lh_kept_top(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                uint32_t flags, void *stream, lh_top_entry *out, size_t *n_out)
+{
+    return kept_select(false, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, stream, out, n_out);
+}
+
+int lh_kept_top_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                       uint32_t flags, void *stream, lh_top_entry *d_out, uint32_t *d_n_out)
+{
+    return kept_select_device(false, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, stream, d_out, d_n_out);
+}
+
+int lh_kept_movers(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
+                   uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_mover_entry *out, size_t *n_out)
+{
+    return kept_select(true, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, stream, out, n_out);
+}
+
+int lh_kept_movers_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                          size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                          lh_mover_entry *d_out, uint32_t *d_n_out)
+{
+    return kept_select_device(true, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, stream, d_out, d_n_out);
+}
+
+int lh_tool_kept_top_passes_ms(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
+                               uint32_t flags, void *stream, float *score_ms, float *select_ms)
+{
+    return kept_select_passes_ms<lh_top_entry>(false, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, stream, score_ms,
+                                               select_ms);
+}
+
+int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
+                                  size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, float *score_ms,
+                                  float *select_ms)
+{
+    return kept_select_passes_ms<lh_mover_entry>(true, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, stream, score_ms,
+                                                 select_ms);
+}
 
 int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_kept **out)
 {

@@ -42,16 +42,8 @@ namespace {
 using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
 
-static_assert(sizeof(lh_mover_entry) == 32, "lh_mover_entry is 32 bytes");
-constexpr u64 CANDIDATE = 1ull << 32; // the candidate word of a row that is ranked; its low 32 bits: key << 16 | key_base
-
-// The rows' records, one array per field, each padded to whole groups of SEL_PER (16-byte loads stay inside the block).
-struct MoversRecords {
-    u64 *key;     // order-preserving, larger is ahead
-    u64 *cand;    // 0: not a candidate
-    u64 *count_a, *count_b;
-    u64 *score;   // the float64's bits
-};
+// (the rows' records, MoversRecords, their candidate word and the winner's entry, MoversEmit: lh_select.h, shared with
+// lh_kept.hip's lh_kept_movers*)
 
 // The first bin of a step whose inclusive prefix reaches T, given that the step's last one does (k_top_score's scheme):
 // c the lane's four cells, tc their sum, inc its inclusive scan over the lanes, carry what lies below the step.
@@ -162,32 +154,12 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_movers_score(const CA *__restrict
     if (lane == 0) {
         const bool is_cand = na != 0 && nb != 0;
         r.key[m] = order_key_f64(score) ^ flip;
-        r.cand[m] = is_cand ? CANDIDATE | keys : 0;
+        r.cand[m] = is_cand ? MOVER_CANDIDATE | keys : 0;
         r.count_a[m] = na;
         r.count_b[m] = nb;
         r.score[m] = (u64)__double_as_longlong(score);
     }
 }
-
-// ---- the select pass: lh_select.h's, with this unit's last step ---------------------------------------------------
-// winner i lands in slot t
-struct MoversEmit {
-    MoversRecords r;
-    uint32_t first;
-    lh_mover_entry *out;
-    __device__ __forceinline__ void operator()(uint32_t i, uint32_t t) const
-    {
-        const uint32_t keys = (uint32_t)r.cand[i];
-        lh_mover_entry e;
-        e.id = first + i;
-        e.key = (int16_t)(uint16_t)(keys >> 16);
-        e.key_base = (int16_t)(uint16_t)keys;
-        e.count_a = r.count_a[i];
-        e.count_b = r.count_b[i];
-        e.score = __longlong_as_double((long long)r.score[i]);
-        out[t] = e;
-    }
-};
 
 // ---- host side: lh_select.h's, around this unit's enqueue --------------------------------------------------------
 // Per-device state of this unit (device_ctx<MoversCtx>).  `mu` is held for the length of a call, the host form's wait for
@@ -228,14 +200,9 @@ int enqueue(const MoversSource &a, const MoversSource &b, uint32_t first, size_t
     u64 *base = nullptr;
     size_t npad = 0;
     int rc = order_behind(cx->order, a.stream, b.stream);
-    if (!rc) rc = select_records(cx->sel, b.stream, nmetrics, 5, base, npad);
+    if (!rc) rc = select_records(cx->sel, b.stream, nmetrics, MOVERS_FIELDS, base, npad);
     if (rc) return rc;
-    MoversRecords r;
-    r.key = base;
-    r.cand = r.key + npad;
-    r.count_a = r.cand + npad;
-    r.count_b = r.count_a + npad;
-    r.score = r.count_b + npad;
+    const MoversRecords r = movers_records(base, npad);
     const uint32_t M = (uint32_t)nmetrics;
     const uint32_t *ra = ranges_from(a, first), *rb = ranges_from(b, first);
     const u64 flip = (flags & LH_MOVERS_ASCENDING) ? ~0ull : 0ull;

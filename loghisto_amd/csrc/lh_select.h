@@ -1,4 +1,5 @@
-// lh_select.h -- the select pass of the units that pick k names out of a range (lh_top.hip, lh_movers.hip): a score pass of
+// lh_select.h -- the select pass of the units that pick k names out of a range (lh_top.hip, lh_movers.hip, and lh_kept.hip's
+// lh_kept_top* / lh_kept_movers*, which share the first two's records and Emit functors: they are here): a score pass of
 // the unit leaves, per row, a 64-bit ORDER-PRESERVING key (larger is ahead; order_key_f64 makes one of a float64) and a
 // candidate word (0: the row is never ranked) in HBM, and k_select takes the k largest keys among the candidates, equal keys
 // lowest index first, and sorts them.  What a winner's entry looks like is the unit's own: its Emit functor writes it.
@@ -219,8 +220,85 @@ __global__ __launch_bounds__(SEL_WG) void k_select(const u64 *__restrict__ key, 
     if (tid == 0) *n_out = nwin;
 }
 
+// ---- the records and the Emit of the two kinds of selection, each shared by the unit that scores snapshots and the one that
+// scores kept intervals (lh_top.hip / lh_movers.hip, lh_kept.hip): one array per field, each padded to whole groups of SEL_PER
+// (16-byte loads stay inside the block).
+struct TopRecords {
+    u64 *key;    // order-preserving, larger is ahead
+    u64 *count;  // 0: not a candidate
+    double *sum;
+    u64 *aux;    // BY_PERCENTILE: the int16 key's 16 bits; BY_COUNT_ABOVE: the count above; else 0
+};
+// winner i lands in slot t
+struct TopEmit {
+    TopRecords r;
+    uint32_t first, by;
+    lh_top_entry *out;
+    __device__ __forceinline__ void operator()(uint32_t i, uint32_t t) const
+    {
+        const u64 aux = r.aux[i];
+        lh_top_entry e;
+        e.id = first + i;
+        e.pkey = by == LH_TOP_BY_PERCENTILE ? (int16_t)(uint16_t)aux : (int16_t)0;
+        e.reserved = 0;
+        e.count = r.count[i];
+        e.sum = r.sum[i];
+        e.above = by == LH_TOP_BY_COUNT_ABOVE ? aux : 0;
+        out[t] = e;
+    }
+};
+
+constexpr u64 MOVER_CANDIDATE = 1ull << 32; // the candidate word of a row that is ranked; its low 32 bits: key << 16 | key_base
+struct MoversRecords {
+    u64 *key;     // order-preserving, larger is ahead
+    u64 *cand;    // 0: not a candidate
+    u64 *count_a, *count_b;
+    u64 *score;   // the float64's bits
+};
+// winner i lands in slot t
+struct MoversEmit {
+    MoversRecords r;
+    uint32_t first;
+    lh_mover_entry *out;
+    __device__ __forceinline__ void operator()(uint32_t i, uint32_t t) const
+    {
+        const uint32_t keys = (uint32_t)r.cand[i];
+        lh_mover_entry e;
+        e.id = first + i;
+        e.key = (int16_t)(uint16_t)(keys >> 16);
+        e.key_base = (int16_t)(uint16_t)keys;
+        e.count_a = r.count_a[i];
+        e.count_b = r.count_b[i];
+        e.score = __longlong_as_double((long long)r.score[i]);
+        out[t] = e;
+    }
+};
+static_assert(sizeof(lh_top_entry) == 32 && sizeof(lh_mover_entry) == 32, "32-byte entries");
+
 // ---- host side --------------------------------------------------------------------------------------
 namespace beside {
+
+// the fields of the two record kinds carved out of select_records' block
+static inline TopRecords top_records(u64 *base, size_t npad)
+{
+    TopRecords r;
+    r.key = base;
+    r.count = r.key + npad;
+    r.sum = reinterpret_cast<double *>(r.count + npad);
+    r.aux = reinterpret_cast<u64 *>(r.sum + npad);
+    return r;
+}
+static inline MoversRecords movers_records(u64 *base, size_t npad)
+{
+    MoversRecords r;
+    r.key = base;
+    r.cand = r.key + npad;
+    r.count_a = r.cand + npad;
+    r.count_b = r.count_a + npad;
+    r.score = r.count_b + npad;
+    return r;
+}
+constexpr size_t TOP_FIELDS = 4, MOVERS_FIELDS = 5;
 
 // What a selecting unit keeps per device beside its own mutex and extras (a member of its context: device_ctx hands out
 // one slot array per context type, so units never wait for each other).  Snapshots of different engines run on

@@ -46,15 +46,7 @@ namespace {
 using namespace lh; // (lh_wave.h)
 using namespace lh::beside;
 
-static_assert(sizeof(lh_top_entry) == 32, "lh_top_entry is 32 bytes");
-
-// The rows' records, one array per field, each padded to whole groups of SEL_PER (16-byte loads stay inside the block).
-struct TopRecords {
-    u64 *key;    // order-preserving, larger is ahead
-    u64 *count;  // 0: not a candidate
-    double *sum;
-    u64 *aux;    // BY_PERCENTILE: the int16 key's 16 bits; BY_COUNT_ABOVE: the count above; else 0
-};
+// (the rows' records, TopRecords, and the winner's entry, TopEmit: lh_select.h, shared with lh_kept.hip's lh_kept_top*)
 
 template <typename CELL>
 __global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict__ cells, const uint32_t *__restrict__ ranges,
@@ -147,26 +139,6 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_top_score(const CELL *__restrict_
     }
 }
 
-// ---- the select pass: lh_select.h's, with this unit's last step ---------------------------------------------------
-// winner i lands in slot t
-struct TopEmit {
-    TopRecords r;
-    uint32_t first, by;
-    lh_top_entry *out;
-    __device__ __forceinline__ void operator()(uint32_t i, uint32_t t) const
-    {
-        const u64 aux = r.aux[i];
-        lh_top_entry e;
-        e.id = first + i;
-        e.pkey = by == LH_TOP_BY_PERCENTILE ? (int16_t)(uint16_t)aux : (int16_t)0;
-        e.reserved = 0;
-        e.count = r.count[i];
-        e.sum = r.sum[i];
-        e.above = by == LH_TOP_BY_COUNT_ABOVE ? aux : 0;
-        out[t] = e;
-    }
-};
-
 // ---- host side: lh_select.h's, around this unit's enqueue --------------------------------------------------------
 // Per-device state of this unit (device_ctx<TopCtx>).  `mu` is held for the length of a call -- the host form's wait for
 // its results included, so host-form calls on one device take turns even when their snapshots belong to different
@@ -198,13 +170,9 @@ int enqueue(const TopSource &q, uint32_t first, size_t nmetrics, uint32_t by, do
     u64 *base = nullptr;
     size_t npad = 0;
     int rc = ensure_table(cx->d_table, q.stream, lh::k_value_table<TopCtx>);
-    if (!rc) rc = select_records(cx->sel, q.stream, nmetrics, 4, base, npad);
+    if (!rc) rc = select_records(cx->sel, q.stream, nmetrics, TOP_FIELDS, base, npad);
     if (rc) return rc;
-    TopRecords r;
-    r.key = base;
-    r.count = r.key + npad;
-    r.sum = reinterpret_cast<double *>(r.count + npad);
-    r.aux = reinterpret_cast<u64 *>(r.sum + npad);
+    const TopRecords r = top_records(base, npad);
     const uint32_t M = (uint32_t)nmetrics;
     const uint32_t *ranges = ranges_from(q, first);
     const u64 flip = (flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;

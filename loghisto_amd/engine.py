@@ -534,16 +534,18 @@ class Snapshot:
         out = a contiguous numpy array of at least k TOP_ENTRY elements takes the host form into it (its first n_out
         entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
         k * 32 and 4 bytes takes the device form: enqueued on the snapshot's stream, the pair is returned as it is."""
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
         return self._leaders("lh_top", (self._h,), self._TOP_BY, ("percentile", "count_above"), "TOP_ENTRY", k, by, arg,
                              N.TOP_ASCENDING if ascending else 0, nmetrics, first, out)
 
-    def _leaders(self, fn, handles, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out):
-        """top / movers: the k leaders of [first, first+nmetrics) from library call `fn` (host form) or fn + "_device", whose
-        arguments begin with `handles`.  by_codes: the names `by` takes -> the library's; takes_arg: those that need an
-        arg; entry: the name of the entry dtype in N."""
+    @staticmethod
+    def _leaders(fn, handles, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out, stream=()):
+        """top / movers, of a Snapshot or of a Kept: the k leaders of [first, first+nmetrics) from library call `fn` (host form)
+        or fn + "_device", whose arguments begin with `handles` (a snapshot's handle or two; a list of kept handles and its
+        length, or two) and -- the kept readers' -- have `stream` = (its handle,) in front of the outputs.  by_codes: the names
+        `by` takes -> the library's; takes_arg: those that need an arg; entry: the name of the entry dtype in N."""
         L = N.lib()
-        if nmetrics is None:
-            nmetrics = self.engine.num_metrics() - first
         if by not in by_codes:
             raise ValueError("by is one of " + ", ".join(by_codes))
         if arg is None:
@@ -551,7 +553,7 @@ class Snapshot:
                 raise ValueError(f"by={by!r} takes an arg")
             arg = 0.0
         dtype = getattr(N, entry)
-        lead = (*handles, first, nmetrics, by_codes[by], float(arg), k, flags)
+        lead = (*handles, first, nmetrics, by_codes[by], float(arg), k, flags, *stream)
         if isinstance(out, tuple):
             entries, n = out
             for t, need in ((entries, k * dtype.itemsize), (n, 4)):
@@ -625,6 +627,8 @@ class Snapshot:
         entries are written and returned as a view); out = (entries, n) of contiguous torch device tensors of at least
         k * 32 and 4 bytes takes the device form: enqueued on this snapshot's stream (`base` must stay unreleased until
         that stream has passed the call), the pair is returned as it is."""
+        if nmetrics is None:
+            nmetrics = self.engine.num_metrics() - first
         return self._leaders("lh_movers", (base._h, self._h), self._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
                              N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out)
 
@@ -958,6 +962,48 @@ class Kept:
         alive, fn, rows, nmetrics, device_ids = self._list_rows(earlier, "lh_kept_spread", nmetrics, first, ids)
         lead = (*rows, p.ctypes.data, int(p.size), 0, _stream_handle(stream))
         return _spread_call(fn, lead, nmetrics, int(p.size), out, device_ids, lambda: self._table)
+
+    # -- the two readers that select across names (lh_top's / lh_movers' entries; what is ranked is what across / count_le /
+    #    compare return for the same lists) ------------------------------------------------------------------------------------
+    def _block(self, nmetrics, first):
+        """first=None: this handle's first; nmetrics=None: up to the end of this handle's block (as _list_rows)."""
+        if first is None:
+            first = self.info["first"]
+        if nmetrics is None:
+            nmetrics = self.info["first"] + self.info["nrows"] - first
+        return nmetrics, first
+
+    def top(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False, earlier=(),
+            nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Snapshot.top over kept intervals (lh_kept_top*): the k names of [first, first+nmetrics) that lead over
+        list(earlier) + [self] taken together, as TOP_ENTRY records, the leader first -- by "count", "sum", "percentile" (arg = p)
+        or "count_above" (arg = a value), as there.  count, sum and pkey are what Kept.across returns for the same list (sum bit
+        for bit), above is count minus Kept.count_le's answer.  first and ids are metric ids; every handle must hold the range;
+        first=None / nmetrics=None: this handle's block.  out= as for Snapshot.top: a numpy array of TOP_ENTRY takes the host
+        form, an (entries, n) pair of torch device tensors the device form, enqueued on `stream` (a torch stream or a raw handle;
+        None: the null stream); every handle may be closed right afterwards: close() waits."""
+        nmetrics, first = self._block(nmetrics, first)
+        kept = list(earlier) + [self]
+        handles = (C.c_void_p * len(kept))(*[h._h.value for h in kept])
+        return Snapshot._leaders("lh_kept_top", (C.addressof(handles), len(kept)), Snapshot._TOP_BY, ("percentile", "count_above"),
+                                 "TOP_ENTRY", k, by, arg, N.TOP_ASCENDING if ascending else 0, nmetrics, first, out,
+                                 (_stream_handle(stream),))
+
+    def movers(self, base, k: int, by: str = "ks", arg: Optional[float] = None, ascending: bool = False, earlier=(),
+               nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Snapshot.movers over kept intervals (lh_kept_movers*): the k names of [first, first+nmetrics) whose distribution over
+        list(earlier) + [self] taken together moved most against the same names of `base`, a Kept or a sequence of them taken
+        together, as MOVER_ENTRY records, the leader first -- by "ks", "w1", "shift" (the bits Kept.compare returns for the same
+        lists) or "percentile" (arg = p: the buckets Kept.across selects on either side).  At most N.MAX_KEPT handles in the
+        two lists together.  first / nmetrics / out / stream as for Kept.top."""
+        nmetrics, first = self._block(nmetrics, first)
+        lists = []
+        for kept in (([base] if isinstance(base, Kept) else list(base)), list(earlier) + [self]):
+            lists.append((C.c_void_p * max(len(kept), 1))(*[h._h.value for h in kept]))
+            lists.append(len(kept))
+        return Snapshot._leaders("lh_kept_movers", (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3]),
+                                 Snapshot._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
+                                 N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out, (_stream_handle(stream),))
 
     def close(self):
         """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
