@@ -720,6 +720,112 @@ int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
 int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream,
                   lh_kept **out);
+/* KEPT INTERVALS SAVED AND LOADED: lh_kept_save*, lh_kept_load*, lh_kept_values.  A handle is otherwise born from a live snapshot
+ * (lh_keep) or from handles of the same device (lh_kept_merge): the history dies with the process and cannot change devices.  A
+ * BLOB carries one handle to a file, to another process, rank or device; a process that only QUERIES history -- a dashboard
+ * backend, a fleet aggregator, a restart -- needs no engine: lh_kept_load* and the lh_kept_* readers.  The names that belong to
+ * the ids are not in the blob (store lh_metric_name's output beside it); no compression, no checksum.
+ *   THE BLOB (format version 1; little-endian; part of this interface) is a 64-byte header followed by the handle's single
+ *   allocation VERBATIM, lh_kept_info.bytes long:
+ *       offset  0  uint8[8]  magic "LHKEPT\x1a\n" (LH_KEPT_BLOB_MAGIC)
+ *               8  uint32    format version, 1 (LH_KEPT_BLOB_VERSION)
+ *              12  uint32    header size, 64 (LH_KEPT_BLOB_HEADER)
+ *              16  uint32    LH_NKEYS, 65 536
+ *              20  uint32    first
+ *              24  uint32    nrows
+ *              28  uint32    reserved, 0
+ *              32  uint64    cells
+ *              40  uint64    samples
+ *              48  uint64    bytes = (2 * nrows + 1) * 8 + cells * 10
+ *              56  uint8[8]  reserved, 0
+ *              64  uint64 offsets[nrows + 1] | uint64 row_count[nrows] | uint64 counts[cells] | int16 keys[cells]
+ *   lh_kept_save_size *bytes = 64 + lh_kept_info.bytes.  LH_EINVAL: NULL k or bytes.
+ *   lh_kept_save      writes the blob of k into HOST memory buf[0 .. cap), pageable or pinned; *written (may be NULL) = its size.
+ *   lh_kept_save_device  the same into DEVICE memory of the handle's device (what a rank hands to RCCL); any alignment.
+ *                     Both: the copies go on `stream` (a hipStream_t of the handle's device; NULL: its null stream) and the save is
+ *                     COMPLETE on return; under the unit's mutex; the handle is only read.  LH_EINVAL: NULL k or buf.  LH_ERANGE:
+ *                     cap below the blob's size -- below LH_KEPT_BLOB_MIN (the smallest blob there is: one row, no cell) before
+ *                     the handle is looked at --, nothing written, *written untouched.
+ *   lh_kept_load      a NEW handle on `device` from a blob in HOST memory buf[0 .. len): an ordinary lh_kept with the exact
+ *                     allocation, layout and bytes lh_keep would give -- every reader, lh_kept_merge, lh_kept_arrays,
+ *                     lh_kept_hold and lh_kept_release take it, in any mix with other handles of that device.
+ *   lh_kept_load_device  the same from a blob in the memory of `device` itself; only its 64 header bytes come to the host.
+ *                     Both: a blob is UNTRUSTED, and every lh_kept_* kernel loops and scatters by the handle's arrays, so the load
+ *                     PROVES on the device what lh_keep guarantees before a handle exists: the block is copied into its exact
+ *                     allocation and checked there on `stream` (a hipStream_t of `device`; NULL: its null stream), a wave per row;
+ *                     the check reads nothing outside the copied block whatever the bytes say, and the verdict does not depend on
+ *                     timing.  Like lh_keep and lh_kept_merge a load is complete on return, under the unit's mutex.  flags must
+ *                     be 0.  Any refusal is LH_EINVAL: *out untouched, nothing leaked (the stream waited for, the block freed),
+ *                     and *why -- optional; why->struct_size = sizeof(lh_kept_check) on entry, anything else is LH_EINVAL with
+ *                     nothing written -- says which: cause, and for the device's causes row and index (0 otherwise).
+ *                     Decided on the HOST, before any device call (lh_kept_load_device: NULL arguments, flags and len < 64
+ *                     before any device call, the rest once the header has come over), in this order:
+ *                       LH_KEPT_BAD_ARG          NULL buf or out, flags != 0, device < 0 or beyond the unit's 64 slots
+ *                       LH_KEPT_BAD_SHORT        len < 64
+ *                       LH_KEPT_BAD_MAGIC, LH_KEPT_BAD_VERSION, LH_KEPT_BAD_HEADER_SIZE
+ *                       LH_KEPT_BAD_NKEYS        the blob's LH_NKEYS is not this library's
+ *                       LH_KEPT_BAD_NROWS        nrows == 0
+ *                       LH_KEPT_BAD_FIRST        first + nrows > 2^32
+ *                       LH_KEPT_BAD_CELLS        cells > nrows * LH_NKEYS
+ *                       LH_KEPT_BAD_BYTES        bytes != (2 * nrows + 1) * 8 + cells * 10
+ *                       LH_KEPT_BAD_LENGTH       len != 64 + bytes
+ *                       LH_KEPT_BAD_RESERVED     a reserved byte that is not 0
+ *                     Decided on the DEVICE, with bin = (uint16)key ^ 0x8000; row m's cells are [offsets[m], offsets[m + 1]):
+ *                       LH_KEPT_BAD_OFFSET_FIRST   offsets[0] != 0                                          (row 0, index 0)
+ *                       LH_KEPT_BAD_OFFSET_ORDER   not offsets[m] <= offsets[m + 1] <= cells                (row m, index 0)
+ *                       LH_KEPT_BAD_ROW_LENGTH     offsets[m + 1] - offsets[m] > LH_NKEYS                   (row m, index 0)
+ *                       LH_KEPT_BAD_OFFSET_LAST    offsets[nrows] != cells                          (row nrows - 1, index 0)
+ *                       LH_KEPT_BAD_KEY_ORDER      cell i > 0 of row m: bin(i - 1) >= bin(i) -- within the row only: its first
+ *                                                  key may lie below the previous row's last        (row m, index i in the row)
+ *                       LH_KEPT_BAD_ZERO_COUNT     cell i of row m has count 0                               (row m, index i)
+ *                       LH_KEPT_BAD_ROW_COUNT      row_count[m] is not the wrapping sum of the row's counts
+ *                                                                                    (row m, index = the row's number of cells)
+ *                       LH_KEPT_BAD_SAMPLES        samples is not the wrapping sum of row_count         (row = nrows, index 0)
+ *                     A row with one of the four offset causes is not walked: no cell of it is read or reported.  Of all
+ *                     violations the one reported is that of the LOWEST ROW, in it the LOWEST INDEX, there the LOWEST CAUSE CODE.
+ *                     LH_ENOMEM: the allocation failed.  LH_EDEVICE: a HIP error.
+ *   lh_kept_values    D[LH_NKEYS] (host, 8-byte aligned): decompress() by bin, the value table the lh_kept_* readers weigh cells
+ *                     with on `device`, generated there on first use -- bit-equal to lh_codec_tables' D.  What a process without
+ *                     an engine turns pkeys into values with: D[(uint16)key ^ 0x8000].  LH_EINVAL: NULL or misaligned D, device
+ *                     < 0 or beyond the unit's 64 slots. */
+#define LH_KEPT_BLOB_MAGIC "LHKEPT\x1a\n"
+#define LH_KEPT_BLOB_VERSION 1
+#define LH_KEPT_BLOB_HEADER 64
+#define LH_KEPT_BLOB_MIN (LH_KEPT_BLOB_HEADER + 24) /* one row, no cell */
+enum {
+    LH_KEPT_BAD_ARG = 1,
+    LH_KEPT_BAD_SHORT = 2,
+    LH_KEPT_BAD_MAGIC = 3,
+    LH_KEPT_BAD_VERSION = 4,
+    LH_KEPT_BAD_HEADER_SIZE = 5,
+    LH_KEPT_BAD_NKEYS = 6,
+    LH_KEPT_BAD_NROWS = 7,
+    LH_KEPT_BAD_FIRST = 8,
+    LH_KEPT_BAD_CELLS = 9,
+    LH_KEPT_BAD_BYTES = 10,
+    LH_KEPT_BAD_LENGTH = 11,
+    LH_KEPT_BAD_RESERVED = 12,
+    LH_KEPT_BAD_OFFSET_FIRST = 16,
+    LH_KEPT_BAD_OFFSET_ORDER = 17,
+    LH_KEPT_BAD_ROW_LENGTH = 18,
+    LH_KEPT_BAD_OFFSET_LAST = 19,
+    LH_KEPT_BAD_KEY_ORDER = 20,
+    LH_KEPT_BAD_ZERO_COUNT = 21,
+    LH_KEPT_BAD_ROW_COUNT = 22,
+    LH_KEPT_BAD_SAMPLES = 23
+};
+typedef struct lh_kept_check {
+    uint32_t struct_size;            /* sizeof(lh_kept_check) */
+    uint32_t cause;                  /* LH_KEPT_BAD_* */
+    uint32_t row, index;             /* row within the block (0 = the handle's `first`), cell within the row */
+} lh_kept_check;
+int lh_kept_save_size(const lh_kept *k, size_t *bytes);
+int lh_kept_save(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written);
+int lh_kept_save_device(lh_kept *k, void *d_buf, size_t cap, void *stream, size_t *written);
+int lh_kept_load(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out);
+int lh_kept_load_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why,
+                        lh_kept **out);
+int lh_kept_values(int device, double *D /* LH_NKEYS */);
 /* DISTRIBUTION SHIFT BETWEEN KEPT INTERVALS: lh_compare* over handles, so that the baseline -- the same minute an hour ago, the
  * interval before the deploy, yesterday's roll-up -- need not be alive as a dense snapshot, nor be poured back into one.  With
  *   a[j] = the sum over the `base` list of the name's cell j, b[j] = the same sum over the `cur` list, both in 64 bits

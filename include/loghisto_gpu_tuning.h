@@ -171,6 +171,13 @@ int lh_tool_kept_top_passes_ms(lh_kept *const *kept, size_t nkept, uint32_t firs
 int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
                                   size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
                                   float *score_ms, float *select_ms);
+/* Device time of lh_kept_load*'s check alone (HIP events on `stream` around each kernel): k_kept_check and k_kept_check_samples
+ * over the handle's OWN block, which holds what they ask for; nothing is copied or allocated, the handle is only read.  Returns
+ * when both times are known.  LH_EINVAL: NULL k or output. */
+int lh_tool_kept_check_ms(lh_kept *k, void *stream, float *check_ms, float *samples_ms);
+/* The yardstick beside it: device time of lh_keep's FIRST pass alone, k_keep_count over rows [first, first + nmetrics) of a
+ * live snapshot (HIP events on the snapshot's stream), into the unit's scratch block; no handle is made.  nmetrics >= 1. */
+int lh_tool_keep_count_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, float *count_ms);
 
 #ifdef __cplusplus
 }

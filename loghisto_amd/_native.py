@@ -138,6 +138,11 @@ class LhKeptInfo(C.Structure):
                 ("cells", C.c_uint64), ("samples", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class LhKeptCheck(C.Structure):
+    """lh_kept_check (16 bytes): why lh_kept_load* refused a blob."""
+    _fields_ = [("struct_size", C.c_uint32), ("cause", C.c_uint32), ("row", C.c_uint32), ("index", C.c_uint32)]
+
+
 FMT_UNDERSCORE_TO_DOT = 1
 SER_AGGREGATES = 1
 FMT_SLOT = 336
@@ -182,6 +187,8 @@ TUNING_SIGNATURES = {
     "lh_tool_kept_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_kept_tile": (C.c_int, [_u32p]),
     "lh_tool_kept_compare_tile": (C.c_int, [_u32p]),
+    "lh_tool_kept_check_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_keep_count_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.POINTER(C.c_float)]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
@@ -271,6 +278,12 @@ SIGNATURES = {
     "lh_kept_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_merge": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_save_size": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "lh_kept_save": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "lh_kept_save_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "lh_kept_load": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
+    "lh_kept_load_device": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
+    "lh_kept_values": (C.c_int, [C.c_int, _dp]),
     "lh_kept_compare": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_compare_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_compare_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -97,6 +97,15 @@
 // under one hold, and the records block is guarded by SelectState's event.  Out of scope: a BY_COUNT pass that skips the cell walk,
 // a multi-workgroup select, _ids forms, more than 64 handles a call (lh_kept_merge first).
 //
+// SAVE AND LOAD, lh_kept_save* / lh_kept_load*: a handle's single allocation verbatim behind a 64-byte header (loghisto_gpu.h has the
+// format), to host or device memory and back into a NEW handle on any device, with no engine anywhere.  A save is two copies and a
+// wait.  A load copies the block into its exact allocation and then PROVES there, on the call's stream, what lh_keep guarantees and
+// every kernel of this unit trusts -- offsets monotone from 0 to `cells`, at most LH_NKEYS cells a row, bins strictly ascending within
+// a row, no zero cell, row_count the wrapping sum of the row, samples the wrapping sum of row_count -- before the handle exists:
+// k_kept_check (a wave per row, safe on arbitrary bytes) and k_kept_check_samples (one workgroup) fold the first violation, by row,
+// index and cause, into one uint64 with an atomic min, which comes back in one 8-byte copy.  The header's own causes are decided
+// on the host.  lh_kept_values hands out the unit's value table, for a process that has no engine to ask.
+//
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
 // a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
@@ -899,7 +908,96 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const 
     }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------
+// ---- lh_kept_load: the check ---------------------------------------------------------------------------------------------------
+// The block of a blob -- offsets[nrows + 1] | row_count[nrows] | counts[cells] | keys[cells], copied verbatim into an allocation of
+// exactly that size -- is UNTRUSTED: every kernel above loops and scatters by these arrays.  k_kept_check proves what lh_keep
+// guarantees before a handle exists, a wave per row like k_keep_count, and is safe on arbitrary bytes: the host has checked
+// that the four arrays of (nrows, cells) fill the allocation; the kernel reads offsets[m], offsets[m + 1] and row_count[m] for
+// m < nrows, and a cell only at an index in [offsets[m], offsets[m + 1]) after it has seen offsets[m] <= offsets[m + 1] <= cells
+// and at most LH_NKEYS of them: a row's walk is bounded by 1 024 steps whatever the bytes say.  No LDS, no scratch; a lane per
+// cell, 64 cells a step: counts by 8-byte loads (512 contiguous bytes a wave), keys by 2-byte loads (128 bytes; the keys start
+// at 8 * cells behind the counts and a row's first key at any even address, so wider loads would be unaligned at both ends of
+// a row).  A violation is (row, index, cause) packed row << 32 | index << 8 | cause and folded into *verdict with a 64-bit
+// atomic min: the lowest row, in it the lowest index, there the lowest cause, whatever the timing.  A row whose offsets are bad
+// reports that (index 0, the lowest such cause) and reads no cell; a cell's causes have the cell's index in the row; a
+// row_count that is not the wrapping sum of the row has index = the row's number of cells, behind every cell.
+constexpr u64 CHECK_NONE = ~0ull;
+constexpr uint32_t CHECK_NONE32 = 0xffffffffu;
+__global__ __launch_bounds__(ROW_BLOCK) void k_kept_check(u64 block, uint32_t nrows, u64 cells, u64 *__restrict__ verdict)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    const gu64 off = (gu64)block, row_count = off + (size_t)nrows + 1, counts = row_count + nrows;
+    const gkeys keys = (gkeys)(block + 8 * (2 * (u64)nrows + 1) + 8 * cells);
+    const u64 a = off[m], b = off[(size_t)m + 1];
+    uint32_t bad = CHECK_NONE32; // index << 8 | cause
+    if (m == nrows - 1 && b != cells) bad = LH_KEPT_BAD_OFFSET_LAST;
+    if (a <= b && b <= cells && b - a > LH_NKEYS) bad = LH_KEPT_BAD_ROW_LENGTH;
+    if (a > b || b > cells) bad = LH_KEPT_BAD_OFFSET_ORDER;
+    if (m == 0 && a != 0) bad = LH_KEPT_BAD_OFFSET_FIRST; // (the lowest cause code last)
+    if (bad == CHECK_NONE32) { // wave-uniform: the row's cells are [a, b), inside the arrays, LH_NKEYS at most
+        const uint32_t n = (uint32_t)(b - a);
+        u64 cnt = 0;
+        uint32_t carry = 0; // the bin of the last cell of the step before
+        for (uint32_t base = 0; base < n; base += 64) { // wave-uniform
+            const uint32_t i = base + lane;
+            const bool in = i < n;
+            uint32_t bin = 0;
+            u64 c = 0;
+            if (in) {
+                bin = bin_of(keys[a + i]);
+                c = counts[a + i];
+            }
+            // the bin of the cell before: lane - 1's (row_shr:1 inside a row of 16 lanes, the three lanes between rows by
+            // readlane), lane 0 the carry
+            uint32_t prev = LH_DPP32(bin, 0x111, 0xf);
+            const uint32_t b15 = (uint32_t)__builtin_amdgcn_readlane((int)bin, 15), b31 = (uint32_t)__builtin_amdgcn_readlane((int)bin, 31),
+                           b47 = (uint32_t)__builtin_amdgcn_readlane((int)bin, 47);
+            prev = lane == 0 ? carry : lane == 16 ? b15 : lane == 32 ? b31 : lane == 48 ? b47 : prev;
+            cnt += c;
+            uint32_t v = CHECK_NONE32;
+            if (in) {
+                if (c == 0) v = i << 8 | LH_KEPT_BAD_ZERO_COUNT;
+                if (i > 0 && prev >= bin) v = i << 8 | LH_KEPT_BAD_KEY_ORDER; // (the lower cause code last)
+            }
+            const uint32_t least = ~wave_max_u32(~v);
+            if (least != CHECK_NONE32) { // wave-uniform: no later step holds a lower index
+                bad = least;
+                break;
+            }
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)bin, 63);
+        }
+        if (bad == CHECK_NONE32 && readlane_u64(wave_scan_incl_u64(cnt), 63) != row_count[m]) bad = n << 8 | LH_KEPT_BAD_ROW_COUNT;
+    }
+    if (bad != CHECK_NONE32 && lane == 0) atomicMin(verdict, (u64)m << 32 | bad);
+}
+static_assert(LH_KEPT_BAD_OFFSET_FIRST < LH_KEPT_BAD_OFFSET_ORDER && LH_KEPT_BAD_OFFSET_ORDER < LH_KEPT_BAD_ROW_LENGTH &&
+                  LH_KEPT_BAD_ROW_LENGTH < LH_KEPT_BAD_OFFSET_LAST && LH_KEPT_BAD_KEY_ORDER < LH_KEPT_BAD_ZERO_COUNT &&
+                  LH_KEPT_BAD_SAMPLES < 256,
+              "k_kept_check assigns a row's and a cell's causes in descending order of their codes; a cause is the low byte");
+
+// one workgroup (k_keep_scan's pattern): the header's `samples` against the wrapping sum of row_count; row = nrows, behind every row
+__global__ __launch_bounds__(WG) void k_kept_check_samples(u64 block, uint32_t nrows, u64 samples, u64 *__restrict__ verdict)
+{
+    __shared__ u64 s_w[WG_WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const gu64 row_count = (gu64)block + (size_t)nrows + 1;
+    u64 s = 0;
+    for (u64 base = 0; base < nrows; base += WG) { // uniform
+        const u64 i = base + threadIdx.x;
+        s += i < nrows ? row_count[i] : 0;
+    }
+    s = wave_scan_incl_u64(s);
+    if (lane == 63) s_w[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 all = 0;
+        for (uint32_t k = 0; k < (uint32_t)WG_WAVES; k++) all += s_w[k];
+        if (all != samples) atomicMin(verdict, (u64)nrows << 32 | LH_KEPT_BAD_SAMPLES);
+    }
+}
+
+// ---- host side------------------------------------------------------------------------------------------------------------
 // behind a device-form call's kernel (or lh_kept_hold's caller's work); `users` handles point to it
 struct CallEvent {
     hipEvent_t ev = nullptr;
@@ -1510,9 +1608,280 @@ int kept_select_passes_ms(bool movers, lh_kept *const *base, size_t nbase, lh_ke
     });
 }
 
+// ---- lh_kept_save* / lh_kept_load*: the blob (loghisto_gpu.h has the format) ----------------------------------------------------
+struct BlobHeader { // little-endian, as the hosts this builds for are
+    unsigned char magic[8];
+    uint32_t version, header_size, nkeys, first, nrows, reserved0;
+    uint64_t cells, samples, bytes;
+    unsigned char reserved1[8];
+};
+static_assert(sizeof(BlobHeader) == LH_KEPT_BLOB_HEADER && sizeof(LH_KEPT_BLOB_MAGIC) == 9, "64 bytes, 8 of them the magic");
+static_assert(sizeof(lh_kept_check) == 16, "part of the ABI");
+
+BlobHeader header_of(const lh_kept *k)
+{
+    BlobHeader h;
+    std::memset(&h, 0, sizeof h);
+    std::memcpy(h.magic, LH_KEPT_BLOB_MAGIC, 8);
+    h.version = LH_KEPT_BLOB_VERSION;
+    h.header_size = LH_KEPT_BLOB_HEADER;
+    h.nkeys = LH_NKEYS;
+    h.first = k->first;
+    h.nrows = k->nrows;
+    h.cells = k->cells;
+    h.samples = k->samples;
+    h.bytes = k->bytes;
+    return h;
+}
+
+// the header's causes of refusal in the documented order, `len` the blob's length; 0: none
+uint32_t header_cause(const BlobHeader &h, size_t len)
+{
+    if (std::memcmp(h.magic, LH_KEPT_BLOB_MAGIC, 8) != 0) return LH_KEPT_BAD_MAGIC;
+    if (h.version != LH_KEPT_BLOB_VERSION) return LH_KEPT_BAD_VERSION;
+    if (h.header_size != LH_KEPT_BLOB_HEADER) return LH_KEPT_BAD_HEADER_SIZE;
+    if (h.nkeys != LH_NKEYS) return LH_KEPT_BAD_NKEYS;
+    if (h.nrows == 0) return LH_KEPT_BAD_NROWS;
+    if ((u64)h.first + h.nrows > (1ull << 32)) return LH_KEPT_BAD_FIRST;
+    if (h.cells > (u64)h.nrows * LH_NKEYS) return LH_KEPT_BAD_CELLS;
+    if (h.bytes != (2 * (u64)h.nrows + 1) * 8 + h.cells * 10) return LH_KEPT_BAD_BYTES; // (cells <= 2^48: no wrap)
+    if ((u64)len != LH_KEPT_BLOB_HEADER + h.bytes) return LH_KEPT_BAD_LENGTH;
+    if (h.reserved0 != 0) return LH_KEPT_BAD_RESERVED;
+    for (unsigned char c : h.reserved1)
+        if (c) return LH_KEPT_BAD_RESERVED;
+    return 0;
+}
+
+int refuse(lh_kept_check *why, uint32_t cause, uint32_t row = 0, uint32_t index = 0)
+{
+    if (why) {
+        why->cause = cause;
+        why->row = row;
+        why->index = index;
+    }
+    return LH_EINVAL;
+}
+
+int kept_save(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written, bool to_device)
+{
+    if (!k || !buf) return LH_EINVAL;
+    if (cap < LH_KEPT_BLOB_MIN) return LH_ERANGE; // before the handle is looked at
+    KeptCtx *cx = k->cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu); // no lh_kept_release frees the block under the copy
+    const u64 size = LH_KEPT_BLOB_HEADER + k->bytes;
+    if ((u64)cap < size) return LH_ERANGE;
+    const BlobHeader h = header_of(k);
+    unsigned char *to = static_cast<unsigned char *>(buf);
+    LH_BESIDE_CHK(hipSetDevice(k->device));
+    int rc = LH_OK;
+    const auto chk = [&](hipError_t e) {
+        if (e != hipSuccess && !rc) {
+            (void)hipGetLastError();
+            rc = e == hipErrorOutOfMemory ? LH_ENOMEM : LH_EDEVICE;
+        }
+    };
+    if (to_device) chk(hipMemcpyAsync(to, &h, sizeof h, hipMemcpyHostToDevice, st)); // (h lives until the wait below)
+    else std::memcpy(to, &h, sizeof h);
+    chk(hipMemcpyAsync(to + sizeof h, k->block, (size_t)k->bytes, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    chk(hipStreamSynchronize(st)); // complete on return, after a failure too
+    if (rc) return rc;
+    if (written) *written = (size_t)size;
+    return LH_OK;
+}
+
+// the grid of a kernel that gives each of nrows rows a wave (64 bits: nrows may come from a blob and lie within ROW_WAVES of 2^32)
+dim3 wave_per_row(uint32_t nrows) { return dim3((uint32_t)(((u64)nrows + ROW_WAVES - 1) / ROW_WAVES)); }
+
+// (cx->mu held, the device current)  The block of a blob whose header `h` passed header_cause, from `src` (host or this device's
+// memory) into k->block -- its exact allocation -- and checked there on `st`.  LH_EINVAL with *why filled for a block that is
+// not what lh_keep makes.  After a failure the caller waits for `st` and frees k->block.
+int load_block(KeptCtx *cx, const BlobHeader &h, const void *src, bool from_device, hipStream_t st, lh_kept_check *why, lh_kept *k)
+{
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, 1, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+    if (rc) return rc;
+    k->first = h.first;
+    k->nrows = h.nrows;
+    k->cells = h.cells;
+    k->samples = h.samples;
+    k->bytes = h.bytes;
+    LH_BESIDE_CHK(hipMalloc((void **)&k->block, (size_t)h.bytes));
+    LH_BESIDE_CHK(hipMemcpyAsync(k->block, src, (size_t)h.bytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    u64 *verdict = cx->d_tmp;
+    LH_BESIDE_CHK(hipMemsetAsync(verdict, 0xff, sizeof(u64), st)); // CHECK_NONE
+    const u64 block = (u64)(uintptr_t)k->block;
+    hipLaunchKernelGGL(k_kept_check, wave_per_row(h.nrows), dim3(ROW_BLOCK), 0, st, block, h.nrows, h.cells, verdict);
+    LH_BESIDE_CHK(hipGetLastError());
+    hipLaunchKernelGGL(k_kept_check_samples, dim3(1), dim3(WG), 0, st, block, h.nrows, h.samples, verdict);
+    LH_BESIDE_CHK(hipGetLastError());
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, verdict, sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    const u64 v = cx->h_totals[0];
+    if (v != CHECK_NONE) return refuse(why, (uint32_t)(v & 0xff), (uint32_t)(v >> 32), (uint32_t)(v >> 8) & 0xffffffu);
+    return LH_OK;
+}
+
+// (the mutex held, the device current)  ms between HIP events on `st` around each of the n steps enqueue(i) puts there;
+// returns when they are known
+template <class Enqueue> int steps_ms(hipStream_t st, int n, float *const *ms, Enqueue enqueue)
+{
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int rc = LH_OK;
+    for (int i = 0; i <= n && rc == LH_OK; i++)
+        if (hipEventCreate(&ev[i]) != hipSuccess) rc = LH_EDEVICE;
+    if (rc == LH_OK && hipEventRecord(ev[0], st) != hipSuccess) rc = LH_EDEVICE;
+    for (int i = 0; i < n && rc == LH_OK; i++) {
+        enqueue(i);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[i + 1], st) != hipSuccess) rc = LH_EDEVICE;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = LH_EDEVICE; // nothing of the call is under way afterwards
+    for (int i = 0; i < n && rc == LH_OK; i++)
+        if (hipEventElapsedTime(ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = LH_EDEVICE;
+    for (int i = 0; i <= n; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (rc == LH_EDEVICE) (void)hipGetLastError();
+    return rc;
+}
+
+int kept_load(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out, bool from_device)
+{
+    if (why && why->struct_size != sizeof(lh_kept_check)) return LH_EINVAL;
+    if (!buf || !out || flags != 0 || device < 0 || device >= MAX_DEVICES) return refuse(why, LH_KEPT_BAD_ARG);
+    if (len < LH_KEPT_BLOB_HEADER) return refuse(why, LH_KEPT_BAD_SHORT);
+    BlobHeader h;
+    if (!from_device) { // the header's causes before any device call
+        std::memcpy(&h, buf, sizeof h);
+        const uint32_t cause = header_cause(h, len);
+        if (cause) return refuse(why, cause);
+    }
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE; // (never: the range was checked)
+    lh_kept *k = new (std::nothrow) lh_kept;
+    if (!k) return LH_ENOMEM;
+    k->device = device;
+    k->cx = cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned char *src = static_cast<const unsigned char *>(buf);
+    int rc;
+    {
+        std::lock_guard<std::mutex> g(cx->mu);
+        rc = hipSetDevice(device) == hipSuccess ? LH_OK : LH_EDEVICE;
+        if (!rc && from_device) { // its 64 header bytes alone come to the host
+            rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+            if (!rc && (hipMemcpyAsync(cx->h_totals, src, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess))
+                rc = LH_EDEVICE;
+            if (!rc) {
+                std::memcpy(&h, cx->h_totals, sizeof h);
+                const uint32_t cause = header_cause(h, len);
+                if (cause) rc = refuse(why, cause);
+            }
+        }
+        if (!rc) rc = load_block(cx, h, src + sizeof h, from_device, st, why, k);
+        if (rc) {
+            (void)hipGetLastError();
+            if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+    }
+    if (rc) {
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return LH_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int lh_kept_save_size(const lh_kept *k, size_t *bytes)
+{
+    if (!k || !bytes) return LH_EINVAL;
+    *bytes = (size_t)(LH_KEPT_BLOB_HEADER + k->bytes);
+    return LH_OK;
+}
+
+int lh_kept_save(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written)
+{
+    return kept_save(k, buf, cap, stream, written, false);
+}
+
+int lh_kept_save_device(lh_kept *k, void *d_buf, size_t cap, void *stream, size_t *written)
+{
+    return kept_save(k, d_buf, cap, stream, written, true);
+}
+
+int lh_kept_load(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out)
+{
+    return kept_load(device, buf, len, flags, stream, why, out, false);
+}
+
+int lh_kept_load_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out)
+{
+    return kept_load(device, d_buf, len, flags, stream, why, out, true);
+}
+
+int lh_tool_kept_check_ms(lh_kept *k, void *stream, float *check_ms, float *samples_ms)
+{
+    if (!k || !check_ms || !samples_ms) return LH_EINVAL;
+    KeptCtx *cx = k->cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(k->device));
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, 1, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+    if (rc) return rc;
+    u64 *verdict = cx->d_tmp;
+    LH_BESIDE_CHK(hipMemsetAsync(verdict, 0xff, sizeof(u64), st));
+    const u64 block = (u64)(uintptr_t)k->block;
+    float *const ms[2] = {check_ms, samples_ms};
+    rc = steps_ms(st, 2, ms, [&](int i) {
+        if (i == 0) hipLaunchKernelGGL(k_kept_check, wave_per_row(k->nrows), dim3(ROW_BLOCK), 0, st, block, k->nrows, k->cells, verdict);
+        else hipLaunchKernelGGL(k_kept_check_samples, dim3(1), dim3(WG), 0, st, block, k->nrows, k->samples, verdict);
+    });
+    if (rc) return rc;
+    LH_BESIDE_CHK(hipMemcpy(cx->h_totals, verdict, sizeof(u64), hipMemcpyDeviceToHost));
+    return cx->h_totals[0] == CHECK_NONE ? LH_OK : LH_ESTATE; // (never: a handle holds what the check asks for)
+}
+
+int lh_tool_keep_count_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, float *count_ms)
+{
+    if (!s || !count_ms || nmetrics == 0) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE;
+    KeptSource q;
+    int rc = source_cells(s, first, nmetrics, q);
+    if (!rc) rc = source_open(s, q);
+    if (rc) return rc;
+    const uint32_t nrows = (uint32_t)nmetrics;
+    std::lock_guard<std::mutex> g(q.cx->mu);
+    rc = grow_device(q.cx->d_tmp, q.cx->tmp_cap, 2 * (size_t)nrows + 3, 4096);
+    if (rc) return rc;
+    u64 *off = q.cx->d_tmp, *row_count = off + nrows + 1;
+    const uint32_t *ranges = ranges_from(q, first);
+    float *const ms[1] = {count_ms};
+    return steps_ms(q.stream, 1, ms, [&](int) {
+        with_cells(q, first, [&](auto c) {
+            hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), wave_per_row(nrows), dim3(ROW_BLOCK), 0, q.stream, c, ranges, q.stride,
+                               nrows, off, row_count);
+        });
+    });
+}
+
+int lh_kept_values(int device, double *D)
+{
+    if (!D || misaligned(D, 8) || device < 0 || device >= MAX_DEVICES) return LH_EINVAL;
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE; // (never: the range was checked)
+    std::lock_guard<std::mutex> g(cx->mu);
+    LH_BESIDE_CHK(hipSetDevice(device));
+    const int rc = ensure_table(cx->d_table, nullptr, lh::k_value_table<KeptCtx>);
+    if (rc) return rc;
+    LH_BESIDE_CHK(hipMemcpy(D, cx->d_table, (size_t)LH_NKEYS * sizeof(double), hipMemcpyDeviceToHost));
+    return LH_OK;
+}
 
 int lh_kept_top(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t by, double arg, size_t k,
                 uint32_t flags, void *stream, lh_top_entry *out, size_t *n_out)

@@ -748,7 +748,8 @@ class Snapshot:
 
 class Kept:
     """One interval's occupied cells of metrics [first, first + nrows), kept in compact form on the device (lh_kept):
-    Snapshot.keep().  It depends on neither its snapshot nor its engine, and never changes."""
+    Snapshot.keep(), Kept.merge(), or -- with no engine at all -- Kept.from_bytes / load / from_device_blob of a saved one.  It
+    depends on neither its snapshot nor its engine, and never changes."""
 
     _OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("nbuckets", 4, 0, np.uint32),
             ("present_bits", 8, 0, np.uint64), ("pkeys", 2, 1, np.int16), ("pvalid", 1, 1, np.uint8))
@@ -1004,6 +1005,84 @@ class Kept:
         return Snapshot._leaders("lh_kept_movers", (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3]),
                                  Snapshot._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
                                  N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out, (_stream_handle(stream),))
+
+    # -- save and load (lh_kept_save* / lh_kept_load*; loghisto_amd.keptfile has the blob's format in NumPy) ------------------------
+    def _save_size(self) -> int:
+        n = C.c_size_t(0)
+        N.check(N.lib().lh_kept_save_size(self._h, C.byref(n)), "lh_kept_save_size")
+        return int(n.value)
+
+    def to_bytes(self, stream=None) -> bytes:
+        """The handle as a blob (lh_kept_save): a 64-byte header and the four arrays verbatim.  Kept.from_bytes takes it back, in
+        this process or another, on this device or another, with no engine."""
+        n = self._save_size()
+        buf = np.empty(n, dtype=np.uint8)
+        written = C.c_size_t(0)
+        N.check(N.lib().lh_kept_save(self._h, buf.ctypes.data, n, _stream_handle(stream), C.byref(written)), "lh_kept_save")
+        return buf[:int(written.value)].tobytes()
+
+    def save(self, path, stream=None):
+        """to_bytes() written to the file `path`.  The names that belong to the ids are not part of it."""
+        with open(path, "wb") as f:
+            f.write(self.to_bytes(stream))
+
+    def to_device_blob(self, stream=None):
+        """The same blob as a torch uint8 tensor on the handle's device (lh_kept_save_device): what a rank hands to a
+        collective.  Kept.from_device_blob takes it back."""
+        import torch
+        n = self._save_size()
+        t = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", self.info["device"]))
+        N.check(N.lib().lh_kept_save_device(self._h, int(t.data_ptr()), n, _stream_handle(stream), None), "lh_kept_save_device")
+        return t
+
+    @staticmethod
+    def values(device: int = 0) -> np.ndarray:
+        """decompress() by bin, float64[N.NKEYS], as the kept readers weigh cells with on `device` (lh_kept_values): bit-equal to
+        Engine.codec_tables()' D, and there for a process that has no engine."""
+        D = Kept._values.get(device)
+        if D is None:                                  # fetched once per device: the table never changes
+            D = np.empty(N.NKEYS, dtype=np.float64)
+            N.check(N.lib().lh_kept_values(device, D.ctypes.data_as(C.POINTER(C.c_double))), "lh_kept_values")
+            D.flags.writeable = False
+            Kept._values[device] = D
+        return D
+
+    _values: dict = {}
+
+    @classmethod
+    def _load(cls, fn, device, addr, n, stream):
+        table = cls.values(device)                     # before the handle exists: a failure here leaves nothing behind
+        why = N.LhKeptCheck(struct_size=C.sizeof(N.LhKeptCheck))
+        h = C.c_void_p(0)
+        rc = getattr(N.lib(), fn)(device, addr, n, 0, _stream_handle(stream), C.byref(why), C.byref(h))
+        if rc == N.EINVAL:
+            from . import keptfile
+            raise ValueError(f"{fn}: not a kept blob: {keptfile.CAUSES.get(why.cause, why.cause)} (row {why.row}, index {why.index})")
+        N.check(rc, fn)
+        return cls(h, table)
+
+    @classmethod
+    def from_bytes(cls, blob, device: int = 0, stream=None) -> "Kept":
+        """A new Kept on `device` from a blob (lh_kept_load): every reader, merge, arrays and close take it like one made by
+        Snapshot.keep.  No engine is needed.  The blob is untrusted: it is checked on the device before the handle exists, and
+        ValueError says what is wrong with one that is refused."""
+        a = np.frombuffer(blob, dtype=np.uint8)
+        keep = a if a.size else np.zeros(1, dtype=np.uint8)   # an empty blob is a SHORT one, as keptfile.check has it: a valid address
+        return cls._load("lh_kept_load", device, keep.ctypes.data, int(a.size), stream)
+
+    @classmethod
+    def load(cls, path, device: int = 0, stream=None) -> "Kept":
+        """from_bytes() of the file `path`."""
+        with open(path, "rb") as f:
+            return cls.from_bytes(f.read(), device, stream)
+
+    @classmethod
+    def from_device_blob(cls, t, stream=None) -> "Kept":
+        """A new Kept on the device of `t`, a contiguous torch uint8 device tensor that holds a blob (lh_kept_load_device): only
+        its 64 header bytes come to the host."""
+        if not (getattr(t, "is_cuda", False) and t.element_size() == 1 and t.is_contiguous()):
+            raise ValueError("a contiguous torch uint8 device tensor")
+        return cls._load("lh_kept_load_device", t.device.index, int(t.data_ptr()), int(t.numel()), stream)
 
     def close(self):
         """Frees the device memory (lh_kept_release); waits first for enqueued device-form work that still reads it."""
