@@ -303,22 +303,8 @@ int compare(lh_snapshot *base, lh_snapshot *cur, uint32_t first, size_t nmetrics
     std::lock_guard<std::mutex> g(cx->mu);
     if (device_form) return enqueue(a, b, first, nmetrics, o);
 
-    // host form: results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys.
-    const size_t n8 = nmetrics * 8;
-    const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
-                            {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
-    return host_results(cx->res, b.stream, out, [&](unsigned char *const(&dev)[8]) {
-        CompareOut d;
-        d.count_a = reinterpret_cast<u64 *>(dev[0]);
-        d.count_b = reinterpret_cast<u64 *>(dev[1]);
-        d.ks = reinterpret_cast<double *>(dev[2]);
-        d.below_a = reinterpret_cast<u64 *>(dev[3]);
-        d.below_b = reinterpret_cast<u64 *>(dev[4]);
-        d.w1 = reinterpret_cast<double *>(dev[5]);
-        d.shift = reinterpret_cast<double *>(dev[6]);
-        d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
-        return enqueue(a, b, first, nmetrics, d);
-    });
+    // host form: results to HBM, then back to the caller's arrays
+    return compare_host_results(cx->res, b.stream, o, nmetrics, [&](const CompareOut &d) { return enqueue(a, b, first, nmetrics, d); });
 }
 
 } // namespace

@@ -1,6 +1,7 @@
 // lh_kept.hip -- lh_keep / lh_kept_* (include/loghisto_gpu.h): an interval's occupied cells kept in COMPACT form in device
-// memory after its snapshot is gone, and lh_across' (further down: lh_compare's, lh_count_le's, lh_spread's) outputs over a list of up to 64 such copies -- p99 over the last minute
-// of 1 s intervals while no dense epoch buffer of them is alive.  A dense buffer is 4 GiB at 8 192 names; the occupied cells
+// memory after its snapshot is gone, and the snapshot readers' outputs over a list of up to 64 such copies -- lh_across' first,
+// then lh_compare's, lh_count_le's, lh_spread's, lh_top's and lh_movers' further down: p99 over the last minute of 1 s
+// intervals while no dense epoch buffer of them is alive.  A dense buffer is 4 GiB at 8 192 names; the occupied cells
 // of an interval are a few hundred (int16 key, uint64 count) pairs per name (RawMetricSet.Histograms, metrics.go:54-60).
 // With c_i[b] the cells of a name in kept[i]:
 //   C[b] = sum over i of c_i[b], in 64 bits -- the cell atomic.AddUint64 would have left had the samples arrived in one
@@ -132,6 +133,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -1042,10 +1044,27 @@ namespace {
 
 typedef lh::beside::Source<KeptCtx> KeptSource;
 
+// The launch of every kernel k<[IDS,] NW> of this unit that walks M rows of a list: f(sh, nw) launches k<decltype(nw)::value>
+// with sh's grid and block -- the shape the unit's switch gives a call of M rows, NW = 1 (a wave per row) or WG_WAVES (a
+// workgroup per row).  With by_id, for the readers that have id forms: f(sh, ids, nw), IDS = decltype(ids)::value.
+template <class F> int launch_rows(uint32_t M, F f)
+{
+    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
+    if (sh.wave) f(sh, std::integral_constant<int, 1>());
+    else f(sh, std::integral_constant<int, WG_WAVES>());
+    LH_BESIDE_CHK(hipGetLastError());
+    return LH_OK;
+}
+template <class F> int launch_rows(uint32_t M, bool by_id, F f)
+{
+    if (by_id) return launch_rows(M, [&](const RowShape &sh, auto nw) { f(sh, std::true_type(), nw); });
+    return launch_rows(M, [&](const RowShape &sh, auto nw) { f(sh, std::false_type(), nw); });
+}
+
 // (cx->mu held, the device current)  The making of a handle of rows [first, first + nrows) on `st`, for lh_keep and
 // lh_kept_merge: count(off, row_count) enqueues the pass that leaves nnz in off[1 ..] and the rows' sums; then the scan, the
 // totals brought back, the allocation; fill(off, keys, counts) enqueues the pass that places the cells -- unless there are
-// none.  Returns when the handle is complete.  After a failure the caller waits for `st` and frees k->block.
+// none; both return a code.  Returns when the handle is complete.  After a failure the caller waits for `st` and frees k->block.
 template <class Count, class Fill>
 int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k, Count count, Fill fill)
 {
@@ -1054,7 +1073,8 @@ int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k
     if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 2, 2);
     if (rc) return rc;
     u64 *off = cx->d_tmp, *row_count = off + nrows + 1, *totals = off + head;
-    count(off, row_count);
+    rc = count(off, row_count);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, row_count, nrows, totals);
     LH_BESIDE_CHK(hipGetLastError());
     LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
@@ -1070,8 +1090,8 @@ int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k
     LH_BESIDE_CHK(hipMemcpyAsync(k->block, off, head * sizeof(u64), hipMemcpyDeviceToDevice, st));
     if (cells) {
         u64 *counts = k->block + head;
-        fill(off, reinterpret_cast<int16_t *>(counts + cells), counts);
-        LH_BESIDE_CHK(hipGetLastError());
+        rc = fill(off, reinterpret_cast<int16_t *>(counts + cells), counts);
+        if (rc) return rc;
     }
     LH_BESIDE_CHK(hipStreamSynchronize(st));
     return LH_OK;
@@ -1089,11 +1109,15 @@ int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
             with_cells(q, first, [&](auto c) {
                 hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, row_count);
             });
+            LH_BESIDE_CHK(hipGetLastError());
+            return LH_OK;
         },
         [&](const u64 *off, int16_t *keys, u64 *counts) {
             with_cells(q, first, [&](auto c) {
                 hipLaunchKernelGGL((k_keep_fill<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, keys, counts);
             });
+            LH_BESIDE_CHK(hipGetLastError());
+            return LH_OK;
         });
 }
 
@@ -1114,16 +1138,17 @@ KeptList list_of(lh_kept *const *kept, size_t nkept)
 int merge(KeptCtx *cx, lh_kept *const *kept, size_t nkept, uint32_t first, uint32_t nrows, hipStream_t st, lh_kept *k)
 {
     const KeptList s = list_of(kept, nkept);
-    const RowShape sh = row_shape(nrows, g_wave_from.load(std::memory_order_relaxed));
     return make(
         cx, st, first, nrows, k,
         [&](u64 *off, u64 *row_count) {
-            if (sh.wave) hipLaunchKernelGGL((k_merge_count<1>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
-            else hipLaunchKernelGGL((k_merge_count<WG_WAVES>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
+            return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_merge_count<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
+            });
         },
         [&](const u64 *off, int16_t *keys, u64 *counts) {
-            if (sh.wave) hipLaunchKernelGGL((k_merge_fill<1>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
-            else hipLaunchKernelGGL((k_merge_fill<WG_WAVES>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
+            return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_merge_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
+            });
         });
 }
 
@@ -1243,16 +1268,10 @@ int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, 
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const double *D = cx->d_table;
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    const auto launch = [&](auto by_id) {
-        constexpr bool IDS = decltype(by_id)::value;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_across<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
-        else hipLaunchKernelGGL((k_kept_across<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
-    };
-    if (sel.by_id) launch(std::true_type());
-    else launch(std::false_type());
-    LH_BESIDE_CHK(hipGetLastError());
-    return LH_OK;
+    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_across<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa,
+                           NP, o, ids);
+    });
 }
 
 int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
@@ -1286,25 +1305,10 @@ int enqueue_count_le(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowS
     for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    const auto launch = [&](auto by_id) {
-        constexpr bool IDS = decltype(by_id)::value;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_count_le<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, sb, NB, d_cum, d_total, ids);
-        else hipLaunchKernelGGL((k_kept_count_le<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, sb, NB, d_cum, d_total, ids);
-    };
-    if (sel.by_id) launch(std::true_type());
-    else launch(std::false_type());
-    LH_BESIDE_CHK(hipGetLastError());
-    return LH_OK;
-}
-
-// a list of 1 .. LH_MAX_KEPT handles, none of them NULL (LH_EINVAL), as check_list_args has it
-bool bad_list(lh_kept *const *kept, size_t nkept)
-{
-    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return true;
-    for (size_t i = 0; i < nkept; i++)
-        if (!kept[i]) return true;
-    return false;
+    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_count_le<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, sb,
+                           NB, d_cum, d_total, ids);
+    });
 }
 
 int kept_count_le(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb,
@@ -1312,7 +1316,7 @@ int kept_count_le(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t 
 {
     // ---- every check that needs neither a handle nor a device: lh_count_le's, with the list in the snapshot's place.  The bounds
     // are one shared row (LH_LE_PER_METRIC is refused with every other flag), so every cause of LH_EINVAL comes first.
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept)) return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT)) return LH_EINVAL;
     if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
     if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
     if (bad_bounds(bounds, nb)) return LH_EINVAL;
@@ -1348,23 +1352,17 @@ int enqueue_spread(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const double *D = cx->d_table;
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    const auto launch = [&](auto by_id) {
-        constexpr bool IDS = decltype(by_id)::value;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_spread<IDS, 1>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
-        else hipLaunchKernelGGL((k_kept_spread<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa, NP, o, ids);
-    };
-    if (sel.by_id) launch(std::true_type());
-    else launch(std::false_type());
-    LH_BESIDE_CHK(hipGetLastError());
-    return LH_OK;
+    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_spread<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa,
+                           NP, o, ids);
+    });
 }
 
 int kept_spread(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
                 void *stream, SpreadOut o, bool device_form)
 {
     // ---- every check that needs neither a handle nor a device: lh_spread's, with the list in the snapshot's place
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept) || flags != 0) return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || flags != 0) return LH_EINVAL;
     int rc = check_spread_args(p, np, o);
     if (rc) return rc;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
@@ -1394,32 +1392,29 @@ int enqueue_compare(KeptCtx *cx, lh_kept *const *all, size_t n, size_t nbase, co
     if (rc) return rc;
     const KeptList s = list_of(all, n);
     const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nbase;
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
-    const auto launch = [&](auto by_id) {
-        constexpr bool IDS = decltype(by_id)::value;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_compare<IDS, 1>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o, ids);
-        else hipLaunchKernelGGL((k_kept_compare<IDS, WG_WAVES>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o, ids);
-    };
-    if (sel.by_id) launch(std::true_type());
-    else launch(std::false_type());
-    LH_BESIDE_CHK(hipGetLastError());
-    return LH_OK;
+    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_compare<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o,
+                           ids);
+    });
+}
+
+// The two lists of lh_kept_compare* and lh_kept_movers* as ONE, base first (a handle per lane).  False unless each is a list of
+// 1 .. LH_MAX_KEPT handles, none of them NULL, and they hold at most LH_MAX_KEPT together.
+bool join_lists(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, lh_kept *(&all)[LH_MAX_KEPT])
+{
+    if (bad_list(base, nbase, LH_MAX_KEPT) || bad_list(cur, ncur, LH_MAX_KEPT) || nbase + ncur > LH_MAX_KEPT) return false;
+    std::copy(base, base + nbase, all);
+    std::copy(cur, cur + ncur, all + nbase);
+    return true;
 }
 
 int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const RowSel &sel, size_t nmetrics,
                  uint32_t flags, void *stream, const CompareOut &o, bool device_form)
 {
     // ---- every check that needs neither a handle nor a device
-    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
-    if (!base || !cur || misaligned(base, alignof(lh_kept *)) || misaligned(cur, alignof(lh_kept *))) return LH_EINVAL;
-    if (nbase == 0 || ncur == 0 || nbase > LH_MAX_KEPT || ncur > LH_MAX_KEPT || nbase + ncur > LH_MAX_KEPT) return LH_EINVAL;
-    lh_kept *all[LH_MAX_KEPT]; // one list, base first: a handle per lane
+    lh_kept *all[LH_MAX_KEPT];
     const size_t n = nbase + ncur;
-    for (size_t i = 0; i < n; i++) {
-        all[i] = i < nbase ? base[i] : cur[i - nbase];
-        if (!all[i]) return LH_EINVAL;
-    }
-    if (flags != 0) return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || !join_lists(base, nbase, cur, ncur, all) || flags != 0) return LH_EINVAL;
     if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
     if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
         misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
@@ -1434,21 +1429,8 @@ int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t
     return run(
         all, n, device, stream, device_form, // (a device form's hold: the handles of BOTH lists)
         [&](KeptCtx *cx, hipStream_t st) { return enqueue_compare(cx, all, n, nbase, sel, nmetrics, o, st); },
-        [&](KeptCtx *cx, hipStream_t st) {
-            // results to HBM, then back to the caller's arrays.  The 8-byte arrays, then the keys (lh_compare's blocks).
-            const size_t n8 = nmetrics * 8;
-            const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
-                                    {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
-            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[8]) {
-                CompareOut d;
-                d.count_a = reinterpret_cast<u64 *>(dev[0]);
-                d.count_b = reinterpret_cast<u64 *>(dev[1]);
-                d.ks = reinterpret_cast<double *>(dev[2]);
-                d.below_a = reinterpret_cast<u64 *>(dev[3]);
-                d.below_b = reinterpret_cast<u64 *>(dev[4]);
-                d.w1 = reinterpret_cast<double *>(dev[5]);
-                d.shift = reinterpret_cast<double *>(dev[6]);
-                d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            return compare_host_results(cx->res, st, o, nmetrics, [&](const CompareOut &d) {
                 return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
             });
         });
@@ -1477,23 +1459,24 @@ template <class Entry> int enqueue_select(KeptCtx *cx, const SelectCall &c, hipS
     if (rc) return rc;
     const KeptList s = list_of(c.all, c.n);
     const uint32_t M = (uint32_t)c.nmetrics;
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
     if (ev) LH_BESIDE_CHK(hipEventRecord(ev[0], st));
     if constexpr (std::is_same<Entry, lh_top_entry>::value) {
         const TopRecords r = top_records(base, npad);
         const u64 flip = (c.flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;
         const double *D = cx->d_table;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_top_score<1>), sh.grid, sh.block, 0, st, s, M, c.first, D, c.by, c.arg, flip, r);
-        else hipLaunchKernelGGL((k_kept_top_score<WG_WAVES>), sh.grid, sh.block, 0, st, s, M, c.first, D, c.by, c.arg, flip, r);
-        LH_BESIDE_CHK(hipGetLastError());
+        rc = launch_rows(M, [&](const RowShape &sh, auto nw) {
+            hipLaunchKernelGGL((k_kept_top_score<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, c.first, D, c.by, c.arg, flip, r);
+        });
+        if (rc) return rc;
         return select_pass(cx->sel, st, r.key, r.count, M, c.k, TopEmit{r, c.first, c.by, d_out}, d_n_out, ev);
     } else {
         const MoversRecords r = movers_records(base, npad);
         const u64 flip = (c.flags & LH_MOVERS_ASCENDING) ? ~0ull : 0ull;
         const uint32_t NB = (uint32_t)c.nbase;
-        if (sh.wave) hipLaunchKernelGGL((k_kept_movers_score<1>), sh.grid, sh.block, 0, st, s, NB, M, c.first, c.by, c.arg, flip, r);
-        else hipLaunchKernelGGL((k_kept_movers_score<WG_WAVES>), sh.grid, sh.block, 0, st, s, NB, M, c.first, c.by, c.arg, flip, r);
-        LH_BESIDE_CHK(hipGetLastError());
+        rc = launch_rows(M, [&](const RowShape &sh, auto nw) {
+            hipLaunchKernelGGL((k_kept_movers_score<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NB, M, c.first, c.by, c.arg, flip, r);
+        });
+        if (rc) return rc;
         return select_pass(cx->sel, st, r.key, r.cand, M, c.k, MoversEmit{r, c.first, d_out}, d_n_out, ev);
     }
 }
@@ -1503,18 +1486,10 @@ template <class Entry> int enqueue_select(KeptCtx *cx, const SelectCall &c, hipS
 int check_select(SelectCall &c, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
                  uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out, uintptr_t n_out_align)
 {
-    if (c.movers) {
-        if (!base || !cur || misaligned(base, alignof(lh_kept *)) || misaligned(cur, alignof(lh_kept *))) return LH_EINVAL;
-        if (nbase == 0 || ncur == 0 || nbase > LH_MAX_KEPT || ncur > LH_MAX_KEPT || nbase + ncur > LH_MAX_KEPT) return LH_EINVAL;
-    } else {
-        if (!cur || misaligned(cur, alignof(lh_kept *)) || ncur == 0 || ncur > LH_MAX_KEPT) return LH_EINVAL;
-    }
+    if (c.movers ? !join_lists(base, nbase, cur, ncur, c.all) : bad_list(cur, ncur, LH_MAX_KEPT)) return LH_EINVAL;
+    if (!c.movers) std::copy(cur, cur + ncur, c.all); // (lh_kept_top*: nbase == 0)
     c.nbase = nbase;
     c.n = nbase + ncur;
-    for (size_t i = 0; i < c.n; i++) {
-        c.all[i] = i < nbase ? base[i] : cur[i - nbase];
-        if (!c.all[i]) return LH_EINVAL;
-    }
     if (c.movers) {
         if (by > LH_MOVERS_BY_PERCENTILE || (flags & ~(uint32_t)LH_MOVERS_ASCENDING)) return LH_EINVAL;
         if (by == LH_MOVERS_BY_PERCENTILE && !(arg >= 0.0 && arg <= 1.0)) return LH_EINVAL; // NaN too: no bucket to rank by
@@ -1953,10 +1928,7 @@ int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_
 
 int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream, lh_kept **out)
 {
-    if (!kept || misaligned(kept, alignof(lh_kept *)) || nkept == 0 || nkept > LH_MAX_KEPT) return LH_EINVAL;
-    for (size_t i = 0; i < nkept; i++)
-        if (!kept[i]) return LH_EINVAL;
-    if (flags != 0 || !out || nmetrics == 0) return LH_EINVAL;
+    if (bad_list(kept, nkept, LH_MAX_KEPT) || flags != 0 || !out || nmetrics == 0) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE;
     // ---- from here on the handles are looked at
     const int device = kept[nkept - 1]->device;

@@ -5,8 +5,10 @@
 // bins (take4) and the wave's largest X at its lowest bin (wave_best, without LDS: DPP max-reductions, lh_wave.h's wave_max_u32, over the
 // 32-bit words of X from the top).  lh_compare.hip's header says what X, ks, w1 and shift are; a unit that wants the bits of
 // k_compare_wave's sums calls these in its order: the steps in ascending order per lane, then one DPP tree over the lanes.
+// Behind the device part, CompareOut's way through host_results (compare_host_results), for lh_compare.hip and lh_kept.hip.
 #pragma once
 
+#include "lh_beside.h"
 #include "lh_wave.h"
 
 #include <hip/hip_runtime.h>
@@ -114,4 +116,30 @@ __device__ __forceinline__ void wave_best(const Best &r, u128 &x, uint32_t &bin,
     x = ((u128)readlane_u64((u64)(r.x >> 64), src) << 64) | readlane_u64((u64)r.x, src);
 }
 
+// ---- host side ----------------------------------------------------------------------------------------------------------
+namespace beside {
+
+// (the context's mutex held)  The host form of lh_compare* and lh_kept_compare*: `enqueue(d)` puts the work that fills d -- o's
+// arrays, in HBM -- on `st`.  The 8-byte arrays, then the keys.
+template <class Enqueue>
+int compare_host_results(ResultBlocks &rb, hipStream_t st, const CompareOut &o, size_t nmetrics, Enqueue enqueue)
+{
+    const size_t n8 = nmetrics * 8;
+    const HostOut out[8] = {{o.count_a, n8}, {o.count_b, n8}, {o.ks, n8},    {o.below_a, n8},
+                            {o.below_b, n8}, {o.w1, n8},      {o.shift, n8}, {o.ks_key, nmetrics * 2}};
+    return host_results(rb, st, out, [&](unsigned char *const(&dev)[8]) {
+        CompareOut d;
+        d.count_a = reinterpret_cast<u64 *>(dev[0]);
+        d.count_b = reinterpret_cast<u64 *>(dev[1]);
+        d.ks = reinterpret_cast<double *>(dev[2]);
+        d.below_a = reinterpret_cast<u64 *>(dev[3]);
+        d.below_b = reinterpret_cast<u64 *>(dev[4]);
+        d.w1 = reinterpret_cast<double *>(dev[5]);
+        d.shift = reinterpret_cast<double *>(dev[6]);
+        d.ks_key = reinterpret_cast<int16_t *>(dev[7]);
+        return enqueue(d);
+    });
+}
+
+} // namespace beside
 } // namespace lh

@@ -265,16 +265,22 @@ int list_host_results(ResultBlocks &rb, hipStream_t st, const ListOut<PRESENT> &
     return host_results(rb, st, out, [&](unsigned char *const(&dev)[6]) { return enqueue(ListOut<PRESENT>::on_device(dev)); });
 }
 
+// unless `list` is a list of 1 .. `most` handles, none of them NULL
+template <class H> bool bad_list(H *const *list, size_t n, size_t most)
+{
+    if (!list || misaligned(list, alignof(H *)) || n == 0 || n > most) return true;
+    for (size_t i = 0; i < n; i++)
+        if (!list[i]) return true;
+    return false;
+}
+
 // Every check that needs neither a source nor a device: a list of 1 .. `most` handles, a row selection, percentiles, the
 // six outputs.  With np == 0 the per-percentile outputs are ignored: they are nulled here, and count for nothing.
 template <class H, class PRESENT>
 int check_list_args(H *const *list, size_t n, size_t most, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
                     uint32_t flags, ListOut<PRESENT> &o)
 {
-    if (bad_ids(sel, nmetrics)) return LH_EINVAL;
-    if (!list || misaligned(list, alignof(H *)) || n == 0 || n > most) return LH_EINVAL;
-    for (size_t i = 0; i < n; i++)
-        if (!list[i]) return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || bad_list(list, n, most)) return LH_EINVAL;
     if (np > LH_MAX_PERCENTILES || (np && !p) || flags != 0) return LH_EINVAL;
     if (np == 0) {
         o.pkeys = nullptr;

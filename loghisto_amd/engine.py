@@ -38,7 +38,7 @@ def _stream_handle(stream) -> int:
 
 
 def _out_arrays(out: dict, spec):
-    """out= of spread / compare, a dict of per-name output arrays, against spec = (key, element width, elements or None:
+    """out= of _dict_call, a dict of per-name output arrays, against spec = (key, element width, elements or None:
     not measured) per output in the library's order -> (the library's pointer arguments, device form?)."""
     if not out or set(out) - {k for k, _, _ in spec}:
         raise ValueError("out holds some of " + ", ".join(k for k, _, _ in spec))
@@ -73,19 +73,29 @@ def _id_list(ids):
     return a, int(a.ctypes.data), int(a.size), False
 
 
-_SPREAD_OUT = (("count", 8, 0), ("sum", 8, 0), ("m2", 8, 0), ("pkeys", 2, 1), ("pvalid", 1, 1), ("count_le", 8, 1), ("sum_le", 8, 1))
+# The outputs of a reader that returns a dict of per-name arrays, in the library's order: (key, element width, an element per
+# name AND percentile -- or bound -- rather than one per name?, numpy dtype)
+_SPREAD_OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("m2", 8, 0, np.float64), ("pkeys", 2, 1, np.int16),
+               ("pvalid", 1, 1, np.uint8), ("count_le", 8, 1, np.uint64), ("sum_le", 8, 1, np.float64))
+_COMPARE_OUT = (("count_a", 8, 0, np.uint64), ("count_b", 8, 0, np.uint64), ("ks", 8, 0, np.float64), ("key", 2, 0, np.int16),
+                ("below_a", 8, 0, np.uint64), ("below_b", 8, 0, np.uint64), ("w1", 8, 0, np.float64), ("shift", 8, 0, np.float64))
+_KEPT_COUNT_LE_OUT = (("cum", 8, 1, np.uint64), ("total", 8, 0, np.uint64))
 
 
-def _spread_call(fn, lead, nmetrics, np_, out, device_ids, table):
-    """Snapshot.spread* and Kept.spread: library call `fn` (host form) or fn + "_device" with `lead`, every argument ahead of
-    the seven outputs, for nmetrics names and np_ percentiles -> the dict with the derived fields.  device_ids: whether an id
-    list lies on the device, which the outputs then do too (None: there is none); table(): decompress() by bin."""
+def _dict_call(fn, lead, spec, nmetrics, np_, out, device_ids=None, derive=None, table=None):
+    """The out= protocol of the readers that return a dict of per-name arrays: library call `fn` (host form) or fn + "_device"
+    with `lead`, every argument ahead of the outputs `spec` lists, for nmetrics names and np_ percentiles (or bounds).
+    out: None (pinned arrays of this call's own), or a dict with some of spec's keys -> numpy arrays (the host form into them)
+    or torch device tensors (the device form: returned as they are, dict(out)).  device_ids: whether an id list lies on the
+    device, which the outputs then do too (None: there is none).  derive(res, table), if given, adds a host form's derived fields;
+    table(): decompress() by bin."""
     L = N.lib()
+    per_p = {k: c for k, _, c, _ in spec}
     if device_ids and out is None:
         raise ValueError("device ids go with an out= of device tensors")
     if out is not None:                                # (without percentiles the per-percentile arrays are not measured)
-        args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
-                                         for k, width, per_p in _SPREAD_OUT])
+        args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p[k] else nmetrics)
+                                         for k, width, *_ in spec])
         if device_ids is not None and device != device_ids:
             raise ValueError("ids and out are both on the device or both on the host")
         if device:
@@ -93,28 +103,51 @@ def _spread_call(fn, lead, nmetrics, np_, out, device_ids, table):
             return dict(out)
         N.check(getattr(L, fn)(*lead, *args), fn)
         res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
-               if v is not None and (np_ or k in ("count", "sum", "m2"))}
+               if v is not None and (np_ or not per_p[k])}                                  # (... and not returned)
     else:
         import torch
-        kinds = dict(count=(torch.int64, np.uint64), sum=(torch.float64, np.float64), m2=(torch.float64, np.float64),
-                     pkeys=(torch.int16, np.int16), pvalid=(torch.uint8, np.uint8), count_le=(torch.int64, np.uint64),
-                     sum_le=(torch.float64, np.float64))
         res = {}
-        for k, _, per_p in _SPREAD_OUT:                # (a row more than an empty call needs: the arrays have addresses)
-            shape = (max(nmetrics, 1), np_) if per_p else (max(nmetrics, 1),)
-            res[k] = torch.zeros(shape, dtype=kinds[k][0], pin_memory=True).numpy().view(kinds[k][1])
-        N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, _, _ in _SPREAD_OUT]), fn)
-        res = {k: v[:nmetrics] for k, v in res.items()}
-    res = {k: (v.reshape(nmetrics, np_) if dict((a, c) for a, _, c in _SPREAD_OUT)[k] else v.reshape(nmetrics))
-           for k, v in res.items()}
+        for k, width, _, dt in spec:                   # (a row more than an empty call needs: the arrays have addresses)
+            n = max(nmetrics, 1) * (np_ if per_p[k] else 1)
+            res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
+        N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in spec]), fn)
+        res = {k: v[:nmetrics * (np_ if per_p[k] else 1)] for k, v in res.items()}
+    res = {k: v.reshape((nmetrics, np_) if per_p[k] else (nmetrics,)) for k, v in res.items()}
+    return derive(res, table) if derive else res
+
+
+def _key_values(keys, table):
+    """decompress(key) for an array of int16 keys; table(): decompress() by bin."""
+    return table()[keys.view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
+
+
+def _across_derived(res, table):
+    """avg and pvals of across, where the arrays they come from were asked for."""
+    if "sum" in res and "count" in res:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res["avg"] = res["sum"] / res["count"].view(np.uint64).astype(np.float64)
+    if "pkeys" in res and "pvalid" in res:
+        res["pvals"] = np.where(res["pvalid"] != 0, _key_values(res["pkeys"], table), np.nan)
+    return res
+
+
+def _spread_derived(res, table):
+    """std, mean_le and upper of spread, where the arrays they come from were asked for."""
     with np.errstate(divide="ignore", invalid="ignore"):
         if "m2" in res and "count" in res:
             res["std"] = np.sqrt(res["m2"] / res["count"].view(np.uint64).astype(np.float64))
         if "sum_le" in res and "count_le" in res:
             res["mean_le"] = res["sum_le"] / res["count_le"].view(np.uint64).astype(np.float64)
     if "pkeys" in res and "pvalid" in res:
-        bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
-        res["upper"] = np.where(res["pvalid"] != 0, table()[bins], np.nan)
+        res["upper"] = np.where(res["pvalid"] != 0, _key_values(res["pkeys"], table), np.nan)
+    return res
+
+
+def _compare_derived(res, table):
+    """ks_value of compare, where key was asked for."""
+    if "key" in res:
+        value = _key_values(res["key"], table)
+        res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
     return res
 
 
@@ -478,8 +511,8 @@ class Snapshot:
         """spread / spread_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments.
         device_ids: whether an id list lies on the device, which the outputs then do too (None: there is none)."""
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
-        return _spread_call(fn, (self._h, *rows, p.ctypes.data, int(p.size)), nmetrics, int(p.size), out, device_ids,
-                            self._decompress_table)
+        return _dict_call(fn, (self._h, *rows, p.ctypes.data, int(p.size)), _SPREAD_OUT, nmetrics, int(p.size), out, device_ids,
+                          _spread_derived, self._decompress_table)
 
     def _decompress_table(self) -> np.ndarray:
         """decompress() by bin (the engine's codec_tables), fetched once per engine."""
@@ -570,8 +603,7 @@ class Snapshot:
         return out.reshape(-1)[:n.value]
 
     # -- distribution shift against another snapshot (percentile()'s bucket walk, metrics.go:389-418, over two rows at once) --
-    _COMPARE_OUT = (("count_a", 8, np.uint64), ("count_b", 8, np.uint64), ("ks", 8, np.float64), ("key", 2, np.int16),
-                    ("below_a", 8, np.uint64), ("below_b", 8, np.uint64), ("w1", 8, np.float64), ("shift", 8, np.float64))
+    _COMPARE_OUT = _COMPARE_OUT
 
     def compare(self, base: "Snapshot", nmetrics: Optional[int] = None, first: int = 0, out=None):
         """How metrics [first, first+nmetrics) of THIS snapshot differ from the same names of `base` (lh_compare*), as a
@@ -586,29 +618,10 @@ class Snapshot:
         elements of 8 bytes (key: 2); outputs left out are not computed.  torch device tensors take the device form:
         enqueued on this snapshot's stream (`base` must stay unreleased until that stream has passed the call), the
         tensors are returned as they are and nothing is derived.  numpy arrays take the host form."""
-        L = N.lib()
         if nmetrics is None:
             nmetrics = self.engine.num_metrics() - first
-        if out is not None:
-            args, device = _out_arrays(out, [(k, width, nmetrics) for k, width, _ in self._COMPARE_OUT])
-            if device:
-                N.check(L.lh_compare_device(base._h, self._h, first, nmetrics, 0, *args), "lh_compare_device")
-                return dict(out)
-            N.check(L.lh_compare(base._h, self._h, first, nmetrics, 0, *args), "lh_compare")
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()).reshape(nmetrics)
-                   for k, v in out.items() if v is not None}
-        else:
-            import torch
-            res = {}
-            for k, width, dt in self._COMPARE_OUT:     # (an element more than an empty call needs: the arrays have addresses)
-                res[k] = torch.zeros((max(nmetrics, 1) * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
-            N.check(L.lh_compare(base._h, self._h, first, nmetrics, 0, *[res[k].ctypes.data for k, _, _ in self._COMPARE_OUT]),
-                    "lh_compare")
-            res = {k: v[:nmetrics] for k, v in res.items()}
-        if "key" in res:
-            value = self._decompress_table()[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
-            res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
-        return res
+        return _dict_call("lh_compare", (base._h, self._h, first, nmetrics, 0), _COMPARE_OUT, nmetrics, 0, out,
+                          derive=_compare_derived, table=self._decompress_table)
 
     # -- the k names whose distribution moved most against another snapshot (compare's scores, top's selection) ------------
     _MOVERS_BY = {"ks": N.MOVERS_BY_KS, "w1": N.MOVERS_BY_W1, "shift": N.MOVERS_BY_SHIFT, "percentile": N.MOVERS_BY_PERCENTILE}
@@ -667,42 +680,12 @@ class Snapshot:
     def _across(self, fn, earlier, rows, nmetrics, percentiles, out, device_ids=None):
         """across / across_ids: library call `fn` (host form) or fn + "_device" over `rows`, its row arguments.
         device_ids: whether an id list lies on the device, which the outputs then do too (None: there is none)."""
-        L = N.lib()
         snaps = list(earlier) + [self]
         handles = (C.c_void_p * len(snaps))(*[s._h.value for s in snaps])
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
-        np_ = int(p.size)
-        lead = (C.addressof(handles), len(snaps), *rows, p.ctypes.data, np_, 0)
-        if device_ids and out is None:
-            raise ValueError("device ids go with an out= of device tensors")
-        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
-            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
-                                             for k, width, per_p, _ in self._ACROSS_OUT])
-            if device_ids is not None and device != device_ids:
-                raise ValueError("ids and out are both on the device or both on the host")
-            if device:
-                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
-                return dict(out)
-            N.check(getattr(L, fn)(*lead, *args), fn)
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
-                   if v is not None and (np_ or k not in ("pkeys", "pvalid"))}
-        else:
-            import torch
-            res = {}
-            for k, width, per_p, dt in self._ACROSS_OUT:   # (a row more than an empty call needs: the arrays have addresses)
-                n = max(nmetrics, 1) * (np_ if per_p else 1)
-                res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
-            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._ACROSS_OUT]), fn)
-            res = {k: v[:nmetrics * (np_ if per_p else 1)] for (k, _, per_p, _), v in zip(self._ACROSS_OUT, res.values())}
-        per_p = {k: c for k, _, c, _ in self._ACROSS_OUT}
-        res = {k: (v.reshape(nmetrics, np_) if per_p[k] else v.reshape(nmetrics)) for k, v in res.items()}
-        if "sum" in res and "count" in res:
-            with np.errstate(divide="ignore", invalid="ignore"):
-                res["avg"] = res["sum"] / res["count"].view(np.uint64).astype(np.float64)
-        if "pkeys" in res and "pvalid" in res:
-            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
-            res["pvals"] = np.where(res["pvalid"] != 0, self._decompress_table()[bins], np.nan)
-        return res
+        lead = (C.addressof(handles), len(snaps), *rows, p.ctypes.data, int(p.size), 0)
+        return _dict_call(fn, lead, self._ACROSS_OUT, nmetrics, int(p.size), out, device_ids,
+                          _across_derived, self._decompress_table)
 
     def keep(self, nmetrics: Optional[int] = None, first: int = 0) -> "Kept":
         """The occupied cells of metrics [first, first+nmetrics) in compact form, in device memory of their own (lh_keep): a
@@ -790,6 +773,42 @@ class Kept:
         snapshot.add_buckets_csr(offsets, keys, counts, first=self.info["first"])
         N.check(N.lib().lh_kept_hold(self._h, snapshot.stream()), "lh_kept_hold")
 
+    # -- what the readers and merge share: the handle lists, the block's defaults, the leading arguments ----------------------
+    @staticmethod
+    def _handles(kept):
+        """-> (the handles of `kept` as the library takes a list, its length).  The caller holds on to the array until the
+        library call has returned."""
+        return (C.c_void_p * max(len(kept), 1))(*[k._h.value for k in kept]), len(kept)
+
+    def _list(self, earlier):
+        """list(earlier) + [self] -> (list, nkept)"""
+        return self._handles(list(earlier) + [self])
+
+    def _pair(self, base, earlier):
+        """`base`, a Kept or a sequence of them, and list(earlier) + [self] -> (base, nbase, cur, ncur)"""
+        return (*self._handles([base] if isinstance(base, Kept) else list(base)), *self._list(earlier))
+
+    def _block(self, nmetrics, first):
+        """first=None: this handle's first; nmetrics=None: up to the end of this handle's block."""
+        if first is None:
+            first = self.info["first"]
+        if nmetrics is None:
+            nmetrics = self.info["first"] + self.info["nrows"] - first
+        return nmetrics, first
+
+    def _decompress_table(self) -> np.ndarray:
+        return self._table
+
+    def _list_rows(self, lists, fn, nmetrics, first, ids):
+        """The leading arguments of a reader over `lists`, _list's or _pair's: -> (what keeps the arrays alive, library call,
+        (list, nkept, [list, nkept,] rows ...), nmetrics, device ids? or None)."""
+        heads = tuple(x if isinstance(x, int) else C.addressof(x) for x in lists)
+        if ids is not None:
+            keep, addr, nmetrics, device_ids = _id_list(ids)
+            return (lists, keep), fn + "_ids", (*heads, addr, nmetrics), nmetrics, device_ids
+        nmetrics, first = self._block(nmetrics, first)
+        return (lists,), fn, (*heads, first, nmetrics), nmetrics, None
+
     def across(self, earlier, percentiles, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
         """Snapshot.across over kept intervals: dict(count, sum, avg, nbuckets, present_bits, pkeys, pvalid, pvals) for metrics
         [first, first+nmetrics) -- or, with ids=, for the metrics `ids` in that order -- over list(earlier) + [self] taken
@@ -797,50 +816,11 @@ class Kept:
         and ids are metric ids; every handle of the list must hold them.  nmetrics=None: up to the end of this handle's block.
         present_bits is uint64.  out= as for Snapshot.across (present_bits 8 bytes); torch device tensors take the device form,
         enqueued on `stream` (a torch stream or a raw handle; None: the null stream), and device ids go with them."""
-        L = N.lib()
-        kept = list(earlier) + [self]
-        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
-        np_ = int(p.size)
-        device_ids = None
-        if ids is not None:
-            keep, addr, nmetrics, device_ids = _id_list(ids)
-            fn, rows = "lh_kept_across_ids", (addr, nmetrics)
-        else:
-            if nmetrics is None:
-                nmetrics = self.info["first"] + self.info["nrows"] - first
-            fn, rows = "lh_kept_across", (first, nmetrics)
-        lead = (C.addressof(handles), len(kept), *rows, p.ctypes.data, np_, 0, _stream_handle(stream))
-        if device_ids and out is None:
-            raise ValueError("device ids go with an out= of device tensors")
-        if out is not None:                            # (without percentiles the per-percentile arrays are not measured)
-            args, device = _out_arrays(out, [(k, width, (nmetrics * np_ if np_ else None) if per_p else nmetrics)
-                                             for k, width, per_p, _ in self._OUT])
-            if device_ids is not None and device != device_ids:
-                raise ValueError("ids and out are both on the device or both on the host")
-            if device:
-                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
-                return dict(out)
-            N.check(getattr(L, fn)(*lead, *args), fn)
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items()
-                   if v is not None and (np_ or k not in ("pkeys", "pvalid"))}
-        else:
-            import torch
-            res = {}
-            for k, width, per_p, dt in self._OUT:      # (a row more than an empty call needs: the arrays have addresses)
-                n = max(nmetrics, 1) * (np_ if per_p else 1)
-                res[k] = torch.zeros((n * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
-            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data if res[k].size else 0 for k, *_ in self._OUT]), fn)
-            res = {k: v[:nmetrics * (np_ if per_p else 1)] for (k, _, per_p, _), v in zip(self._OUT, res.values())}
-        per_p = {k: c for k, _, c, _ in self._OUT}
-        res = {k: (v.reshape(nmetrics, np_) if per_p[k] else v.reshape(nmetrics)) for k, v in res.items()}
-        if "sum" in res and "count" in res:
-            with np.errstate(divide="ignore", invalid="ignore"):
-                res["avg"] = res["sum"] / res["count"].view(np.uint64).astype(np.float64)
-        if "pkeys" in res and "pvalid" in res:
-            bins = res["pkeys"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000
-            res["pvals"] = np.where(res["pvalid"] != 0, self._table[bins], np.nan)
-        return res
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(self._list(earlier), "lh_kept_across", nmetrics, first, ids)
+        lead = (*rows, p.ctypes.data, int(p.size), 0, _stream_handle(stream))
+        return _dict_call(fn, lead, self._OUT, nmetrics, int(p.size), out, device_ids,
+                          _across_derived, self._decompress_table)
 
     def merge(self, earlier=(), nmetrics: Optional[int] = None, first: Optional[int] = None, stream=None) -> "Kept":
         """list(earlier) + [self] rolled up into ONE new Kept of metrics [first, first+nmetrics) (lh_kept_merge): per metric the
@@ -848,14 +828,10 @@ class Kept:
         in one interval.  A handle listed twice counts twice; every handle of the list must hold the block.  first=None: this
         handle's first; nmetrics=None: up to the end of this handle's block.  The work goes on `stream` (a torch stream or a
         raw handle; None: the null stream) and is complete on return; the new handle depends on none of the listed ones."""
-        kept = list(earlier) + [self]
-        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
-        if first is None:
-            first = self.info["first"]
-        if nmetrics is None:
-            nmetrics = self.info["first"] + self.info["nrows"] - first
+        nmetrics, first = self._block(nmetrics, first)
+        handles, nkept = self._list(earlier)
         h = C.c_void_p(0)
-        N.check(N.lib().lh_kept_merge(C.addressof(handles), len(kept), first, nmetrics, 0, _stream_handle(stream), C.byref(h)),
+        N.check(N.lib().lh_kept_merge(C.addressof(handles), nkept, first, nmetrics, 0, _stream_handle(stream), C.byref(h)),
                 "lh_kept_merge")
         return Kept(h, self._table)
 
@@ -868,56 +844,9 @@ class Kept:
         them.  nmetrics=None: up to the end of this handle's block.  out= as for Snapshot.compare; torch device tensors take
         the device form, enqueued on `stream` (a torch stream or a raw handle; None: the null stream), and device ids go with
         them.  Every handle may be closed right afterwards: close() waits."""
-        L = N.lib()
-        spec = Snapshot._COMPARE_OUT
-        lists = []
-        for kept in (([base] if isinstance(base, Kept) else list(base)), list(earlier) + [self]):
-            lists.append((C.c_void_p * max(len(kept), 1))(*[k._h.value for k in kept]))
-            lists.append(len(kept))
-        device_ids = None
-        if ids is not None:
-            keep, addr, nmetrics, device_ids = _id_list(ids)
-            fn, rows = "lh_kept_compare_ids", (addr, nmetrics)
-        else:
-            if nmetrics is None:
-                nmetrics = self.info["first"] + self.info["nrows"] - first
-            fn, rows = "lh_kept_compare", (first, nmetrics)
-        lead = (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3], *rows, 0, _stream_handle(stream))
-        if device_ids and out is None:
-            raise ValueError("device ids go with an out= of device tensors")
-        if out is not None:
-            args, device = _out_arrays(out, [(k, width, nmetrics) for k, width, _ in spec])
-            if device_ids is not None and device != device_ids:
-                raise ValueError("ids and out are both on the device or both on the host")
-            if device:
-                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
-                return dict(out)
-            N.check(getattr(L, fn)(*lead, *args), fn)
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()).reshape(nmetrics)
-                   for k, v in out.items() if v is not None}
-        else:
-            import torch
-            res = {}
-            for k, width, dt in spec:                  # (an element more than an empty call needs: the arrays have addresses)
-                res[k] = torch.zeros((max(nmetrics, 1) * width,), dtype=torch.uint8, pin_memory=True).numpy().view(dt)
-            N.check(getattr(L, fn)(*lead, *[res[k].ctypes.data for k, _, _ in spec]), fn)
-            res = {k: v[:nmetrics] for k, v in res.items()}
-        if "key" in res:
-            value = self._table[res["key"].view(np.int16).astype(np.int64) & 0xffff ^ 0x8000]
-            res["ks_value"] = np.where(np.isnan(res["ks"]), np.nan, value) if "ks" in res else value
-        return res
-
-    def _list_rows(self, earlier, fn, nmetrics, first, ids):
-        """The leading arguments of a reader over list(earlier) + [self]: -> (what keeps the arrays alive, library call, (list,
-        nkept, rows ...), nmetrics, device ids? or None).  nmetrics=None: up to the end of this handle's block."""
-        kept = list(earlier) + [self]
-        handles = (C.c_void_p * len(kept))(*[k._h.value for k in kept])
-        if ids is not None:
-            keep, addr, nmetrics, device_ids = _id_list(ids)
-            return (handles, keep), fn + "_ids", (C.addressof(handles), len(kept), addr, nmetrics), nmetrics, device_ids
-        if nmetrics is None:
-            nmetrics = self.info["first"] + self.info["nrows"] - first
-        return (handles,), fn, (C.addressof(handles), len(kept), first, nmetrics), nmetrics, None
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(self._pair(base, earlier), "lh_kept_compare", nmetrics, first, ids)
+        return _dict_call(fn, (*rows, 0, _stream_handle(stream)), _COMPARE_OUT, nmetrics, 0, out, device_ids,
+                          _compare_derived, self._decompress_table)
 
     def count_le(self, bounds, earlier=(), nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
         """Snapshot.count_le over kept intervals (lh_kept_count_le*): dict(cum=uint64[nmetrics, nb], total=uint64[nmetrics]) for
@@ -927,30 +856,12 @@ class Kept:
         handles).  first and ids are metric ids; every handle must hold them.  out= a dict with cum and / or total, as for
         Kept.across: torch device tensors take the device form, enqueued on `stream` (a torch stream or a raw handle; None: the
         null stream), and device ids go with them; every handle may be closed right afterwards: close() waits."""
-        L = N.lib()
         b = np.ascontiguousarray(bounds, dtype=np.float64)
         if b.ndim != 1:
             raise ValueError("bounds over kept intervals are 1-D: one row shared by all names")
-        nb = int(b.size)
-        alive, fn, rows, nmetrics, device_ids = self._list_rows(earlier, "lh_kept_count_le", nmetrics, first, ids)
-        lead = (*rows, b.ctypes.data, nb, 0, _stream_handle(stream))
-        if device_ids and out is None:
-            raise ValueError("device ids go with an out= of device tensors")
-        if out is not None:
-            args, device = _out_arrays(out, [("cum", 8, nmetrics * nb), ("total", 8, nmetrics)])
-            if device_ids is not None and device != device_ids:
-                raise ValueError("ids and out are both on the device or both on the host")
-            if device:
-                N.check(getattr(L, fn + "_device")(*lead, *args), fn + "_device")
-                return dict(out)
-            N.check(getattr(L, fn)(*lead, *args), fn)
-            res = {k: (np.asarray(v) if not hasattr(v, "data_ptr") else v.numpy()) for k, v in out.items() if v is not None}
-        else:
-            import torch
-            res = {k: torch.zeros((max(n, 1),), dtype=torch.int64, pin_memory=True).numpy().view(np.uint64)[:n]
-                   for k, n in (("cum", nmetrics * nb), ("total", nmetrics))}
-            N.check(getattr(L, fn)(*lead, res["cum"].ctypes.data, res["total"].ctypes.data), fn)
-        return {k: (v.reshape(nmetrics, nb) if k == "cum" else v.reshape(nmetrics)) for k, v in res.items()}
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(self._list(earlier), "lh_kept_count_le", nmetrics, first, ids)
+        lead = (*rows, b.ctypes.data, int(b.size), 0, _stream_handle(stream))
+        return _dict_call(fn, lead, _KEPT_COUNT_LE_OUT, nmetrics, int(b.size), out, device_ids)
 
     def spread(self, percentiles, earlier=(), nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
         """Snapshot.spread over kept intervals (lh_kept_spread*): the same dict -- count, sum, m2, std, pkeys, pvalid, count_le,
@@ -960,20 +871,13 @@ class Kept:
         `stream` (a torch stream or a raw handle; None: the null stream), nothing is derived, and device ids go with them;
         every handle may be closed right afterwards: close() waits."""
         p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
-        alive, fn, rows, nmetrics, device_ids = self._list_rows(earlier, "lh_kept_spread", nmetrics, first, ids)
+        alive, fn, rows, nmetrics, device_ids = self._list_rows(self._list(earlier), "lh_kept_spread", nmetrics, first, ids)
         lead = (*rows, p.ctypes.data, int(p.size), 0, _stream_handle(stream))
-        return _spread_call(fn, lead, nmetrics, int(p.size), out, device_ids, lambda: self._table)
+        return _dict_call(fn, lead, _SPREAD_OUT, nmetrics, int(p.size), out, device_ids,
+                          _spread_derived, self._decompress_table)
 
     # -- the two readers that select across names (lh_top's / lh_movers' entries; what is ranked is what across / count_le /
     #    compare return for the same lists) ------------------------------------------------------------------------------------
-    def _block(self, nmetrics, first):
-        """first=None: this handle's first; nmetrics=None: up to the end of this handle's block (as _list_rows)."""
-        if first is None:
-            first = self.info["first"]
-        if nmetrics is None:
-            nmetrics = self.info["first"] + self.info["nrows"] - first
-        return nmetrics, first
-
     def top(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False, earlier=(),
             nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
         """Snapshot.top over kept intervals (lh_kept_top*): the k names of [first, first+nmetrics) that lead over
@@ -984,9 +888,8 @@ class Kept:
         form, an (entries, n) pair of torch device tensors the device form, enqueued on `stream` (a torch stream or a raw handle;
         None: the null stream); every handle may be closed right afterwards: close() waits."""
         nmetrics, first = self._block(nmetrics, first)
-        kept = list(earlier) + [self]
-        handles = (C.c_void_p * len(kept))(*[h._h.value for h in kept])
-        return Snapshot._leaders("lh_kept_top", (C.addressof(handles), len(kept)), Snapshot._TOP_BY, ("percentile", "count_above"),
+        handles, nkept = self._list(earlier)
+        return Snapshot._leaders("lh_kept_top", (C.addressof(handles), nkept), Snapshot._TOP_BY, ("percentile", "count_above"),
                                  "TOP_ENTRY", k, by, arg, N.TOP_ASCENDING if ascending else 0, nmetrics, first, out,
                                  (_stream_handle(stream),))
 
@@ -998,10 +901,7 @@ class Kept:
         lists) or "percentile" (arg = p: the buckets Kept.across selects on either side).  At most N.MAX_KEPT handles in the
         two lists together.  first / nmetrics / out / stream as for Kept.top."""
         nmetrics, first = self._block(nmetrics, first)
-        lists = []
-        for kept in (([base] if isinstance(base, Kept) else list(base)), list(earlier) + [self]):
-            lists.append((C.c_void_p * max(len(kept), 1))(*[h._h.value for h in kept]))
-            lists.append(len(kept))
+        lists = self._pair(base, earlier)
         return Snapshot._leaders("lh_kept_movers", (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3]),
                                  Snapshot._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
                                  N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out, (_stream_handle(stream),))
