@@ -691,7 +691,33 @@ int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const 
  *                     any handle is looked at -- LH_EINVAL: NULL or misaligned list, a NULL entry, nkept == 0 or
  *                     > LH_MAX_KEPT, flags != 0, NULL out, nmetrics == 0; LH_ERANGE: nmetrics > 0xffffffff -- then LH_EINVAL:
  *                     handles on different devices; LH_ERANGE: [first, first + nmetrics) not inside EVERY handle's block
- *                     (lh_kept_across' rule).  LH_ENOMEM: the allocation failed.  *out is untouched on any failure. */
+ *                     (lh_kept_across' rule).  LH_ENOMEM: the allocation failed.  *out is untouched on any failure.
+ *   lh_kept_slide     A ROLLING WINDOW ADVANCED EXACTLY: new window = old window + newest interval - oldest interval, as one new
+ *                     handle of rows [first, first + nmetrics) -- a process that emits the last minute every second reads one
+ *                     merged handle and two small ones a tick, where lh_kept_merge would read all sixty.  With A[b] = the sum over
+ *                     the `add` list of the name's cell b and S[b] = the same sum over `sub`, both in 64 bits, wrapping
+ *                     (lh_kept_merge's C[b], once per side), *out holds exactly what lh_keep would return for a snapshot whose
+ *                     cells are A[b] - S[b]: per row the bins ascending, a bin whose difference is 0 not listed, row_count[m] =
+ *                     (the wrapping sum of the add handles' row_count[m]) - (the same over sub), wrapping, samples the wrapping
+ *                     sum of those; the same single allocation, layout and bytes as every other handle.  Cells are unsigned
+ *                     integer counts (atomic.AddUint64, metrics.go:278), so the result is bit for bit lh_kept_merge's of the
+ *                     window's handles and nothing drifts however long the window runs; every reader, lh_kept_save* and
+ *                     lh_kept_merge take it like any other handle.  1 <= nadd, 0 <= nsub, nadd + nsub <= LH_MAX_KEPT; with
+ *                     nsub == 0 `sub` may be NULL and the result is byte-identical to lh_kept_merge(add, nadd, ...).  A handle
+ *                     may appear several times, and on both sides, where it cancels.
+ *                     UNDERFLOW: if S[b] > A[b] for any cell of the rows asked for -- decided on the wrapped sums -- the call
+ *                     returns LH_ERANGE: *out is untouched and nothing is leaked (no block is allocated), and *why -- optional;
+ *                     why->struct_size = sizeof(lh_kept_under) on entry -- names the violating cell of the LOWEST ROW, in it the
+ *                     LOWEST BIN (bin = (uint16)key ^ 0x8000), whatever the timing and the kernel shape.  The corner where the
+ *                     adds wrapped past 2^64 and a legitimate subtrahend then looks too large is refused like any other
+ *                     underflow.  *why is written by an underflow refusal only.
+ *                     Checked on the host, in this order, before any handle is looked at -- LH_EINVAL: NULL or misaligned add,
+ *                     nadd == 0, sub NULL or misaligned with nsub > 0, a NULL entry in either list, nadd + nsub > LH_MAX_KEPT,
+ *                     flags != 0, NULL out, why non-NULL with why->struct_size != sizeof(lh_kept_under), nmetrics == 0;
+ *                     LH_ERANGE: nmetrics > 0xffffffff -- then LH_EINVAL: handles on different devices; LH_ERANGE (*why left
+ *                     as it was): [first, first + nmetrics) not inside EVERY handle's block.  LH_ENOMEM, LH_EDEVICE, the stream,
+ *                     the two kernel shapes, the unit's mutex and "complete on return" as for lh_kept_merge: the listed handles
+ *                     are only read, and the new handle depends on none of them. */
 typedef struct lh_kept lh_kept;      /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
 #define LH_MAX_KEPT 64
 typedef struct lh_kept_info {
@@ -720,6 +746,15 @@ int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
 int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream,
                   lh_kept **out);
+typedef struct lh_kept_under {
+    uint32_t struct_size;            /* sizeof(lh_kept_under) == 16 */
+    uint32_t row;                    /* ABSOLUTE row number (metric id) of the first cell that would go below zero */
+    int16_t key;                     /* its bucket key */
+    uint16_t reserved0;              /* written as 0 */
+    uint32_t reserved1;              /* written as 0 */
+} lh_kept_under;
+int lh_kept_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics,
+                  uint32_t flags, void *stream, lh_kept_under *why, lh_kept **out);
 /* KEPT INTERVALS SAVED AND LOADED: lh_kept_save*, lh_kept_load*, lh_kept_values.  A handle is otherwise born from a live snapshot
  * (lh_keep) or from handles of the same device (lh_kept_merge): the history dies with the process and cannot change devices.  A
  * BLOB carries one handle to a file, to another process, rank or device; a process that only QUERIES history -- a dashboard

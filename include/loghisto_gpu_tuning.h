@@ -171,6 +171,13 @@ int lh_tool_kept_top_passes_ms(lh_kept *const *kept, size_t nkept, uint32_t firs
 int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
                                   size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
                                   float *score_ms, float *select_ms);
+/* Device time of lh_kept_slide's two passes alone (HIP events on `stream` around each): one lh_kept_slide with these lists makes
+ * the handle, then k_slide_count runs once more into the unit's scratch block and k_slide_fill once more into that handle's own
+ * arrays (the bytes they hold already), and the handle is freed.  lh_kept_slide's checks and codes (flags 0, no `why`: an
+ * underflow is plain LH_ERANGE); LH_EINVAL too for a NULL output or a result without a cell (no fill pass).  Returns when both
+ * times are known.  lh_tool_kept_switch switches the passes' two shapes. */
+int lh_tool_kept_slide_passes_ms(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first,
+                                 size_t nmetrics, void *stream, float *count_ms, float *fill_ms);
 /* Device time of lh_kept_load*'s check alone (HIP events on `stream` around each kernel): k_kept_check and k_kept_check_samples
  * over the handle's OWN block, which holds what they ask for; nothing is copied or allocated, the handle is only read.  Returns
  * when both times are known.  LH_EINVAL: NULL k or output. */

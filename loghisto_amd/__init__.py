@@ -8,6 +8,8 @@ liblhgpu.so is not built.
 """
 from ._native import (LIB_PATH, MAX_PERCENTILES, NKEYS, NTHRESH, LhError, NativeLibraryError)
 from .engine import Engine, Kept, Names, Snapshot
+from .keptfile import KeptUnderflow
+from .window import KeptWindow
 
-__all__ = ["Engine", "Kept", "Names", "Snapshot", "LhError", "NativeLibraryError", "LIB_PATH", "NKEYS", "NTHRESH",
+__all__ = ["Engine", "Kept", "KeptUnderflow", "KeptWindow", "Names", "Snapshot", "LhError", "NativeLibraryError", "LIB_PATH", "NKEYS", "NTHRESH",
            "MAX_PERCENTILES"]

@@ -143,6 +143,12 @@ class LhKeptCheck(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("cause", C.c_uint32), ("row", C.c_uint32), ("index", C.c_uint32)]
 
 
+class LhKeptUnder(C.Structure):
+    """lh_kept_under (16 bytes): the cell that made lh_kept_slide refuse a window, one that would go below zero."""
+    _fields_ = [("struct_size", C.c_uint32), ("row", C.c_uint32), ("key", C.c_int16), ("reserved0", C.c_uint16),
+                ("reserved1", C.c_uint32)]
+
+
 FMT_UNDERSCORE_TO_DOT = 1
 SER_AGGREGATES = 1
 FMT_SLOT = 336
@@ -189,6 +195,7 @@ TUNING_SIGNATURES = {
     "lh_tool_kept_compare_tile": (C.c_int, [_u32p]),
     "lh_tool_kept_check_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_keep_count_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.POINTER(C.c_float)]),
+    "lh_tool_kept_slide_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
     "lh_tool_movers_passes_ms": (C.c_int, [_vp, _vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
@@ -278,6 +285,7 @@ SIGNATURES = {
     "lh_kept_across_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_merge": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_slide": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(LhKeptUnder), C.POINTER(_vp)]),
     "lh_kept_save_size": (C.c_int, [_vp, C.POINTER(_sz)]),
     "lh_kept_save": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "lh_kept_save_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),

@@ -49,6 +49,15 @@
 // the caller's stream, under the unit's mutex from the first look at a handle to the end (no lh_kept_release frees an input
 // under it); it only reads its inputs, so it records no event on them, and the new handle depends on none of them.
 //
+// THE SLIDE, lh_kept_slide: new window = old window + newest interval - oldest interval as a NEW handle, so that a rolling minute
+// emitted every second reads one merged handle and two small ones a tick where lh_kept_merge reads all sixty.  A[b] / S[b] = the
+// wrapping sums over the `add` / `sub` lists (the merge's C[b], once per side), the handle holds A[b] - S[b]: cells are unsigned
+// integer counts, so the result is bit for bit lh_kept_merge's of the window's handles and nothing drifts however long it runs.  The
+// merge's three steps with the compare's TWO tiles a row (turns_of<NW, 2, KEPT_COMPARE_TILE>, the lists as one, add first):
+// k_slide_count / k_slide_fill take the difference in the step, never in LDS.  A cell with S[b] > A[b] refuses the call: the count
+// pass folds row << 16 | bin into one word behind the two totals with a 64-bit atomic min (k_kept_check's pattern), make() brings
+// it back with them and returns before anything is allocated; the fill pass is not launched.
+//
 // THE COMPARE, lh_kept_compare*: lh_compare's outputs (lh_compare.hip's header has X, ks, w1 and shift) for a[j] = the sum over
 // the `base` list of the name's cell j and b[j] = the same over the `cur` list -- a kept baseline against a kept interval
 // with no dense buffer alive.  Up to 64 handles in the two lists together, which travel as ONE list (base first) with the
@@ -529,6 +538,79 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const K
     if (lane < s.n) row.open(s.h[lane], first + m);
     row.settle();
     turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        const uint32_t b0 = base + 4 * lane, n = occupied4(C), inc = wave_scan_incl_u32(n);
+        u64 pos = to + (inc - n);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (C[k] && pos < lim) {
+                keys[pos] = (int16_t)bin_to_key(b0 + k);
+                counts[pos] = C[k];
+                pos++;
+            }
+        to += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+    });
+}
+
+// ---- lh_kept_slide ------------------------------------------------------------------------------------------------------------
+// The merge's two passes with the compare's two tiles: handles 0 .. nadd - 1 of the list are `add`, the others `sub`; each side
+// is an UNSIGNED sum in its own tile (no subtraction happens in LDS) and the step takes A[k] - B[k].  count: nnz[m + 1] = the
+// non-zero differences, row_count[m] = the wrapping sum of the add handles' row_count entries minus the same over sub; a cell
+// with B[k] > A[k] -- decided on the wrapped sums -- is folded into *verdict as row << 16 | bin (the ABSOLUTE row) with a 64-bit
+// atomic min, k_kept_check's pattern: the lowest row, in it the lowest bin, whatever the timing and the shape (SLIDE_CLEAN: none).
+// Wave 0 alone walks in both shapes.  With no sub handle every B is 0 and the bytes are k_merge_count's / k_merge_fill's.
+constexpr u64 SLIDE_CLEAN = ~0ull;
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_slide_count(const KeptList s, uint32_t nadd, uint32_t nrows,
+                                                                          uint32_t first, u64 *__restrict__ nnz,
+                                                                          u64 *__restrict__ row_count, u64 *__restrict__ verdict)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nrows) return; // uniform for all that share the tiles
+    at.clear();
+    Row row; // lane i opens handle i
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    const u64 ra = readlane_u64(wave_scan_incl_u64(lane < nadd ? row.rc : 0), 63);
+    const u64 rb = readlane_u64(wave_scan_incl_u64(lane < nadd ? 0 : row.rc), 63);
+    uint32_t occ = 0, under = NO_BIN; // the lane's lowest bin that would go below zero
+    turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nadd, at.tile, lane, at.w, [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            occ += A[k] != B[k] ? 1u : 0u;
+            if (B[k] > A[k]) under = min(under, base + 4 * lane + k); // (ascending steps: the first one stays)
+        }
+    });
+    if (at.w != 0) return;
+    occ = wave_scan_incl_u32(occ);
+    under = ~wave_max_u32(~under);
+    if (lane == 63) {
+        nnz[(size_t)m + 1] = occ;
+        row_count[m] = ra - rb;
+    }
+    if (under != NO_BIN && lane == 0) atomicMin(verdict, (u64)(first + m) << 16 | under);
+}
+
+// fill (launched for a clean verdict only: A[k] >= B[k] everywhere): k_merge_fill's placing, of the non-zero differences
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_slide_fill(const KeptList s, uint32_t nadd, uint32_t nrows,
+                                                                         uint32_t first, const u64 *__restrict__ off,
+                                                                         int16_t *__restrict__ keys, u64 *__restrict__ counts)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    const uint32_t lane = at.lane, m = at.m;
+    if (m >= nrows) return; // uniform for all that share the tiles
+    u64 to = off[m];
+    const u64 lim = off[(size_t)m + 1];
+    if (to >= lim) return; // (the same)
+    at.clear();
+    Row row;
+    if (lane < s.n) row.open(s.h[lane], first + m);
+    row.settle();
+    turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nadd, at.tile, lane, at.w, [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+        const u64 C[4] = {A[0] - B[0], A[1] - B[1], A[2] - B[2], A[3] - B[3]};
         const uint32_t b0 = base + 4 * lane, n = occupied4(C), inc = wave_scan_incl_u32(n);
         u64 pos = to + (inc - n);
 #pragma unroll
@@ -1062,23 +1144,29 @@ template <class F> int launch_rows(uint32_t M, bool by_id, F f)
 }
 
 // (cx->mu held, the device current)  The making of a handle of rows [first, first + nrows) on `st`, for lh_keep and
-// lh_kept_merge: count(off, row_count) enqueues the pass that leaves nnz in off[1 ..] and the rows' sums; then the scan, the
+// lh_kept_merge: count(off, row_count, slot) enqueues the pass that leaves nnz in off[1 ..] and the rows' sums; then the scan, the
 // totals brought back, the allocation; fill(off, keys, counts) enqueues the pass that places the cells -- unless there are
 // none; both return a code.  Returns when the handle is complete.  After a failure the caller waits for `st` and frees k->block.
+// verdict (lh_kept_slide; null for the others, whose copies and launches are what they were): a slot right behind the two totals
+// starts as SLIDE_CLEAN, count(off, row_count, slot) may fold a refusal into it, and it comes back WITH the totals into *verdict;
+// unless it is still clean the call ends there with LH_ERANGE: nothing is allocated and fill is not enqueued.
 template <class Count, class Fill>
-int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k, Count count, Fill fill)
+int make(KeptCtx *cx, hipStream_t st, uint32_t first, uint32_t nrows, lh_kept *k, Count count, Fill fill, u64 *verdict = nullptr)
 {
     const size_t head = 2 * (size_t)nrows + 1; // offsets and row_count, in uint64
-    int rc = grow_device(cx->d_tmp, cx->tmp_cap, head + 2, 4096);
-    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 2, 2);
+    const size_t back = verdict ? 3 : 2;       // what comes back: the two totals, the verdict
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, head + back, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, back, back);
     if (rc) return rc;
     u64 *off = cx->d_tmp, *row_count = off + nrows + 1, *totals = off + head;
-    rc = count(off, row_count);
+    if (verdict) LH_BESIDE_CHK(hipMemsetAsync(totals + 2, 0xff, sizeof(u64), st)); // SLIDE_CLEAN
+    rc = count(off, row_count, verdict ? totals + 2 : nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, row_count, nrows, totals);
     LH_BESIDE_CHK(hipGetLastError());
-    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, back * sizeof(u64), hipMemcpyDeviceToHost, st));
     LH_BESIDE_CHK(hipStreamSynchronize(st));
+    if (verdict && (*verdict = cx->h_totals[2]) != SLIDE_CLEAN) return LH_ERANGE;
     const u64 cells = cx->h_totals[0];
     if (cells > (u64)nrows * LH_NKEYS) return LH_EDEVICE; // (never)
     k->first = first;
@@ -1105,7 +1193,7 @@ int keep(const KeptSource &q, uint32_t first, uint32_t nrows, lh_kept *k)
     const dim3 grid((nrows + ROW_WAVES - 1) / ROW_WAVES), block(ROW_BLOCK);
     return make(
         q.cx, st, first, nrows, k,
-        [&](u64 *off, u64 *row_count) {
+        [&](u64 *off, u64 *row_count, u64 *) {
             with_cells(q, first, [&](auto c) {
                 hipLaunchKernelGGL((k_keep_count<cell_of<decltype(c)>>), grid, block, 0, st, c, ranges, q.stride, nrows, off, row_count);
             });
@@ -1140,7 +1228,7 @@ int merge(KeptCtx *cx, lh_kept *const *kept, size_t nkept, uint32_t first, uint3
     const KeptList s = list_of(kept, nkept);
     return make(
         cx, st, first, nrows, k,
-        [&](u64 *off, u64 *row_count) {
+        [&](u64 *off, u64 *row_count, u64 *) {
             return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
                 hipLaunchKernelGGL((k_merge_count<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, nrows, first, off, row_count);
             });
@@ -1150,6 +1238,58 @@ int merge(KeptCtx *cx, lh_kept *const *kept, size_t nkept, uint32_t first, uint3
                 hipLaunchKernelGGL((k_merge_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
             });
         });
+}
+
+// (cx->mu held, the device current)  lh_kept_slide: the same with all[0 .. nadd) added and all[nadd .. n) taken away.  *verdict:
+// SLIDE_CLEAN, or row << 16 | bin of the first cell that would go below zero (LH_ERANGE then, k->block still null).
+int slide(KeptCtx *cx, lh_kept *const *all, size_t n, size_t nadd, uint32_t first, uint32_t nrows, hipStream_t st, lh_kept *k,
+          u64 *verdict)
+{
+    const KeptList s = list_of(all, n);
+    const uint32_t NA = (uint32_t)nadd;
+    return make(
+        cx, st, first, nrows, k,
+        [&](u64 *off, u64 *row_count, u64 *slot) {
+            return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_slide_count<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NA, nrows, first, off, row_count, slot);
+            });
+        },
+        [&](const u64 *off, int16_t *keys, u64 *counts) {
+            return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_slide_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NA, nrows, first, off, keys, counts);
+            });
+        },
+        verdict);
+}
+
+// What lh_kept_merge and lh_kept_slide do around their making of a handle, work(cx, st, k), once the handles of the list have
+// been looked at: the unit's context on their device, a new handle, the mutex for the WHOLE call -- no lh_kept_release frees an
+// input under it (they are only read: no hold) --, and after a failure the stream waited for, the block freed, *out untouched.
+template <class Work> int born_of(int device, void *stream, lh_kept **out, Work work)
+{
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE;
+    lh_kept *k = new (std::nothrow) lh_kept;
+    if (!k) return LH_ENOMEM;
+    k->device = device;
+    k->cx = cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    {
+        std::lock_guard<std::mutex> g(cx->mu);
+        rc = hipSetDevice(device) == hipSuccess ? work(cx, st, k) : LH_EDEVICE;
+        if (rc) {
+            (void)hipGetLastError();
+            if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+    }
+    if (rc) {
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return LH_OK;
 }
 
 // (cx->mu held) one user less of `e`
@@ -1231,6 +1371,20 @@ int one_device(lh_kept *const *kept, size_t nkept, int *device)
         if (kept[i]->device != *device) return LH_EINVAL;
     return LH_OK;
 }
+// lh_kept_slide's checks, in the documented order, into `all` (add first): those that need no handle, then the two that look
+// at them (one_device, rows_in_all)
+int check_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics, uint32_t flags,
+                const lh_kept_under *why, const void *out, lh_kept *(&all)[LH_MAX_KEPT], int *device)
+{
+    if (bad_list(add, nadd, LH_MAX_KEPT) || (nsub != 0 && bad_list(sub, nsub, LH_MAX_KEPT)) || nadd + nsub > LH_MAX_KEPT) return LH_EINVAL;
+    if (flags != 0 || !out || (why && why->struct_size != sizeof(lh_kept_under)) || nmetrics == 0) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE;
+    std::copy(add, add + nadd, all);
+    if (nsub) std::copy(sub, sub + nsub, all + nadd);
+    const int rc = one_device(all, nadd + nsub, device);
+    return rc ? rc : rows_in_all(all, nadd + nsub, rows_from(first), nmetrics);
+}
+
 // The way of a call from there on: the unit's context on the handles' device, its mutex for the length of the call, the
 // device made current.  A device form's work -- direct(cx, st) enqueues it on the caller's stream -- goes under ONE hold of
 // all listed handles; a host form's -- through(cx, st) brings the results back to the caller's arrays and waits -- leaves
@@ -1591,7 +1745,7 @@ struct BlobHeader { // little-endian, as the hosts this builds for are
     unsigned char reserved1[8];
 };
 static_assert(sizeof(BlobHeader) == LH_KEPT_BLOB_HEADER && sizeof(LH_KEPT_BLOB_MAGIC) == 9, "64 bytes, 8 of them the magic");
-static_assert(sizeof(lh_kept_check) == 16, "part of the ABI");
+static_assert(sizeof(lh_kept_check) == 16 && sizeof(lh_kept_under) == 16, "part of the ABI");
 
 BlobHeader header_of(const lh_kept *k)
 {
@@ -1936,29 +2090,69 @@ int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nme
         if (kept[i]->device != device) return LH_EINVAL;
     for (size_t i = 0; i < nkept; i++) // the block lies inside every handle's: lh_kept_across' rule
         if (first < kept[i]->first || (u64)first + nmetrics > (u64)kept[i]->first + kept[i]->nrows) return LH_ERANGE;
-    KeptCtx *cx = device_ctx<KeptCtx>(device);
-    if (!cx) return LH_EDEVICE;
-    lh_kept *k = new (std::nothrow) lh_kept;
-    if (!k) return LH_ENOMEM;
-    k->device = device;
-    k->cx = cx;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    { // the mutex for the whole call: no lh_kept_release frees an input under it (it only reads them: no hold)
-        std::lock_guard<std::mutex> g(cx->mu);
-        rc = hipSetDevice(device) == hipSuccess ? merge(cx, kept, nkept, first, (uint32_t)nmetrics, st, k) : LH_EDEVICE;
-        if (rc) {
-            (void)hipGetLastError();
-            if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
-        }
+    return born_of(device, stream, out, [&](KeptCtx *cx, hipStream_t st, lh_kept *k) {
+        return merge(cx, kept, nkept, first, (uint32_t)nmetrics, st, k);
+    });
+}
+
+int lh_kept_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics, uint32_t flags,
+                  void *stream, lh_kept_under *why, lh_kept **out)
+{
+    lh_kept *all[LH_MAX_KEPT];
+    int device = -1;
+    int rc = check_slide(add, nadd, sub, nsub, first, nmetrics, flags, why, out, all, &device);
+    if (rc) return rc;
+    u64 verdict = SLIDE_CLEAN;
+    rc = born_of(device, stream, out, [&](KeptCtx *cx, hipStream_t st, lh_kept *k) {
+        return slide(cx, all, nadd + nsub, nadd, first, (uint32_t)nmetrics, st, k, &verdict);
+    });
+    if (verdict != SLIDE_CLEAN && why) { // (rc is LH_ERANGE: make ended there)
+        why->row = (uint32_t)(verdict >> 16);
+        why->key = (int16_t)bin_to_key((uint32_t)(verdict & 0xffff));
+        why->reserved0 = 0;
+        why->reserved1 = 0;
     }
-    if (rc) {
-        delete k;
-        return rc;
-    }
-    *out = k;
-    return LH_OK;
+    return rc;
+}
+
+int lh_tool_kept_slide_passes_ms(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics,
+                                 void *stream, float *count_ms, float *fill_ms)
+{
+    alignas(8) unsigned char own[8] = {0}; // (stands in for `out`: the handle made here is freed again)
+    lh_kept *all[LH_MAX_KEPT];
+    int device = -1;
+    int rc = check_slide(add, nadd, sub, nsub, first, nmetrics, 0, nullptr, own, all, &device);
+    if (rc) return rc;
+    if (!count_ms || !fill_ms) return LH_EINVAL;
+    lh_kept *made = nullptr;
+    const uint32_t nrows = (uint32_t)nmetrics, NA = (uint32_t)nadd;
+    rc = born_of(device, stream, &made, [&](KeptCtx *cx, hipStream_t st, lh_kept *k) -> int {
+        u64 verdict = SLIDE_CLEAN;
+        int r = slide(cx, all, nadd + nsub, nadd, first, nrows, st, k, &verdict); // the allocation, and d_tmp's offsets
+        if (r) return r;
+        if (k->cells == 0) return LH_EINVAL; // no fill pass to time
+        const KeptList s = list_of(all, nadd + nsub);
+        u64 *off = cx->d_tmp, *row_count = off + nrows + 1, *totals = off + 2 * (size_t)nrows + 1, *counts = k->block + 2 * (size_t)nrows + 1;
+        int16_t *keys = reinterpret_cast<int16_t *>(counts + k->cells);
+        float *const c_ms[1] = {count_ms}, *const f_ms[1] = {fill_ms};
+        int launched = LH_OK;
+        r = steps_ms(st, 1, c_ms, [&](int) {
+            launched = launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_slide_count<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NA, nrows, first, off, row_count, totals + 2);
+            });
+        });
+        if (r || launched) return r ? r : launched;
+        hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, row_count, nrows, totals); // off[]: nnz -> offsets again
+        LH_BESIDE_CHK(hipGetLastError());
+        r = steps_ms(st, 1, f_ms, [&](int) { // into the handle's own arrays: the bytes they hold already
+            launched = launch_rows(nrows, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_slide_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NA, nrows, first, off, keys, counts);
+            });
+        });
+        return r ? r : launched;
+    });
+    if (rc) return rc;
+    return lh_kept_release(made);
 }
 
 int lh_kept_release(lh_kept *k)

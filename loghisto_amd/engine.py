@@ -731,7 +731,7 @@ class Snapshot:
 
 class Kept:
     """One interval's occupied cells of metrics [first, first + nrows), kept in compact form on the device (lh_kept):
-    Snapshot.keep(), Kept.merge(), or -- with no engine at all -- Kept.from_bytes / load / from_device_blob of a saved one.  It
+    Snapshot.keep(), Kept.merge(), Kept.slide(), or -- with no engine at all -- Kept.from_bytes / load / from_device_blob of a saved one.  It
     depends on neither its snapshot nor its engine, and never changes."""
 
     _OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("nbuckets", 4, 0, np.uint32),
@@ -833,6 +833,27 @@ class Kept:
         h = C.c_void_p(0)
         N.check(N.lib().lh_kept_merge(C.addressof(handles), nkept, first, nmetrics, 0, _stream_handle(stream), C.byref(h)),
                 "lh_kept_merge")
+        return Kept(h, self._table)
+
+    def slide(self, add=(), sub=(), nmetrics: Optional[int] = None, first: Optional[int] = None, stream=None) -> "Kept":
+        """A rolling window advanced exactly (lh_kept_slide): ONE new Kept of metrics [first, first+nmetrics) that holds, per
+        metric and bin, the 64-bit sum over [self] + list(add) minus the sum over list(sub) -- with self the window so far,
+        add the newest interval and sub the oldest, bit for bit what merge() of the new window's intervals gives.  sub=(): plain
+        merge.  A handle may appear several times and on both sides; at most N.MAX_KEPT in the two lists together; every one
+        must hold the block.  A cell that would go below zero raises loghisto_amd.KeptUnderflow with the row (a metric id) and
+        key of the lowest such row's lowest bin, and nothing is made.  first / nmetrics / stream as for merge; complete on
+        return, and the new handle depends on none of the listed ones."""
+        from .keptfile import KeptUnderflow
+        nmetrics, first = self._block(nmetrics, first)
+        plus, nadd = self._handles([self] + list(add))
+        minus, nsub = self._handles(list(sub))
+        why = N.LhKeptUnder(struct_size=C.sizeof(N.LhKeptUnder), reserved1=1)
+        h = C.c_void_p(0)
+        rc = N.lib().lh_kept_slide(C.addressof(plus), nadd, C.addressof(minus) if nsub else None, nsub, first, nmetrics, 0,
+                                   _stream_handle(stream), C.byref(why), C.byref(h))
+        if rc == N.ERANGE and why.reserved1 == 0:      # written, as 0, by an underflow refusal only
+            raise KeptUnderflow(int(why.row), int(why.key))
+        N.check(rc, "lh_kept_slide")
         return Kept(h, self._table)
 
     def compare(self, base, nmetrics: Optional[int] = None, first: int = 0, earlier=(), ids=None, stream=None, out=None):

@@ -6,6 +6,8 @@ A 64-byte little-endian header, then the handle's single allocation verbatim:
 pack() makes a blob from CSR arrays, unpack() takes one apart, and check() restates every rule lh_kept_load* holds a blob
 to -- the header's on the host, the block's on the device -- with the same verdict: of all violations the one of the lowest
 row, in it the lowest index, there the lowest cause code.  The device's check is held to check() by the tests.
+combine() states lh_kept_slide on blobs -- per row and bin the add side's sum minus the sub side's, KeptUnderflow for a cell that
+would go below zero -- and is the reference the device's slide is held to.
 """
 from __future__ import annotations
 
@@ -156,3 +158,65 @@ def check(blob):
     if sum(int(c) for c in row_count) & _M64 != h["samples"]:
         return (BAD_SAMPLES, nrows, 0)
     return None
+
+
+class KeptUnderflow(ArithmeticError):
+    """lh_kept_slide / combine() refused a window: the cell (row, key) -- row an ABSOLUTE metric id, key its bucket key; of all
+    such cells the one of the lowest row, in it the lowest bin -- would go below zero."""
+
+    def __init__(self, row: int, key: int):
+        super().__init__(f"kept slide: the cell of metric {row}, key {key}, would go below zero")
+        self.row, self.key = row, key
+
+
+def _side(blobs, first, nrows):
+    """Per row of [first, first + nrows): {bin: the sum mod 2^64 of the blobs' cells}, and the sum mod 2^64 of their row_count."""
+    cells, rcs = [{} for _ in range(nrows)], [0] * nrows
+    for u in blobs:
+        at = first - u["first"]
+        bins = u["keys"].view("<u2") ^ np.uint16(0x8000)
+        for m in range(nrows):
+            a, b = int(u["offsets"][at + m]), int(u["offsets"][at + m + 1])
+            row = cells[m]
+            for j, c in zip(bins[a:b].tolist(), u["counts"][a:b].tolist()):
+                row[j] = (row.get(j, 0) + c) & _M64
+            rcs[m] = (rcs[m] + int(u["row_count"][at + m])) & _M64
+    return cells, rcs
+
+
+def combine(add_blobs, sub_blobs=(), first=None, nrows=None) -> bytes:
+    """The blob lh_kept_save writes for lh_kept_slide(add, sub) of rows [first, first + nrows): per row and bin A - S, with A / S
+    the sums mod 2^64 of the add / sub blobs' cells; a difference of 0 is not listed; row_count is the add side's sum of
+    row_count minus the sub side's, mod 2^64, samples the sum of those.  first=None: the first add blob's; nrows=None: up to
+    the end of its block.  KeptUnderflow for a cell with S > A (decided on the wrapped sums): the lowest row, then the lowest
+    bin.  ValueError for a blob that is not sound (check()), no add blob, or rows outside some blob's block."""
+    add, sub = [bytes(b) for b in add_blobs], [bytes(b) for b in sub_blobs]
+    if not add:
+        raise ValueError("at least one add blob")
+    for b in add + sub:
+        bad = check(b)
+        if bad:
+            raise ValueError(f"not a kept blob: {CAUSES[bad[0]]} (row {bad[1]}, index {bad[2]})")
+    A, S = [unpack(b) for b in add], [unpack(b) for b in sub]
+    if first is None:
+        first = A[0]["first"]
+    if nrows is None:
+        nrows = A[0]["first"] + A[0]["nrows"] - first
+    if nrows < 1 or any(first < u["first"] or first + nrows > u["first"] + u["nrows"] for u in A + S):
+        raise ValueError("rows [first, first + nrows) lie inside every blob's block, and there is at least one")
+    (ca, ra), (cs, rs) = _side(A, first, nrows), _side(S, first, nrows)
+    offsets, keys, counts, row_count = [0], [], [], []
+    for m in range(nrows):
+        under = [j for j, c in cs[m].items() if c > ca[m].get(j, 0)]        # (a bin the add side lacks counts as 0)
+        if under:
+            raise KeptUnderflow(first + m, ((min(under) ^ 0x8000) + 0x8000) % NKEYS - 0x8000)
+        for j in sorted(ca[m]):
+            d = ca[m][j] - cs[m].get(j, 0)
+            if d:
+                keys.append(j ^ 0x8000)
+                counts.append(d)
+        offsets.append(len(keys))
+        row_count.append((ra[m] - rs[m]) & _M64)
+    off, rc, c = np.array(offsets, dtype="<u8"), np.array(row_count, dtype="<u8"), np.array(counts, dtype="<u8")
+    k = np.array(keys, dtype="<u2").view("<i2")
+    return header(first, nrows, len(keys), sum(row_count) & _M64) + off.tobytes() + rc.tobytes() + c.tobytes() + k.tobytes()

@@ -1,0 +1,52 @@
+"""A rolling window of kept intervals whose total is advanced, not rebuilt (Kept.slide, lh_kept_slide): p99 over the last
+minute, emitted every second, reads one handle of the window and the two that changed instead of all sixty.
+
+    w = KeptWindow(60)
+    every second:  old = w.push(snapshot.keep());  if old: old.close();  w.total.across((), [0.99])
+
+The totals are exact: cells are unsigned 64-bit counts, so after any number of pushes w.total is byte for byte what
+Kept.merge of w.handles gives.  No threads; the caller's handles stay the caller's.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Optional
+
+from .engine import Kept
+
+
+class KeptWindow:
+    """The last `size` kept intervals and their running total."""
+
+    def __init__(self, size: int):
+        if size < 1:
+            raise ValueError("a window holds at least one interval")
+        self.size = size
+        self.handles: deque = deque()          # the live intervals, the oldest first: the caller's
+        self.total: Optional[Kept] = None      # their sum: the window's own, replaced by every push
+
+    def push(self, kept: Kept) -> Optional[Kept]:
+        """`kept` becomes the newest interval.  Returns the interval that left the window (the caller closes it), or None
+        while the window fills.  After a KeptUnderflow or any other failure the window is as it was."""
+        oldest = self.handles[0] if len(self.handles) == self.size else None
+        if self.total is None:
+            total = kept.slide()                                   # a copy: the window owns its total
+        else:
+            total = self.total.slide(add=[kept], sub=[oldest] if oldest else ())
+            self.total.close()
+        self.total = total
+        self.handles.append(kept)
+        return self.handles.popleft() if oldest else None
+
+    def close(self):
+        """Releases what the window made, its total; the intervals pushed stay usable and are the caller's to close."""
+        if self.total is not None:
+            self.total.close()
+            self.total = None
+        self.handles.clear()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
