@@ -42,6 +42,7 @@ _UNITS = [
 # standalone C++ programs linked against liblhgpu.so: (source relative to the repo root, output name)
 _PROGRAMS = [
     ("tests/cpp/metrics_test.cc", "metrics_test"),   # metrics_test.go restated
+    ("tests/cpp/host_parity.cc", "host_parity"),     # scenario replayer behind tests/test_gpu_host_parity.py
     ("tools/c5_driver.cc", "c5_driver"),             # BASELINE config 5 driver
     ("tools/wire_bench.cc", "wire_bench"),           # per-key vs bulk (K6) ProcessedMetricSet serialization
     ("tools/latency.cc", "latency"),                 # flip -> extract latency at the C ABI
