@@ -962,6 +962,64 @@ int lh_kept_spread_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, 
 int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
                               uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
                               uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le);
+/* PER-WINDOW READS OF KEPT INTERVALS: lh_kept_across* and lh_kept_count_le* for MANY sub-lists of one list of handles in ONE call
+ * and one launch -- the p99 of each of the last 60 seconds for the 20 endpoints a dashboard shows (a sparkline), the last minute
+ * at 5 s or 10 s resolution, a rolling 10 s p99 stepped by 1 s, a latency heat map (counts per `le` band per second) -- where one
+ * lh_kept_* call per window pays the unit's mutex, a launch, an id copy and a hold each time.  Nothing is summed across names and no
+ * new statistic is defined: every output is one that an existing reader returns for a sub-list.
+ *   WINDOWS.  win is a HOST array of 2 * nwin values, 1 <= nwin <= LH_MAX_WINDOWS.  Window w is the slice
+ *   kept[win[2w] .. win[2w+1]) of the list: half open, with 0 <= lo < hi <= nkept.  Windows may overlap, repeat and come in any
+ *   order.  The windows travel by value, as the list, p and bounds do.
+ *   LAYOUT, window-major: entry (w, m) lies at index e = w * n + m (n: nmetrics, or the ids' n); pkeys / pvalid lie at
+ *   e * np + i; cum lies at e * nb + j.  Window w's block of every output is therefore a per-name column that lh_lines* takes as
+ *   it is.
+ *   CONTRACT -- this is the whole definition:
+ *   - Window w's block of every output of lh_kept_series* is byte for byte what lh_kept_across* (the same form, the same rows or
+ *     ids, p, np) writes for the list (kept + lo_w, hi_w - lo_w).
+ *   - The one exception is present_bits: bit i means kept[i] of the WHOLE list, which is the slice call's value shifted left by
+ *     lo_w.
+ *   - Window w's block of lh_kept_heat* is byte for byte lh_kept_count_le*'s cum / total for that slice.
+ *   - This includes sum: it is taken in the same fixed order, the same in both kernel shapes and independent of timing.
+ *   - A handle listed twice counts twice.
+ *   - A name with no sample in a window has the empty entry there.
+ *   - Totals that wrap past 2^64: lh_kept_series* behaves as lh_kept_across* does; lh_kept_heat*'s cum and total stay exact modulo
+ *     2^64, as lh_kept_count_le*'s are.
+ *   - A DEVICE id outside the block of some handle of window w yields the empty entry in that window, and nothing is read for it.
+ *   CHECKS on the host, before any handle is looked at, in this order.  LH_EINVAL: (ids forms) NULL ids with n > 0, or misaligned
+ *   ids; a NULL or misaligned list; nkept == 0 or > LH_MAX_KEPT; a NULL entry; NULL or misaligned win; nwin == 0 or
+ *   > LH_MAX_WINDOWS; a window with lo >= hi or hi > nkept; flags != 0; the family's own argument rules, exactly as
+ *   lh_kept_across* / lh_kept_count_le* have them (np, NULL p, NaN or decreasing bounds, nb limits, all outputs NULL, alignment).
+ *   Then LH_ERANGE: nmetrics > 0xffffffff.  Then nmetrics == 0 / n == 0 -> LH_OK with nothing written.  After the host checks,
+ *   in this order: LH_EINVAL for handles on different devices; LH_ERANGE, with nothing enqueued and nothing written, unless the
+ *   rows or every HOST id lie inside EVERY listed handle's block, whether or not a window names the handle.  No output is written
+ *   on any refusal.
+ *   ORDERING, staging and lifetime as for lh_kept_across*: the work goes on `stream`, under the unit's mutex; host forms bring
+ *   nwin * n entries back through the unit's staging block and are complete on return; device forms return after enqueueing,
+ *   with ALL listed handles under one hold; READ-ONLY.  One window per blockIdx.y of the reader's two kernel shapes, which give
+ *   identical bytes; the switch between them (lh_tool_kept_switch) takes the ENTRIES of a call, nwin * n, not its rows.
+ *   OUT OF SCOPE: sharing cell reads between overlapping windows; a tile-free fast path for one-handle windows (it would have to
+ *   reproduce sum's order bit for bit); spread / compare / top per window; more than LH_MAX_KEPT handles per call. */
+#define LH_MAX_WINDOWS 128
+int lh_kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                   const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
+                   uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid);
+int lh_kept_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
+                          uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
+int lh_kept_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                       const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
+                       uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid);
+int lh_kept_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                              const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
+                              uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
+int lh_kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                 const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_heat_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                        const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_heat_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                     const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_heat_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                            const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
 /* THE K NAMES THAT LEAD, AND THE K THAT MOVED MOST, OVER KEPT INTERVALS: lh_top* and lh_movers* over handles, the two readers that
  * SELECT across names, for the windows that exist only as handles -- "which 20 of my 65 536 endpoints have the worst p99 over the
  * last minute", "whose distribution moved most against the same minute an hour ago" -- so that k entries travel instead of the

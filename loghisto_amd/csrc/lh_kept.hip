@@ -90,6 +90,15 @@
 //                    lanes: the two shapes agree BIT FOR BIT, floating-point outputs included (lh_spread's own two shapes
 //                    associate differently and agree to rounding only).
 //
+// PER WINDOW OF THE LIST, lh_kept_series* and lh_kept_heat*: lh_kept_across*' and lh_kept_count_le*'s outputs for up to LH_MAX_WINDOWS
+// contiguous slices [lo, hi) of the list in ONE launch -- each second's p99 of the last minute, a heat map of `le` bands per second --
+// where a call per window pays the mutex, a launch, an id copy and a hold each time.  The bodies of k_kept_across and k_kept_count_le
+// are device functions that take the slice (across_entry, count_le_entry: lane i opens handle lo + i, the turns run over hi - lo
+// handles); those kernels hand them the whole list, k_kept_series / k_kept_heat one window per blockIdx.y.  Window-major outputs,
+// entry (w, m) at w * n + m: window w's block is byte for byte the reader's output for (kept + lo, hi - lo), sum included, in both
+// shapes -- but for present_bits, the ballot shifted left by lo (bit i: kept[i] of the WHOLE list).  The windows travel by value
+// (KeptWindows, 256 bytes).  The shape switch takes the ENTRIES of a call, windows x rows.
+//
 // THE TWO SELECTING READERS, lh_kept_top* and lh_kept_movers*: lh_top's and lh_movers' selections -- the k names of a range that lead,
 // or that moved most between two lists -- for a snapshot whose cells are C, so that k entries travel and no dense buffer is filled.
 // Two score kernels in front of lh_select.h's k_select, whose records (TopRecords, MoversRecords) and Emit functors that header
@@ -440,28 +449,27 @@ template <int NW, uint32_t WORDS = KEPT_TILE> struct Seat {
     }
 };
 
-// IDS: entry m reads row ids[m] (an absolute row number, as `first` is); otherwise row first + m.  A row outside the block
-// of ANY handle gives the empty entry, and nothing is read for it.
-template <bool IDS, int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const KeptList s, uint32_t nmetrics, uint32_t first,
-                                                                          const double *__restrict__ D, const PctArgs pa,
-                                                                          uint32_t np, const KeptOut o,
-                                                                          const uint32_t *__restrict__ ids)
-{
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
-    const Seat<NW> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
+// A window of the list: its handles [lo, lo + len), which one entry of a call reads.  The whole list is {0, s.n}.
+struct Slice {
+    uint32_t lo, len;
+};
+// the windows of lh_kept_series* / lh_kept_heat*, by value in the kernel arguments beside the list (256 bytes): w[k] = {lo, hi}
+struct KeptWindows { uint8_t w[LH_MAX_WINDOWS][2]; };
+static_assert(LH_MAX_KEPT <= 255, "a window's ends in a byte each");
 
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], r);
+// (every wave that shares the tile, which is zero)  Entry e of the outputs: row r over the handles of `win`.  Lane i opens handle
+// win.lo + i and the turns run over win.len handles; present_bits speaks of the WHOLE list (bit i: s.h[i]).  A row outside the
+// block of ANY handle of the window gives the empty entry, and nothing is read for it.
+template <int NW>
+__device__ __forceinline__ void across_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
+                                             const double *__restrict__ D, const PctArgs &pa, uint32_t np, const KeptOut &o)
+{
+    const uint32_t lane = at.lane;
+    Row row;
+    if (lane < win.len) row.open(s.h[win.lo + lane], r);
     row.settle();
     const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
-    const u64 present = __builtin_amdgcn_ballot_w64(row.end > row.cur);
+    const u64 present = __builtin_amdgcn_ballot_w64(row.end > row.cur) << win.lo;
     const uint32_t hi = row.hi;
 
     double ps = 0.0;
@@ -469,7 +477,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
     Open pct; // lane i < np: percentile i
     if (total) {                       // uniform
         pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
-        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
             double d[4], t[4];
             load4_values(D, base + 4 * lane, hi, d);
             const u64 tc = sum4(C);
@@ -482,15 +490,59 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
     const double sum = readlane_f64(wave_scan_incl_f64(ps), 63);
     const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl_u32(occ), 63);
     if (lane == 0) {
-        if (o.count) o.count[m] = total;
-        if (o.sum) o.sum[m] = total ? sum : 0.0;
-        if (o.nbuckets) o.nbuckets[m] = total ? nb : 0;
-        if (o.present) o.present[m] = total ? present : 0;
+        if (o.count) o.count[e] = total;
+        if (o.sum) o.sum[e] = total ? sum : 0.0;
+        if (o.nbuckets) o.nbuckets[e] = total ? nb : 0;
+        if (o.present) o.present[e] = total ? present : 0;
     }
     if (lane < np) {
-        store_pct(o.pkeys, o.pvalid, (size_t)m * np + lane, pct.found);
+        store_pct(o.pkeys, o.pvalid, e * np + lane, pct.found);
     }
 }
+
+// IDS: entry m reads row ids[m] (an absolute row number, as `first` is); otherwise row first + m.  A row outside the block
+// of ANY handle gives the empty entry, and nothing is read for it.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                          const double *__restrict__ D, const PctArgs pa,
+                                                                          uint32_t np, const KeptOut o,
+                                                                          const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    across_entry<NW>(at, s, Slice{0, s.n}, r, m, D, pa, np, o); // lane i opens handle i
+}
+
+// lh_kept_series*: the same entry per WINDOW of the list, one window per blockIdx.y, window-major: entry (w, m) at w * nmetrics
+// + m, so that window w's block of every output is what k_kept_across writes for the list (kept + lo_w, hi_w - lo_w) -- the same
+// open, turns, step and order, hence the same bytes, sum included -- but for present_bits, shifted left by lo_w.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_series(const KeptList s, const KeptWindows sw, uint32_t nmetrics,
+                                                                          uint32_t first, const double *__restrict__ D,
+                                                                          const PctArgs pa, uint32_t np, const KeptOut o,
+                                                                          const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m, w = blockIdx.y;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
+    across_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, D, pa, np, o);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(KeptOut) + 5 * 8 < 4096,
+              "k_kept_series' arguments inside the 4 KiB argument segment");
 
 // ---- lh_kept_merge ----------------------------------------------------------------------------------------------------------
 // The two passes around k_keep_scan, rows [first, first + nrows) of every handle of the list (the host checked that each
@@ -853,23 +905,14 @@ struct KeptBounds { double b[LH_MAX_BOUNDS]; };
 // tile or in a stretch no tile covers, and takes the running carry; one beyond the last step takes everything.  total is the
 // wrapping sum of the handles' row_count entries: no cell is read for it (and the row is walked whatever it is: cells whose
 // sum wraps to 0 still count towards cum).  Integer sums only: the two shapes agree exactly.
-template <bool IDS, int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(const KeptList s, uint32_t nmetrics, uint32_t first,
-                                                                            const KeptBounds sb, uint32_t nb, u64 *__restrict__ cum,
-                                                                            u64 *__restrict__ total,
-                                                                            const uint32_t *__restrict__ ids)
+// (every wave that shares the tile, which is zero)  Entry e of the outputs: row r over the handles of `win` (across_entry's open)
+template <int NW>
+__device__ __forceinline__ void count_le_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
+                                               const KeptBounds &sb, uint32_t nb, u64 *__restrict__ cum, u64 *__restrict__ total)
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
-    const Seat<NW> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], r);
+    const uint32_t lane = at.lane;
+    Row row;
+    if (lane < win.len) row.open(s.h[win.lo + lane], r);
     row.settle();
     const u64 tot = readlane_u64(wave_scan_incl_u64(row.rc), 63);
 
@@ -877,7 +920,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(cons
     if (lane < nb) E = le_take(sb.b[lane]);
     bool pend = lane < nb && E > 0; // a bound that takes in no bin: 0
     u64 res = 0, carry = 0;
-    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+    turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
         if (pend && E <= base) { // every bin it takes in lies below this step: what the steps so far hold
             res = carry;
             pend = false;
@@ -899,9 +942,50 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(cons
     });
     if (at.w != 0) return;
     if (pend) res = carry; // beyond the last step: everything
-    if (cum && lane < nb) cum[(size_t)m * nb + lane] = res;
-    if (total && lane == 0) total[m] = tot;
+    if (cum && lane < nb) cum[e * nb + lane] = res;
+    if (total && lane == 0) total[e] = tot;
 }
+
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                            const KeptBounds sb, uint32_t nb, u64 *__restrict__ cum,
+                                                                            u64 *__restrict__ total,
+                                                                            const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    count_le_entry<NW>(at, s, Slice{0, s.n}, r, m, sb, nb, cum, total); // lane i opens handle i
+}
+
+// lh_kept_heat*: the same entry per window of the list (k_kept_series' layout): window w's block of cum / total is what
+// k_kept_count_le writes for the list (kept + lo_w, hi_w - lo_w).
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_heat(const KeptList s, const KeptWindows sw, uint32_t nmetrics,
+                                                                        uint32_t first, const KeptBounds sb, uint32_t nb,
+                                                                        u64 *__restrict__ cum, u64 *__restrict__ total,
+                                                                        const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m, w = blockIdx.y;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
+    count_le_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, sb, nb, cum, total);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(KeptBounds) + 6 * 8 < 4096,
+              "k_kept_heat's arguments inside the 4 KiB argument segment");
 
 // ---- lh_kept_spread -----------------------------------------------------------------------------------------------------------
 // Rows as in k_kept_across.  lh_spread's two walks as TWO turns over the same row (the turns advance the cursors: the opened
@@ -1129,18 +1213,27 @@ typedef lh::beside::Source<KeptCtx> KeptSource;
 // The launch of every kernel k<[IDS,] NW> of this unit that walks M rows of a list: f(sh, nw) launches k<decltype(nw)::value>
 // with sh's grid and block -- the shape the unit's switch gives a call of M rows, NW = 1 (a wave per row) or WG_WAVES (a
 // workgroup per row).  With by_id, for the readers that have id forms: f(sh, ids, nw), IDS = decltype(ids)::value.
-template <class F> int launch_rows(uint32_t M, F f)
+template <class F> int launch_shape(const RowShape &sh, F f)
 {
-    const RowShape sh = row_shape(M, g_wave_from.load(std::memory_order_relaxed));
     if (sh.wave) f(sh, std::integral_constant<int, 1>());
     else f(sh, std::integral_constant<int, WG_WAVES>());
     LH_BESIDE_CHK(hipGetLastError());
     return LH_OK;
 }
+template <class F> int launch_rows(uint32_t M, F f) { return launch_shape(row_shape(M, g_wave_from.load(std::memory_order_relaxed)), f); }
 template <class F> int launch_rows(uint32_t M, bool by_id, F f)
 {
     if (by_id) return launch_rows(M, [&](const RowShape &sh, auto nw) { f(sh, std::true_type(), nw); });
     return launch_rows(M, [&](const RowShape &sh, auto nw) { f(sh, std::false_type(), nw); });
+}
+// The launch of k_kept_series / k_kept_heat, M rows in each of nwin windows: the rows' grid with a window per blockIdx.y.  The
+// switch takes the ENTRIES, nwin * M: twenty ids in sixty windows are 1 200 rows' worth of work, not twenty.
+template <class F> int launch_windows(uint32_t M, uint32_t nwin, bool by_id, F f)
+{
+    const bool wave = (u64)M * nwin >= g_wave_from.load(std::memory_order_relaxed);
+    const RowShape sh = {wave, dim3(wave ? (M + ROW_WAVES - 1) / ROW_WAVES : M, nwin), dim3(wave ? ROW_BLOCK : WG)};
+    if (by_id) return launch_shape(sh, [&](const RowShape &shape, auto nw) { f(shape, std::true_type(), nw); });
+    return launch_shape(sh, [&](const RowShape &shape, auto nw) { f(shape, std::false_type(), nw); });
 }
 
 // (cx->mu held, the device current)  The making of a handle of rows [first, first + nrows) on `st`, for lh_keep and
@@ -1489,6 +1582,124 @@ int kept_count_le(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t 
             return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) {
                 return enqueue_count_le(cx, kept, nkept, sel, nmetrics, bounds, nb, reinterpret_cast<u64 *>(dev[0]),
                                         reinterpret_cast<u64 *>(dev[1]), st);
+            });
+        });
+}
+
+// ---- lh_kept_series* and lh_kept_heat*: lh_kept_across* / lh_kept_count_le* per window of the list, in one launch
+// unless `win` holds nwin windows [lo, hi) of a list of nkept handles, 1 .. LH_MAX_WINDOWS of them, each with 0 <= lo < hi <= nkept
+bool bad_windows(const uint32_t *win, size_t nwin, size_t nkept)
+{
+    if (!win || misaligned(win, 4) || nwin == 0 || nwin > LH_MAX_WINDOWS) return true;
+    for (size_t w = 0; w < nwin; w++)
+        if (win[2 * w] >= win[2 * w + 1] || win[2 * w + 1] > nkept) return true;
+    return false;
+}
+// the windows as the kernels take them (bad_windows came first: every end fits a byte)
+KeptWindows windows_of(const uint32_t *win, size_t nwin)
+{
+    KeptWindows sw;
+    for (size_t w = 0; w < LH_MAX_WINDOWS; w++) {
+        sw.w[w][0] = w < nwin ? (uint8_t)win[2 * w] : 0;
+        sw.w[w][1] = w < nwin ? (uint8_t)win[2 * w + 1] : 0;
+    }
+    return sw;
+}
+// What the two families do once their own arguments are checked and the call is not empty: the two checks that look at the
+// handles -- one device first, then the rows inside EVERY listed handle's block, whether or not a window names it -- and the
+// way of a call (run), with direct(cx, st, sw) / through(cx, st, sw) given the windows by value.
+template <class Direct, class Through>
+int run_windows(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics, void *stream,
+                bool device_form, Direct direct, Through through)
+{
+    int device = -1;
+    int rc = one_device(kept, nkept, &device);
+    if (!rc) rc = rows_in_all(kept, nkept, sel, nmetrics);
+    if (rc) return rc;
+    const KeptWindows sw = windows_of(win, nwin);
+    return run(
+        kept, nkept, device, stream, device_form, [&](KeptCtx *cx, hipStream_t st) { return direct(cx, st, sw); },
+        [&](KeptCtx *cx, hipStream_t st) { return through(cx, st, sw); });
+}
+
+// (cx->mu held, the device current) the walks of the rows in every window, on `st`
+int enqueue_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
+                   size_t nmetrics, const double *p, size_t np, const KeptOut &o, hipStream_t st)
+{
+    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    const uint32_t *ids = nullptr;
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    const PctArgs pa = pct_args(p, np);
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
+    const double *D = cx->d_table;
+    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_series<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, D,
+                           pa, NP, o, ids);
+    });
+}
+
+int kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
+                const double *p, size_t np, uint32_t flags, void *stream, KeptOut o, bool device_form)
+{
+    // every cause of LH_EINVAL, the windows' among them, ahead of the early LH_ERANGE (check_list_args' last)
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept)) return LH_EINVAL;
+    const int rc = check_list_args(kept, nkept, LH_MAX_KEPT, sel, nmetrics, p, np, flags, o);
+    if (rc) return rc;
+    if (nmetrics == 0) return LH_OK; // before any handle is looked at
+    const size_t entries = nwin * nmetrics;
+    return run_windows(
+        kept, nkept, win, nwin, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
+            return enqueue_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, o, st);
+        },
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
+            return list_host_results(cx->res, st, o, entries, np, [&](const KeptOut &d) {
+                return enqueue_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, d, st);
+            });
+        });
+}
+
+// (cx->mu held, the device current) the walks of the rows in every window, on `st`
+int enqueue_heat(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
+                 size_t nmetrics, const double *bounds, size_t nb, u64 *d_cum, u64 *d_total, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    KeptBounds sb;
+    for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
+    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_heat<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, sb,
+                           NB, d_cum, d_total, ids);
+    });
+}
+
+int kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
+              const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: kept_count_le's, and the windows'
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept)) return LH_EINVAL;
+    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
+    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
+    if (bad_bounds(bounds, nb)) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    const size_t entries = nwin * nmetrics;
+    u64 *c = reinterpret_cast<u64 *>(cum), *t = reinterpret_cast<u64 *>(total);
+    return run_windows(
+        kept, nkept, win, nwin, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
+            return enqueue_heat(cx, kept, nkept, sw, nwin, sel, nmetrics, bounds, nb, c, t, st);
+        },
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
+            const HostOut out[2] = {{cum, entries * nb * sizeof(u64)}, {total, entries * sizeof(u64)}};
+            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) {
+                return enqueue_heat(cx, kept, nkept, sw, nwin, sel, nmetrics, bounds, nb, reinterpret_cast<u64 *>(dev[0]),
+                                    reinterpret_cast<u64 *>(dev[1]), st);
             });
         });
 }
@@ -2295,6 +2506,62 @@ int lh_kept_count_le_ids_device(lh_kept *const *kept, size_t nkept, const uint32
                                 uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
 {
     return kept_count_le(kept, nkept, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                   const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
+                   uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
+    return kept_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+}
+
+int lh_kept_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
+                          uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
+    return kept_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+}
+
+int lh_kept_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                       const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
+                       uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
+    return kept_series(kept, nkept, win, nwin, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+}
+
+int lh_kept_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                              const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
+                              uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
+{
+    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
+    return kept_series(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+}
+
+int lh_kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                 const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_heat(kept, nkept, win, nwin, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_heat_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                        const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_heat(kept, nkept, win, nwin, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_heat_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                     const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_heat(kept, nkept, win, nwin, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_heat_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                            const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_heat(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
 }
 
 int lh_kept_spread(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,

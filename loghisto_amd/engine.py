@@ -897,6 +897,50 @@ class Kept:
         return _dict_call(fn, lead, _SPREAD_OUT, nmetrics, int(p.size), out, device_ids,
                           _spread_derived, self._decompress_table)
 
+    # -- across and count_le per WINDOW of the list, in one call (lh_kept_series* / lh_kept_heat*) ---------------------------------
+    @staticmethod
+    def _windows(windows, nkept):
+        """windows of series / heat -> (the library's array of 2 * nwin uint32, nwin); None: one window per handle."""
+        pairs = [(i, i + 1) for i in range(nkept)] if windows is None else [(int(lo), int(hi)) for lo, hi in windows]
+        if any(not 0 <= v <= 0xffffffff for pair in pairs for v in pair):
+            raise ValueError("a window is a pair (lo, hi) of list positions")
+        return (C.c_uint32 * max(2 * len(pairs), 1))(*[v for pair in pairs for v in pair]), len(pairs)
+
+    def _windowed(self, fn, earlier, windows, nmetrics, first, ids, tail, spec, per, out, derive=None):
+        """The call of a per-window reader through _list_rows / _dict_call: nwin * n entries, window-major, which a host form's
+        arrays then show as a leading window axis."""
+        handles, nkept = self._list(earlier)
+        win, nwin = self._windows(windows, nkept)
+        alive, fn, rows, n, device_ids = self._list_rows((handles, nkept, win, nwin), fn, nmetrics, first, ids)
+        res = _dict_call(fn, (*rows, *tail), spec, nwin * n, per, out, device_ids, derive, self._decompress_table)
+        if out is not None and any(hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()):
+            return res                                 # the device form: the caller's tensors as they are
+        return {k: v.reshape((nwin, n) + v.shape[1:]) for k, v in res.items()}
+
+    def series(self, percentiles, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
+               stream=None):
+        """Kept.across per WINDOW of list(earlier) + [self], in one call (lh_kept_series*): `windows` is a sequence of (lo, hi)
+        pairs, window w the handles [lo, hi) of the list (0 <= lo < hi <= its length; they may overlap, repeat and come in any
+        order; at most N.MAX_WINDOWS), None: one window per handle -- the p99 of each of the last 60 seconds.  Returns
+        Kept.across's dict with a leading window axis -- count[nwin, n], pkeys[nwin, n, np], and the derived avg / pvals --
+        where block w is byte for byte what across() over that slice returns, but for present_bits, whose bit i means handle i
+        of the WHOLE list.  out= and device tensors follow Kept.across's rules, with nwin * n (* np) elements, window-major."""
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        tail = (p.ctypes.data, int(p.size), 0, _stream_handle(stream))
+        return self._windowed("lh_kept_series", earlier, windows, nmetrics, first, ids, tail, self._OUT, int(p.size), out,
+                              _across_derived)
+
+    def heat(self, bounds, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
+             stream=None):
+        """Kept.count_le per WINDOW of list(earlier) + [self], in one call (lh_kept_heat*): dict(cum=uint64[nwin, n, nb],
+        total=uint64[nwin, n]), block w byte for byte what count_le() over the handles [lo, hi) of window w returns -- a
+        latency heat map, counts per `le` band per second.  windows, out= and device tensors as for Kept.series."""
+        b = np.ascontiguousarray(bounds, dtype=np.float64)
+        if b.ndim != 1:
+            raise ValueError("bounds over kept intervals are 1-D: one row shared by all names")
+        tail = (b.ctypes.data, int(b.size), 0, _stream_handle(stream))
+        return self._windowed("lh_kept_heat", earlier, windows, nmetrics, first, ids, tail, _KEPT_COUNT_LE_OUT, int(b.size), out)
+
     # -- the two readers that select across names (lh_top's / lh_movers' entries; what is ranked is what across / count_le /
     #    compare return for the same lists) ------------------------------------------------------------------------------------
     def top(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False, earlier=(),

@@ -12,6 +12,7 @@ from __future__ import annotations
 from collections import deque
 from typing import Optional
 
+from . import _native as N
 from .engine import Kept
 
 
@@ -37,6 +38,25 @@ class KeptWindow:
         self.total = total
         self.handles.append(kept)
         return self.handles.popleft() if oldest else None
+
+    def _newest_and_earlier(self):
+        handles = list(self.handles)
+        if not handles:
+            raise ValueError("the window holds no interval yet")
+        if len(handles) > N.MAX_KEPT:
+            raise ValueError(f"a call reads at most {N.MAX_KEPT} handles; the window holds {len(handles)}")
+        return handles[-1], handles[:-1]
+
+    def series(self, percentiles, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Kept.series over self.handles, the oldest first: `windows` are (lo, hi) positions among them, None: one per
+        interval.  nmetrics / first / ids / out / stream as there.  ValueError above N.MAX_KEPT intervals."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.series(percentiles, earlier, windows, nmetrics, first, ids, out, stream)
+
+    def heat(self, bounds, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Kept.heat over self.handles, the oldest first; as series()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.heat(bounds, earlier, windows, nmetrics, first, ids, out, stream)
 
     def close(self):
         """Releases what the window made, its total; the intervals pushed stay usable and are the caller's to close."""
