@@ -1020,6 +1020,73 @@ int lh_kept_heat_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, si
                      const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
 int lh_kept_heat_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
                             const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+/* SPREAD AND COMPARE PER WINDOW OF KEPT INTERVALS: lh_kept_spread* and lh_kept_compare* for MANY windows of one list of handles in ONE
+ * call and one launch.  This lifts spread / compare per window from the out-of-scope list of the block above; top per window stays
+ * out (it needs a select per window).  lh_kept_spread_series*: the std, mean_90, sum_90 and upper_90 of each of the last 60 seconds,
+ * or of the minute at 10 s resolution -- the statsd-style emit at a resolution chosen afterwards.  lh_kept_drift*: "when did it
+ * start" -- the KS distance, earth mover's distance and shift of every second against a fixed baseline such as the minute before the
+ * deploy, of each second against the second before it, of a rolling 10 s window against the 10 s before it.  Nothing is summed
+ * across names and no new statistic is defined: every output is one that lh_kept_spread* / lh_kept_compare* returns for sub-lists.
+ *   SPREAD WINDOWS.  win is lh_kept_series*' HOST array of 2 * nwin values under its rules: half-open slices [lo, hi) of the list
+ *   with 0 <= lo < hi <= nkept, 1 <= nwin <= LH_MAX_WINDOWS, which may overlap, repeat and come in any order.
+ *   DRIFT WINDOWS.  win is a HOST array of 4 * nwin uint32 values, 1 <= nwin <= LH_MAX_WINDOWS.  Window w compares
+ *   base = kept[win[4w] .. win[4w+1]) with cur = kept[win[4w+2] .. win[4w+3]): both are slices of the ONE list, each with
+ *   0 <= lo < hi <= nkept, and (base_hi - base_lo) + (cur_hi - cur_lo) <= LH_MAX_KEPT.  The two slices may overlap, coincide and
+ *   stand in either order in the list.  A fixed baseline is the same base slice in every window.  Both kinds of windows travel by
+ *   value.
+ *   LAYOUT, window-major, as for lh_kept_series*: entry (w, m) lies at index e = w * n + m (n: nmetrics, or the ids' n);
+ *   per-percentile outputs lie at e * np + i.
+ *   CONTRACT -- this is the whole definition:
+ *   - Window w's block of every output of lh_kept_spread_series* is byte for byte what lh_kept_spread* (the same form, the same
+ *     rows or ids, p, np) writes for the list (kept + lo_w, hi_w - lo_w).
+ *   - This includes sum, m2 and sum_le: they are taken in the same fixed order, the same in both kernel shapes.
+ *   - Wrapped totals behave as lh_kept_spread*'s do; np == 0 is allowed; a handle listed twice counts twice.
+ *   - Window w's block of every output of lh_kept_drift* is byte for byte what lh_kept_compare* (the same form, the same rows or
+ *     ids) writes for the lists (kept + base_lo, base_hi - base_lo) and (kept + cur_lo, cur_hi - cur_lo).
+ *   - This covers all eight outputs, w1 and shift among them, in both kernel shapes.
+ *   - A name with no samples on one side of a window has NaN distances with key and prefixes 0 in that window, and only there.
+ *   - Identical slices give exact zeros for non-empty names.
+ *   - A DEVICE id outside the block of some handle of window w yields, in that window only, the all-zero entry of
+ *     lh_kept_spread_series* or the entry of two empty sides of lh_kept_drift* (the window's two slices count), and nothing is read
+ *     for it.
+ *   CHECKS on the host, before any handle is looked at, in lh_kept_series*' order.  LH_EINVAL: the ids and list rules; NULL or
+ *   misaligned win; nwin == 0 or > LH_MAX_WINDOWS; a slice with lo >= hi or hi > nkept; a drift window whose two slices hold more
+ *   than LH_MAX_KEPT handles together; flags != 0; the family's own argument rules, exactly as lh_kept_spread* / lh_kept_compare*
+ *   have them.  Then LH_ERANGE: nmetrics > 0xffffffff.  Then nmetrics == 0 / n == 0 -> LH_OK with nothing written.  After the host
+ *   checks, in this order: LH_EINVAL for handles on different devices; LH_ERANGE, with nothing enqueued and nothing written, unless
+ *   the rows or every HOST id lie inside EVERY listed handle's block, whether or not a window names the handle.  No output is
+ *   written on any refusal.
+ *   ORDERING, staging, hold and lifetime as for lh_kept_series*: host forms bring nwin * n entries back through the unit's staging
+ *   block and are complete on return; device forms return after enqueueing, with ALL listed handles under one hold; READ-ONLY.  One
+ *   window per blockIdx.y of the parents' two kernel shapes, which give identical bytes; the switch takes the ENTRIES, nwin * n.
+ *   OUT OF SCOPE: top and movers per window; sharing cell reads between overlapping windows; more than LH_MAX_KEPT handles per
+ *   call; LH_LE_PER_METRIC. */
+int lh_kept_spread_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
+                          int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le);
+int lh_kept_spread_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                 size_t nmetrics, const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count,
+                                 double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
+                                 double *d_sum_le);
+int lh_kept_spread_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                              const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
+                              int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le);
+int lh_kept_spread_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids,
+                                     size_t n, const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count,
+                                     double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
+                                     double *d_sum_le);
+int lh_kept_drift(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                  uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                  uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift);
+int lh_kept_drift_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                         uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key,
+                         uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift);
+int lh_kept_drift_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                      uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                      uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift);
+int lh_kept_drift_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                             uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
+                             int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift);
 /* THE K NAMES THAT LEAD, AND THE K THAT MOVED MOST, OVER KEPT INTERVALS: lh_top* and lh_movers* over handles, the two readers that
  * SELECT across names, for the windows that exist only as handles -- "which 20 of my 65 536 endpoints have the worst p99 over the
  * last minute", "whose distribution moved most against the same minute an hour ago" -- so that k entries travel instead of the

@@ -27,7 +27,7 @@ MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   #
 MOVERS_ASCENDING = 1
 MAX_ACROSS = 16        # lh_across*: snapshots of one call
 MAX_KEPT = 64          # lh_kept_across*: handles of one call
-MAX_WINDOWS = 128      # lh_kept_series* / lh_kept_heat*: windows of one call
+MAX_WINDOWS = 128      # lh_kept_series* / lh_kept_heat* / lh_kept_spread_series* / lh_kept_drift*: windows of one call
 MAX_COLUMNS = 128      # lh_lines*
 COL_F64, COL_U64, COL_U32, COL_KEY = range(4)
 OP_VALUE, OP_RATIO, OP_SQRT_RATIO, OP_DIFF = range(4)
@@ -313,6 +313,14 @@ SIGNATURES = {
     "lh_kept_spread_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_spread_series": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_spread_series_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_spread_series_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_spread_series_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_drift": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_drift_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_drift_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_drift_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_top": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_top_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_movers": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),

@@ -98,6 +98,13 @@
 // entry (w, m) at w * n + m: window w's block is byte for byte the reader's output for (kept + lo, hi - lo), sum included, in both
 // shapes -- but for present_bits, the ballot shifted left by lo (bit i: kept[i] of the WHOLE list).  The windows travel by value
 // (KeptWindows, 256 bytes).  The shape switch takes the ENTRIES of a call, windows x rows.
+// lh_kept_spread_series* and lh_kept_drift* do the same for lh_kept_spread* and lh_kept_compare*: the bodies of k_kept_spread and
+// k_kept_compare are spread_entry (a slice, both turns over its handles) and compare_entry (a PAIR of slices (base, cur) of the one
+// list: lane i < base.len opens handle base.lo + i, lane base.len + j handle cur.lo + j -- the parent's lanes for "base's handles,
+// then cur's", so the slices may overlap, coincide and stand in either order); the parents hand them the whole list, k_kept_spread_series
+// / k_kept_drift one window per blockIdx.y (KeptDriftWindows: four bytes a window, 512 bytes by value; at most LH_MAX_KEPT handles in
+// a window's two slices, which the host checks).  Window w's block is byte for byte the parent's output for the slice(s), floats
+// included, in both shapes: the same LDS, no scratch, wave 0 alone walking.  Top and movers per window stay out (a select per window).
 //
 // THE TWO SELECTING READERS, lh_kept_top* and lh_kept_movers*: lh_top's and lh_movers' selections -- the k names of a range that lead,
 // or that moved most between two lists -- for a snapshot whose cells are C, so that k entries travel and no dense buffer is filled.
@@ -707,6 +714,37 @@ __device__ __forceinline__ void compare_turns(Row &row, uint32_t n, uint32_t nba
     });
 }
 
+// the windows of lh_kept_drift*, by value in the kernel arguments beside the list (512 bytes): w[k] = {base_lo, base_hi, cur_lo, cur_hi}
+struct KeptDriftWindows { uint8_t w[LH_MAX_WINDOWS][4]; };
+
+// (every wave that shares the tiles, which are zero)  Entry e of the outputs: row r, the handles of `base` against those of `cur`,
+// two slices of the ONE list that may overlap, coincide and stand in either order.  Lane i < base.len opens handle base.lo + i,
+// lane base.len + j handle cur.lo + j: the lanes are what k_kept_compare's are for the list (base's handles, then cur's), so na
+// comes from the first group, nb from the second, and the turns run over base.len + cur.len lanes with base.len in the first tile.
+// A row outside the block of ANY handle of the two slices gives the entry of two empty sides.
+template <int NW>
+__device__ __forceinline__ void compare_entry(const Seat<NW, 2 * KEPT_COMPARE_TILE> &at, const KeptList &s, const Slice base,
+                                              const Slice cur, uint32_t r, size_t e, const CompareOut &o)
+{
+    const uint32_t lane = at.lane, n = base.len + cur.len;
+    Row row;
+    if (lane < n) row.open(s.h[lane < base.len ? base.lo + lane : cur.lo + (lane - base.len)], r);
+    row.settle();
+    const u64 na = readlane_u64(wave_scan_incl_u64(lane < base.len ? row.rc : 0), 63);
+    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < base.len ? 0 : row.rc), 63);
+
+    Best b;
+    best_init(b);
+    if (na && nb) compare_turns<NW>(row, n, base.len, at.tile, lane, at.w, na, nb, b); // uniform
+    if (at.w != 0) return;
+    u128 x;
+    uint32_t bin;
+    u64 ba, bb;
+    wave_best(b, x, bin, ba, bb);
+    const double w1 = readlane_f64(wave_scan_incl_f64(b.w), 63), shift = readlane_f64(wave_scan_incl_f64(b.s), 63);
+    if (lane == 0) store_row(o, e, na, nb, bin, ba, bb, w1, shift);
+}
+
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const KeptList s, uint32_t nbase, uint32_t nmetrics,
                                                                            uint32_t first, const CompareOut o,
@@ -714,30 +752,39 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
     const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
+    const uint32_t m = at.m;
     if (m >= nmetrics) return; // uniform for all that share the tiles
     at.clear();
 
     uint32_t r;
     if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
     else r = first + m;
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], r);
-    row.settle();
-    const u64 na = readlane_u64(wave_scan_incl_u64(lane < nbase ? row.rc : 0), 63);
-    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < nbase ? 0 : row.rc), 63);
-
-    Best b;
-    best_init(b);
-    if (na && nb) compare_turns<NW>(row, s.n, nbase, at.tile, lane, at.w, na, nb, b); // uniform
-    if (at.w != 0) return;
-    u128 x;
-    uint32_t bin;
-    u64 ba, bb;
-    wave_best(b, x, bin, ba, bb);
-    const double w1 = readlane_f64(wave_scan_incl_f64(b.w), 63), shift = readlane_f64(wave_scan_incl_f64(b.s), 63);
-    if (lane == 0) store_row(o, m, na, nb, bin, ba, bb, w1, shift);
+    compare_entry<NW>(at, s, Slice{0, nbase}, Slice{nbase, s.n - nbase}, r, m, o); // lane i opens handle i
 }
+
+// lh_kept_drift*: the same entry per WINDOW, a pair of slices of the one list, one window per blockIdx.y, window-major (k_kept_series'
+// layout): window w's block of every output is what k_kept_compare writes for the lists (kept + base_lo, base_hi - base_lo) and
+// (kept + cur_lo, cur_hi - cur_lo) -- the same lanes, totals, turns and order, hence the same bytes, w1 and shift included.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_drift(const KeptList s, const KeptDriftWindows sw, uint32_t nmetrics,
+                                                                         uint32_t first, const CompareOut o,
+                                                                         const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    const uint32_t m = at.m, w = blockIdx.y;
+    if (m >= nmetrics) return; // uniform for all that share the tiles
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    // (lo < hi <= s.n on both sides, at most LH_MAX_KEPT handles together: the host checked)
+    const uint32_t blo = sw.w[w][0], bhi = sw.w[w][1], clo = sw.w[w][2], chi = sw.w[w][3];
+    compare_entry<NW>(at, s, Slice{blo, bhi - blo}, Slice{clo, chi - clo}, r, (size_t)w * nmetrics + m, o);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptDriftWindows) + sizeof(CompareOut) + 4 * 8 < 4096,
+              "k_kept_drift's arguments inside the 4 KiB argument segment");
 
 // ---- lh_kept_top / lh_kept_movers: the score passes in front of lh_select.h's k_select ---------------------------------------------
 // Rows first + m (the host refused a range outside any handle's block; such a row would still be the empty entry).  ONE turn over
@@ -993,23 +1040,14 @@ static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(KeptBounds) + 6 * 
 // are known before a cell is read.  Walk 1: sum.  Walk 2: k_spread_wave's -- the centred moment about sum / float64(count) and,
 // in the steps a threshold falls into, the key, count_le and sum_le (lh_pct.h's central4, sums_in_step).  Wave 0 alone walks
 // in both shapes, per lane over the steps in ascending order, then one DPP tree over the lanes: the shapes agree bit for bit.
-template <bool IDS, int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const KeptList s, uint32_t nmetrics, uint32_t first,
-                                                                          const double *__restrict__ D, const PctArgs pa,
-                                                                          uint32_t np, const SpreadOut o,
-                                                                          const uint32_t *__restrict__ ids)
+// (every wave that shares the tile, which is zero)  Entry e of the outputs: row r over the handles of `win` (across_entry's open)
+template <int NW>
+__device__ __forceinline__ void spread_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
+                                             const double *__restrict__ D, const PctArgs &pa, uint32_t np, const SpreadOut &o)
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
-    const Seat<NW> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], r);
+    const uint32_t lane = at.lane;
+    Row row;
+    if (lane < win.len) row.open(s.h[win.lo + lane], r);
     row.settle();
     const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
     const uint32_t hi = row.hi;
@@ -1021,7 +1059,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const 
         const Row opened = row;
         // ---- walk 1: the sum
         double ps = 0.0;
-        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
             double d[4], t[4];
             load4_values(D, base + 4 * lane, hi, d);
             ps += terms4(C, d, t);
@@ -1032,7 +1070,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const 
         pct.open(lane < np ? pct_threshold(pa.p[lane], total) : PCT_NONE);
         double run = 0.0, q = 0.0; // the lane's terms of the steps so far; its share of m2
         row = opened;
-        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
             double d[4], t[4];
             load4_values(D, base + 4 * lane, hi, d);
             q += central4(C, d, mean);
@@ -1064,17 +1102,60 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const 
     }
     if (at.w != 0) return;
     if (lane == 0) {
-        if (o.count) o.count[m] = total;
-        if (o.sum) o.sum[m] = sum;
-        if (o.m2) o.m2[m] = m2;
+        if (o.count) o.count[e] = total;
+        if (o.sum) o.sum[e] = sum;
+        if (o.m2) o.m2[e] = m2;
     }
     if (lane < np) {
-        const size_t to = (size_t)m * np + lane;
+        const size_t to = e * np + lane;
         store_pct(o.pkeys, o.pvalid, to, pct.found);
         if (o.count_le) o.count_le[to] = r_cle;
         if (o.sum_le) o.sum_le[to] = r_sle;
     }
 }
+
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                          const double *__restrict__ D, const PctArgs pa,
+                                                                          uint32_t np, const SpreadOut o,
+                                                                          const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    spread_entry<NW>(at, s, Slice{0, s.n}, r, m, D, pa, np, o); // lane i opens handle i
+}
+
+// lh_kept_spread_series*: the same entry per window of the list (k_kept_series' layout): window w's block of every output is what
+// k_kept_spread writes for the list (kept + lo_w, hi_w - lo_w) -- the same open, two turns, steps and order, hence the same bytes,
+// sum, m2 and sum_le included.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread_series(const KeptList s, const KeptWindows sw,
+                                                                                 uint32_t nmetrics, uint32_t first,
+                                                                                 const double *__restrict__ D, const PctArgs pa,
+                                                                                 uint32_t np, const SpreadOut o,
+                                                                                 const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    const uint32_t m = at.m, w = blockIdx.y;
+    if (m >= nmetrics) return; // uniform for all that share a tile
+    at.clear();
+
+    uint32_t r;
+    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+    else r = first + m;
+    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
+    spread_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, D, pa, np, o);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(SpreadOut) + 5 * 8 < 4096,
+              "k_kept_spread_series' arguments inside the 4 KiB argument segment");
 
 // ---- lh_kept_load: the check ---------------------------------------------------------------------------------------------------
 // The block of a blob -- offsets[nrows + 1] | row_count[nrows] | counts[cells] | keys[cells], copied verbatim into an allocation of
@@ -1607,16 +1688,16 @@ KeptWindows windows_of(const uint32_t *win, size_t nwin)
 }
 // What the two families do once their own arguments are checked and the call is not empty: the two checks that look at the
 // handles -- one device first, then the rows inside EVERY listed handle's block, whether or not a window names it -- and the
-// way of a call (run), with direct(cx, st, sw) / through(cx, st, sw) given the windows by value.
-template <class Direct, class Through>
-int run_windows(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics, void *stream,
+// way of a call (run), with direct(cx, st, sw) / through(cx, st, sw) given the windows as the kernels take them (windows_of; for
+// lh_kept_drift*, drift_windows_of).
+template <class Windows, class Direct, class Through>
+int run_windows(lh_kept *const *kept, size_t nkept, const Windows &sw, const RowSel &sel, size_t nmetrics, void *stream,
                 bool device_form, Direct direct, Through through)
 {
     int device = -1;
     int rc = one_device(kept, nkept, &device);
     if (!rc) rc = rows_in_all(kept, nkept, sel, nmetrics);
     if (rc) return rc;
-    const KeptWindows sw = windows_of(win, nwin);
     return run(
         kept, nkept, device, stream, device_form, [&](KeptCtx *cx, hipStream_t st) { return direct(cx, st, sw); },
         [&](KeptCtx *cx, hipStream_t st) { return through(cx, st, sw); });
@@ -1650,7 +1731,7 @@ int kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t 
     if (nmetrics == 0) return LH_OK; // before any handle is looked at
     const size_t entries = nwin * nmetrics;
     return run_windows(
-        kept, nkept, win, nwin, sel, nmetrics, stream, device_form,
+        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
         [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
             return enqueue_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, o, st);
         },
@@ -1691,7 +1772,7 @@ int kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nw
     const size_t entries = nwin * nmetrics;
     u64 *c = reinterpret_cast<u64 *>(cum), *t = reinterpret_cast<u64 *>(total);
     return run_windows(
-        kept, nkept, win, nwin, sel, nmetrics, stream, device_form,
+        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
         [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
             return enqueue_heat(cx, kept, nkept, sw, nwin, sel, nmetrics, bounds, nb, c, t, st);
         },
@@ -1742,6 +1823,47 @@ int kept_spread(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nm
         [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
             return spread_host_results(cx->res, st, o, nmetrics, np, [&](const SpreadOut &d) {
                 return enqueue_spread(cx, kept, nkept, sel, nmetrics, p, np, d, st);
+            });
+        });
+}
+
+// ---- lh_kept_spread_series*: lh_kept_spread* per window of the list, in one launch (lh_kept_series*' windows, checks and way)
+// (cx->mu held, the device current) the walks of the rows in every window, on `st`
+int enqueue_spread_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
+                          size_t nmetrics, const double *p, size_t np, const SpreadOut &o, hipStream_t st)
+{
+    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    const uint32_t *ids = nullptr;
+    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    const PctArgs pa = pct_args(p, np);
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
+    const double *D = cx->d_table;
+    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_spread_series<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M,
+                           sel.first, D, pa, NP, o, ids);
+    });
+}
+
+int kept_spread_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
+                       const double *p, size_t np, uint32_t flags, void *stream, SpreadOut o, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: kept_spread's, and the windows'
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept) || flags != 0) return LH_EINVAL;
+    const int rc = check_spread_args(p, np, o);
+    if (rc) return rc;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    const size_t entries = nwin * nmetrics;
+    return run_windows(
+        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
+            return enqueue_spread_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, o, st);
+        },
+        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
+            return spread_host_results(cx->res, st, o, entries, np, [&](const SpreadOut &d) {
+                return enqueue_spread_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, d, st);
             });
         });
 }
@@ -1797,6 +1919,68 @@ int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t
         [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
             return compare_host_results(cx->res, st, o, nmetrics, [&](const CompareOut &d) {
                 return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
+            });
+        });
+}
+
+// ---- lh_kept_drift*: lh_kept_compare* per window -- a pair of slices of ONE list -- in one launch (lh_kept_series*' checks and way)
+// unless `win` holds nwin windows {base_lo, base_hi, cur_lo, cur_hi} of a list of nkept handles, 1 .. LH_MAX_WINDOWS of them, each
+// slice with 0 <= lo < hi <= nkept and the two of a window with at most LH_MAX_KEPT handles together (a handle per lane)
+bool bad_drift_windows(const uint32_t *win, size_t nwin, size_t nkept)
+{
+    if (!win || misaligned(win, 4) || nwin == 0 || nwin > LH_MAX_WINDOWS) return true;
+    for (size_t w = 0; w < nwin; w++) {
+        const uint32_t *q = win + 4 * w;
+        if (q[0] >= q[1] || q[1] > nkept || q[2] >= q[3] || q[3] > nkept) return true;
+        if ((size_t)(q[1] - q[0]) + (q[3] - q[2]) > LH_MAX_KEPT) return true;
+    }
+    return false;
+}
+// the windows as k_kept_drift takes them (bad_drift_windows came first: every end fits a byte)
+KeptDriftWindows drift_windows_of(const uint32_t *win, size_t nwin)
+{
+    KeptDriftWindows sw;
+    for (size_t w = 0; w < LH_MAX_WINDOWS; w++)
+        for (size_t k = 0; k < 4; k++) sw.w[w][k] = w < nwin ? (uint8_t)win[4 * w + k] : 0;
+    return sw;
+}
+
+// (cx->mu held, the device current) the walks of the rows in every window, on `st`
+int enqueue_drift(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptDriftWindows &sw, size_t nwin, const RowSel &sel,
+                  size_t nmetrics, const CompareOut &o, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (rc) return rc;
+    const KeptList s = list_of(kept, nkept);
+    const uint32_t M = (uint32_t)nmetrics;
+    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_drift<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, o,
+                           ids);
+    });
+}
+
+int kept_drift(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics, uint32_t flags,
+               void *stream, const CompareOut &o, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: kept_compare's, with the windows in the second list's place
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_drift_windows(win, nwin, nkept) || flags != 0)
+        return LH_EINVAL;
+    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
+    if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
+        misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
+        return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    const size_t entries = nwin * nmetrics;
+    return run_windows(
+        kept, nkept, drift_windows_of(win, nwin), sel, nmetrics, stream, device_form, // (a device form's hold: ALL listed handles)
+        [&](KeptCtx *cx, hipStream_t st, const KeptDriftWindows &sw) {
+            return enqueue_drift(cx, kept, nkept, sw, nwin, sel, nmetrics, o, st);
+        },
+        [&](KeptCtx *cx, hipStream_t st, const KeptDriftWindows &sw) { // results to HBM, then back to the caller's arrays
+            return compare_host_results(cx->res, st, o, entries, [&](const CompareOut &d) {
+                return enqueue_drift(cx, kept, nkept, sw, nwin, sel, nmetrics, d, st);
             });
         });
 }
@@ -2596,6 +2780,77 @@ int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
     const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
                          d_sum_le};
     return kept_spread(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+}
+
+int lh_kept_spread_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
+                          int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
+    return kept_spread_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+}
+
+int lh_kept_spread_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                                 const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
+                                 double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
+                         d_sum_le};
+    return kept_spread_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+}
+
+int lh_kept_spread_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                              const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
+                              int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
+    return kept_spread_series(kept, nkept, win, nwin, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+}
+
+int lh_kept_spread_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids,
+                                     size_t n, const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count,
+                                     double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
+                                     double *d_sum_le)
+{
+    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
+                         d_sum_le};
+    return kept_spread_series(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+}
+
+int lh_kept_drift(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics, uint32_t flags,
+                  void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key, uint64_t *ks_below_a,
+                  uint64_t *ks_below_b, double *w1, double *shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
+                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+    return kept_drift(kept, nkept, win, nwin, rows_from(first), nmetrics, flags, stream, o, false);
+}
+
+int lh_kept_drift_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                         uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key,
+                         uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
+                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
+    return kept_drift(kept, nkept, win, nwin, rows_from(first), nmetrics, flags, stream, o, true);
+}
+
+int lh_kept_drift_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                      uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
+                      uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
+                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+    return kept_drift(kept, nkept, win, nwin, rows_by_id(ids, false), n, flags, stream, o, false);
+}
+
+int lh_kept_drift_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                             uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key,
+                             uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
+{
+    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
+                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
+    return kept_drift(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, flags, stream, o, true);
 }
 
 int lh_tool_kept_compare_tile(uint32_t *bins)

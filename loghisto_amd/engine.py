@@ -906,11 +906,11 @@ class Kept:
             raise ValueError("a window is a pair (lo, hi) of list positions")
         return (C.c_uint32 * max(2 * len(pairs), 1))(*[v for pair in pairs for v in pair]), len(pairs)
 
-    def _windowed(self, fn, earlier, windows, nmetrics, first, ids, tail, spec, per, out, derive=None):
+    def _windowed(self, fn, earlier, windows, nmetrics, first, ids, tail, spec, per, out, derive=None, make=None):
         """The call of a per-window reader through _list_rows / _dict_call: nwin * n entries, window-major, which a host form's
-        arrays then show as a leading window axis."""
+        arrays then show as a leading window axis.  make(windows, nkept) -> (the library's array, nwin); None: _windows."""
         handles, nkept = self._list(earlier)
-        win, nwin = self._windows(windows, nkept)
+        win, nwin = (make or self._windows)(windows, nkept)
         alive, fn, rows, n, device_ids = self._list_rows((handles, nkept, win, nwin), fn, nmetrics, first, ids)
         res = _dict_call(fn, (*rows, *tail), spec, nwin * n, per, out, device_ids, derive, self._decompress_table)
         if out is not None and any(hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) for t in out.values()):
@@ -940,6 +940,51 @@ class Kept:
             raise ValueError("bounds over kept intervals are 1-D: one row shared by all names")
         tail = (b.ctypes.data, int(b.size), 0, _stream_handle(stream))
         return self._windowed("lh_kept_heat", earlier, windows, nmetrics, first, ids, tail, _KEPT_COUNT_LE_OUT, int(b.size), out)
+
+    # -- spread and compare per WINDOW of the list, in one call (lh_kept_spread_series* / lh_kept_drift*) ---------------------------
+    def spread_series(self, percentiles, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None,
+                      out=None, stream=None):
+        """Kept.spread per WINDOW of list(earlier) + [self], in one call (lh_kept_spread_series*): the std, mean_le, sum_le and
+        upper of each of the last 60 seconds, or of the minute at 10 s resolution.  Returns Kept.spread's dict, derived fields
+        included, with a leading window axis -- count[nwin, n], sum_le[nwin, n, np] -- where block w is byte for byte what
+        spread() over the handles [lo, hi) of window w returns.  `percentiles` may be empty.  windows, out= and device tensors
+        as for Kept.series."""
+        p = np.ascontiguousarray(percentiles, dtype=np.float64).ravel()
+        tail = (p.ctypes.data, int(p.size), 0, _stream_handle(stream))
+        return self._windowed("lh_kept_spread_series", earlier, windows, nmetrics, first, ids, tail, _SPREAD_OUT, int(p.size), out,
+                              _spread_derived)
+
+    @staticmethod
+    def _drift_windows(against):
+        """-> make(windows, nkept) for _windowed: the library's array of 4 * nwin uint32 {base_lo, base_hi, cur_lo, cur_hi}."""
+        def make(windows, nkept):
+            if against is not None:
+                cur = [(i, i + 1) for i in range(nkept)] if windows is None else list(windows)
+                quads = [(*against, *c) for c in cur]
+            elif windows is None:
+                if nkept < 2:
+                    raise ValueError("drift of each handle against the one before it needs two handles")
+                quads = [(i, i + 1, i + 1, i + 2) for i in range(nkept - 1)]
+            else:
+                quads = [(*base, *cur) for base, cur in windows]
+            quads = [tuple(int(v) for v in q) for q in quads]
+            if any(len(q) != 4 or not 0 <= v <= 0xffffffff for q in quads for v in q):
+                raise ValueError("a drift window is ((base_lo, base_hi), (cur_lo, cur_hi)) in list positions")
+            return (C.c_uint32 * max(4 * len(quads), 1))(*[v for q in quads for v in q]), len(quads)
+        return make
+
+    def drift(self, windows=None, earlier=(), against=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
+              stream=None):
+        """Kept.compare per WINDOW of list(earlier) + [self], in one call (lh_kept_drift*) -- "when did it start": `windows`
+        is a sequence of ((base_lo, base_hi), (cur_lo, cur_hi)), window w comparing the handles [cur_lo, cur_hi) of the list with
+        the handles [base_lo, base_hi) of the same list (each 0 <= lo < hi <= its length, at most N.MAX_KEPT handles in the two
+        together; the slices may overlap, coincide and stand in either order; at most N.MAX_WINDOWS windows).  With
+        against=(lo, hi), a fixed baseline, `windows` are (cur_lo, cur_hi) slices only, None: one per handle of the list.  With
+        neither, each handle is compared with the one before it: len(list) - 1 windows.  Returns Kept.compare's dict with a
+        leading window axis, block w byte for byte what compare() of the two slices returns (count_a: the base slice).  out=
+        and device tensors as for Kept.series."""
+        return self._windowed("lh_kept_drift", earlier, windows, nmetrics, first, ids, (0, _stream_handle(stream)), _COMPARE_OUT,
+                              0, out, _compare_derived, self._drift_windows(against))
 
     # -- the two readers that select across names (lh_top's / lh_movers' entries; what is ranked is what across / count_le /
     #    compare return for the same lists) ------------------------------------------------------------------------------------

@@ -58,6 +58,19 @@ class KeptWindow:
         newest, earlier = self._newest_and_earlier()
         return newest.heat(bounds, earlier, windows, nmetrics, first, ids, out, stream)
 
+    def spread_series(self, percentiles, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
+                      stream=None):
+        """Kept.spread_series over self.handles, the oldest first; as series()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.spread_series(percentiles, earlier, windows, nmetrics, first, ids, out, stream)
+
+    def drift(self, windows=None, against=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Kept.drift over self.handles, the oldest first: `windows` are ((base_lo, base_hi), (cur_lo, cur_hi)) positions among
+        them -- with against=(lo, hi), a fixed baseline, (cur_lo, cur_hi) only, None: one per interval --, None without
+        `against`: each interval against the one before it.  The rest as series()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.drift(windows, earlier, against, nmetrics, first, ids, out, stream)
+
     def close(self):
         """Releases what the window made, its total; the intervals pushed stay usable and are the caller's to close."""
         if self.total is not None:
