@@ -105,6 +105,14 @@
 // / k_kept_drift one window per blockIdx.y (KeptDriftWindows: four bytes a window, 512 bytes by value; at most LH_MAX_KEPT handles in
 // a window's two slices, which the host checks).  Window w's block is byte for byte the parent's output for the slice(s), floats
 // included, in both shapes: the same LDS, no scratch, wave 0 alone walking.  Top and movers per window stay out (a select per window).
+// A FAMILY'S TWO FORMS ARE ONE PATH.  On the device each of the eight kernels is its `__shared__` tile, the start every kernel of
+// a call's entries has (Seat::take: the bound check, the tile clear; Seat::row: ids[m] or first + m) and the family's entry function,
+// handed the whole list or the window of blockIdx.y (KeptWindows::slice, KeptDriftWindows::slices, window_entry); the two score
+// kernels start the same way.  On the host a family has ONE front end and ONE enqueue (kept_across, kept_count_le, kept_spread,
+// kept_compare and their enqueue_*), which take the windows as something optional (Windows; WHOLE_LIST for the parents, and
+// lh_kept_compare* joins its two lists into lh_kept_drift*'s one): the forms differ in the windows' term of the first LH_EINVAL test,
+// in the launch, in the entries a host form brings back and in the order of the two handle checks, which run() makes from an
+// explicit argument.  The extern "C" wrappers build the output structs with kept_out / compare_out / spread_out.
 //
 // THE TWO SELECTING READERS, lh_kept_top* and lh_kept_movers*: lh_top's and lh_movers' selections -- the k names of a range that lead,
 // or that moved most between two lists -- for a snapshot whose cells are C, so that k entries travel and no dense buffer is filled.
@@ -454,15 +462,40 @@ template <int NW, uint32_t WORDS = KEPT_TILE> struct Seat {
     {
         for (uint32_t i = NW == 1 ? lane : threadIdx.x; i < WORDS; i += NW * 64) tile[i] = 0;
     }
+    // How a kernel over M entries starts: false for a seat beyond them (uniform for all that share a tile), else the tile is cleared
+    __device__ __forceinline__ bool take(uint32_t M) const
+    {
+        if (m >= M) return false;
+        clear();
+        return true;
+    }
+    // The row of entry m.  IDS: ids[m] (an absolute row number, as `first` is); otherwise first + m.  A row outside the block of
+    // ANY handle read gives the empty entry, and nothing is read for it (Row::settle).
+    template <bool IDS> __device__ __forceinline__ uint32_t row(uint32_t first, const uint32_t *__restrict__ ids) const
+    {
+        if constexpr (IDS) return (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
+        else return first + m;
+    }
 };
 
 // A window of the list: its handles [lo, lo + len), which one entry of a call reads.  The whole list is {0, s.n}.
 struct Slice {
     uint32_t lo, len;
 };
-// the windows of lh_kept_series* / lh_kept_heat*, by value in the kernel arguments beside the list (256 bytes): w[k] = {lo, hi}
-struct KeptWindows { uint8_t w[LH_MAX_WINDOWS][2]; };
+// The windows of lh_kept_series* / lh_kept_heat* / lh_kept_spread_series*, by value in the kernel arguments beside the list (256
+// bytes): w[k] = {lo, hi}.  A window kernel has one window per blockIdx.y: slice() is its own (lo < hi <= s.n: the host checked).
+struct KeptWindows {
+    uint8_t w[LH_MAX_WINDOWS][2];
+    __device__ __forceinline__ Slice slice() const
+    {
+        const uint32_t lo = w[blockIdx.y][0], hi = w[blockIdx.y][1];
+        return Slice{lo, hi - lo};
+    }
+};
 static_assert(LH_MAX_KEPT <= 255, "a window's ends in a byte each");
+// Window-major outputs: entry (w, m) of a window kernel at w * nmetrics + m, so that window w's block of every output is what the
+// parent kernel writes for the window's slice(s) of the list -- the same entry function, hence the same bytes.
+__device__ __forceinline__ size_t window_entry(uint32_t m, uint32_t nmetrics) { return (size_t)blockIdx.y * nmetrics + m; }
 
 // (every wave that shares the tile, which is zero)  Entry e of the outputs: row r over the handles of `win`.  Lane i opens handle
 // win.lo + i and the turns run over win.len handles; present_bits speaks of the WHOLE list (bit i: s.h[i]).  A row outside the
@@ -507,8 +540,7 @@ __device__ __forceinline__ void across_entry(const Seat<NW> &at, const KeptList 
     }
 }
 
-// IDS: entry m reads row ids[m] (an absolute row number, as `first` is); otherwise row first + m.  A row outside the block
-// of ANY handle gives the empty entry, and nothing is read for it.
+// lh_kept_across*: the entry over the whole list (lane i opens handle i)
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const KeptList s, uint32_t nmetrics, uint32_t first,
                                                                           const double *__restrict__ D, const PctArgs pa,
@@ -517,19 +549,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_across(const 
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    across_entry<NW>(at, s, Slice{0, s.n}, r, m, D, pa, np, o); // lane i opens handle i
+    if (!at.take(nmetrics)) return;
+    across_entry<NW>(at, s, Slice{0, s.n}, at.template row<IDS>(first, ids), at.m, D, pa, np, o);
 }
 
-// lh_kept_series*: the same entry per WINDOW of the list, one window per blockIdx.y, window-major: entry (w, m) at w * nmetrics
-// + m, so that window w's block of every output is what k_kept_across writes for the list (kept + lo_w, hi_w - lo_w) -- the same
-// open, turns, step and order, hence the same bytes, sum included -- but for present_bits, shifted left by lo_w.
+// lh_kept_series*: the same entry per WINDOW of the list -- but for present_bits, which across_entry shifts left by the window's lo
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_series(const KeptList s, const KeptWindows sw, uint32_t nmetrics,
                                                                           uint32_t first, const double *__restrict__ D,
@@ -538,15 +562,9 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_series(const 
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m, w = blockIdx.y;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
-    across_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, D, pa, np, o);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    across_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), D, pa, np, o);
 }
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(KeptOut) + 5 * 8 < 4096,
               "k_kept_series' arguments inside the 4 KiB argument segment");
@@ -714,8 +732,18 @@ __device__ __forceinline__ void compare_turns(Row &row, uint32_t n, uint32_t nba
     });
 }
 
-// the windows of lh_kept_drift*, by value in the kernel arguments beside the list (512 bytes): w[k] = {base_lo, base_hi, cur_lo, cur_hi}
-struct KeptDriftWindows { uint8_t w[LH_MAX_WINDOWS][4]; };
+// The windows of lh_kept_drift*, by value in the kernel arguments beside the list (512 bytes): w[k] = {base_lo, base_hi, cur_lo,
+// cur_hi}.  One window per blockIdx.y: slices() gives its own pair (lo < hi <= s.n on both sides, at most LH_MAX_KEPT handles
+// together: the host checked).
+struct KeptDriftWindows {
+    uint8_t w[LH_MAX_WINDOWS][4];
+    __device__ __forceinline__ void slices(Slice &base, Slice &cur) const
+    {
+        const uint32_t blo = w[blockIdx.y][0], bhi = w[blockIdx.y][1], clo = w[blockIdx.y][2], chi = w[blockIdx.y][3];
+        base = Slice{blo, bhi - blo};
+        cur = Slice{clo, chi - clo};
+    }
+};
 
 // (every wave that shares the tiles, which are zero)  Entry e of the outputs: row r, the handles of `base` against those of `cur`,
 // two slices of the ONE list that may overlap, coincide and stand in either order.  Lane i < base.len opens handle base.lo + i,
@@ -745,6 +773,7 @@ __device__ __forceinline__ void compare_entry(const Seat<NW, 2 * KEPT_COMPARE_TI
     if (lane == 0) store_row(o, e, na, nb, bin, ba, bb, w1, shift);
 }
 
+// lh_kept_compare*: the entry over the whole list, handles 0 .. nbase - 1 against the others (lane i opens handle i)
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const KeptList s, uint32_t nbase, uint32_t nmetrics,
                                                                            uint32_t first, const CompareOut o,
@@ -752,19 +781,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_compare(const
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
     const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
-    const uint32_t m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share the tiles
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    compare_entry<NW>(at, s, Slice{0, nbase}, Slice{nbase, s.n - nbase}, r, m, o); // lane i opens handle i
+    if (!at.take(nmetrics)) return;
+    compare_entry<NW>(at, s, Slice{0, nbase}, Slice{nbase, s.n - nbase}, at.template row<IDS>(first, ids), at.m, o);
 }
 
-// lh_kept_drift*: the same entry per WINDOW, a pair of slices of the one list, one window per blockIdx.y, window-major (k_kept_series'
-// layout): window w's block of every output is what k_kept_compare writes for the lists (kept + base_lo, base_hi - base_lo) and
-// (kept + cur_lo, cur_hi - cur_lo) -- the same lanes, totals, turns and order, hence the same bytes, w1 and shift included.
+// lh_kept_drift*: the same entry per WINDOW, a pair of slices of the one list
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_drift(const KeptList s, const KeptDriftWindows sw, uint32_t nmetrics,
                                                                          uint32_t first, const CompareOut o,
@@ -772,16 +793,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_drift(const K
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
     const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
-    const uint32_t m = at.m, w = blockIdx.y;
-    if (m >= nmetrics) return; // uniform for all that share the tiles
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    // (lo < hi <= s.n on both sides, at most LH_MAX_KEPT handles together: the host checked)
-    const uint32_t blo = sw.w[w][0], bhi = sw.w[w][1], clo = sw.w[w][2], chi = sw.w[w][3];
-    compare_entry<NW>(at, s, Slice{blo, bhi - blo}, Slice{clo, chi - clo}, r, (size_t)w * nmetrics + m, o);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    Slice base, cur;
+    sw.slices(base, cur);
+    compare_entry<NW>(at, s, base, cur, r, window_entry(at.m, nmetrics), o);
 }
 static_assert(sizeof(KeptList) + sizeof(KeptDriftWindows) + sizeof(CompareOut) + 4 * 8 < 4096,
               "k_kept_drift's arguments inside the 4 KiB argument segment");
@@ -802,8 +818,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(con
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
     const uint32_t lane = at.lane, m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
+    if (!at.take(nmetrics)) return;
 
     Row row; // lane i opens handle i
     if (lane < s.n) row.open(s.h[lane], first + m);
@@ -870,8 +885,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
     const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
     const uint32_t lane = at.lane, m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share the tiles
-    at.clear();
+    if (!at.take(nmetrics)) return;
 
     Row row; // lane i opens handle i
     if (lane < s.n) row.open(s.h[lane], first + m);
@@ -993,6 +1007,7 @@ __device__ __forceinline__ void count_le_entry(const Seat<NW> &at, const KeptLis
     if (total && lane == 0) total[e] = tot;
 }
 
+// lh_kept_count_le*: the entry over the whole list (lane i opens handle i)
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(const KeptList s, uint32_t nmetrics, uint32_t first,
                                                                             const KeptBounds sb, uint32_t nb, u64 *__restrict__ cum,
@@ -1001,18 +1016,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(cons
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    count_le_entry<NW>(at, s, Slice{0, s.n}, r, m, sb, nb, cum, total); // lane i opens handle i
+    if (!at.take(nmetrics)) return;
+    count_le_entry<NW>(at, s, Slice{0, s.n}, at.template row<IDS>(first, ids), at.m, sb, nb, cum, total);
 }
 
-// lh_kept_heat*: the same entry per window of the list (k_kept_series' layout): window w's block of cum / total is what
-// k_kept_count_le writes for the list (kept + lo_w, hi_w - lo_w).
+// lh_kept_heat*: the same entry per WINDOW of the list
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_heat(const KeptList s, const KeptWindows sw, uint32_t nmetrics,
                                                                         uint32_t first, const KeptBounds sb, uint32_t nb,
@@ -1021,15 +1029,9 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_heat(const Ke
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m, w = blockIdx.y;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
-    count_le_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, sb, nb, cum, total);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    count_le_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), sb, nb, cum, total);
 }
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(KeptBounds) + 6 * 8 < 4096,
               "k_kept_heat's arguments inside the 4 KiB argument segment");
@@ -1114,6 +1116,7 @@ __device__ __forceinline__ void spread_entry(const Seat<NW> &at, const KeptList 
     }
 }
 
+// lh_kept_spread*: the entry over the whole list (lane i opens handle i)
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const KeptList s, uint32_t nmetrics, uint32_t first,
                                                                           const double *__restrict__ D, const PctArgs pa,
@@ -1122,19 +1125,11 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread(const 
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    spread_entry<NW>(at, s, Slice{0, s.n}, r, m, D, pa, np, o); // lane i opens handle i
+    if (!at.take(nmetrics)) return;
+    spread_entry<NW>(at, s, Slice{0, s.n}, at.template row<IDS>(first, ids), at.m, D, pa, np, o);
 }
 
-// lh_kept_spread_series*: the same entry per window of the list (k_kept_series' layout): window w's block of every output is what
-// k_kept_spread writes for the list (kept + lo_w, hi_w - lo_w) -- the same open, two turns, steps and order, hence the same bytes,
-// sum, m2 and sum_le included.
+// lh_kept_spread_series*: the same entry per WINDOW of the list
 template <bool IDS, int NW>
 __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread_series(const KeptList s, const KeptWindows sw,
                                                                                  uint32_t nmetrics, uint32_t first,
@@ -1144,15 +1139,9 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_spread_series
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
-    const uint32_t m = at.m, w = blockIdx.y;
-    if (m >= nmetrics) return; // uniform for all that share a tile
-    at.clear();
-
-    uint32_t r;
-    if constexpr (IDS) r = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[__builtin_amdgcn_readfirstlane((int)m)]);
-    else r = first + m;
-    const uint32_t lo = sw.w[w][0], hi = sw.w[w][1]; // (lo < hi <= s.n: the host checked)
-    spread_entry<NW>(at, s, Slice{lo, hi - lo}, r, (size_t)w * nmetrics + m, D, pa, np, o);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    spread_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), D, pa, np, o);
 }
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(SpreadOut) + 5 * 8 < 4096,
               "k_kept_spread_series' arguments inside the 4 KiB argument segment");
@@ -1559,19 +1548,28 @@ int check_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t ns
     return rc ? rc : rows_in_all(all, nadd + nsub, rows_from(first), nmetrics);
 }
 
-// The way of a call from there on: the unit's context on the handles' device, its mutex for the length of the call, the
-// device made current.  A device form's work -- direct(cx, st) enqueues it on the caller's stream -- goes under ONE hold of
-// all listed handles; a host form's -- through(cx, st) brings the results back to the caller's arrays and waits -- leaves
-// nothing of the call under way, after a failure either.
+// The order of those two checks is documented per entry point and differs: lh_kept_across*, lh_kept_count_le* and lh_kept_spread*
+// look at the rows first; their window forms, lh_kept_compare*, lh_kept_drift* and the selecting readers at the devices first.
+enum HandleChecks { ROWS_THEN_DEVICE, DEVICE_THEN_ROWS };
+
+// The way of a call once its own arguments are checked and it is not empty: the two checks that look at the handles, in the
+// caller's order -- the rows inside EVERY listed handle's block, whether or not a window names it --, then the unit's context on
+// the handles' device, its mutex for the length of the call, the device made current.  A device form's work -- direct(cx, st)
+// enqueues it on the caller's stream -- goes under ONE hold of all listed handles; a host form's -- through(cx, st) brings the
+// results back to the caller's arrays and waits -- leaves nothing of the call under way, after a failure either.
 template <class Direct, class Through>
-int run(lh_kept *const *kept, size_t nkept, int device, void *stream, bool device_form, Direct direct, Through through)
+int run(lh_kept *const *kept, size_t nkept, HandleChecks order, const RowSel &sel, size_t nmetrics, void *stream, bool device_form,
+        Direct direct, Through through)
 {
+    int device = -1;
+    int rc = order == ROWS_THEN_DEVICE ? rows_in_all(kept, nkept, sel, nmetrics) : one_device(kept, nkept, &device);
+    if (!rc) rc = order == ROWS_THEN_DEVICE ? one_device(kept, nkept, &device) : rows_in_all(kept, nkept, sel, nmetrics);
+    if (rc) return rc;
     KeptCtx *cx = device_ctx<KeptCtx>(device);
     if (!cx) return LH_EDEVICE;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> g(cx->mu);
     LH_BESIDE_CHK(hipSetDevice(device));
-    int rc;
     if (device_form) {
         rc = direct(cx, st);
         if (rc) return rc;
@@ -1584,90 +1582,20 @@ int run(lh_kept *const *kept, size_t nkept, int device, void *stream, bool devic
     if (rc && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); // nothing of this call is under way afterwards
     return rc;
 }
-// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
-int enqueue(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
-            const KeptOut &o, hipStream_t st)
-{
-    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
-    const uint32_t *ids = nullptr;
-    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
-    if (rc) return rc;
-    const PctArgs pa = pct_args(p, np);
-    const KeptList s = list_of(kept, nkept);
-    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
-    const double *D = cx->d_table;
-    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
-        hipLaunchKernelGGL((k_kept_across<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa,
-                           NP, o, ids);
-    });
-}
 
-int kept_across(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
-                void *stream, KeptOut o, bool device_form)
-{
-    int rc = check_list_args(kept, nkept, LH_MAX_KEPT, sel, nmetrics, p, np, flags, o);
-    if (rc) return rc;
-    if (nmetrics == 0) return LH_OK; // before any handle is looked at
-    int device = -1;
-    rc = rows_in_all(kept, nkept, sel, nmetrics);
-    if (!rc) rc = one_device(kept, nkept, &device);
-    if (rc) return rc;
-    return run(
-        kept, nkept, device, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, o, st); },
-        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
-            return list_host_results(cx->res, st, o, nmetrics, np,
-                                     [&](const KeptOut &d) { return enqueue(cx, kept, nkept, sel, nmetrics, p, np, d, st); });
-        });
-}
+// ---- the four per-name readers, each with its per-window form: ONE front end and ONE enqueue a family ----------------------------
+// The windows a front end was given: none for the whole-list forms (lh_kept_across*, lh_kept_count_le*, lh_kept_spread*,
+// lh_kept_compare*), else win[0 .. n) as the caller passed them, still to be checked.  A window form differs from its parent in
+// four places only: the windows' term in the first LH_EINVAL test, the launch (launch_windows, the switch on n * M entries), the
+// entries a host form brings back, and the order of the two handle checks.
+struct Windows {
+    bool given;
+    const uint32_t *win;
+    size_t n;
+    size_t entries(size_t nmetrics) const { return given ? n * nmetrics : nmetrics; }
+};
+constexpr Windows WHOLE_LIST = {false, nullptr, 0};
 
-// ---- lh_kept_count_le*
-// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
-int enqueue_count_le(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *bounds,
-                     size_t nb, u64 *d_cum, u64 *d_total, hipStream_t st)
-{
-    const uint32_t *ids = nullptr;
-    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
-    if (rc) return rc;
-    KeptBounds sb;
-    for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
-    const KeptList s = list_of(kept, nkept);
-    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
-    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
-        hipLaunchKernelGGL((k_kept_count_le<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, sb,
-                           NB, d_cum, d_total, ids);
-    });
-}
-
-int kept_count_le(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb,
-                  uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
-{
-    // ---- every check that needs neither a handle nor a device: lh_count_le's, with the list in the snapshot's place.  The bounds
-    // are one shared row (LH_LE_PER_METRIC is refused with every other flag), so every cause of LH_EINVAL comes first.
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT)) return LH_EINVAL;
-    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
-    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
-    if (bad_bounds(bounds, nb)) return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    int device = -1;
-    int rc = rows_in_all(kept, nkept, sel, nmetrics);
-    if (!rc) rc = one_device(kept, nkept, &device);
-    if (rc) return rc;
-    u64 *c = reinterpret_cast<u64 *>(cum), *t = reinterpret_cast<u64 *>(total);
-    return run(
-        kept, nkept, device, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st) { return enqueue_count_le(cx, kept, nkept, sel, nmetrics, bounds, nb, c, t, st); },
-        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
-            const HostOut out[2] = {{cum, nmetrics * nb * sizeof(u64)}, {total, nmetrics * sizeof(u64)}};
-            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) {
-                return enqueue_count_le(cx, kept, nkept, sel, nmetrics, bounds, nb, reinterpret_cast<u64 *>(dev[0]),
-                                        reinterpret_cast<u64 *>(dev[1]), st);
-            });
-        });
-}
-
-// ---- lh_kept_series* and lh_kept_heat*: lh_kept_across* / lh_kept_count_le* per window of the list, in one launch
 // unless `win` holds nwin windows [lo, hi) of a list of nkept handles, 1 .. LH_MAX_WINDOWS of them, each with 0 <= lo < hi <= nkept
 bool bad_windows(const uint32_t *win, size_t nwin, size_t nkept)
 {
@@ -1686,26 +1614,19 @@ KeptWindows windows_of(const uint32_t *win, size_t nwin)
     }
     return sw;
 }
-// What the two families do once their own arguments are checked and the call is not empty: the two checks that look at the
-// handles -- one device first, then the rows inside EVERY listed handle's block, whether or not a window names it -- and the
-// way of a call (run), with direct(cx, st, sw) / through(cx, st, sw) given the windows as the kernels take them (windows_of; for
-// lh_kept_drift*, drift_windows_of).
-template <class Windows, class Direct, class Through>
-int run_windows(lh_kept *const *kept, size_t nkept, const Windows &sw, const RowSel &sel, size_t nmetrics, void *stream,
-                bool device_form, Direct direct, Through through)
+// the bounds as the kernels take them
+KeptBounds bounds_of(const double *bounds, size_t nb)
 {
-    int device = -1;
-    int rc = one_device(kept, nkept, &device);
-    if (!rc) rc = rows_in_all(kept, nkept, sel, nmetrics);
-    if (rc) return rc;
-    return run(
-        kept, nkept, device, stream, device_form, [&](KeptCtx *cx, hipStream_t st) { return direct(cx, st, sw); },
-        [&](KeptCtx *cx, hipStream_t st) { return through(cx, st, sw); });
+    KeptBounds sb;
+    for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
+    return sb;
 }
 
-// (cx->mu held, the device current) the walks of the rows in every window, on `st`
-int enqueue_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
-                   size_t nmetrics, const double *p, size_t np, const KeptOut &o, hipStream_t st)
+// ---- lh_kept_across* / lh_kept_series*
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`: over the
+// whole list, or in every window
+int enqueue_across(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics,
+                   const double *p, size_t np, const KeptOut &o, hipStream_t st)
 {
     int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
     const uint32_t *ids = nullptr;
@@ -1715,122 +1636,94 @@ int enqueue_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWi
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const double *D = cx->d_table;
-    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+    if (!w.given)
+        return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+            hipLaunchKernelGGL((k_kept_across<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D,
+                               pa, NP, o, ids);
+        });
+    const KeptWindows sw = windows_of(w.win, w.n);
+    return launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
         hipLaunchKernelGGL((k_kept_series<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, D,
                            pa, NP, o, ids);
     });
 }
 
-int kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
-                const double *p, size_t np, uint32_t flags, void *stream, KeptOut o, bool device_form)
+int kept_across(lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
+                uint32_t flags, void *stream, KeptOut o, bool device_form)
 {
     // every cause of LH_EINVAL, the windows' among them, ahead of the early LH_ERANGE (check_list_args' last)
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept)) return LH_EINVAL;
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || (w.given && bad_windows(w.win, w.n, nkept))) return LH_EINVAL;
     const int rc = check_list_args(kept, nkept, LH_MAX_KEPT, sel, nmetrics, p, np, flags, o);
     if (rc) return rc;
     if (nmetrics == 0) return LH_OK; // before any handle is looked at
-    const size_t entries = nwin * nmetrics;
-    return run_windows(
-        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
-            return enqueue_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, o, st);
-        },
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
-            return list_host_results(cx->res, st, o, entries, np, [&](const KeptOut &d) {
-                return enqueue_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, d, st);
-            });
+    const auto work = [&](KeptCtx *cx, hipStream_t st, const KeptOut &d) {
+        return enqueue_across(cx, kept, nkept, w, sel, nmetrics, p, np, d, st);
+    };
+    return run(
+        kept, nkept, w.given ? DEVICE_THEN_ROWS : ROWS_THEN_DEVICE, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return work(cx, st, o); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            return list_host_results(cx->res, st, o, w.entries(nmetrics), np, [&](const KeptOut &d) { return work(cx, st, d); });
         });
 }
 
-// (cx->mu held, the device current) the walks of the rows in every window, on `st`
-int enqueue_heat(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
-                 size_t nmetrics, const double *bounds, size_t nb, u64 *d_cum, u64 *d_total, hipStream_t st)
+// ---- lh_kept_count_le* / lh_kept_heat*
+// (cx->mu held, the device current) the same walks with the bounds in the percentiles' place
+int enqueue_count_le(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics,
+                     const double *bounds, size_t nb, u64 *d_cum, u64 *d_total, hipStream_t st)
 {
     const uint32_t *ids = nullptr;
     const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
     if (rc) return rc;
-    KeptBounds sb;
-    for (size_t j = 0; j < LH_MAX_BOUNDS; j++) sb.b[j] = j < nb ? bounds[j] : 0.0;
+    const KeptBounds sb = bounds_of(bounds, nb);
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
-    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+    if (!w.given)
+        return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+            hipLaunchKernelGGL((k_kept_count_le<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first,
+                               sb, NB, d_cum, d_total, ids);
+        });
+    const KeptWindows sw = windows_of(w.win, w.n);
+    return launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
         hipLaunchKernelGGL((k_kept_heat<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, sb,
                            NB, d_cum, d_total, ids);
     });
 }
 
-int kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
-              const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
+// lh_count_le's rules for the bounds, the two outputs and the flags.  The bounds are one row shared by all names
+// (LH_LE_PER_METRIC is refused with every other flag), so every cause is an LH_EINVAL that needs no handle.
+bool bad_count_le_args(const double *bounds, size_t nb, const uint64_t *cum, const uint64_t *total, uint32_t flags)
 {
-    // ---- every check that needs neither a handle nor a device: kept_count_le's, and the windows'
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept)) return LH_EINVAL;
-    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
-    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
-    if (bad_bounds(bounds, nb)) return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    const size_t entries = nwin * nmetrics;
-    u64 *c = reinterpret_cast<u64 *>(cum), *t = reinterpret_cast<u64 *>(total);
-    return run_windows(
-        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
-            return enqueue_heat(cx, kept, nkept, sw, nwin, sel, nmetrics, bounds, nb, c, t, st);
-        },
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
-            const HostOut out[2] = {{cum, entries * nb * sizeof(u64)}, {total, entries * sizeof(u64)}};
-            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) {
-                return enqueue_heat(cx, kept, nkept, sw, nwin, sel, nmetrics, bounds, nb, reinterpret_cast<u64 *>(dev[0]),
-                                    reinterpret_cast<u64 *>(dev[1]), st);
-            });
-        });
+    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return true;
+    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return true;
+    return bad_bounds(bounds, nb);
 }
 
-// ---- lh_kept_spread*
-// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`
-int enqueue_spread(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
-                   const SpreadOut &o, hipStream_t st)
+int kept_count_le(lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const double *bounds,
+                  size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
 {
-    int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
-    const uint32_t *ids = nullptr;
-    if (!rc) rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
-    if (rc) return rc;
-    const PctArgs pa = pct_args(p, np);
-    const KeptList s = list_of(kept, nkept);
-    const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
-    const double *D = cx->d_table;
-    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
-        hipLaunchKernelGGL((k_kept_spread<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D, pa,
-                           NP, o, ids);
-    });
-}
-
-int kept_spread(lh_kept *const *kept, size_t nkept, const RowSel &sel, size_t nmetrics, const double *p, size_t np, uint32_t flags,
-                void *stream, SpreadOut o, bool device_form)
-{
-    // ---- every check that needs neither a handle nor a device: lh_spread's, with the list in the snapshot's place
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || flags != 0) return LH_EINVAL;
-    int rc = check_spread_args(p, np, o);
-    if (rc) return rc;
+    // ---- every check that needs neither a handle nor a device: lh_count_le's, with the list in the snapshot's place
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || (w.given && bad_windows(w.win, w.n, nkept))) return LH_EINVAL;
+    if (bad_count_le_args(bounds, nb, cum, total, flags)) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    int device = -1;
-    rc = rows_in_all(kept, nkept, sel, nmetrics);
-    if (!rc) rc = one_device(kept, nkept, &device);
-    if (rc) return rc;
+    const size_t entries = w.entries(nmetrics);
+    const auto work = [&](KeptCtx *cx, hipStream_t st, void *d_cum, void *d_total) {
+        return enqueue_count_le(cx, kept, nkept, w, sel, nmetrics, bounds, nb, static_cast<u64 *>(d_cum), static_cast<u64 *>(d_total), st);
+    };
     return run(
-        kept, nkept, device, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st) { return enqueue_spread(cx, kept, nkept, sel, nmetrics, p, np, o, st); },
+        kept, nkept, w.given ? DEVICE_THEN_ROWS : ROWS_THEN_DEVICE, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return work(cx, st, cum, total); },
         [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
-            return spread_host_results(cx->res, st, o, nmetrics, np, [&](const SpreadOut &d) {
-                return enqueue_spread(cx, kept, nkept, sel, nmetrics, p, np, d, st);
-            });
+            const HostOut out[2] = {{cum, entries * nb * sizeof(u64)}, {total, entries * sizeof(u64)}};
+            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) { return work(cx, st, dev[0], dev[1]); });
         });
 }
 
-// ---- lh_kept_spread_series*: lh_kept_spread* per window of the list, in one launch (lh_kept_series*' windows, checks and way)
-// (cx->mu held, the device current) the walks of the rows in every window, on `st`
-int enqueue_spread_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptWindows &sw, size_t nwin, const RowSel &sel,
-                          size_t nmetrics, const double *p, size_t np, const SpreadOut &o, hipStream_t st)
+// ---- lh_kept_spread* / lh_kept_spread_series*
+// (cx->mu held, the device current) enqueue_across' walks with k_kept_spread / k_kept_spread_series
+int enqueue_spread(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics,
+                   const double *p, size_t np, const SpreadOut &o, hipStream_t st)
 {
     int rc = ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
     const uint32_t *ids = nullptr;
@@ -1840,90 +1733,41 @@ int enqueue_spread_series(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const
     const KeptList s = list_of(kept, nkept);
     const uint32_t M = (uint32_t)nmetrics, NP = (uint32_t)np;
     const double *D = cx->d_table;
-    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+    if (!w.given)
+        return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+            hipLaunchKernelGGL((k_kept_spread<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, M, sel.first, D,
+                               pa, NP, o, ids);
+        });
+    const KeptWindows sw = windows_of(w.win, w.n);
+    return launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
         hipLaunchKernelGGL((k_kept_spread_series<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M,
                            sel.first, D, pa, NP, o, ids);
     });
 }
 
-int kept_spread_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics,
-                       const double *p, size_t np, uint32_t flags, void *stream, SpreadOut o, bool device_form)
+int kept_spread(lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const double *p, size_t np,
+                uint32_t flags, void *stream, SpreadOut o, bool device_form)
 {
-    // ---- every check that needs neither a handle nor a device: kept_spread's, and the windows'
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(win, nwin, nkept) || flags != 0) return LH_EINVAL;
+    // ---- every check that needs neither a handle nor a device: lh_spread's, with the list in the snapshot's place
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || (w.given && bad_windows(w.win, w.n, nkept)) || flags != 0)
+        return LH_EINVAL;
     const int rc = check_spread_args(p, np, o);
     if (rc) return rc;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    const size_t entries = nwin * nmetrics;
-    return run_windows(
-        kept, nkept, windows_of(win, nwin), sel, nmetrics, stream, device_form,
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) {
-            return enqueue_spread_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, o, st);
-        },
-        [&](KeptCtx *cx, hipStream_t st, const KeptWindows &sw) { // results to HBM, then back to the caller's arrays
-            return spread_host_results(cx->res, st, o, entries, np, [&](const SpreadOut &d) {
-                return enqueue_spread_series(cx, kept, nkept, sw, nwin, sel, nmetrics, p, np, d, st);
-            });
-        });
-}
-
-// ---- lh_kept_compare*
-// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`;
-// all[0 .. nbase) is the base list, all[nbase .. n) the cur list
-int enqueue_compare(KeptCtx *cx, lh_kept *const *all, size_t n, size_t nbase, const RowSel &sel, size_t nmetrics,
-                    const CompareOut &o, hipStream_t st)
-{
-    const uint32_t *ids = nullptr;
-    const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
-    if (rc) return rc;
-    const KeptList s = list_of(all, n);
-    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nbase;
-    return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
-        hipLaunchKernelGGL((k_kept_compare<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NB, M, sel.first, o,
-                           ids);
-    });
-}
-
-// The two lists of lh_kept_compare* and lh_kept_movers* as ONE, base first (a handle per lane).  False unless each is a list of
-// 1 .. LH_MAX_KEPT handles, none of them NULL, and they hold at most LH_MAX_KEPT together.
-bool join_lists(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, lh_kept *(&all)[LH_MAX_KEPT])
-{
-    if (bad_list(base, nbase, LH_MAX_KEPT) || bad_list(cur, ncur, LH_MAX_KEPT) || nbase + ncur > LH_MAX_KEPT) return false;
-    std::copy(base, base + nbase, all);
-    std::copy(cur, cur + ncur, all + nbase);
-    return true;
-}
-
-int kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const RowSel &sel, size_t nmetrics,
-                 uint32_t flags, void *stream, const CompareOut &o, bool device_form)
-{
-    // ---- every check that needs neither a handle nor a device
-    lh_kept *all[LH_MAX_KEPT];
-    const size_t n = nbase + ncur;
-    if (bad_ids(sel, nmetrics) || !join_lists(base, nbase, cur, ncur, all) || flags != 0) return LH_EINVAL;
-    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
-    if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
-        misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
-        return LH_EINVAL;
-    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
-    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    // ---- the handles are looked at: one device, and the rows every handle of either list has
-    int device = -1;
-    int rc = one_device(all, n, &device);
-    if (!rc) rc = rows_in_all(all, n, sel, nmetrics);
-    if (rc) return rc;
+    const auto work = [&](KeptCtx *cx, hipStream_t st, const SpreadOut &d) {
+        return enqueue_spread(cx, kept, nkept, w, sel, nmetrics, p, np, d, st);
+    };
     return run(
-        all, n, device, stream, device_form, // (a device form's hold: the handles of BOTH lists)
-        [&](KeptCtx *cx, hipStream_t st) { return enqueue_compare(cx, all, n, nbase, sel, nmetrics, o, st); },
+        kept, nkept, w.given ? DEVICE_THEN_ROWS : ROWS_THEN_DEVICE, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return work(cx, st, o); },
         [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
-            return compare_host_results(cx->res, st, o, nmetrics, [&](const CompareOut &d) {
-                return enqueue_compare(cx, all, n, nbase, sel, nmetrics, d, st);
-            });
+            return spread_host_results(cx->res, st, o, w.entries(nmetrics), np, [&](const SpreadOut &d) { return work(cx, st, d); });
         });
 }
 
-// ---- lh_kept_drift*: lh_kept_compare* per window -- a pair of slices of ONE list -- in one launch (lh_kept_series*' checks and way)
+// ---- lh_kept_compare* / lh_kept_drift*: ONE list either way -- the parent's two lists joined, base first (join_lists), or
+// lh_kept_drift*'s own, of which each window names a pair of slices
 // unless `win` holds nwin windows {base_lo, base_hi, cur_lo, cur_hi} of a list of nkept handles, 1 .. LH_MAX_WINDOWS of them, each
 // slice with 0 <= lo < hi <= nkept and the two of a window with at most LH_MAX_KEPT handles together (a handle per lane)
 bool bad_drift_windows(const uint32_t *win, size_t nwin, size_t nkept)
@@ -1945,44 +1789,73 @@ KeptDriftWindows drift_windows_of(const uint32_t *win, size_t nwin)
     return sw;
 }
 
-// (cx->mu held, the device current) the walks of the rows in every window, on `st`
-int enqueue_drift(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const KeptDriftWindows &sw, size_t nwin, const RowSel &sel,
-                  size_t nmetrics, const CompareOut &o, hipStream_t st)
+// (cx->mu held, the device current) the walks of rows [first, first + nmetrics), or of rows ids[0 .. nmetrics), on `st`: all[0 ..
+// nbase) against all[nbase .. n), or the pair of slices of every window
+int enqueue_compare(KeptCtx *cx, lh_kept *const *all, size_t n, size_t nbase, const Windows &w, const RowSel &sel, size_t nmetrics,
+                    const CompareOut &o, hipStream_t st)
 {
     const uint32_t *ids = nullptr;
     const int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
     if (rc) return rc;
-    const KeptList s = list_of(kept, nkept);
-    const uint32_t M = (uint32_t)nmetrics;
-    return launch_windows(M, (uint32_t)nwin, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+    const KeptList s = list_of(all, n);
+    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nbase;
+    if (!w.given)
+        return launch_rows(M, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+            hipLaunchKernelGGL((k_kept_compare<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, NB, M, sel.first,
+                               o, ids);
+        });
+    const KeptDriftWindows sw = drift_windows_of(w.win, w.n);
+    return launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
         hipLaunchKernelGGL((k_kept_drift<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, o,
                            ids);
     });
 }
 
-int kept_drift(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const RowSel &sel, size_t nmetrics, uint32_t flags,
-               void *stream, const CompareOut &o, bool device_form)
+// lh_compare's rules for the eight outputs: at least one, each aligned to its type
+bool bad_compare_out(const CompareOut &o)
 {
-    // ---- every check that needs neither a handle nor a device: kept_compare's, with the windows in the second list's place
-    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_drift_windows(win, nwin, nkept) || flags != 0)
+    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return true;
+    return misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
+           misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8);
+}
+
+// `all`: null for two lists that join_lists refused
+int kept_compare(lh_kept *const *all, size_t n, size_t nbase, const Windows &w, const RowSel &sel, size_t nmetrics, uint32_t flags,
+                 void *stream, const CompareOut &o, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device
+    if (bad_ids(sel, nmetrics) || bad_list(all, n, LH_MAX_KEPT) || (w.given && bad_drift_windows(w.win, w.n, n)) || flags != 0)
         return LH_EINVAL;
-    if (!o.count_a && !o.count_b && !o.ks && !o.ks_key && !o.below_a && !o.below_b && !o.w1 && !o.shift) return LH_EINVAL;
-    if (misaligned(o.count_a, 8) || misaligned(o.count_b, 8) || misaligned(o.ks, 8) || misaligned(o.ks_key, 2) ||
-        misaligned(o.below_a, 8) || misaligned(o.below_b, 8) || misaligned(o.w1, 8) || misaligned(o.shift, 8))
-        return LH_EINVAL;
+    if (bad_compare_out(o)) return LH_EINVAL;
     if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32)
     if (nmetrics == 0) return LH_OK;              // before any handle is looked at
-    const size_t entries = nwin * nmetrics;
-    return run_windows(
-        kept, nkept, drift_windows_of(win, nwin), sel, nmetrics, stream, device_form, // (a device form's hold: ALL listed handles)
-        [&](KeptCtx *cx, hipStream_t st, const KeptDriftWindows &sw) {
-            return enqueue_drift(cx, kept, nkept, sw, nwin, sel, nmetrics, o, st);
-        },
-        [&](KeptCtx *cx, hipStream_t st, const KeptDriftWindows &sw) { // results to HBM, then back to the caller's arrays
-            return compare_host_results(cx->res, st, o, entries, [&](const CompareOut &d) {
-                return enqueue_drift(cx, kept, nkept, sw, nwin, sel, nmetrics, d, st);
-            });
+    const auto work = [&](KeptCtx *cx, hipStream_t st, const CompareOut &d) {
+        return enqueue_compare(cx, all, n, nbase, w, sel, nmetrics, d, st);
+    };
+    return run(
+        all, n, DEVICE_THEN_ROWS, sel, nmetrics, stream, device_form, // (a device form's hold: ALL listed handles, of both lists)
+        [&](KeptCtx *cx, hipStream_t st) { return work(cx, st, o); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
+            return compare_host_results(cx->res, st, o, w.entries(nmetrics), [&](const CompareOut &d) { return work(cx, st, d); });
         });
+}
+
+// The two lists of lh_kept_compare* and lh_kept_movers* as ONE, base first (a handle per lane).  False unless each is a list of
+// 1 .. LH_MAX_KEPT handles, none of them NULL, and they hold at most LH_MAX_KEPT together.
+bool join_lists(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, lh_kept *(&all)[LH_MAX_KEPT])
+{
+    if (bad_list(base, nbase, LH_MAX_KEPT) || bad_list(cur, ncur, LH_MAX_KEPT) || nbase + ncur > LH_MAX_KEPT) return false;
+    std::copy(base, base + nbase, all);
+    std::copy(cur, cur + ncur, all + nbase);
+    return true;
+}
+// lh_kept_compare*'s entry into that path
+int kept_compare_lists(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const RowSel &sel, size_t nmetrics,
+                       uint32_t flags, void *stream, const CompareOut &o, bool device_form)
+{
+    lh_kept *all[LH_MAX_KEPT];
+    const bool joined = join_lists(base, nbase, cur, ncur, all);
+    return kept_compare(joined ? all : nullptr, nbase + ncur, nbase, WHOLE_LIST, sel, nmetrics, flags, stream, o, device_form);
 }
 
 // ---- lh_kept_top* / lh_kept_movers*: lh_select.h's host side around this unit's score passes -----------------------------------
@@ -2056,13 +1929,6 @@ int check_select(SelectCall &c, lh_kept *const *base, size_t nbase, lh_kept *con
     return select_check_args(nmetrics, k, out, n_out, n_out_align);
 }
 
-// the two checks that look at the handles: one device (LH_EINVAL), then the rows every handle has (LH_ERANGE)
-int open_select(const SelectCall &c, int *device)
-{
-    const int rc = one_device(c.all, c.n, device);
-    return rc ? rc : rows_in_all(c.all, c.n, rows_from(c.first), c.nmetrics);
-}
-
 template <class Entry>
 int kept_select(bool movers, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
                 uint32_t by, double arg, size_t k, uint32_t flags, void *stream, Entry *out, size_t *n_out)
@@ -2075,11 +1941,8 @@ int kept_select(bool movers, lh_kept *const *base, size_t nbase, lh_kept *const 
         *n_out = 0;
         return LH_OK;
     }
-    int device = -1;
-    rc = open_select(c, &device);
-    if (rc) return rc;
     const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
-    return run(c.all, c.n, device, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
         return select_host_form(cx->sel, st, k, out, n_out, [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
             return enqueue_select(cx, c, st, d_out, d_n_out, ev);
         });
@@ -2103,10 +1966,8 @@ int kept_select_device(bool movers, lh_kept *const *base, size_t nbase, lh_kept 
         LH_BESIDE_CHK(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream)));
         return LH_OK;
     }
-    rc = open_select(c, &device);
-    if (rc) return rc;
     const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
-    return run(c.all, c.n, device, stream, true, // (one hold: the handles of BOTH lists)
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, true, // (one hold: the handles of BOTH lists)
                [&](KeptCtx *cx, hipStream_t st) { return enqueue_select(cx, c, st, d_out, d_n_out, (hipEvent_t *)nullptr); }, never);
 }
 
@@ -2121,11 +1982,8 @@ int kept_select_passes_ms(bool movers, lh_kept *const *base, size_t nbase, lh_ke
     int rc = check_select(c, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, own, own, 1);
     if (rc) return rc;
     if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
-    int device = -1;
-    rc = open_select(c, &device);
-    if (rc) return rc;
     const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
-    return run(c.all, c.n, device, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
         return select_passes_ms<Entry>(cx->sel, st, k, score_ms, select_ms, [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
             return enqueue_select(cx, c, st, d_out, d_n_out, ev);
         });
@@ -2315,6 +2173,22 @@ int kept_load(int device, const void *buf, size_t len, uint32_t flags, void *str
     }
     *out = k;
     return LH_OK;
+}
+
+// The readers' output structs from the pointers of the C ABI, host and device forms alike
+KeptOut kept_out(uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
+{
+    return {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
+}
+CompareOut compare_out(uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key, uint64_t *ks_below_a, uint64_t *ks_below_b,
+                       double *w1, double *shift)
+{
+    return {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key, reinterpret_cast<u64 *>(ks_below_a),
+            reinterpret_cast<u64 *>(ks_below_b), w1, shift};
+}
+SpreadOut spread_out(uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
+{
+    return {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
 }
 
 } // namespace
@@ -2604,207 +2478,202 @@ int lh_kept_across(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nm
                    void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys,
                    uint8_t *pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
-    return kept_across(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+    return kept_across(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, p, np, flags, stream,
+                       kept_out(count, sum, nbuckets, present_bits, pkeys, pvalid), false);
 }
 
 int lh_kept_across_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
                           uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
                           uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
-    return kept_across(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+    return kept_across(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, p, np, flags, stream,
+                       kept_out(d_count, d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid), true);
 }
 
 int lh_kept_across_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np, uint32_t flags,
                        void *stream, uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys,
                        uint8_t *pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
-    return kept_across(kept, nkept, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+    return kept_across(kept, nkept, WHOLE_LIST, rows_by_id(ids, false), n, p, np, flags, stream,
+                       kept_out(count, sum, nbuckets, present_bits, pkeys, pvalid), false);
 }
 
 int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
                               uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, uint32_t *d_nbuckets,
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
-    return kept_across(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+    return kept_across(kept, nkept, WHOLE_LIST, rows_by_id(d_ids, true), n, p, np, flags, stream,
+                       kept_out(d_count, d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid), true);
 }
 
 int lh_kept_compare(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
                     uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
                     uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
-                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
-    return kept_compare(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream, o, false);
+    return kept_compare_lists(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream,
+                              compare_out(count_a, count_b, ks, ks_key, ks_below_a, ks_below_b, w1, shift), false);
 }
 
 int lh_kept_compare_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
                            uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
                            int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
-                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
-    return kept_compare(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream, o, true);
+    return kept_compare_lists(base, nbase, cur, ncur, rows_from(first), nmetrics, flags, stream,
+                              compare_out(d_count_a, d_count_b, d_ks, d_ks_key, d_ks_below_a, d_ks_below_b, d_w1, d_shift), true);
 }
 
 int lh_kept_compare_ids(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *ids, size_t n,
                         uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
                         uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
-                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
-    return kept_compare(base, nbase, cur, ncur, rows_by_id(ids, false), n, flags, stream, o, false);
+    return kept_compare_lists(base, nbase, cur, ncur, rows_by_id(ids, false), n, flags, stream,
+                              compare_out(count_a, count_b, ks, ks_key, ks_below_a, ks_below_b, w1, shift), false);
 }
 
 int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, const uint32_t *d_ids,
                                size_t n, uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks,
                                int16_t *d_ks_key, uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
-                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
-    return kept_compare(base, nbase, cur, ncur, rows_by_id(d_ids, true), n, flags, stream, o, true);
+    return kept_compare_lists(base, nbase, cur, ncur, rows_by_id(d_ids, true), n, flags, stream,
+                              compare_out(d_count_a, d_count_b, d_ks, d_ks_key, d_ks_below_a, d_ks_below_b, d_w1, d_shift), true);
 }
 
 int lh_kept_count_le(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
                      uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
 {
-    return kept_count_le(kept, nkept, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
+    return kept_count_le(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
 }
 
 int lh_kept_count_le_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *bounds, size_t nb,
                             uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
 {
-    return kept_count_le(kept, nkept, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total, true);
+    return kept_count_le(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total, true);
 }
 
 int lh_kept_count_le_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *bounds, size_t nb,
                          uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
 {
-    return kept_count_le(kept, nkept, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
+    return kept_count_le(kept, nkept, WHOLE_LIST, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
 }
 
 int lh_kept_count_le_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *bounds, size_t nb,
                                 uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
 {
-    return kept_count_le(kept, nkept, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
+    return kept_count_le(kept, nkept, WHOLE_LIST, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
 }
 
 int lh_kept_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                    const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
                    uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
-    return kept_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+    return kept_across(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, p, np, flags, stream,
+                       kept_out(count, sum, nbuckets, present_bits, pkeys, pvalid), false);
 }
 
 int lh_kept_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                           const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
                           uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
-    return kept_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+    return kept_across(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, p, np, flags, stream,
+                       kept_out(d_count, d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid), true);
 }
 
 int lh_kept_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
                        const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, uint32_t *nbuckets,
                        uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(count), sum, nbuckets, reinterpret_cast<u64 *>(present_bits), pkeys, pvalid};
-    return kept_series(kept, nkept, win, nwin, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+    return kept_across(kept, nkept, Windows{true, win, nwin}, rows_by_id(ids, false), n, p, np, flags, stream,
+                       kept_out(count, sum, nbuckets, present_bits, pkeys, pvalid), false);
 }
 
 int lh_kept_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
                               const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
                               uint32_t *d_nbuckets, uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid)
 {
-    const KeptOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_nbuckets, reinterpret_cast<u64 *>(d_present_bits), d_pkeys, d_pvalid};
-    return kept_series(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+    return kept_across(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, p, np, flags, stream,
+                       kept_out(d_count, d_sum, d_nbuckets, d_present_bits, d_pkeys, d_pvalid), true);
 }
 
 int lh_kept_heat(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                  const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
 {
-    return kept_heat(kept, nkept, win, nwin, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
+    return kept_count_le(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
 }
 
 int lh_kept_heat_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                         const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
 {
-    return kept_heat(kept, nkept, win, nwin, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total, true);
+    return kept_count_le(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, bounds, nb, flags, stream, d_cum, d_total,
+                         true);
 }
 
 int lh_kept_heat_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
                      const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
 {
-    return kept_heat(kept, nkept, win, nwin, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
+    return kept_count_le(kept, nkept, Windows{true, win, nwin}, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
 }
 
 int lh_kept_heat_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
                             const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
 {
-    return kept_heat(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total, true);
+    return kept_count_le(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total,
+                         true);
 }
 
 int lh_kept_spread(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,
                    void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le,
                    double *sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
-    return kept_spread(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+    return kept_spread(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, p, np, flags, stream,
+                       spread_out(count, sum, m2, pkeys, pvalid, count_le, sum_le), false);
 }
 
 int lh_kept_spread_device(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np,
                           uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
                           uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
-                         d_sum_le};
-    return kept_spread(kept, nkept, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+    return kept_spread(kept, nkept, WHOLE_LIST, rows_from(first), nmetrics, p, np, flags, stream,
+                       spread_out(d_count, d_sum, d_m2, d_pkeys, d_pvalid, d_count_le, d_sum_le), true);
 }
 
 int lh_kept_spread_ids(lh_kept *const *kept, size_t nkept, const uint32_t *ids, size_t n, const double *p, size_t np, uint32_t flags,
                        void *stream, uint64_t *count, double *sum, double *m2, int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le,
                        double *sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
-    return kept_spread(kept, nkept, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+    return kept_spread(kept, nkept, WHOLE_LIST, rows_by_id(ids, false), n, p, np, flags, stream,
+                       spread_out(count, sum, m2, pkeys, pvalid, count_le, sum_le), false);
 }
 
 int lh_kept_spread_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_ids, size_t n, const double *p, size_t np,
                               uint32_t flags, void *stream, uint64_t *d_count, double *d_sum, double *d_m2, int16_t *d_pkeys,
                               uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
-                         d_sum_le};
-    return kept_spread(kept, nkept, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+    return kept_spread(kept, nkept, WHOLE_LIST, rows_by_id(d_ids, true), n, p, np, flags, stream,
+                       spread_out(d_count, d_sum, d_m2, d_pkeys, d_pvalid, d_count_le, d_sum_le), true);
 }
 
 int lh_kept_spread_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                           const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
                           int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
-    return kept_spread_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, false);
+    return kept_spread(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, p, np, flags, stream,
+                       spread_out(count, sum, m2, pkeys, pvalid, count_le, sum_le), false);
 }
 
 int lh_kept_spread_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                                  const double *p, size_t np, uint32_t flags, void *stream, uint64_t *d_count, double *d_sum,
                                  double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le, double *d_sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
-                         d_sum_le};
-    return kept_spread_series(kept, nkept, win, nwin, rows_from(first), nmetrics, p, np, flags, stream, o, true);
+    return kept_spread(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, p, np, flags, stream,
+                       spread_out(d_count, d_sum, d_m2, d_pkeys, d_pvalid, d_count_le, d_sum_le), true);
 }
 
 int lh_kept_spread_series_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
                               const double *p, size_t np, uint32_t flags, void *stream, uint64_t *count, double *sum, double *m2,
                               int16_t *pkeys, uint8_t *pvalid, uint64_t *count_le, double *sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(count), sum, m2, pkeys, pvalid, reinterpret_cast<u64 *>(count_le), sum_le};
-    return kept_spread_series(kept, nkept, win, nwin, rows_by_id(ids, false), n, p, np, flags, stream, o, false);
+    return kept_spread(kept, nkept, Windows{true, win, nwin}, rows_by_id(ids, false), n, p, np, flags, stream,
+                       spread_out(count, sum, m2, pkeys, pvalid, count_le, sum_le), false);
 }
 
 int lh_kept_spread_series_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids,
@@ -2812,45 +2681,40 @@ int lh_kept_spread_series_ids_device(lh_kept *const *kept, size_t nkept, const u
                                      double *d_sum, double *d_m2, int16_t *d_pkeys, uint8_t *d_pvalid, uint64_t *d_count_le,
                                      double *d_sum_le)
 {
-    const SpreadOut o = {reinterpret_cast<u64 *>(d_count), d_sum, d_m2, d_pkeys, d_pvalid, reinterpret_cast<u64 *>(d_count_le),
-                         d_sum_le};
-    return kept_spread_series(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, p, np, flags, stream, o, true);
+    return kept_spread(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, p, np, flags, stream,
+                       spread_out(d_count, d_sum, d_m2, d_pkeys, d_pvalid, d_count_le, d_sum_le), true);
 }
 
 int lh_kept_drift(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics, uint32_t flags,
                   void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key, uint64_t *ks_below_a,
                   uint64_t *ks_below_b, double *w1, double *shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
-                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
-    return kept_drift(kept, nkept, win, nwin, rows_from(first), nmetrics, flags, stream, o, false);
+    return kept_compare(kept, nkept, 0, Windows{true, win, nwin}, rows_from(first), nmetrics, flags, stream,
+                        compare_out(count_a, count_b, ks, ks_key, ks_below_a, ks_below_b, w1, shift), false);
 }
 
 int lh_kept_drift_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
                          uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key,
                          uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
-                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
-    return kept_drift(kept, nkept, win, nwin, rows_from(first), nmetrics, flags, stream, o, true);
+    return kept_compare(kept, nkept, 0, Windows{true, win, nwin}, rows_from(first), nmetrics, flags, stream,
+                        compare_out(d_count_a, d_count_b, d_ks, d_ks_key, d_ks_below_a, d_ks_below_b, d_w1, d_shift), true);
 }
 
 int lh_kept_drift_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
                       uint32_t flags, void *stream, uint64_t *count_a, uint64_t *count_b, double *ks, int16_t *ks_key,
                       uint64_t *ks_below_a, uint64_t *ks_below_b, double *w1, double *shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(count_a), reinterpret_cast<u64 *>(count_b), ks, ks_key,
-                          reinterpret_cast<u64 *>(ks_below_a), reinterpret_cast<u64 *>(ks_below_b), w1, shift};
-    return kept_drift(kept, nkept, win, nwin, rows_by_id(ids, false), n, flags, stream, o, false);
+    return kept_compare(kept, nkept, 0, Windows{true, win, nwin}, rows_by_id(ids, false), n, flags, stream,
+                        compare_out(count_a, count_b, ks, ks_key, ks_below_a, ks_below_b, w1, shift), false);
 }
 
 int lh_kept_drift_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
                              uint32_t flags, void *stream, uint64_t *d_count_a, uint64_t *d_count_b, double *d_ks, int16_t *d_ks_key,
                              uint64_t *d_ks_below_a, uint64_t *d_ks_below_b, double *d_w1, double *d_shift)
 {
-    const CompareOut o = {reinterpret_cast<u64 *>(d_count_a), reinterpret_cast<u64 *>(d_count_b), d_ks, d_ks_key,
-                          reinterpret_cast<u64 *>(d_ks_below_a), reinterpret_cast<u64 *>(d_ks_below_b), d_w1, d_shift};
-    return kept_drift(kept, nkept, win, nwin, rows_by_id(d_ids, true), n, flags, stream, o, true);
+    return kept_compare(kept, nkept, 0, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, flags, stream,
+                        compare_out(d_count_a, d_count_b, d_ks, d_ks_key, d_ks_below_a, d_ks_below_b, d_w1, d_shift), true);
 }
 
 int lh_tool_kept_compare_tile(uint32_t *bins)
