@@ -409,10 +409,13 @@ def test_epoch_semantics(engine, la, torch_cuda):
     assert np.array_equal(s2.dense_row(0), oracle.histogram_dense(b))
     s2.release()
     # recycled buffers come back clean
+    from tests import _span_contract as sc
     for _ in range(3):
         with engine.flip() as s:
             assert s.extract(PCTS, 1)["count"][0] == 0
             assert s.buckets(0)[0].size == 0
+            # ... cell by cell, not only inside the range that was just reset: the whole store is zero, every range (65 536, 0)
+            sc.assert_clean(sc.check_store(s, engine.max_metrics, torch_cuda))
 
 
 def test_linearity_and_buckets_listing(engine, torch_cuda):
