@@ -1137,6 +1137,59 @@ int lh_kept_movers(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size
 int lh_kept_movers_device(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
                           size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
                           lh_mover_entry *d_out, uint32_t *d_n_out);
+/* TOP-K PER WINDOW OF KEPT INTERVALS: lh_kept_top* and lh_kept_movers* for MANY windows of one list of handles in ONE call -- which
+ * 20 endpoints had the worst p99 in each of the last 60 seconds, which 20 moved most in each second against the minute before the
+ * deploy, and from when on a given name appears among them -- where one lh_kept_top* / lh_kept_movers* call per window pays the
+ * unit's mutex, a hold, two launches and, in the host form, a round trip each time.  This lifts top and movers per window from the
+ * out-of-scope lists of the two blocks above (lh_kept_series* and lh_kept_spread_series* / lh_kept_drift*): the select per window
+ * they waited for is one select workgroup per window.
+ *   WINDOWS.  lh_kept_top_series* takes lh_kept_series*' HOST array of 2 * nwin values under its rules: half-open [lo, hi),
+ *   0 <= lo < hi <= nkept, 1 <= nwin <= LH_MAX_WINDOWS; windows may overlap, repeat and come in any order.
+ *   lh_kept_movers_series* takes lh_kept_drift*'s 4 * nwin values {base_lo, base_hi, cur_lo, cur_hi} under its rules: both are
+ *   slices of the one list, they may overlap, coincide and stand in either order, and the two slices hold at most LH_MAX_KEPT
+ *   handles together.
+ *   LAYOUT.  n_out is an array of nwin counts: size_t in the host forms, uint32_t in the device forms.  Window w's entries lie at
+ *   out[w * k .. w * k + n_out[w]).  Entries of a window's block at and beyond n_out[w] are never written.
+ *   CONTRACT -- this is the whole definition:
+ *   - Window w's block of out and n_out[w] are byte for byte what lh_kept_top* (the same form, the same first, nmetrics, by, arg, k,
+ *     flags) writes for the list (kept + lo_w, hi_w - lo_w).
+ *   - For lh_kept_movers_series* they are what lh_kept_movers* writes for base = (kept + base_lo, base_hi - base_lo) and
+ *     cur = (kept + cur_lo, cur_hi - cur_lo).
+ *   - This holds for sum and score, in both kernel shapes.
+ *   - A window with no candidate has n_out[w] = 0, and nothing of its block is written.
+ *   - A handle listed twice counts twice.
+ *   - Wrapped totals behave as the parents' do.
+ *   - Nothing is summed across names and no new statistic is defined.
+ *   CHECKS on the host, before any handle is looked at, in lh_kept_top*'s order with the windows' term behind the list's rules --
+ *   LH_EINVAL: a NULL or misaligned list; nkept == 0 or > LH_MAX_KEPT; a NULL entry; NULL or misaligned win; nwin == 0 or
+ *   > LH_MAX_WINDOWS; a slice with lo >= hi or hi > nkept; a movers window whose two slices hold more than LH_MAX_KEPT handles
+ *   together; unknown `by`; unknown flag bits; lh_top's / lh_movers' rules for arg; k == 0 or k > LH_MAX_TOP; NULL out or n_out, out
+ *   not 8-byte aligned, n_out not aligned to its type.  Then LH_ERANGE: nmetrics > 0xffffffff.  nmetrics == 0: the host forms write
+ *   nwin zeros to n_out and return LH_OK before any handle is looked at; the device forms look at the handles' devices only
+ *   (LH_EINVAL for more than one), zero nwin counts on `stream` and return LH_OK.  Then the handles are looked at, as for the other
+ *   window forms -- LH_EINVAL: handles on different devices; LH_ERANGE, nothing enqueued and nothing written: [first, first +
+ *   nmetrics) not inside EVERY listed handle's block, whether or not a window names the handle.  No output is written on any
+ *   refusal.  There are no _ids forms, as for the parents.
+ *   ORDERING, staging and hold: the work goes on `stream`, under the unit's mutex: the parents' score pass with one window per
+ *   blockIdx.y (the shape switch, lh_tool_kept_switch, takes the ENTRIES, nwin * nmetrics; identical bytes in both shapes), then
+ *   lh_top's exact radix select and sort with one workgroup per window.  The records of a call go to ONE block of at most 64 MiB:
+ *   the two passes run over chunks of consecutive windows that fit (a call of up to 8 192 names is one chunk at any nwin, 65 536
+ *   names take 25 windows a chunk), one behind the other on `stream`.  Host forms bring nwin * k entries and nwin counts back in
+ *   ONE copy through the unit's pinned block (at most 4 MiB + 512 B), then copy n_out[w] entries per window to the caller, and are
+ *   complete on return.  Device forms return after enqueueing, with ALL listed handles under one hold; the records block is
+ *   guarded by the unit's event as for lh_kept_top*.  READ-ONLY.
+ *   OUT OF SCOPE: sharing cell reads between overlapping windows; a select that spreads ONE window over several workgroups; _ids
+ *   forms; more than LH_MAX_KEPT handles a call. */
+int lh_kept_top_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                       uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_top_entry *out, size_t *n_out);
+int lh_kept_top_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                              uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_top_entry *d_out,
+                              uint32_t *d_n_out);
+int lh_kept_movers_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_mover_entry *out, size_t *n_out);
+int lh_kept_movers_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                 size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                 lh_mover_entry *d_out, uint32_t *d_n_out);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

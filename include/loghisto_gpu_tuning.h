@@ -171,6 +171,20 @@ int lh_tool_kept_top_passes_ms(lh_kept *const *kept, size_t nkept, uint32_t firs
 int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first,
                                   size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
                                   float *score_ms, float *select_ms);
+/* The same for lh_kept_top_series*'s and lh_kept_movers_series*'s two passes: one call with the arguments of the host forms up to
+ * `stream`, its entries left in the unit's own block; the two times are summed over the chunks of the call; returns when they are
+ * known.  nmetrics >= 1. */
+int lh_tool_kept_top_series_passes_ms(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                      size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                      float *score_ms, float *select_ms);
+int lh_tool_kept_movers_series_passes_ms(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                         size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                         float *score_ms, float *select_ms);
+/* The bytes of records lh_kept_top_series* / lh_kept_movers_series* keep at once (default 64 MiB): a call runs over chunks of the
+ * largest number of consecutive windows whose records, 40 bytes a name padded to four names, fit -- never less than one window.
+ * Process-wide; 0 restores the default; *previous (may be NULL) receives the value in force before.  The chunking moves memory
+ * and time only: the outputs are the same bytes (tests reach several chunks at 70 names with it). */
+int lh_tool_kept_select_bytes(uint64_t bytes, uint64_t *previous);
 /* Device time of lh_kept_slide's two passes alone (HIP events on `stream` around each): one lh_kept_slide with these lists makes
  * the handle, then k_slide_count runs once more into the unit's scratch block and k_slide_fill once more into that handle's own
  * arrays (the bytes they hold already), and the handle is freed.  lh_kept_slide's checks and codes (flags 0, no `why`: an

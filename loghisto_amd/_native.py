@@ -27,7 +27,7 @@ MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   #
 MOVERS_ASCENDING = 1
 MAX_ACROSS = 16        # lh_across*: snapshots of one call
 MAX_KEPT = 64          # lh_kept_across*: handles of one call
-MAX_WINDOWS = 128      # lh_kept_series* / lh_kept_heat* / lh_kept_spread_series* / lh_kept_drift*: windows of one call
+MAX_WINDOWS = 128      # lh_kept_series* / _heat* / _spread_series* / _drift* / _top_series* / _movers_series*: windows of one call
 MAX_COLUMNS = 128      # lh_lines*
 COL_F64, COL_U64, COL_U32, COL_KEY = range(4)
 OP_VALUE, OP_RATIO, OP_SQRT_RATIO, OP_DIFF = range(4)
@@ -205,6 +205,11 @@ TUNING_SIGNATURES = {
                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_kept_movers_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp,
                                                 C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_kept_top_series_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp,
+                                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_kept_movers_series_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp,
+                                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_kept_select_bytes": (C.c_int, [C.c_uint64, _u64p]),
 }
 
 # name -> (restype, argtypes): every symbol include/loghisto_gpu.h declares.
@@ -325,6 +330,11 @@ SIGNATURES = {
     "lh_kept_top_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_movers": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_movers_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_top_series": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_top_series_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_movers_series": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_movers_series_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, _vp, _vp,
+                                               _vp]),
     "lh_names_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "lh_names_refresh": (C.c_int, [_vp, _u32p]),
     "lh_names_destroy": (C.c_int, [_vp]),

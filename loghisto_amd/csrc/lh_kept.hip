@@ -130,6 +130,21 @@
 // take turns under its mutex), its records block always sized for the movers' five fields; device forms put ALL listed handles
 // under one hold, and the records block is guarded by SelectState's event.  Out of scope: a BY_COUNT pass that skips the cell walk,
 // a multi-workgroup select, _ids forms, more than 64 handles a call (lh_kept_merge first).
+// PER WINDOW, lh_kept_top_series* and lh_kept_movers_series*, which lift top and movers per window from the lists above: the select
+// per window they waited for is ONE SELECT WORKGROUP PER WINDOW.  The bodies of the two score kernels are top_score_entry (a slice, as
+// across_entry) and movers_score_entry (a pair of slices, compare_entry's lanes) and write record e; the parents hand them the whole
+// list and e = m, k_kept_top_score_series / k_kept_movers_score_series one window per blockIdx.y (KeptWindows / KeptDriftWindows) and
+// e = w * npad + m, npad the rows padded to SEL_PER as select_records pads them.  lh_select.h's k_select_windows then runs k_select's
+// body with workgroup w over key + w * npad, cand + w * npad, its Emit advanced by w * npad records and w * k entries, the count to
+// n_out[w]: no atomic and no order between windows, k_select's LDS a workgroup.  Window w's block is byte for byte the parent's output
+// for the slice(s), sum and score included, in both shapes.  nwin * npad records of 40 bytes would be 320 MiB at 128 windows x 65 536
+// names, so the host runs the two passes over CHUNKS of consecutive windows on the one stream -- the largest window count whose
+// records fit KEPT_SELECT_BYTES (64 MiB; lh_tool_kept_select_bytes), never less than one: up to 8 192 names one chunk at any nwin,
+// 25 windows a chunk at 65 536 -- each chunk's kernels given the windows from its first on and out / n_out advanced; stream order
+// protects the reused block between chunks and the guard's event is recorded behind the last select.  Host forms bring nwin * k
+// entries and nwin counts back in ONE copy (4 MiB + 512 B at most) and hand n_out[w] entries a window on.  Still out of scope:
+// sharing cell reads between overlapping windows, a select that spreads ONE window over several workgroups, _ids forms, more than
+// 64 handles a call.
 //
 // SAVE AND LOAD, lh_kept_save* / lh_kept_load*: a handle's single allocation verbatim behind a 64-byte header (loghisto_gpu.h has the
 // format), to host or device memory and back into a NEW handle on any device, with no engine anywhere.  A save is two copies and a
@@ -810,18 +825,14 @@ static_assert(sizeof(KeptList) + sizeof(KeptDriftWindows) + sizeof(CompareOut) +
 // first tile takes every cell, one in a stretch no tile covers the cells of the tiles behind it, one beyond the last step none:
 // count minus what k_kept_count_le returns for the bound.  Wave 0 alone walks; its lane 0 writes the row's record (TopRecords,
 // the key complemented for LH_TOP_ASCENDING: `flip`).
+// (every wave that shares the tile, which is zero)  Record e: row r over the handles of `win` (across_entry's open)
 template <int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(const KeptList s, uint32_t nmetrics, uint32_t first,
-                                                                             const double *__restrict__ D, uint32_t by, double arg,
-                                                                             u64 flip, const TopRecords r)
+__device__ __forceinline__ void top_score_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
+                                                const double *__restrict__ D, uint32_t by, double arg, u64 flip, const TopRecords &rec)
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
-    const Seat<NW> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
-    if (!at.take(nmetrics)) return;
-
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], first + m);
+    const uint32_t lane = at.lane;
+    Row row; // lane i opens handle win.lo + i
+    if (lane < win.len) row.open(s.h[win.lo + lane], r);
     row.settle();
     const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
     const uint32_t hi = row.hi;
@@ -833,7 +844,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(con
         const bool want_pct = by == LH_TOP_BY_PERCENTILE, want_above = by == LH_TOP_BY_COUNT_ABOVE; // uniform
         const uint32_t take = want_above ? le_take(arg) : 0u;
         pct.open(want_pct && lane == 0 ? pct_threshold(arg, total) : PCT_NONE);
-        turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+        turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
             double d[4], t[4];
             load4_values(D, base + 4 * lane, hi, d);
             const u64 tc = sum4(C);
@@ -864,12 +875,40 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(con
             key = above;
             aux = above;
         }
-        r.key[m] = key ^ flip;
-        r.count[m] = total;
-        r.sum[m] = sum;
-        r.aux[m] = aux;
+        rec.key[e] = key ^ flip;
+        rec.count[e] = total;
+        rec.sum[e] = sum;
+        rec.aux[e] = aux;
     }
 }
+
+// lh_kept_top*: the record over the whole list (lane i opens handle i), record m
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(const KeptList s, uint32_t nmetrics, uint32_t first,
+                                                                             const double *__restrict__ D, uint32_t by, double arg,
+                                                                             u64 flip, const TopRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    top_score_entry<NW>(at, s, Slice{0, s.n}, first + at.m, at.m, D, by, arg, flip, r);
+}
+
+// lh_kept_top_series*: the same record per WINDOW of the list, window w's at w * npad + m (npad: nmetrics padded to whole groups
+// of SEL_PER, as select_records pads a call's records: every window's block is one k_select_windows' workgroup reads as it is)
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score_series(const KeptList s, const KeptWindows sw,
+                                                                                    uint32_t nmetrics, uint32_t npad, uint32_t first,
+                                                                                    const double *__restrict__ D, uint32_t by,
+                                                                                    double arg, u64 flip, const TopRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    top_score_entry<NW>(at, s, sw.slice(), first + at.m, window_entry(at.m, npad), D, by, arg, flip, r);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(TopRecords) + 7 * 8 < 4096,
+              "k_kept_top_score_series' arguments inside the 4 KiB argument segment");
 
 // Handles 0 .. nbase - 1 of the list are `base`, the others `cur`, as in k_kept_compare, whose open, totals and -- for the three
 // distances -- walk, wave_best and sums these are (compare_turns): the scores are the bits lh_kept_compare returns.
@@ -877,21 +916,19 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_top_score(con
 // that side's threshold (k_kept_across' search, find_in_step); the turns are not left early -- the tiles must come back zeroed --
 // so once both bins are found the step does nothing, and the turns only put zeros back.  Lane 0 of wave 0 writes the row's record
 // (MoversRecords).
+// (every wave that shares the tiles, which are zero)  Record e: row r, the handles of `base` against those of `cur` (compare_entry's
+// pair of slices of the one list, and its lanes)
 template <int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(const KeptList s, uint32_t nbase, uint32_t nmetrics,
-                                                                                uint32_t first, uint32_t by, double arg, u64 flip,
-                                                                                const MoversRecords r)
+__device__ __forceinline__ void movers_score_entry(const Seat<NW, 2 * KEPT_COMPARE_TILE> &at, const KeptList &s, const Slice base,
+                                                   const Slice cur, uint32_t r, size_t e, uint32_t by, double arg, u64 flip,
+                                                   const MoversRecords &rec)
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
-    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
-    const uint32_t lane = at.lane, m = at.m;
-    if (!at.take(nmetrics)) return;
-
-    Row row; // lane i opens handle i
-    if (lane < s.n) row.open(s.h[lane], first + m);
+    const uint32_t lane = at.lane, n = base.len + cur.len;
+    Row row; // compare_entry's lanes: base's handles, then cur's
+    if (lane < n) row.open(s.h[lane < base.len ? base.lo + lane : cur.lo + (lane - base.len)], r);
     row.settle();
-    const u64 na = readlane_u64(wave_scan_incl_u64(lane < nbase ? row.rc : 0), 63);
-    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < nbase ? 0 : row.rc), 63);
+    const u64 na = readlane_u64(wave_scan_incl_u64(lane < base.len ? row.rc : 0), 63);
+    const u64 nb = readlane_u64(wave_scan_incl_u64(lane < base.len ? 0 : row.rc), 63);
     const bool is_cand = na != 0 && nb != 0; // uniform
 
     double score = 0.0;
@@ -899,7 +936,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(
     if (by != LH_MOVERS_BY_PERCENTILE) { // uniform
         Best b;
         best_init(b);
-        if (is_cand) compare_turns<NW>(row, s.n, nbase, at.tile, lane, at.w, na, nb, b);
+        if (is_cand) compare_turns<NW>(row, n, base.len, at.tile, lane, at.w, na, nb, b);
         if (at.w != 0) return;
         u128 x;
         uint32_t bin;
@@ -920,8 +957,8 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(
             // (the host keeps arg in [0, 1]: 1 <= T <= total)
             const u64 Ta = readlane_u64(pct_threshold(arg, na), 0), Tb = readlane_u64(pct_threshold(arg, nb), 0);
             u64 ca = 0, cb = 0; // what lies below the step
-            turns_of<NW, 2, KEPT_COMPARE_TILE>(row, s.n, nbase, at.tile, lane, at.w,
-                                               [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t base) {
+            turns_of<NW, 2, KEPT_COMPARE_TILE>(row, n, base.len, at.tile, lane, at.w,
+                                               [&](const u64 (&A)[4], const u64 (&B)[4], uint32_t b0) {
                 if (fa != NO_BIN && fb != NO_BIN) return; // uniform: both found
                 const u64 ta = sum4(A), tb = sum4(B);
                 const u64 ia = wave_scan_incl_u64(ta), ib = wave_scan_incl_u64(tb);
@@ -929,12 +966,12 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(
                 if (fa == NO_BIN && Ta <= ea) { // uniform: it is in this step
                     u64 pre[4];
                     prefix4(A, ca, ta, ia, pre);
-                    fa = base + find_in_step(pre, Ta);
+                    fa = b0 + find_in_step(pre, Ta);
                 }
                 if (fb == NO_BIN && Tb <= eb) {
                     u64 pre[4];
                     prefix4(B, cb, tb, ib, pre);
-                    fb = base + find_in_step(pre, Tb);
+                    fb = b0 + find_in_step(pre, Tb);
                 }
                 ca = ea;
                 cb = eb;
@@ -948,13 +985,42 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(
     }
     if (lane == 0) {
         if (!is_cand) score = 0.0;
-        r.key[m] = order_key_f64(score) ^ flip;
-        r.cand[m] = is_cand ? MOVER_CANDIDATE | keys : 0;
-        r.count_a[m] = na;
-        r.count_b[m] = nb;
-        r.score[m] = (u64)__double_as_longlong(score);
+        rec.key[e] = order_key_f64(score) ^ flip;
+        rec.cand[e] = is_cand ? MOVER_CANDIDATE | keys : 0;
+        rec.count_a[e] = na;
+        rec.count_b[e] = nb;
+        rec.score[e] = (u64)__double_as_longlong(score);
     }
 }
+
+// lh_kept_movers*: the record over the whole list, handles 0 .. nbase - 1 against the others (lane i opens handle i), record m
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score(const KeptList s, uint32_t nbase, uint32_t nmetrics,
+                                                                                uint32_t first, uint32_t by, double arg, u64 flip,
+                                                                                const MoversRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    movers_score_entry<NW>(at, s, Slice{0, nbase}, Slice{nbase, s.n - nbase}, first + at.m, at.m, by, arg, flip, r);
+}
+
+// lh_kept_movers_series*: the same record per WINDOW, a pair of slices of the one list, window w's at w * npad + m
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_movers_score_series(const KeptList s, const KeptDriftWindows sw,
+                                                                                       uint32_t nmetrics, uint32_t npad,
+                                                                                       uint32_t first, uint32_t by, double arg,
+                                                                                       u64 flip, const MoversRecords r)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][2 * KEPT_COMPARE_TILE];
+    const Seat<NW, 2 * KEPT_COMPARE_TILE> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    Slice base, cur;
+    sw.slices(base, cur);
+    movers_score_entry<NW>(at, s, base, cur, first + at.m, window_entry(at.m, npad), by, arg, flip, r);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptDriftWindows) + sizeof(MoversRecords) + 6 * 8 < 4096,
+              "k_kept_movers_score_series' arguments inside the 4 KiB argument segment");
 
 // ---- lh_kept_count_le ---------------------------------------------------------------------------------------------------------
 // the bounds, shared by all names, by value in the kernel arguments (512 bytes beside the list's 1 544)
@@ -1903,13 +1969,76 @@ template <class Entry> int enqueue_select(KeptCtx *cx, const SelectCall &c, hipS
     }
 }
 
-// Every check that needs neither a handle nor a device, in the documented order: the list(s), `by`, the flags, lh_top's /
+// The records block of the per-window forms holds at most this many bytes of records (five fields of 8 bytes each, as always): a
+// call runs its two passes over CHUNKS of consecutive windows that fit, never less than one window.  128 windows of 65 536 names
+// would be 320 MiB at once; up to 8 192 names a call of any nwin is one chunk, 65 536 names take 25 windows a chunk.
+constexpr u64 KEPT_SELECT_BYTES = 64ull << 20;
+std::atomic<u64> g_select_bytes{KEPT_SELECT_BYTES};
+size_t select_chunk(size_t npad, size_t nwin)
+{
+    const u64 fit = g_select_bytes.load(std::memory_order_relaxed) / ((u64)npad * MOVERS_FIELDS * sizeof(u64));
+    return (size_t)std::min<u64>(std::max<u64>(fit, 1), nwin);
+}
+
+// (cx->mu held, the device current)  lh_kept_top_series* / lh_kept_movers_series*: both passes for windows [w0, w0 + wn) of the
+// call's nwin on `st`, chunk after chunk -- each chunk's score kernel and k_select_windows get the windows from its first window on,
+// its records go to the ONE block (stream order protects it between chunks), its entries to d_out + (w - w0) * k and its counts to
+// d_n_out + (w - w0), w its first window -- and the guard's event behind the last select.  ev (may be null; then [w0, w0 + wn) is
+// ONE chunk): select_pass' three events.
+template <class Entry>
+int enqueue_select_windows(KeptCtx *cx, const SelectCall &c, const Windows &w, size_t w0, size_t wn, hipStream_t st, Entry *d_out,
+                           uint32_t *d_n_out, hipEvent_t *ev)
+{
+    const size_t npad = (c.nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1), chunk = select_chunk(npad, wn);
+    u64 *base = nullptr;
+    size_t cap = 0;
+    int rc = c.movers ? LH_OK : ensure_table(cx->d_table, st, lh::k_value_table<KeptCtx>);
+    if (!rc) rc = select_records(cx->sel, st, chunk * npad, MOVERS_FIELDS, base, cap); // (cap == chunk * npad: whole groups already)
+    if (rc) return rc;
+    const KeptList s = list_of(c.all, c.n);
+    const uint32_t M = (uint32_t)c.nmetrics, NP = (uint32_t)npad;
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[0], st));
+    for (size_t at = 0; at < wn && !rc; at += chunk) {
+        const uint32_t nw_here = (uint32_t)std::min(chunk, wn - at);
+        Entry *to = d_out + at * c.k;
+        uint32_t *n_to = d_n_out + at;
+        if constexpr (std::is_same<Entry, lh_top_entry>::value) {
+            const TopRecords r = top_records(base, cap);
+            const u64 flip = (c.flags & LH_TOP_ASCENDING) ? ~0ull : 0ull;
+            const double *D = cx->d_table;
+            const KeptWindows sw = windows_of(w.win + 2 * (w0 + at), nw_here);
+            rc = launch_windows(M, nw_here, false, [&](const RowShape &sh, auto, auto nw) {
+                hipLaunchKernelGGL((k_kept_top_score_series<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, NP, c.first, D, c.by,
+                                   c.arg, flip, r);
+            });
+            if (!rc) rc = select_windows_pass(st, r.key, r.count, M, NP, nw_here, c.k, TopEmit{r, c.first, c.by, to}, n_to, ev);
+        } else {
+            const MoversRecords r = movers_records(base, cap);
+            const u64 flip = (c.flags & LH_MOVERS_ASCENDING) ? ~0ull : 0ull;
+            const KeptDriftWindows sw = drift_windows_of(w.win + 4 * (w0 + at), nw_here);
+            rc = launch_windows(M, nw_here, false, [&](const RowShape &sh, auto, auto nw) {
+                hipLaunchKernelGGL((k_kept_movers_score_series<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, NP, c.first, c.by,
+                                   c.arg, flip, r);
+            });
+            if (!rc) rc = select_windows_pass(st, r.key, r.cand, M, NP, nw_here, c.k, MoversEmit{r, c.first, to}, n_to, ev);
+        }
+    }
+    // behind the last select -- after a failure too: what was enqueued uses the block
+    const int rg = cx->sel.guard.record(st);
+    return rc ? rc : rg;
+}
+
+// Every check that needs neither a handle nor a device, in the documented order: the list(s), the windows of a per-window form
+// (w.given: ONE list, `cur`, of which lh_kept_movers_series*' windows name pairs of slices), `by`, the flags, lh_top's /
 // lh_movers' rules for arg, then select_check_args (k, out, n_out, and the early LH_ERANGE behind every LH_EINVAL).  Fills c.
 int check_select(SelectCall &c, lh_kept *const *base, size_t nbase, lh_kept *const *cur, size_t ncur, uint32_t first, size_t nmetrics,
-                 uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out, uintptr_t n_out_align)
+                 uint32_t by, double arg, size_t k, uint32_t flags, const void *out, const void *n_out, uintptr_t n_out_align,
+                 const Windows &w = WHOLE_LIST)
 {
-    if (c.movers ? !join_lists(base, nbase, cur, ncur, c.all) : bad_list(cur, ncur, LH_MAX_KEPT)) return LH_EINVAL;
-    if (!c.movers) std::copy(cur, cur + ncur, c.all); // (lh_kept_top*: nbase == 0)
+    const bool two_lists = c.movers && !w.given;
+    if (two_lists ? !join_lists(base, nbase, cur, ncur, c.all) : bad_list(cur, ncur, LH_MAX_KEPT)) return LH_EINVAL;
+    if (w.given && (c.movers ? bad_drift_windows(w.win, w.n, ncur) : bad_windows(w.win, w.n, ncur))) return LH_EINVAL;
+    if (!two_lists) std::copy(cur, cur + ncur, c.all); // (nbase == 0)
     c.nbase = nbase;
     c.n = nbase + ncur;
     if (c.movers) {
@@ -1987,6 +2116,87 @@ int kept_select_passes_ms(bool movers, lh_kept *const *base, size_t nbase, lh_ke
         return select_passes_ms<Entry>(cx->sel, st, k, score_ms, select_ms, [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) {
             return enqueue_select(cx, c, st, d_out, d_n_out, ev);
         });
+    });
+}
+
+// ---- lh_kept_top_series* / lh_kept_movers_series*: the same two passes per WINDOW of ONE list, a select workgroup per window.  The
+// checks are check_select's with the windows' term behind the list's; the handle checks, the mutex and the hold are run()'s.
+template <class Entry>
+int kept_select_series(bool movers, lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                       size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, Entry *out, size_t *n_out)
+{
+    const Windows w = {true, win, nwin};
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, out, n_out, alignof(size_t), w);
+    if (rc) return rc;
+    if (nmetrics == 0) { // before any handle is looked at
+        std::fill(n_out, n_out + nwin, (size_t)0);
+        return LH_OK;
+    }
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+        return select_windows_host_form(cx->sel, st, nwin, k, out, n_out, [&](Entry *d_out, uint32_t *d_n_out) {
+            return enqueue_select_windows(cx, c, w, 0, nwin, st, d_out, d_n_out, (hipEvent_t *)nullptr);
+        });
+    });
+}
+
+template <class Entry>
+int kept_select_series_device(bool movers, lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                              size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, Entry *d_out,
+                              uint32_t *d_n_out)
+{
+    const Windows w = {true, win, nwin};
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, d_out, d_n_out, alignof(uint32_t), w);
+    if (rc) return rc;
+    int device = -1;
+    if (nmetrics == 0) { // the handles' devices alone are looked at: that is where the nwin counts are zeroed
+        rc = one_device(c.all, c.n, &device);
+        if (rc) return rc;
+        LH_BESIDE_CHK(hipSetDevice(device));
+        LH_BESIDE_CHK(hipMemsetAsync(d_n_out, 0, nwin * sizeof(uint32_t), static_cast<hipStream_t>(stream)));
+        return LH_OK;
+    }
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, true, // (one hold: ALL listed handles)
+               [&](KeptCtx *cx, hipStream_t st) { return enqueue_select_windows(cx, c, w, 0, nwin, st, d_out, d_n_out, (hipEvent_t *)nullptr); },
+               never);
+}
+
+// lh_tool_kept_*_series_passes_ms: select_passes_ms once per chunk of the call, the two times summed over the chunks
+template <class Entry>
+int kept_select_series_passes_ms(bool movers, lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                 size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream, float *score_ms,
+                                 float *select_ms)
+{
+    alignas(8) unsigned char own[8] = {0}; // (the results stay in the unit's own block)
+    const Windows w = {true, win, nwin};
+    SelectCall c;
+    c.movers = movers;
+    int rc = check_select(c, nullptr, 0, kept, nkept, first, nmetrics, by, arg, k, flags, own, own, 1, w);
+    if (rc) return rc;
+    if (!score_ms || !select_ms || nmetrics == 0) return LH_EINVAL;
+    const auto never = [](KeptCtx *, hipStream_t) { return LH_ESTATE; };
+    return run(c.all, c.n, DEVICE_THEN_ROWS, rows_from(first), nmetrics, stream, false, never, [&](KeptCtx *cx, hipStream_t st) {
+        const size_t npad = (nmetrics + SEL_PER - 1) & ~(size_t)(SEL_PER - 1), chunk = select_chunk(npad, nwin);
+        float score = 0.f, select = 0.f;
+        for (size_t w0 = 0; w0 < nwin; w0 += chunk) {
+            const size_t wn = std::min(chunk, nwin - w0);
+            float a = 0.f, b = 0.f;
+            const int rs = select_passes_ms<Entry>(
+                cx->sel, st, k, &a, &b,
+                [&](Entry *d_out, uint32_t *d_n_out, hipEvent_t *ev) { return enqueue_select_windows(cx, c, w, w0, wn, st, d_out, d_n_out, ev); },
+                wn);
+            if (rs) return rs;
+            score += a;
+            select += b;
+        }
+        *score_ms = score;
+        *select_ms = select;
+        return (int)LH_OK;
     });
 }
 
@@ -2319,6 +2529,54 @@ int lh_tool_kept_movers_passes_ms(lh_kept *const *base, size_t nbase, lh_kept *c
 {
     return kept_select_passes_ms<lh_mover_entry>(true, base, nbase, cur, ncur, first, nmetrics, by, arg, k, flags, stream, score_ms,
                                                  select_ms);
+}
+
+int lh_kept_top_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                       uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_top_entry *out, size_t *n_out)
+{
+    return kept_select_series(false, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, out, n_out);
+}
+
+int lh_kept_top_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                              uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_top_entry *d_out, uint32_t *d_n_out)
+{
+    return kept_select_series_device(false, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, d_out, d_n_out);
+}
+
+int lh_kept_movers_series(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                          uint32_t by, double arg, size_t k, uint32_t flags, void *stream, lh_mover_entry *out, size_t *n_out)
+{
+    return kept_select_series(true, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, out, n_out);
+}
+
+int lh_kept_movers_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                 size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                 lh_mover_entry *d_out, uint32_t *d_n_out)
+{
+    return kept_select_series_device(true, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, d_out, d_n_out);
+}
+
+int lh_tool_kept_top_series_passes_ms(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                      size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                      float *score_ms, float *select_ms)
+{
+    return kept_select_series_passes_ms<lh_top_entry>(false, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, score_ms,
+                                                      select_ms);
+}
+
+int lh_tool_kept_movers_series_passes_ms(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
+                                         size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
+                                         float *score_ms, float *select_ms)
+{
+    return kept_select_series_passes_ms<lh_mover_entry>(true, kept, nkept, win, nwin, first, nmetrics, by, arg, k, flags, stream, score_ms,
+                                                        select_ms);
+}
+
+int lh_tool_kept_select_bytes(uint64_t bytes, uint64_t *previous)
+{
+    const u64 old = g_select_bytes.exchange(bytes ? (u64)bytes : KEPT_SELECT_BYTES, std::memory_order_relaxed);
+    if (previous) *previous = old;
+    return LH_OK;
 }
 
 int lh_keep(lh_snapshot *s, uint32_t first, size_t nmetrics, uint32_t flags, lh_kept **out)

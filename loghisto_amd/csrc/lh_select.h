@@ -10,11 +10,14 @@
 //             whose order depends on timing; then a bitonic sort of the at most 1 024 winners by (key descending, index
 //             ascending) in LDS; then emit(i, t) for the winner i of every slot t, and n_out.  One total order: the result
 //             depends on neither timing nor launch shape.
+//   k_select_windows  the same body (select_block) with one workgroup per WINDOW of a call that selects in many at once: window w's
+//             records lie w * npad records into every field, its entries w * k entries into out, its count in n_out[w].
 // Both arrays are padded to whole groups of SEL_PER records (16-byte loads stay inside the block).
 //
 // Behind the kernels, the host side of "score pass, then k_select" (a new selecting reader starts there): SelectState,
-// select_check_args, select_records, select_pass, select_host_form and select_passes_ms.  The unit keeps its context type
-// with its own mutex, its record struct, its score kernel, its Emit and its enqueue.
+// select_check_args, select_records, select_pass, select_host_form and select_passes_ms; for a call of many windows,
+// select_windows_pass and select_windows_host_form.  The unit keeps its context type with its own mutex, its record struct,
+// its score kernel, its Emit and its enqueue.
 #pragma once
 
 #include "../../include/loghisto_gpu.h"
@@ -86,11 +89,12 @@ __device__ __forceinline__ void load_records(const u64 *__restrict__ key, const 
 // NO_SLOT) stay behind every record.
 __device__ __forceinline__ bool ahead(u64 ka, uint32_t ia, u64 kb, uint32_t ib) { return ka > kb || (ka == kb && ia < ib); }
 
-// key / cand: the n records (cand[i] == 0: record i is no candidate).  emit(i, t): winner i lands in slot t (t < *n_out =
-// min(k, candidates); slot 0 is the leader).  1 <= k <= LH_MAX_TOP.
+// (the whole workgroup of SEL_WG threads)  key / cand: the n records (cand[i] == 0: record i is no candidate).  emit(i, t): winner
+// i lands in slot t (t < *n_out = min(k, candidates); slot 0 is the leader).  1 <= k <= LH_MAX_TOP.  The body of k_select and of
+// k_select_windows: the LDS below is the kernel's that calls it.
 template <class Emit>
-__global__ __launch_bounds__(SEL_WG) void k_select(const u64 *__restrict__ key, const u64 *__restrict__ cand, uint32_t n, uint32_t k,
-                                                   const Emit emit, uint32_t *__restrict__ n_out)
+__device__ __forceinline__ void select_block(const u64 *__restrict__ key, const u64 *__restrict__ cand, uint32_t n, uint32_t k,
+                                             const Emit emit, uint32_t *__restrict__ n_out)
 {
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_part[SEL_WAVES];
@@ -220,6 +224,26 @@ __global__ __launch_bounds__(SEL_WG) void k_select(const u64 *__restrict__ key, 
     if (tid == 0) *n_out = nwin;
 }
 
+// ONE selection: one workgroup over the n records
+template <class Emit>
+__global__ __launch_bounds__(SEL_WG) void k_select(const u64 *__restrict__ key, const u64 *__restrict__ cand, uint32_t n, uint32_t k,
+                                                   const Emit emit, uint32_t *__restrict__ n_out)
+{
+    select_block(key, cand, n, k, emit, n_out);
+}
+
+// ONE SELECTION PER WINDOW (lh_kept_top_series* / lh_kept_movers_series*): workgroup w = blockIdx.x runs the same body over window
+// w's records, key + w * npad and cand + w * npad (npad: n padded to whole groups of SEL_PER, so every window's block starts on
+// 32 bytes), with the Emit advanced to that window -- its record fields by w * npad, its out by w * k -- and the count to
+// n_out[w].  The windows share nothing: no atomic and no order between them, and each keeps k_select's one total order.
+template <class Emit>
+__global__ __launch_bounds__(SEL_WG) void k_select_windows(const u64 *__restrict__ key, const u64 *__restrict__ cand, uint32_t n,
+                                                           uint32_t npad, uint32_t k, const Emit emit, uint32_t *__restrict__ n_out)
+{
+    const size_t at = (size_t)blockIdx.x * npad;
+    select_block(key + at, cand + at, n, k, emit.window(at, (size_t)blockIdx.x * k), n_out + blockIdx.x);
+}
+
 // ---- the records and the Emit of the two kinds of selection, each shared by the unit that scores snapshots and the one that
 // scores kept intervals (lh_top.hip / lh_movers.hip, lh_kept.hip): one array per field, each padded to whole groups of SEL_PER
 // (16-byte loads stay inside the block).
@@ -246,6 +270,11 @@ struct TopEmit {
         e.above = by == LH_TOP_BY_COUNT_ABOVE ? aux : 0;
         out[t] = e;
     }
+    // the Emit of the window whose records begin `at` records into every field and whose entries begin `to` entries into out
+    __device__ __forceinline__ TopEmit window(size_t at, size_t to) const
+    {
+        return TopEmit{TopRecords{r.key + at, r.count + at, r.sum + at, r.aux + at}, first, by, out + to};
+    }
 };
 
 constexpr u64 MOVER_CANDIDATE = 1ull << 32; // the candidate word of a row that is ranked; its low 32 bits: key << 16 | key_base
@@ -271,6 +300,11 @@ struct MoversEmit {
         e.count_b = r.count_b[i];
         e.score = __longlong_as_double((long long)r.score[i]);
         out[t] = e;
+    }
+    // (TopEmit::window's)
+    __device__ __forceinline__ MoversEmit window(size_t at, size_t to) const
+    {
+        return MoversEmit{MoversRecords{r.key + at, r.cand + at, r.count_a + at, r.count_b + at, r.score + at}, first, out + to};
     }
 };
 static_assert(sizeof(lh_top_entry) == 32 && sizeof(lh_mover_entry) == 32, "32-byte entries");
@@ -349,6 +383,28 @@ int select_pass(SelectState &ss, hipStream_t st, const u64 *key, const u64 *cand
     return ss.guard.record(st);
 }
 
+// (the context's mutex held; behind the unit's score launch over nwin windows' records)  select_pass' launch for a call of nwin
+// windows, window w's n records at w * npad, its entries at d_out + w * k (inside `emit`), its count at d_n_out[w].  The guard's
+// event is NOT recorded here: such a call runs chunk after chunk over one reused block, which stream order protects, and records
+// the guard behind the last one.
+template <class Emit>
+int select_windows_pass(hipStream_t st, const u64 *key, const u64 *cand, uint32_t n, uint32_t npad, uint32_t nwin, size_t k,
+                        const Emit &emit, uint32_t *d_n_out, hipEvent_t *ev)
+{
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(k_select_windows<Emit>, dim3(nwin), dim3(SEL_WG), 0, st, key, cand, n, npad, (uint32_t)k, emit, d_n_out);
+    LH_BESIDE_CHK(hipGetLastError());
+    if (ev) LH_BESIDE_CHK(hipEventRecord(ev[2], st));
+    return LH_OK;
+}
+
+// where the nwin counts lie behind nwin * k entries of a landing block, and what the two take together
+static inline size_t select_counts_at(size_t nwin, size_t k, size_t entry_bytes) { return nwin * k * entry_bytes; }
+static inline size_t select_landing_bytes(size_t nwin, size_t k, size_t entry_bytes)
+{
+    return select_counts_at(nwin, k, entry_bytes) + ((nwin * sizeof(uint32_t) + 7) & ~(size_t)7);
+}
+
 // (the context's mutex held) the host form's landing blocks: k entries, then n_out
 static inline int select_result_blocks(ResultBlocks &res, size_t need)
 {
@@ -379,13 +435,40 @@ int select_host_form(SelectState &ss, hipStream_t st, size_t k, Entry *out, size
     return LH_OK;
 }
 
-// (the context's mutex held)  lh_tool_*_passes_ms: both passes once, the results left in the unit's own block, with the
-// device time of each.  A failure before the times are read leaves score_ms / select_ms untouched.
+// (the context's mutex held, the wait included)  The host form of a call of nwin windows around the unit's enqueue(d_out, d_n_out)
+// -> status, which puts every pass on `st` and records the guard: nwin * k entries and nwin counts come back in ONE copy into the
+// unit's pinned block (at most LH_MAX_WINDOWS * LH_MAX_TOP entries of 32 bytes and 512 bytes of counts), and the first n_out[w]
+// entries of each window go on from there to out + w * k.  Nothing is written to the caller's arrays unless every count is sane.
 template <class Entry, class Enqueue>
-int select_passes_ms(SelectState &ss, hipStream_t st, size_t k, float *score_ms, float *select_ms, Enqueue enqueue)
+int select_windows_host_form(SelectState &ss, hipStream_t st, size_t nwin, size_t k, Entry *out, size_t *n_out, Enqueue enqueue)
 {
-    const size_t bytes = k * sizeof(Entry);
-    int rc = select_result_blocks(ss.res, bytes + 8);
+    const size_t counts_at = select_counts_at(nwin, k, sizeof(Entry)), bytes = select_landing_bytes(nwin, k, sizeof(Entry));
+    int rc = select_result_blocks(ss.res, bytes);
+    if (rc) return rc;
+    rc = enqueue(reinterpret_cast<Entry *>(ss.res.d_res), reinterpret_cast<uint32_t *>(ss.res.d_res + counts_at));
+    if (rc) return rc;
+    LH_BESIDE_CHK(hipMemcpyAsync(ss.res.h_res, ss.res.d_res, bytes, hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    ss.guard.covered(); // this call recorded the event on the stream it has just waited for
+    const uint32_t *h_n = reinterpret_cast<const uint32_t *>(ss.res.h_res + counts_at);
+    const Entry *h_out = reinterpret_cast<const Entry *>(ss.res.h_res);
+    for (size_t w = 0; w < nwin; w++)
+        if (h_n[w] > k) return LH_ESTATE;
+    for (size_t w = 0; w < nwin; w++) {
+        std::memcpy(out + w * k, h_out + w * k, (size_t)h_n[w] * sizeof(Entry));
+        n_out[w] = h_n[w];
+    }
+    return LH_OK;
+}
+
+// (the context's mutex held)  lh_tool_*_passes_ms: both passes once, the results left in the unit's own block, with the
+// device time of each.  A failure before the times are read leaves score_ms / select_ms untouched.  nwin: the windows of a
+// per-window call's chunk (k entries and a count each); 1 for the others.
+template <class Entry, class Enqueue>
+int select_passes_ms(SelectState &ss, hipStream_t st, size_t k, float *score_ms, float *select_ms, Enqueue enqueue, size_t nwin = 1)
+{
+    const size_t bytes = select_counts_at(nwin, k, sizeof(Entry));
+    int rc = select_result_blocks(ss.res, select_landing_bytes(nwin, k, sizeof(Entry)));
     if (rc) return rc;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < 3 && rc == LH_OK; i++)

@@ -573,11 +573,13 @@ class Snapshot:
                              N.TOP_ASCENDING if ascending else 0, nmetrics, first, out)
 
     @staticmethod
-    def _leaders(fn, handles, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out, stream=()):
+    def _leaders(fn, handles, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out, stream=(), nwin=None):
         """top / movers, of a Snapshot or of a Kept: the k leaders of [first, first+nmetrics) from library call `fn` (host form)
         or fn + "_device", whose arguments begin with `handles` (a snapshot's handle or two; a list of kept handles and its
-        length, or two) and -- the kept readers' -- have `stream` = (its handle,) in front of the outputs.  by_codes: the names
-        `by` takes -> the library's; takes_arg: those that need an arg; entry: the name of the entry dtype in N."""
+        length, or two; the per-window forms' list, length, windows and their number) and -- the kept readers' -- have `stream`
+        = (its handle,) in front of the outputs.  by_codes: the names `by` takes -> the library's; takes_arg: those that need an
+        arg; entry: the name of the entry dtype in N.  nwin: the windows of a per-window form, whose outputs hold nwin blocks of
+        k entries and nwin counts and whose host form returns a list of nwin arrays, window w's of length n_out[w]."""
         L = N.lib()
         if by not in by_codes:
             raise ValueError("by is one of " + ", ".join(by_codes))
@@ -586,21 +588,24 @@ class Snapshot:
                 raise ValueError(f"by={by!r} takes an arg")
             arg = 0.0
         dtype = getattr(N, entry)
+        blocks, per = (1, "") if nwin is None else (nwin, ", per window")
         lead = (*handles, first, nmetrics, by_codes[by], float(arg), k, flags, *stream)
         if isinstance(out, tuple):
             entries, n = out
-            for t, need in ((entries, k * dtype.itemsize), (n, 4)):
+            for t, need in ((entries, blocks * k * dtype.itemsize), (n, 4 * blocks)):
                 if not t.is_contiguous() or t.element_size() * int(t.numel()) < need:
-                    raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4")
+                    raise ValueError("device form: entries holds k * 32 contiguous bytes and n 4" + per)
             N.check(getattr(L, fn + "_device")(*lead, _ptr(entries), _ptr(n)), fn + "_device")
             return out
         if out is None:
-            out = np.zeros(max(k, 1), dtype=dtype)
-        elif not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size >= k and out.flags.c_contiguous):
-            raise ValueError(f"out holds at least k contiguous {entry} elements")
-        n = C.c_size_t(0)
+            out = np.zeros(max(blocks * k, 1), dtype=dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size >= blocks * k and out.flags.c_contiguous):
+            raise ValueError(f"out holds at least k contiguous {entry} elements" + per)
+        n = (C.c_size_t * max(blocks, 1))()
         N.check(getattr(L, fn)(*lead, out.ctypes.data, C.addressof(n)), fn)
-        return out.reshape(-1)[:n.value]
+        if nwin is None:
+            return out.reshape(-1)[:n[0]]
+        return [out.reshape(-1)[w * k:w * k + n[w]] for w in range(nwin)]
 
     # -- distribution shift against another snapshot (percentile()'s bucket walk, metrics.go:389-418, over two rows at once) --
     _COMPARE_OUT = _COMPARE_OUT
@@ -1015,6 +1020,38 @@ class Kept:
         return Snapshot._leaders("lh_kept_movers", (C.addressof(lists[0]), lists[1], C.addressof(lists[2]), lists[3]),
                                  Snapshot._MOVERS_BY, ("percentile",), "MOVER_ENTRY", k, by, arg,
                                  N.MOVERS_ASCENDING if ascending else 0, nmetrics, first, out, (_stream_handle(stream),))
+
+    # -- top and movers per WINDOW of the list, in one call (lh_kept_top_series* / lh_kept_movers_series*) ---------------------------
+    _TOP_SERIES, _MOVERS_SERIES = "lh_kept_top_series", "lh_kept_movers_series"
+
+    def _leaders_series(self, fn, make, windows, earlier, by_codes, takes_arg, entry, k, by, arg, flags, nmetrics, first, out, stream):
+        """The call of a per-window selecting reader through Snapshot._leaders: the list, the windows make(windows, nkept) gives."""
+        nmetrics, first = self._block(nmetrics, first)
+        handles, nkept = self._list(earlier)
+        win, nwin = make(windows, nkept)
+        return Snapshot._leaders(fn, (C.addressof(handles), nkept, C.addressof(win), nwin), by_codes, takes_arg, entry, k, by, arg,
+                                 flags, nmetrics, first, out, (_stream_handle(stream),), nwin)
+
+    def top_series(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False, earlier=(), windows=None,
+                   nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Kept.top per WINDOW of list(earlier) + [self], in one call (lh_kept_top_series*) -- which k names led in each of the
+        last 60 seconds: `windows` as for Kept.series ((lo, hi) pairs of list positions; None: one window per handle).  Returns a
+        list of nwin TOP_ENTRY arrays, window w's byte for byte what top() over the handles [lo, hi) returns, of its length.
+        out= follows Kept.top's forms: a numpy array of nwin * k TOP_ENTRY takes the host form (window w's entries at
+        out[w * k:], the returned arrays view it); an (entries, n) pair of torch device tensors, of nwin * k * 32 bytes and nwin
+        uint32, takes the device form on `stream` and is returned as it is."""
+        return self._leaders_series(self._TOP_SERIES, self._windows, windows, earlier, Snapshot._TOP_BY, ("percentile", "count_above"),
+                                    "TOP_ENTRY", k, by, arg, N.TOP_ASCENDING if ascending else 0, nmetrics, first, out, stream)
+
+    def movers_series(self, k: int, by: str = "ks", arg: Optional[float] = None, ascending: bool = False, earlier=(), windows=None,
+                      against=None, nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Kept.movers per WINDOW of list(earlier) + [self], in one call (lh_kept_movers_series*) -- which k names moved most in
+        each second against the minute before the deploy: `windows` / `against` exactly as Kept.drift takes them.  Returns a
+        list of nwin MOVER_ENTRY arrays, window w's byte for byte what movers() of the two slices returns (count_a: the base
+        slice).  out= as for Kept.top_series."""
+        return self._leaders_series(self._MOVERS_SERIES, self._drift_windows(against), windows, earlier, Snapshot._MOVERS_BY,
+                                    ("percentile",), "MOVER_ENTRY", k, by, arg, N.MOVERS_ASCENDING if ascending else 0, nmetrics,
+                                    first, out, stream)
 
     # -- save and load (lh_kept_save* / lh_kept_load*; loghisto_amd.keptfile has the blob's format in NumPy) ------------------------
     def _save_size(self) -> int:

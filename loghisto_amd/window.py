@@ -71,6 +71,19 @@ class KeptWindow:
         newest, earlier = self._newest_and_earlier()
         return newest.drift(windows, earlier, against, nmetrics, first, ids, out, stream)
 
+    def top_series(self, k: int, by: str = "count", arg: Optional[float] = None, ascending: bool = False, windows=None,
+                   nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Kept.top_series over self.handles, the oldest first: the k leaders of each window, `windows` as for series()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.top_series(k, by, arg, ascending, earlier, windows, nmetrics, first, out, stream)
+
+    def movers_series(self, k: int, by: str = "ks", arg: Optional[float] = None, ascending: bool = False, windows=None,
+                      against=None, nmetrics: Optional[int] = None, first: Optional[int] = None, out=None, stream=None):
+        """Kept.movers_series over self.handles, the oldest first: the k names that moved most in each window, `windows` /
+        `against` as for drift()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.movers_series(k, by, arg, ascending, earlier, windows, against, nmetrics, first, out, stream)
+
     def close(self):
         """Releases what the window made, its total; the intervals pushed stay usable and are the caller's to close."""
         if self.total is not None:
