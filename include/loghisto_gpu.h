@@ -913,7 +913,8 @@ int lh_kept_compare_ids_device(lh_kept *const *base, size_t nbase, lh_kept *cons
  *                     wrap past 2^64.  bounds is ONE HOST array of nb doubles shared by all names, which travels by value beside
  *                     the list of handles.  flags must be 0: LH_LE_PER_METRIC is NOT supported here and returns LH_EINVAL -- a
  *                     row of bounds per name would need a block in device memory guarded across streams, which is why the
- *                     list itself travels by value.  One walk of the row, over its occupied stretches only.
+ *                     list itself travels by value.  One walk of the row, over its occupied stretches only.  (A row of bounds
+ *                     per name over kept intervals is lh_kept_slo*, further down, which takes the rows as the ids are taken.)
  *                     Checked on the host before any handle is looked at -- LH_EINVAL: (ids forms: NULL ids with n > 0,
  *                     misaligned ids,) a NULL or misaligned list, nkept == 0 or > LH_MAX_KEPT, a NULL entry, nb == 0 or
  *                     nb > LH_MAX_BOUNDS, NULL bounds, both outputs NULL (either one may be), flags != 0, arrays not 8-byte
@@ -1190,6 +1191,81 @@ int lh_kept_movers_series(lh_kept *const *kept, size_t nkept, const uint32_t *wi
 int lh_kept_movers_series_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first,
                                  size_t nmetrics, uint32_t by, double arg, size_t k, uint32_t flags, void *stream,
                                  lh_mover_entry *d_out, uint32_t *d_n_out);
+/* PER-NAME BOUNDS AND BURN-RATE ALERTS OVER KEPT INTERVALS: lh_kept_slo*, lh_kept_burn*.  A real SLO has its own threshold per
+ * endpoint: lh_kept_slo* is lh_kept_heat* with a ROW OF BOUNDS PER ENTRY (lh_count_le's LH_LE_PER_METRIC layout), which the entry
+ * points above keep refusing; lh_kept_burn* is the multi-window burn-rate rule over one bound and one error budget per entry -- the
+ * names whose bad fraction exceeds rate x budget in the short window AND in the long one -- of which k records travel, not every
+ * name's counts.  Nothing is summed across names and no new statistic is defined: every count is one lh_kept_heat* returns.
+ *   THE PER-ENTRY ARRAYS are the ids' kind of argument.  A host form takes HOST arrays, checks them, copies them to the device on
+ *   `stream` (a pinned block and a device block of the unit's, under its mutex) and waits before it returns, after a failure too.
+ *   A device form takes DEVICE arrays, 8-byte aligned, on the handles' device, which the kernel reads behind `stream`; the host
+ *   never sees them, and the kernel is safe on any bytes: each bound is taken on its own, so a decreasing device row is simply
+ *   answered bound by bound, and a NaN bound takes in no bin and gives cum 0.
+ *   WINDOWS, rows, ids and `stream` exactly as for lh_kept_heat*; the whole list is the one window [0, nkept).
+ *   lh_kept_slo, lh_kept_slo_device, lh_kept_slo_ids, lh_kept_slo_ids_device
+ *     bounds is [n * nb] doubles, row m for entry m (row first + m, or ids[m]), 1 <= nb <= LH_MAX_BOUNDS; flags must be 0.
+ *     cum[(w * n + m) * nb + j] and total[w * n + m]; either may be NULL, not both.
+ *     CONTRACT -- this is the whole definition:
+ *     - Entry (w, m) of cum and total is byte for byte what lh_kept_heat_ids* writes for window w and the one row of entry m with
+ *       bounds + m * nb, nb.
+ *     - This holds in both kernel shapes, which agree exactly: only integers are involved.
+ *     - total is exact modulo 2^64, as lh_kept_heat*'s is, and so is cum.
+ *     - A DEVICE id outside some handle's block gives the empty entry in that window.
+ *     CHECKS on the host, before any handle is looked at, in lh_kept_heat*'s order.  LH_EINVAL: the ids, list and window rules;
+ *     nb == 0 or nb > LH_MAX_BOUNDS; NULL bounds; both outputs NULL; flags != 0; arrays not 8-byte aligned.  Then LH_ERANGE:
+ *     n > 0xffffffff, before a bound is read, as for lh_count_le (bounds holds n * nb doubles whatever the call returns, and no
+ *     caller has 2^32 rows of them).  Then n == 0 -> LH_OK with nothing written.  Then, host forms only, every row of bounds by
+ *     lh_count_le's rule -- LH_EINVAL for a NaN or a decreasing row (equal neighbours allowed; -0.0 == 0.0).  Then the handles, as
+ *     for lh_kept_heat*: LH_EINVAL for more than one device, LH_ERANGE for rows or HOST ids outside some listed handle's block.
+ *   lh_kept_burn, lh_kept_burn_device, lh_kept_burn_ids, lh_kept_burn_ids_device
+ *     rate[nwin]: HOST doubles in all forms, which travel by value like the windows.  bounds[n]: one bound per entry.  budget[n]:
+ *     the allowed bad fraction per entry, e.g. 0.001.  flags must be 0.  With cum and total as lh_kept_slo* defines them for nb = 1,
+ *     for window w and entry m:
+ *         bad   = total - cum
+ *         t     = rate[w] * budget[m]                              one rounded product
+ *         fires = total != 0 && (double)bad > t * (double)total    a second rounded product; strict
+ *     in IEEE doubles, the conversions the language's uint64 -> double, nothing contracted.  Entry m is REPORTED iff it fires in
+ *     EVERY window of the call.  out receives the records {entry = m, row = first + m or ids[m]} of the reported entries in
+ *     ascending m: the first min(*n_out, k) are written and the rest of out is left untouched; *n_out (uint64) is the number of
+ *     reported entries whatever k is; k == 0 with NULL out is a count-only call.  cum / total (optional, [nwin * n]) have exactly
+ *     lh_kept_slo*'s bytes for nb = 1.  Device forms take device pointers for out, n_out, cum and total; host forms bring the
+ *     records and the count back in one copy.  The result depends on neither timing nor the kernel shape: an entry that does not
+ *     fire adds 1 to an integer word of its m, and ONE workgroup then walks m in ascending order.
+ *     A NaN in a device budget never fires (the comparison is false); a device id outside a handle's block never fires (its total
+ *     is 0 there).  Firing is unspecified once a total has wrapped past 2^64; cum and total stay exact modulo 2^64.
+ *     CHECKS on the host, before any handle is looked at.  LH_EINVAL: the ids, list and window rules; flags != 0; NULL rate, bounds,
+ *     budget or n_out; k > 0 with NULL out; rate, bounds, budget, n_out, cum or total not 8-byte aligned, out not 4-byte aligned; a
+ *     NaN or negative rate (all forms).  Then LH_ERANGE: n > 0xffffffff, before a bound or a budget is read.  Then n == 0 -> LH_OK
+ *     with nothing written, n_out included.  Then, host forms only, LH_EINVAL for a NaN or negative budget or a NaN bound.  Then
+ *     the handles as above.  No output is written on any refusal.
+ *   ORDERING, hold and lifetime as for lh_kept_heat*: the work goes on `stream` under the unit's mutex; host forms are complete on
+ *   return; device forms return after enqueueing with ALL listed handles under one hold.  lh_kept_burn*'s n words of scratch come
+ *   from the records block of lh_kept_top*, guarded by the unit's event, and are zeroed on `stream`.  READ-ONLY.  The shape switch
+ *   (lh_tool_kept_switch) takes the ENTRIES of a call, nwin * n.
+ *   OUT OF SCOPE: sharing cell reads between overlapping windows; more than LH_MAX_KEPT handles a call; per-name bounds for
+ *   lh_kept_top*'s count-above; an OR or a per-pair rule across windows (make two calls); retuning the shape switch; any change to
+ *   the snapshot-side lh_count_le. */
+typedef struct { uint32_t entry, row; } lh_burn_hit;
+int lh_kept_slo(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_slo_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                       const double *d_bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_slo_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                    const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total);
+int lh_kept_slo_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                           const double *d_bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_burn(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                 const double *rate, const double *bounds, const double *budget, size_t k, uint32_t flags, void *stream,
+                 lh_burn_hit *out, uint64_t *n_out, uint64_t *cum, uint64_t *total);
+int lh_kept_burn_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                        const double *rate, const double *d_bounds, const double *d_budget, size_t k, uint32_t flags,
+                        void *stream, lh_burn_hit *d_out, uint64_t *d_n_out, uint64_t *d_cum, uint64_t *d_total);
+int lh_kept_burn_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                     const double *rate, const double *bounds, const double *budget, size_t k, uint32_t flags, void *stream,
+                     lh_burn_hit *out, uint64_t *n_out, uint64_t *cum, uint64_t *total);
+int lh_kept_burn_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                            const double *rate, const double *d_bounds, const double *d_budget, size_t k, uint32_t flags,
+                            void *stream, lh_burn_hit *d_out, uint64_t *d_n_out, uint64_t *d_cum, uint64_t *d_total);
 /* WIRE LINES FOR ANY PER-NAME COLUMNS: lh_names_*, lh_lines*.  The reference's serializers do not care where a key came from:
  *   GraphiteProtocol    /root/reference/graphite.go:37-48    formats every key -> float64 pair of the set
  *   OpenTSDBProtocol    /root/reference/opentsdb.go:45-58    likewise

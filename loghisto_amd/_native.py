@@ -161,8 +161,8 @@ class LhStats(C.Structure):
 
 
 def __getattr__(name):
-    """TOP_ENTRY / MOVER_ENTRY: lh_top_entry / lh_mover_entry (32 bytes each) as numpy dtypes, built on first use -- this
-    module itself needs ctypes only."""
+    """TOP_ENTRY / MOVER_ENTRY / BURN_HIT: lh_top_entry / lh_mover_entry (32 bytes each) and lh_burn_hit (8) as numpy dtypes, built on
+    first use -- this module itself needs ctypes only."""
     if name == "TOP_ENTRY":
         import numpy as np
         dt = np.dtype([("id", "<u4"), ("pkey", "<i2"), ("reserved", "<u2"), ("count", "<u8"), ("sum", "<f8"), ("above", "<u8")])
@@ -172,6 +172,11 @@ def __getattr__(name):
         import numpy as np
         dt = np.dtype([("id", "<u4"), ("key", "<i2"), ("key_base", "<i2"), ("count_a", "<u8"), ("count_b", "<u8"), ("score", "<f8")])
         globals()["MOVER_ENTRY"] = dt
+        return dt
+    if name == "BURN_HIT":                             # lh_burn_hit (8 bytes)
+        import numpy as np
+        dt = np.dtype([("entry", "<u4"), ("row", "<u4")])
+        globals()["BURN_HIT"] = dt
         return dt
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
@@ -314,6 +319,14 @@ SIGNATURES = {
     "lh_kept_heat_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_heat_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
     "lh_kept_heat_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_slo": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_slo_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_slo_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_slo_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp]),
+    "lh_kept_burn": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_burn_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_burn_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "lh_kept_burn_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_device": (C.c_int, [_vp, _sz, C.c_uint32, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_spread_ids": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

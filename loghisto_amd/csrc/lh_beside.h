@@ -11,7 +11,7 @@
 // What is here: the HIP error check, pointer tests, one context slot per (unit, device), the opener, growing blocks, the
 // way a host form's results travel back, the event that guards a block across streams, and the measurement switch's
 // exchange.  For the readers, which all walk rows [first, first + nmetrics) or a list of row ids (RowSel, rows_in; stage_ids
-// brings a host list to the device): their source record and its two-step opener
+// brings a host list to the device, stage_doubles per-entry host arrays of doubles): their source record and its two-step opener
 // (Source, source_cells, source_open), the same two steps for a reader of a list of snapshots (list_cells, list_open: two
 // for lh_compare.hip and lh_movers.hip, up to 16 for lh_across.hip) with the events that put the last snapshot's stream
 // behind the others' (order_behind), the launch shape (row_shape), the dispatch on the cells' width (with_cells) and the
@@ -337,6 +337,30 @@ inline int settle_ids(int rc, const RowSel &sel, hipStream_t st)
 {
     if (rc && sel.by_id && !sel.on_device && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
     return rc;
+}
+
+// Host arrays of doubles, one element or one row per entry, on their way to the kernel as stage_ids' list is: the unit's two grown
+// blocks (part of its context).
+struct DoubleBlocks {
+    double *h = nullptr, *d = nullptr; // the caller's arrays, copied (pinned); in HBM for the kernel
+    size_t h_cap = 0, d_cap = 0;
+};
+// (the context's mutex held)  What the kernel of a HOST form reads for the caller's arrays a[0 .. na) and b[0 .. nb) (b may be null
+// with nb == 0), which the call has checked: both copied into the pinned block before this returns, one behind the other, and from
+// there into HBM by ONE copy on `st`, ahead of the kernel.  The host form waits for `st` before it returns, after a failure too, so
+// the two blocks are free again when the mutex is.  A device form stages nothing: its kernel reads the caller's own device arrays.
+inline int stage_doubles(DoubleBlocks &blk, const double *a, size_t na, const double *b, size_t nb, hipStream_t st, const double *&d_a,
+                         const double *&d_b)
+{
+    int rc = grow_pinned(blk.h, blk.h_cap, na + nb, 1024);
+    if (!rc) rc = grow_device(blk.d, blk.d_cap, na + nb, 1024);
+    if (rc) return rc;
+    std::memcpy(blk.h, a, na * sizeof(double));
+    if (nb) std::memcpy(blk.h + na, b, nb * sizeof(double));
+    LH_BESIDE_CHK(hipMemcpyAsync(blk.d, blk.h, (na + nb) * sizeof(double), hipMemcpyHostToDevice, st));
+    d_a = blk.d;
+    d_b = blk.d + na;
+    return LH_OK;
 }
 
 // f(c): c the cells of row `first`, typed by their width (const uint32_t * or const unsigned long long *).  A generic

@@ -105,6 +105,19 @@
 // / k_kept_drift one window per blockIdx.y (KeptDriftWindows: four bytes a window, 512 bytes by value; at most LH_MAX_KEPT handles in
 // a window's two slices, which the host checks).  Window w's block is byte for byte the parent's output for the slice(s), floats
 // included, in both shapes: the same LDS, no scratch, wave 0 alone walking.  Top and movers per window stay out (a select per window).
+// A ROW OF BOUNDS PER ENTRY, lh_kept_slo* and lh_kept_burn*: the per-name thresholds k_kept_count_le refuses, as NEW entry points whose
+// rows are handled the way the id lists are -- a host form stages its host array on the call's stream (lh_beside.h's stage_doubles
+// beside stage_ids: a pinned block and a device block of KeptCtx) and waits before it returns, a device form reads the caller's own
+// device array -- so no block of the unit's outlives a call and nothing needs a guard.  count_le_entry takes its bounds through a
+// source type (SharedBounds: the by-value row of the two kernels above; RowBounds: lane j loads bounds[m * nb + j], one coalesced
+// load a wave), and its walk is count_le_walk, which hands lane j its count and every lane the total.  k_kept_slo is k_kept_heat
+// with RowBounds: entry (w, m) is byte for byte what lh_kept_heat_ids* writes for window w and the one row of entry m.  A device
+// array is any bytes: the lanes never look at each other's bound (a decreasing row is answered bound by bound), le_take gives a
+// NaN no bin.  lh_kept_burn*: one bound and one budget an entry, one rate a window (by value, KeptRates); k_kept_burn_score decides
+// fires = total != 0 && (double)(total - cum) > (rate[w] * budget[m]) * (double)total in lane 0 of the wave that owns entry (w, m)
+// and adds 1 to miss[m] when it does NOT (n words from SelectState's guarded block, zeroed on the call's stream: an integer sum,
+// whatever the order); k_kept_burn_emit, ONE workgroup in k_keep_scan's pattern, walks m ascending, writes the first k records
+// {entry, row} of the entries with miss == 0 and the count of all of them.  No result depends on timing or on the kernel shape.
 // A FAMILY'S TWO FORMS ARE ONE PATH.  On the device each of the eight kernels is its `__shared__` tile, the start every kernel of
 // a call's entries has (Seat::take: the bound check, the tile clear; Seat::row: ids[m] or first + m) and the family's entry function,
 // handed the whole list or the window of blockIdx.y (KeptWindows::slice, KeptDriftWindows::slices, window_entry); the two score
@@ -1025,6 +1038,18 @@ static_assert(sizeof(KeptList) + sizeof(KeptDriftWindows) + sizeof(MoversRecords
 // ---- lh_kept_count_le ---------------------------------------------------------------------------------------------------------
 // the bounds, shared by all names, by value in the kernel arguments (512 bytes beside the list's 1 544)
 struct KeptBounds { double b[LH_MAX_BOUNDS]; };
+// Where count_le_entry's lane j < nb takes bound j of entry m from: the one shared row above (k_kept_count_le, k_kept_heat), or row m
+// of a device array of nb doubles an entry, the caller's own or the staged copy of a host form (k_kept_slo, k_kept_burn_score: one
+// coalesced load a wave).  Nothing is assumed of a row: every lane takes its bound on its own, and le_take gives a NaN no bin.
+struct SharedBounds {
+    const KeptBounds &sb;
+    __device__ __forceinline__ double of(uint32_t lane, uint32_t) const { return sb.b[lane]; }
+};
+struct RowBounds {
+    const double *__restrict__ rows;
+    uint32_t m;
+    __device__ __forceinline__ double of(uint32_t lane, uint32_t nb) const { return rows[(size_t)m * nb + lane]; }
+};
 
 // Rows as in k_kept_across.  One turn over the row with k_count_le_wave's step: lane j owns bound j, which takes in the first
 // E = le_take(bounds[j]) bins, and the prefix at bin E - 1 is fetched from the lane that owns it only in a step some pending
@@ -1032,19 +1057,21 @@ struct KeptBounds { double b[LH_MAX_BOUNDS]; };
 // tile or in a stretch no tile covers, and takes the running carry; one beyond the last step takes everything.  total is the
 // wrapping sum of the handles' row_count entries: no cell is read for it (and the row is walked whatever it is: cells whose
 // sum wraps to 0 still count towards cum).  Integer sums only: the two shapes agree exactly.
-// (every wave that shares the tile, which is zero)  Entry e of the outputs: row r over the handles of `win` (across_entry's open)
-template <int NW>
-__device__ __forceinline__ void count_le_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
-                                               const KeptBounds &sb, uint32_t nb, u64 *__restrict__ cum, u64 *__restrict__ total)
+// (every wave that shares the tile, which is zero)  Row r over the handles of `win` (across_entry's open) against the bounds `from`
+// hands out: in wave 0 of those that share the tile, lane j < nb returns what bound j takes in, and every lane has the row's total
+// in `tot`.
+template <int NW, class Bounds>
+__device__ __forceinline__ u64 count_le_walk(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, const Bounds &from,
+                                             uint32_t nb, u64 &tot)
 {
     const uint32_t lane = at.lane;
     Row row;
     if (lane < win.len) row.open(s.h[win.lo + lane], r);
     row.settle();
-    const u64 tot = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    tot = readlane_u64(wave_scan_incl_u64(row.rc), 63);
 
     uint32_t E = 0;
-    if (lane < nb) E = le_take(sb.b[lane]);
+    if (lane < nb) E = le_take(from.of(lane, nb));
     bool pend = lane < nb && E > 0; // a bound that takes in no bin: 0
     u64 res = 0, carry = 0;
     turns<NW>(row, win.len, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
@@ -1067,10 +1094,18 @@ __device__ __forceinline__ void count_le_entry(const Seat<NW> &at, const KeptLis
         }
         carry += readlane_u64(inc, 63);
     });
+    return pend ? carry : res; // beyond the last step: everything
+}
+// Entry e of the outputs from that walk
+template <int NW, class Bounds>
+__device__ __forceinline__ void count_le_entry(const Seat<NW> &at, const KeptList &s, const Slice win, uint32_t r, size_t e,
+                                               const Bounds &from, uint32_t nb, u64 *__restrict__ cum, u64 *__restrict__ total)
+{
+    u64 tot;
+    const u64 res = count_le_walk<NW>(at, s, win, r, from, nb, tot);
     if (at.w != 0) return;
-    if (pend) res = carry; // beyond the last step: everything
-    if (cum && lane < nb) cum[e * nb + lane] = res;
-    if (total && lane == 0) total[e] = tot;
+    if (cum && at.lane < nb) cum[e * nb + at.lane] = res;
+    if (total && at.lane == 0) total[e] = tot;
 }
 
 // lh_kept_count_le*: the entry over the whole list (lane i opens handle i)
@@ -1083,7 +1118,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_count_le(cons
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
     if (!at.take(nmetrics)) return;
-    count_le_entry<NW>(at, s, Slice{0, s.n}, at.template row<IDS>(first, ids), at.m, sb, nb, cum, total);
+    count_le_entry<NW>(at, s, Slice{0, s.n}, at.template row<IDS>(first, ids), at.m, SharedBounds{sb}, nb, cum, total);
 }
 
 // lh_kept_heat*: the same entry per WINDOW of the list
@@ -1097,10 +1132,95 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_heat(const Ke
     const Seat<NW> at(s_tile);
     if (!at.take(nmetrics)) return;
     const uint32_t r = at.template row<IDS>(first, ids);
-    count_le_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), sb, nb, cum, total);
+    count_le_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), SharedBounds{sb}, nb, cum, total);
 }
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(KeptBounds) + 6 * 8 < 4096,
               "k_kept_heat's arguments inside the 4 KiB argument segment");
+
+// ---- lh_kept_slo / lh_kept_burn: a row of bounds PER ENTRY ----------------------------------------------------------------------
+// lh_kept_slo*: k_kept_heat's entry with row m of `bounds` ([nmetrics * nb] doubles in device memory) in the shared row's place: lane
+// j < nb loads bounds[m * nb + j], one coalesced load a wave.  The array may be the caller's own, which no host has seen: a row
+// that decreases is answered bound by bound (the lanes of count_le_walk never look at each other's bound) and a NaN takes in no bin.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_slo(const KeptList s, const KeptWindows sw, uint32_t nmetrics,
+                                                                       uint32_t first, const double *__restrict__ bounds, uint32_t nb,
+                                                                       u64 *__restrict__ cum, u64 *__restrict__ total,
+                                                                       const uint32_t *__restrict__ ids)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    count_le_entry<NW>(at, s, sw.slice(), r, window_entry(at.m, nmetrics), RowBounds{bounds, at.m}, nb, cum, total);
+}
+
+// The rates of lh_kept_burn*, one per window, by value beside the list and the windows (1 KiB)
+struct KeptRates { double r[LH_MAX_WINDOWS]; };
+// lh_kept_burn*, pass 1: k_kept_slo's entry with ONE bound an entry, decided where it is known -- lane 0 of the wave that owns entry
+// (w, m): bad = total - cum, t = rate[w] * budget[m], fires = total != 0 && (double)bad > t * (double)total; two rounded products
+// (the unit is built with -ffp-contract=off), a strict compare that a NaN fails.  An entry that does NOT fire adds 1 to miss[m]
+// (zero before the launch): an integer sum, whatever the order of the windows' workgroups.  cum / total (may be null) as k_kept_slo's.
+template <bool IDS, int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_burn_score(const KeptList s, const KeptWindows sw, const KeptRates rates,
+                                                                              uint32_t nmetrics, uint32_t first,
+                                                                              const double *__restrict__ bounds,
+                                                                              const double *__restrict__ budget, u64 *__restrict__ cum,
+                                                                              u64 *__restrict__ total, const uint32_t *__restrict__ ids,
+                                                                              uint32_t *__restrict__ miss)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    const Seat<NW> at(s_tile);
+    if (!at.take(nmetrics)) return;
+    const uint32_t r = at.template row<IDS>(first, ids);
+    u64 tot;
+    const u64 res = count_le_walk<NW>(at, s, sw.slice(), r, RowBounds{bounds, at.m}, 1u, tot);
+    if (at.w != 0 || at.lane != 0) return;
+    const size_t e = window_entry(at.m, nmetrics);
+    if (cum) cum[e] = res;
+    if (total) total[e] = tot;
+    const u64 bad = tot - res;
+    const double t = rates.r[blockIdx.y] * budget[at.m];
+    const bool fires = tot != 0 && (double)bad > t * (double)tot;
+    if (!fires) atomicAdd(&miss[at.m], 1u);
+}
+static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(KeptRates) + 8 * 8 < 4096,
+              "k_kept_burn_score's arguments inside the 4 KiB argument segment");
+
+// lh_kept_burn*, pass 2, ONE workgroup in k_keep_scan's pattern: the entries with miss[m] == 0 -- they fired in every window -- in
+// ascending m, WG at a time; entry m's place is the number of reported entries below it, the first k of them are written as {m, its
+// row} and *n_out is the number of all of them.  Nothing of out at or beyond min(*n_out, k) is written.
+template <bool IDS>
+__global__ __launch_bounds__(WG) void k_kept_burn_emit(const uint32_t *__restrict__ miss, uint32_t nmetrics, uint32_t first,
+                                                       const uint32_t *__restrict__ ids, u64 k, lh_burn_hit *__restrict__ out,
+                                                       u64 *__restrict__ n_out)
+{
+    __shared__ uint32_t s_w[WG_WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry = 0;
+    for (u64 base = 0; base < nmetrics; base += WG) { // uniform
+        const u64 i = base + threadIdx.x;
+        const bool hit = i < nmetrics && miss[i] == 0;
+        const uint32_t inc = wave_scan_incl_u32(hit ? 1u : 0u);
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        uint32_t below = 0, all = 0;
+        for (uint32_t j = 0; j < (uint32_t)WG_WAVES; j++) {
+            const uint32_t t = s_w[j];
+            below += j < wave ? t : 0;
+            all += t;
+        }
+        const u64 pos = carry + below + inc - 1;
+        if (hit && pos < k) {
+            lh_burn_hit h;
+            h.entry = (uint32_t)i;
+            h.row = IDS ? ids[i] : first + (uint32_t)i;
+            out[pos] = h;
+        }
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *n_out = carry;
+}
 
 // ---- lh_kept_spread -----------------------------------------------------------------------------------------------------------
 // Rows as in k_kept_across.  lh_spread's two walks as TWO turns over the same row (the turns advance the cursors: the opened
@@ -1320,6 +1440,7 @@ struct KeptCtx {
     size_t totals_cap = 0;
     ResultBlocks res;          // host forms
     IdBlocks ids;              // host form of lh_kept_across_ids
+    DoubleBlocks bounds;       // host forms of lh_kept_slo* / lh_kept_burn*: the per-entry bounds (and budgets), staged as the ids are
     CallEvent *pool = nullptr; // events no handle points to
     u64 holds = 0;
     SelectState sel;           // lh_kept_top* / lh_kept_movers*: ONE records block, sized for the kind with more fields (calls take
@@ -1783,6 +1904,162 @@ int kept_count_le(lh_kept *const *kept, size_t nkept, const Windows &w, const Ro
         [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays
             const HostOut out[2] = {{cum, entries * nb * sizeof(u64)}, {total, entries * sizeof(u64)}};
             return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) { return work(cx, st, dev[0], dev[1]); });
+        });
+}
+
+// ---- lh_kept_slo* / lh_kept_burn*: lh_kept_heat* with bounds PER ENTRY, and the alert over them.  Per-window forms only (the whole
+// list is the one window [0, nkept)), so `w` is always given.  The per-entry arrays are the ids' kind of argument: a host form's are
+// checked here and staged on the call's stream (stage_doubles), a device form's are the caller's own device arrays, which the host
+// never sees and the kernels take as any bytes.
+// (cx->mu held, the device current)  what the kernels read for a[0 .. na) and b[0 .. nb)
+int entry_doubles(KeptCtx *cx, bool device_form, const double *a, size_t na, const double *b, size_t nb, hipStream_t st,
+                  const double *&d_a, const double *&d_b)
+{
+    if (!device_form) return stage_doubles(cx->bounds, a, na, b, nb, st, d_a, d_b);
+    d_a = a;
+    d_b = b;
+    return LH_OK;
+}
+
+// (cx->mu held, the device current) enqueue_count_le's per-window walks with row m of `bounds` for entry m
+int enqueue_slo(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics,
+                const double *bounds, size_t nb, bool device_form, u64 *d_cum, u64 *d_total, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const double *rows = nullptr, *none = nullptr;
+    int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (!rc) rc = entry_doubles(cx, device_form, bounds, nmetrics * nb, nullptr, 0, st, rows, none);
+    if (rc) return rc;
+    const KeptList s = list_of(kept, nkept);
+    const KeptWindows sw = windows_of(w.win, w.n);
+    const uint32_t M = (uint32_t)nmetrics, NB = (uint32_t)nb;
+    return launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+        hipLaunchKernelGGL((k_kept_slo<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, M, sel.first, rows,
+                           NB, d_cum, d_total, ids);
+    });
+}
+
+int kept_slo(lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const double *bounds, size_t nb,
+             uint32_t flags, void *stream, uint64_t *cum, uint64_t *total, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device, lh_kept_heat*'s in its order
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(w.win, w.n, nkept)) return LH_EINVAL;
+    if (nb == 0 || nb > LH_MAX_BOUNDS || !bounds || (!cum && !total) || flags != 0) return LH_EINVAL;
+    if (misaligned(bounds, 8) || misaligned(cum, 8) || misaligned(total, 8)) return LH_EINVAL;
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32): not a row of bounds is read (as lh_count_le)
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at
+    if (!device_form)                             // a host array's rows, each by lh_count_le's rule, still before any handle
+        for (size_t m = 0; m < nmetrics; m++)
+            if (bad_bounds(bounds + m * nb, nb)) return LH_EINVAL;
+    const size_t entries = w.entries(nmetrics);
+    const auto work = [&](KeptCtx *cx, hipStream_t st, void *d_cum, void *d_total) {
+        return enqueue_slo(cx, kept, nkept, w, sel, nmetrics, bounds, nb, device_form, static_cast<u64 *>(d_cum),
+                           static_cast<u64 *>(d_total), st);
+    };
+    return run(
+        kept, nkept, DEVICE_THEN_ROWS, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return work(cx, st, cum, total); },
+        [&](KeptCtx *cx, hipStream_t st) { // results to HBM, then back to the caller's arrays; the wait frees the staged bounds too
+            const HostOut out[2] = {{cum, entries * nb * sizeof(u64)}, {total, entries * sizeof(u64)}};
+            return host_results(cx->res, st, out, [&](unsigned char *const(&dev)[2]) { return work(cx, st, dev[0], dev[1]); });
+        });
+}
+
+// What an lh_kept_burn* call is given beside its list, windows and rows; the four outputs are the caller's (a device form's: device
+// pointers) or, handed to enqueue_burn by the host form, places in the unit's result block.
+struct BurnCall {
+    const double *rate, *bounds, *budget;
+    size_t k;
+    lh_burn_hit *out;
+    uint64_t *n_out, *cum, *total;
+};
+
+// (cx->mu held, the device current)  Both passes on `st`: the n words "windows in which entry m did not fire" come from SelectState's
+// guarded block (asked for in records of the movers' five fields, as every user of the block asks) and are zeroed on `st`; the
+// score pass, one window per blockIdx.y in the reader's two shapes; one ordered workgroup that writes the records and the count;
+// the guard's event behind it, after a failure too.
+int enqueue_burn(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const BurnCall &c,
+                 bool device_form, hipStream_t st)
+{
+    const uint32_t *ids = nullptr;
+    const double *bounds = nullptr, *budget = nullptr;
+    u64 *base = nullptr;
+    size_t npad = 0;
+    int rc = stage_ids(cx->ids, sel, nmetrics, st, ids);
+    if (!rc) rc = entry_doubles(cx, device_form, c.bounds, nmetrics, c.budget, nmetrics, st, bounds, budget);
+    const size_t words_per_record = MOVERS_FIELDS * sizeof(u64) / sizeof(uint32_t);
+    if (!rc) rc = select_records(cx->sel, st, (nmetrics + words_per_record - 1) / words_per_record, MOVERS_FIELDS, base, npad);
+    if (rc) return rc;
+    uint32_t *miss = reinterpret_cast<uint32_t *>(base);
+    const KeptList s = list_of(kept, nkept);
+    const KeptWindows sw = windows_of(w.win, w.n);
+    KeptRates rates;
+    for (size_t i = 0; i < LH_MAX_WINDOWS; i++) rates.r[i] = i < w.n ? c.rate[i] : 0.0;
+    const uint32_t M = (uint32_t)nmetrics;
+    const u64 K = c.k;
+    u64 *d_cum = reinterpret_cast<u64 *>(c.cum), *d_total = reinterpret_cast<u64 *>(c.total), *d_n_out = reinterpret_cast<u64 *>(c.n_out);
+    rc = hipMemsetAsync(miss, 0, nmetrics * sizeof(uint32_t), st) == hipSuccess ? LH_OK : LH_EDEVICE;
+    if (!rc)
+        rc = launch_windows(M, (uint32_t)w.n, sel.by_id, [&](const RowShape &sh, auto by_id, auto nw) {
+            hipLaunchKernelGGL((k_kept_burn_score<decltype(by_id)::value, decltype(nw)::value>), sh.grid, sh.block, 0, st, s, sw, rates, M,
+                               sel.first, bounds, budget, d_cum, d_total, ids, miss);
+        });
+    if (!rc) {
+        if (sel.by_id) hipLaunchKernelGGL(k_kept_burn_emit<true>, dim3(1), dim3(WG), 0, st, miss, M, sel.first, ids, K, c.out, d_n_out);
+        else hipLaunchKernelGGL(k_kept_burn_emit<false>, dim3(1), dim3(WG), 0, st, miss, M, sel.first, ids, K, c.out, d_n_out);
+        if (hipGetLastError() != hipSuccess) rc = LH_EDEVICE;
+    }
+    if (rc == LH_EDEVICE) (void)hipGetLastError();
+    const int rg = cx->sel.guard.record(st); // what was enqueued uses the block
+    return rc ? rc : rg;
+}
+
+int kept_burn(lh_kept *const *kept, size_t nkept, const Windows &w, const RowSel &sel, size_t nmetrics, const BurnCall &c, uint32_t flags,
+              void *stream, bool device_form)
+{
+    // ---- every check that needs neither a handle nor a device: the ids', the list's and the windows' as lh_kept_heat* has them
+    if (bad_ids(sel, nmetrics) || bad_list(kept, nkept, LH_MAX_KEPT) || bad_windows(w.win, w.n, nkept)) return LH_EINVAL;
+    if (flags != 0 || !c.rate || !c.bounds || !c.budget || !c.n_out || (c.k > 0 && !c.out)) return LH_EINVAL;
+    if (misaligned(c.rate, 8) || misaligned(c.bounds, 8) || misaligned(c.budget, 8) || misaligned(c.out, 4) || misaligned(c.n_out, 8) ||
+        misaligned(c.cum, 8) || misaligned(c.total, 8))
+        return LH_EINVAL;
+    for (size_t i = 0; i < w.n; i++)
+        if (!(c.rate[i] >= 0.0)) return LH_EINVAL; // a NaN too
+    if (nmetrics > 0xffffffffu) return LH_ERANGE; // beyond any max_metrics (uint32): not a bound or a budget is read
+    if (nmetrics == 0) return LH_OK;              // before any handle is looked at; nothing is written
+    if (!device_form)                             // the host arrays, still before any handle
+        for (size_t m = 0; m < nmetrics; m++)
+            if (!(c.budget[m] >= 0.0) || c.bounds[m] != c.bounds[m]) return LH_EINVAL;
+    return run(
+        kept, nkept, DEVICE_THEN_ROWS, sel, nmetrics, stream, device_form,
+        [&](KeptCtx *cx, hipStream_t st) { return enqueue_burn(cx, kept, nkept, w, sel, nmetrics, c, true, st); },
+        [&](KeptCtx *cx, hipStream_t st) -> int {
+            // the count and the records that can be written, min(k, n), lie first in the result block and come back in ONE copy with
+            // whatever of cum / total was asked for; the first min(*n_out, k) records go on to the caller
+            const size_t kk = std::min(c.k, nmetrics), head = sizeof(u64) + kk * sizeof(lh_burn_hit);
+            const size_t block = w.entries(nmetrics) * sizeof(u64), at_total = head + (c.cum ? block : 0);
+            const size_t need = at_total + (c.total ? block : 0);
+            int rc = select_result_blocks(cx->res, need);
+            if (rc) return rc;
+            unsigned char *d = cx->res.d_res, *h = cx->res.h_res;
+            BurnCall dev = c;
+            dev.n_out = reinterpret_cast<uint64_t *>(d);
+            dev.out = reinterpret_cast<lh_burn_hit *>(d + sizeof(u64));
+            dev.cum = c.cum ? reinterpret_cast<uint64_t *>(d + head) : nullptr;
+            dev.total = c.total ? reinterpret_cast<uint64_t *>(d + at_total) : nullptr;
+            rc = enqueue_burn(cx, kept, nkept, w, sel, nmetrics, dev, false, st);
+            if (rc) return rc;
+            LH_BESIDE_CHK(hipMemcpyAsync(h, d, need, hipMemcpyDeviceToHost, st));
+            LH_BESIDE_CHK(hipStreamSynchronize(st));
+            cx->sel.guard.covered(); // this call recorded the event on the stream it has just waited for
+            u64 n = 0;
+            std::memcpy(&n, h, sizeof n);
+            if (n > nmetrics) return LH_ESTATE;
+            if (c.out) std::memcpy(c.out, h + sizeof(u64), (size_t)std::min<u64>(n, kk) * sizeof(lh_burn_hit));
+            if (c.cum) std::memcpy(c.cum, h + head, block);
+            if (c.total) std::memcpy(c.total, h + at_total, block);
+            *c.n_out = n;
+            return LH_OK;
         });
 }
 
@@ -2876,6 +3153,62 @@ int lh_kept_heat_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *
 {
     return kept_count_le(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, bounds, nb, flags, stream, d_cum, d_total,
                          true);
+}
+
+int lh_kept_slo(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_slo(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_slo_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                       const double *d_bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_slo(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics, d_bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_slo_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                    const double *bounds, size_t nb, uint32_t flags, void *stream, uint64_t *cum, uint64_t *total)
+{
+    return kept_slo(kept, nkept, Windows{true, win, nwin}, rows_by_id(ids, false), n, bounds, nb, flags, stream, cum, total, false);
+}
+
+int lh_kept_slo_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                           const double *d_bounds, size_t nb, uint32_t flags, void *stream, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_slo(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n, d_bounds, nb, flags, stream, d_cum, d_total, true);
+}
+
+int lh_kept_burn(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                 const double *rate, const double *bounds, const double *budget, size_t k, uint32_t flags, void *stream,
+                 lh_burn_hit *out, uint64_t *n_out, uint64_t *cum, uint64_t *total)
+{
+    return kept_burn(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics,
+                     BurnCall{rate, bounds, budget, k, out, n_out, cum, total}, flags, stream, false);
+}
+
+int lh_kept_burn_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, uint32_t first, size_t nmetrics,
+                        const double *rate, const double *d_bounds, const double *d_budget, size_t k, uint32_t flags, void *stream,
+                        lh_burn_hit *d_out, uint64_t *d_n_out, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_burn(kept, nkept, Windows{true, win, nwin}, rows_from(first), nmetrics,
+                     BurnCall{rate, d_bounds, d_budget, k, d_out, d_n_out, d_cum, d_total}, flags, stream, true);
+}
+
+int lh_kept_burn_ids(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *ids, size_t n,
+                     const double *rate, const double *bounds, const double *budget, size_t k, uint32_t flags, void *stream,
+                     lh_burn_hit *out, uint64_t *n_out, uint64_t *cum, uint64_t *total)
+{
+    return kept_burn(kept, nkept, Windows{true, win, nwin}, rows_by_id(ids, false), n,
+                     BurnCall{rate, bounds, budget, k, out, n_out, cum, total}, flags, stream, false);
+}
+
+int lh_kept_burn_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t *win, size_t nwin, const uint32_t *d_ids, size_t n,
+                            const double *rate, const double *d_bounds, const double *d_budget, size_t k, uint32_t flags, void *stream,
+                            lh_burn_hit *d_out, uint64_t *d_n_out, uint64_t *d_cum, uint64_t *d_total)
+{
+    return kept_burn(kept, nkept, Windows{true, win, nwin}, rows_by_id(d_ids, true), n,
+                     BurnCall{rate, d_bounds, d_budget, k, d_out, d_n_out, d_cum, d_total}, flags, stream, true);
 }
 
 int lh_kept_spread(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, const double *p, size_t np, uint32_t flags,

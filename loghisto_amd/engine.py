@@ -946,6 +946,97 @@ class Kept:
         tail = (b.ctypes.data, int(b.size), 0, _stream_handle(stream))
         return self._windowed("lh_kept_heat", earlier, windows, nmetrics, first, ids, tail, _KEPT_COUNT_LE_OUT, int(b.size), out)
 
+    # -- bounds PER NAME per window, and the burn-rate alert over them (lh_kept_slo* / lh_kept_burn*) --------------------------------
+    def _entries(self, nmetrics, first, ids):
+        """the entries of a call: len(ids), or nmetrics (None: up to the end of this handle's block)"""
+        if ids is not None:
+            return int(ids.numel()) if hasattr(ids, "numel") else int(np.asarray(ids).size)
+        return self._block(nmetrics, first)[0]
+
+    @staticmethod
+    def _per_entry(arrays, n, width_of):
+        """The per-entry float64 arrays of slo / burn, name -> array, n entries each -> (what keeps them alive, their addresses,
+        the trailing width of the first, device arrays?).  Torch device tensors are handed over as they are (all of them or none),
+        anything else becomes a contiguous float64 host array.  width_of(shape) -> the elements an entry has, or None: refused."""
+        device = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in arrays.values()]
+        if any(device) != all(device):
+            raise ValueError(" and ".join(arrays) + " are device tensors or host arrays, not both")
+        keep, widths = [], []
+        for name, a in arrays.items():
+            if not device[0]:
+                a = np.ascontiguousarray(a.numpy() if hasattr(a, "data_ptr") else a, dtype=np.float64)
+            elif a.element_size() != 8 or not a.is_floating_point() or not a.is_contiguous():
+                raise ValueError(f"device {name} are contiguous float64")
+            width = width_of(tuple(a.shape))
+            if width is None or (len(a.shape) and int(a.shape[0]) != n) or (not len(a.shape)):
+                raise ValueError(f"{name} holds one entry per name: {n}")
+            keep.append(a)
+            widths.append(width)
+        return keep, [_ptr(a) for a in keep], widths[0], device[0]
+
+    def slo(self, bounds, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
+            stream=None):
+        """Kept.heat with a row of bounds PER NAME, in one call (lh_kept_slo*) -- every endpoint's own SLO threshold over each
+        window of the history: `bounds` has shape (n,) or (n, nb), row m for metric first + m or ids[m].  Returns
+        dict(cum=uint64[nwin, n, nb], total=uint64[nwin, n]), entry (w, m) byte for byte what heat(ids=[id of m], bounds=row m)
+        returns for window w.  Host rows are non-decreasing and free of NaN.  A torch device tensor for `bounds` takes the device
+        form, which goes with an out= of device tensors (and device ids, if any): a device row is answered bound by bound, a NaN
+        takes in nothing.  windows, nmetrics, first, ids, out= and stream as for Kept.heat."""
+        n = self._entries(nmetrics, first, ids)
+        keep, (addr,), nb, device = self._per_entry({"bounds": bounds}, n, lambda s: 1 if len(s) == 1 else s[1] if len(s) == 2 else None)
+        if device and out is None:
+            raise ValueError("device bounds go with an out= of device tensors")
+        if out is not None and device != any(getattr(t, "is_cuda", False) for t in out.values()):
+            raise ValueError("bounds and out are both on the device or both on the host")
+        tail = (addr, nb, 0, _stream_handle(stream))
+        return self._windowed("lh_kept_slo", earlier, windows, nmetrics, first, ids, tail, _KEPT_COUNT_LE_OUT, nb, out)
+
+    def burn(self, bounds, budget, rates, k: int, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0,
+             ids=None, counts: bool = False, out=None, stream=None):
+        """The multi-window burn-rate alert over kept intervals (lh_kept_burn*): the names whose bad fraction -- the samples above
+        their own bound, `bounds[m]`, over all their samples -- exceeds rates[w] * budget[m] in EVERY window w of the call
+        (loghisto_amd.burn_fires is the rule; strictly above, a name with no sample in a window does not fire).  `windows` as for
+        Kept.series, `rates` one per window.  Returns dict(entry=uint32[min(n, k)], row=uint32[...], n=int): the reported entries
+        in ascending m -- entry m, row its metric id -- the first k of them, and how many there are whatever k is (k=0 only
+        counts).  counts=True adds cum=uint64[nwin, n] and total=uint64[nwin, n], Kept.slo's for the one bound a name.
+        Torch device tensors for `bounds` and `budget` take the device form, enqueued on `stream`: out= is then a dict of device
+        tensors -- hits (at least k * 8 bytes), n (8 bytes), and optionally cum and total (nwin * n * 8 bytes each) -- which is
+        returned as it is; device ids go with it."""
+        L = N.lib()
+        k = int(k)
+        n = self._entries(nmetrics, first, ids)
+        keep, (b_addr, g_addr), _, device = self._per_entry({"bounds": bounds, "budget": budget}, n, lambda s: 1 if len(s) == 1 else None)
+        handles, nkept = self._list(earlier)
+        win, nwin = self._windows(windows, nkept)
+        r = np.ascontiguousarray(rates, dtype=np.float64).ravel()
+        if int(r.size) != nwin:
+            raise ValueError(f"rates holds one rate per window: {nwin}")
+        alive, fn, rows, n, device_ids = self._list_rows((handles, nkept, win, nwin), "lh_kept_burn", nmetrics, first, ids)
+        if device_ids is not None and device_ids != device:
+            raise ValueError("ids, bounds and budget are all on the device or all on the host")
+        lead = (*rows, r.ctypes.data, b_addr, g_addr, k, 0, _stream_handle(stream))
+        if device:
+            if not isinstance(out, dict) or set(out) - {"hits", "n", "cum", "total"} or "n" not in out or (k and "hits" not in out):
+                raise ValueError("device form: out holds device tensors hits, n and optionally cum, total")
+            need = {"hits": k * 8, "n": 8, "cum": nwin * n * 8, "total": nwin * n * 8}
+            for key, t in out.items():
+                if not getattr(t, "is_cuda", False) or not t.is_contiguous() or t.element_size() * int(t.numel()) < need[key]:
+                    raise ValueError(f"device form: out[{key!r}] is a contiguous device tensor of at least {need[key]} bytes")
+            N.check(getattr(L, fn + "_device")(*lead, _ptr(out.get("hits")), _ptr(out["n"]), _ptr(out.get("cum")),
+                                               _ptr(out.get("total"))), fn + "_device")
+            return out
+        if out is not None:
+            raise ValueError("out= goes with the device form")
+        hits = np.zeros(max(min(k, n), 1), dtype=N.BURN_HIT)
+        n_out = C.c_uint64(0)
+        blocks = [np.zeros(max(nwin * n, 1), dtype=np.uint64) for _ in range(2)] if counts else [None, None]
+        N.check(getattr(L, fn)(*lead, hits.ctypes.data if k else None, C.addressof(n_out), *[_ptr(b) for b in blocks]), fn)
+        hits = hits[:min(int(n_out.value), k)]
+        res = {"entry": hits["entry"].copy(), "row": hits["row"].copy(), "n": int(n_out.value)}
+        if counts:
+            res["cum"], res["total"] = (b[:nwin * n].reshape(nwin, n) for b in blocks)
+        return res
+
     # -- spread and compare per WINDOW of the list, in one call (lh_kept_spread_series* / lh_kept_drift*) ---------------------------
     def spread_series(self, percentiles, earlier=(), windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None,
                       out=None, stream=None):

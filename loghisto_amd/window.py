@@ -12,8 +12,31 @@ from __future__ import annotations
 from collections import deque
 from typing import Optional
 
+import numpy as np
+
 from . import _native as N
 from .engine import Kept
+
+
+def burn_fires(cum, total, budget, rate):
+    """The burn-rate rule of Kept.burn / lh_kept_burn* in NumPy, for one window or several: with cum and total of shape (n,) or
+    (nwin, n) -- the samples at or below each name's bound and all of its samples, as Kept.slo returns them for one bound a name --
+    budget of shape (n,) and rate a scalar or of shape (nwin,):
+
+        bad = total - cum;  t = rate * budget;  fires = total != 0 and float64(bad) > t * float64(total)
+
+    in IEEE doubles, each product rounded once, the compare strict: a tie does not fire, a name without samples does not, and a NaN
+    budget never does.  Returns the boolean array of cum's shape; a name is reported iff it fires in every window:
+    burn_fires(...).all(axis=0).  This is the reference the device's decisions are held to, and what a user can recompute from
+    Kept.burn(counts=True)."""
+    cum, total = np.asarray(cum, dtype=np.uint64), np.asarray(total, dtype=np.uint64)
+    rate = np.asarray(rate, dtype=np.float64)
+    if rate.ndim == 1 and cum.ndim == 2:
+        rate = rate[:, None]
+    t = rate * np.asarray(budget, dtype=np.float64)
+    bad = total - cum                                              # uint64: wraps as the device's does
+    with np.errstate(invalid="ignore"):
+        return (total != 0) & (bad.astype(np.float64) > t * total.astype(np.float64))
 
 
 class KeptWindow:
@@ -57,6 +80,17 @@ class KeptWindow:
         """Kept.heat over self.handles, the oldest first; as series()."""
         newest, earlier = self._newest_and_earlier()
         return newest.heat(bounds, earlier, windows, nmetrics, first, ids, out, stream)
+
+    def slo(self, bounds, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None, stream=None):
+        """Kept.slo over self.handles, the oldest first: a row of bounds per name; as series()."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.slo(bounds, earlier, windows, nmetrics, first, ids, out, stream)
+
+    def burn(self, bounds, budget, rates, k: int, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None,
+             counts: bool = False, out=None, stream=None):
+        """Kept.burn over self.handles, the oldest first: the names that burn their budget in every one of `windows`."""
+        newest, earlier = self._newest_and_earlier()
+        return newest.burn(bounds, budget, rates, k, earlier, windows, nmetrics, first, ids, counts, out, stream)
 
     def spread_series(self, percentiles, windows=None, nmetrics: Optional[int] = None, first: int = 0, ids=None, out=None,
                       stream=None):
