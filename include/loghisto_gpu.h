@@ -717,8 +717,39 @@ int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const 
  *                     LH_ERANGE: nmetrics > 0xffffffff -- then LH_EINVAL: handles on different devices; LH_ERANGE (*why left
  *                     as it was): [first, first + nmetrics) not inside EVERY handle's block.  LH_ENOMEM, LH_EDEVICE, the stream,
  *                     the two kernel shapes, the unit's mutex and "complete on return" as for lh_kept_merge: the listed handles
- *                     are only read, and the new handle depends on none of them. */
-typedef struct lh_kept lh_kept;      /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
+ *                     are only read, and the new handle depends on none of them.
+ *   lh_kept_gather*   KEPT ROWS RE-MAPPED PER HANDLE, SUMMED INTO ONE: history that came from somewhere else -- another process of a
+ *                     fleet, the same process before a restart, a rank that owns another block of names -- interned its names in
+ *                     another order, so row r does not mean the same name in every handle and no reader, lh_kept_merge or
+ *                     lh_kept_slide can take such a list as it is.  `src` is handle-major: src[i * n + j] is the ABSOLUTE row number
+ *                     of kept[i] that feeds output row first_out + j (ids are absolute everywhere in the family);
+ *                     LH_KEPT_NO_ROW: handle i has nothing for that row.  *out is a new handle of rows [first_out, first_out + n)
+ *                     that holds exactly what lh_keep would return for a snapshot whose row first_out + j has cells C[b] = the
+ *                     sum over i of cell b of row src[i * n + j] of kept[i], in 64 bits, wrapping: bins ascending, a bin whose sum
+ *                     wraps to 0 not listed, row_count the wrapping sum of the source rows' row_count entries, samples the
+ *                     wrapping sum of those; the same single allocation, layout and bytes as every other handle, so every
+ *                     reader, lh_kept_merge, lh_kept_slide and lh_kept_save* take it as they are.  The same source row may feed
+ *                     several output rows, and a handle may be listed several times, with different maps.
+ *                     1 <= nkept <= LH_MAX_KEPT.  With src[i * n + j] = first + j for all i the bytes are lh_kept_merge(kept,
+ *                     nkept, first, n)'s; with nkept == 1 it is a pure row permutation, selection or duplication and no cell
+ *                     changes (a route without the tile; identical bytes); the gather of a list equals lh_kept_merge of the nkept
+ *                     one-handle gathers.  Row 0xffffffff of a handle cannot be named: the value is LH_KEPT_NO_ROW.
+ *                     ONE DELIBERATE DIFFERENCE FROM THE READERS, which make an entry empty if its row lies outside ANY handle's
+ *                     block: here a LH_KEPT_NO_ROW entry, and in the device form any row outside handle i's block, makes handle i's
+ *                     segment empty for that output row and nothing else.  Nothing is read for it.
+ *                     Checked on the host, in lh_kept_merge's style and order, before any handle is looked at -- LH_EINVAL: a NULL or
+ *                     misaligned list or src, a NULL entry, nkept == 0 or > LH_MAX_KEPT, flags != 0, NULL out, n == 0; LH_ERANGE:
+ *                     n > 0xffffffff or first_out + n > 2^32 -- then LH_EINVAL: handles on different devices; the host form only:
+ *                     LH_ERANGE if some src value is neither LH_KEPT_NO_ROW nor inside its handle's block (nothing is enqueued).
+ *                     LH_ENOMEM and LH_EDEVICE as for lh_kept_merge; *out is untouched on any failure and nothing is leaked.
+ *                     The work goes on `stream`, is complete on return and runs under the unit's mutex; the listed handles are
+ *                     only read and the new handle depends on none of them.  The host form copies src (nkept * n * 4 bytes) to the
+ *                     device on the call's stream, as the id lists travel; the device form reads the caller's device array, which
+ *                     must stay valid and unchanged until the call returns.  The two kernel shapes give identical bytes.
+ *                     OUT OF SCOPE: more than LH_MAX_KEPT handles a call (gather in groups, then lh_kept_merge); many-to-one
+ *                     roll-ups of names within one handle; names inside the blob (loghisto_amd.keptfile.pack_names is a sidecar);
+ *                     a cross-rank collective; retuning the shape switch. */
+typedef struct lh_kept lh_kept;     /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
 #define LH_MAX_KEPT 64
 typedef struct lh_kept_info {
     uint32_t struct_size;            /* sizeof(lh_kept_info) */
@@ -746,6 +777,11 @@ int lh_kept_across_ids_device(lh_kept *const *kept, size_t nkept, const uint32_t
                               uint64_t *d_present_bits, int16_t *d_pkeys, uint8_t *d_pvalid);
 int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nmetrics, uint32_t flags, void *stream,
                   lh_kept **out);
+#define LH_KEPT_NO_ROW 0xffffffffu
+int lh_kept_gather(lh_kept *const *kept, size_t nkept, const uint32_t *src, size_t n, uint32_t first_out, uint32_t flags,
+                   void *stream, lh_kept **out);
+int lh_kept_gather_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_src, size_t n, uint32_t first_out,
+                          uint32_t flags, void *stream, lh_kept **out);
 typedef struct lh_kept_under {
     uint32_t struct_size;            /* sizeof(lh_kept_under) == 16 */
     uint32_t row;                    /* ABSOLUTE row number (metric id) of the first cell that would go below zero */

@@ -149,6 +149,17 @@ int lh_tool_across_switch(uint32_t wave_from_rows, uint32_t *previous);
 /* The same switch of lh_kept_across* (default 1 024; profiles/kept.txt has both shapes).  The two shapes walk a tile the same
  * way: they agree exactly in every output, sum included. */
 int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous);
+/* The route lh_kept_gather* takes, process-wide; *previous (may be NULL) receives the value in force before.  DEFAULT: one handle
+ * goes the direct route (the source rows' lengths, then their keys and counts verbatim: no LDS tile), several handles the tile
+ * route (lh_kept_merge's two passes with the row of each handle taken from the map).  TILE forces the tile route for one handle
+ * too, DIRECT the direct route for one handle (it is the default today; several handles take the tile route regardless),
+ * TRANSPOSED the tile route over a map first turned row-major on the device (one line a row where the handle-major map touches one
+ * line a handle).  All routes give identical bytes (tests compare them).  A value above TRANSPOSED -> LH_EINVAL. */
+#define LH_TOOL_GATHER_DEFAULT 0u
+#define LH_TOOL_GATHER_TILE 1u
+#define LH_TOOL_GATHER_DIRECT 2u
+#define LH_TOOL_GATHER_TRANSPOSED 3u
+int lh_tool_kept_gather_route(uint32_t route, uint32_t *previous);
 /* *bins receives the width in bins of the LDS tile lh_kept_across* covers a row's union span with (tests put cells either
  * side of a tile's edge).  NULL -> LH_EINVAL. */
 int lh_tool_kept_tile(uint32_t *bins);

@@ -27,6 +27,8 @@ MOVERS_BY_KS, MOVERS_BY_W1, MOVERS_BY_SHIFT, MOVERS_BY_PERCENTILE = range(4)   #
 MOVERS_ASCENDING = 1
 MAX_ACROSS = 16        # lh_across*: snapshots of one call
 MAX_KEPT = 64          # lh_kept_across*: handles of one call
+KEPT_NO_ROW = 0xffffffff   # lh_kept_gather*: LH_KEPT_NO_ROW, "this handle has nothing for that row"
+GATHER_DEFAULT, GATHER_TILE, GATHER_DIRECT, GATHER_TRANSPOSED = range(4)   # lh_tool_kept_gather_route
 MAX_WINDOWS = 128      # lh_kept_series* / _heat* / _spread_series* / _drift* / _top_series* / _movers_series*: windows of one call
 MAX_COLUMNS = 128      # lh_lines*
 COL_F64, COL_U64, COL_U32, COL_KEY = range(4)
@@ -197,6 +199,7 @@ TUNING_SIGNATURES = {
     "lh_tool_compare_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_across_switch": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_kept_switch": (C.c_int, [C.c_uint32, _u32p]),
+    "lh_tool_kept_gather_route": (C.c_int, [C.c_uint32, _u32p]),
     "lh_tool_kept_tile": (C.c_int, [_u32p]),
     "lh_tool_kept_compare_tile": (C.c_int, [_u32p]),
     "lh_tool_kept_check_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -297,6 +300,8 @@ SIGNATURES = {
     "lh_kept_across_ids_device": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_merge": (C.c_int, [_vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
     "lh_kept_slide": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(LhKeptUnder), C.POINTER(_vp)]),
+    "lh_kept_gather": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_gather_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
     "lh_kept_save_size": (C.c_int, [_vp, C.POINTER(_sz)]),
     "lh_kept_save": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "lh_kept_save_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),

@@ -49,6 +49,13 @@
 // the caller's stream, under the unit's mutex from the first look at a handle to the end (no lh_kept_release frees an input
 // under it); it only reads its inputs, so it records no event on them, and the new handle depends on none of them.
 //
+// THE GATHER, lh_kept_gather*: the merge with the row of handle i chosen PER HANDLE by a map (src[i * n + m], LH_KEPT_NO_ROW: none) --
+// handles of other processes, of the time before a restart, of ranks that own other name blocks, whose row numbers mean other names.
+// The merge's two passes take the row of lane i through a row-source type (BlockRows / MappedRows: one device body each for both
+// entry points); a row outside handle i's block empties lane i's segment alone (Row::open_own), where the readers' settle empties
+// the entry.  One handle is a permutation of rows and goes without the tile: lengths, then keys and counts verbatim (k_gather1_*).
+// The host form stages the map as an id list is staged; synchronous, under the mutex, no hold: lh_kept_merge's host side (born_of).
+//
 // THE SLIDE, lh_kept_slide: new window = old window + newest interval - oldest interval as a NEW handle, so that a rolling minute
 // emitted every second reads one merged handle and two small ones a tick where lh_kept_merge reads all sixty.  A[b] / S[b] = the
 // wrapping sums over the `add` / `sub` lists (the merge's C[b], once per side), the handle holds A[b] - S[b]: cells are unsigned
@@ -372,6 +379,12 @@ struct Row {
             if (end > h.cells || cur > end) cur = end = 0; // (never: lh_keep made them)
         }
     }
+    // (lane < the list's n)  lh_kept_gather's: row r of handle h for THIS handle alone.  LH_KEPT_NO_ROW, or a row outside h's block,
+    // leaves the lane's segment empty (rc 0) and nothing is read for it; the other lanes' segments stay what they are.
+    __device__ __forceinline__ void open_own(const KeptRec h, uint32_t r)
+    {
+        if (r != LH_KEPT_NO_ROW && r >= h.first && r - h.first < h.nrows) open(h, r);
+    }
     // (the whole wave)  A row outside the block of ANY handle is empty in all; the first and the last bin of each segment
     __device__ __forceinline__ void settle()
     {
@@ -597,21 +610,39 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_series(const 
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(KeptOut) + 5 * 8 < 4096,
               "k_kept_series' arguments inside the 4 KiB argument segment");
 
-// ---- lh_kept_merge ----------------------------------------------------------------------------------------------------------
-// The two passes around k_keep_scan, rows [first, first + nrows) of every handle of the list (the host checked that each
-// holds them), in the reader's two shapes.  count: nnz[m + 1] = the non-zero cells of the union -- a sum that wrapped to 0 is
-// none --, row_count[m] = the wrapping sum of the handles' own row_count entries (which is the wrapping sum of the cells).
-template <int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_count(const KeptList s, uint32_t nrows, uint32_t first,
-                                                                          u64 *__restrict__ nnz, u64 *__restrict__ row_count)
+// ---- lh_kept_merge, lh_kept_gather -------------------------------------------------------------------------------------------------
+// The two passes around k_keep_scan in the reader's two shapes, ONE device body each (merge_count, merge_fill) that takes the row of
+// lane i through a row-source type, as count_le_entry takes its bounds:
+//   BlockRows{first}    lh_kept_merge: row first + m of EVERY handle (the host checked that each holds the block; Row::open)
+//   MappedRows{src, n}  lh_kept_gather: row src[i * n + m] of handle i, for that handle alone (Row::open_own: LH_KEPT_NO_ROW or a row
+//                       outside handle i's block leaves lane i's segment empty and nothing else).  One 4-byte load a lane, from 64
+//                       lines that neighbouring rows share.  TRANSPOSED: the map as k_gather_transpose leaves it, src[m * nk + i],
+//                       one line a row (lh_tool_kept_gather_route; profiles/kept_gather.txt has both).
+// count: nnz[m + 1] = the non-zero cells of the union -- a sum that wrapped to 0 is none --, row_count[m] = the wrapping sum of the
+// handles' own row_count entries (which is the wrapping sum of the cells).
+struct BlockRows {
+    uint32_t first;
+    __device__ __forceinline__ void open(Row &row, const KeptRec h, uint32_t, uint32_t m) const { row.open(h, first + m); }
+};
+template <bool TRANSPOSED> struct MappedRows {
+    const uint32_t *__restrict__ src;
+    uint32_t n, nk; // output rows, handles
+    __device__ __forceinline__ void open(Row &row, const KeptRec h, uint32_t i, uint32_t m) const
+    {
+        row.open_own(h, TRANSPOSED ? src[(size_t)m * nk + i] : src[(size_t)i * n + m]);
+    }
+};
+
+template <int NW, class Rows>
+__device__ __forceinline__ void merge_count(const KeptList &s, uint32_t nrows, const Rows rows, u64 *__restrict__ nnz,
+                                            u64 *__restrict__ row_count, u64 (*s_tile)[KEPT_TILE])
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
     const uint32_t lane = at.lane, m = at.m;
     if (m >= nrows) return; // uniform for all that share a tile
     at.clear();
     Row row;
-    if (lane < s.n) row.open(s.h[lane], first + m);
+    if (lane < s.n) rows.open(row, s.h[lane], lane, m);
     row.settle();
     const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
     uint32_t occ = 0;
@@ -626,12 +657,10 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_count(const 
 
 // fill: the same turns; each step's non-zero cells to keys / counts[off[m] .. off[m + 1]), ascending by bin, as k_keep_fill
 // places them.  (Nothing is stored at or beyond off[m + 1].)
-template <int NW>
-__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const KeptList s, uint32_t nrows, uint32_t first,
-                                                                         const u64 *__restrict__ off, int16_t *__restrict__ keys,
-                                                                         u64 *__restrict__ counts)
+template <int NW, class Rows>
+__device__ __forceinline__ void merge_fill(const KeptList &s, uint32_t nrows, const Rows rows, const u64 *__restrict__ off,
+                                           int16_t *__restrict__ keys, u64 *__restrict__ counts, u64 (*s_tile)[KEPT_TILE])
 {
-    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     const Seat<NW> at(s_tile);
     const uint32_t lane = at.lane, m = at.m;
     if (m >= nrows) return; // uniform for all that share a tile
@@ -640,7 +669,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const K
     if (to >= lim) return; // (the same)
     at.clear();
     Row row;
-    if (lane < s.n) row.open(s.h[lane], first + m);
+    if (lane < s.n) rows.open(row, s.h[lane], lane, m);
     row.settle();
     turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
         const uint32_t b0 = base + 4 * lane, n = occupied4(C), inc = wave_scan_incl_u32(n);
@@ -654,6 +683,104 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const K
             }
         to += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
     });
+}
+
+// lh_kept_merge: rows [first, first + nrows) of every handle of the list
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_count(const KeptList s, uint32_t nrows, uint32_t first,
+                                                                          u64 *__restrict__ nnz, u64 *__restrict__ row_count)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    merge_count<NW>(s, nrows, BlockRows{first}, nnz, row_count, s_tile);
+}
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_merge_fill(const KeptList s, uint32_t nrows, uint32_t first,
+                                                                         const u64 *__restrict__ off, int16_t *__restrict__ keys,
+                                                                         u64 *__restrict__ counts)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    merge_fill<NW>(s, nrows, BlockRows{first}, off, keys, counts, s_tile);
+}
+
+// lh_kept_gather*: output row m takes row src[i * n + m] of handle i (the map holds s.n * n entries: the host sized it)
+template <int NW, bool TRANSPOSED>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_gather_count(const KeptList s, uint32_t n,
+                                                                           const uint32_t *__restrict__ src, u64 *__restrict__ nnz,
+                                                                           u64 *__restrict__ row_count)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    merge_count<NW>(s, n, MappedRows<TRANSPOSED>{src, n, s.n}, nnz, row_count, s_tile);
+}
+template <int NW, bool TRANSPOSED>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_gather_fill(const KeptList s, uint32_t n, const uint32_t *__restrict__ src,
+                                                                          const u64 *__restrict__ off, int16_t *__restrict__ keys,
+                                                                          u64 *__restrict__ counts)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    merge_fill<NW>(s, n, MappedRows<TRANSPOSED>{src, n, s.n}, off, keys, counts, s_tile);
+}
+// the map of nk handles x n rows, handle-major, to row-major: to[m * nk + i] = src[i * n + m] (one thread an entry of `to`)
+__global__ __launch_bounds__(ROW_BLOCK) void k_gather_transpose(const uint32_t *__restrict__ src, uint32_t n, uint32_t nk,
+                                                                uint32_t *__restrict__ to)
+{
+    const u64 e = (u64)blockIdx.x * ROW_BLOCK + threadIdx.x;
+    if (e >= (u64)n * nk) return;
+    const u64 m = e / nk, i = e % nk;
+    to[e] = src[i * n + m];
+}
+
+// THE DIRECT ROUTE of a gather of ONE handle: a permutation, selection or duplication of rows, no cell changes and no tile is
+// needed.  A handle's cells are non-zero and ascending by invariant (lh_keep made them, lh_kept_load* proved them), so the bytes are
+// the tile route's.  count: a thread per output row, nnz[m + 1] = the source row's length, row_count[m] its row_count entry.
+__global__ __launch_bounds__(ROW_BLOCK) void k_gather1_count(const KeptRec h, uint32_t n, const uint32_t *__restrict__ src,
+                                                            u64 *__restrict__ nnz, u64 *__restrict__ row_count)
+{
+    const u64 m = (u64)blockIdx.x * ROW_BLOCK + threadIdx.x;
+    if (m >= n) return;
+    Row row;
+    row.open_own(h, src[m]);
+    nnz[m + 1] = row.end - row.cur;
+    row_count[m] = row.rc;
+}
+// n elements from the global address `from` to `to`, by the nt threads of which this is thread t: 16 bytes an access over the
+// stretch where source and destination are 16-byte aligned TOGETHER (their addresses agree modulo 16), element by element before
+// and behind it, and everywhere when they never are.
+typedef uint32_t v4u __attribute__((ext_vector_type(4))); // 16 bytes, a native vector: one global_load_dwordx4
+typedef const __attribute__((address_space(1))) v4u *gvec;
+template <class T> __device__ __forceinline__ void copy_run(T *__restrict__ to, u64 from, u64 n, uint32_t t, uint32_t nt)
+{
+    typedef const __attribute__((address_space(1))) T *gsrc;
+    constexpr u64 PER = 16 / sizeof(T);
+    const gsrc src = (gsrc)from;
+    u64 head = 0, body = 0;
+    if ((((u64)(uintptr_t)to ^ from) & 15) == 0) {
+        head = ((16 - (from & 15)) & 15) / sizeof(T);
+        head = head < n ? head : n;
+        body = (n - head) / PER;
+    }
+    for (u64 i = t; i < head; i += nt) to[i] = src[i];
+    const gvec s4 = (gvec)(from + head * sizeof(T));
+    v4u *d4 = reinterpret_cast<v4u *>(to + head);
+    for (u64 i = t; i < body; i += nt) d4[i] = s4[i];
+    for (u64 i = head + body * PER + t; i < n; i += nt) to[i] = src[i];
+}
+// fill: the source row's keys and counts verbatim to keys / counts[off[m] .. off[m + 1]); a wave per row, or a workgroup per row.
+// (Nothing is stored at or beyond off[m + 1], whatever the map holds now.)
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_gather1_fill(const KeptRec h, uint32_t n, const uint32_t *__restrict__ src,
+                                                                           const u64 *__restrict__ off, int16_t *__restrict__ keys,
+                                                                           u64 *__restrict__ counts)
+{
+    const uint32_t wave = threadIdx.x >> 6, m = NW == 1 ? blockIdx.x * ROW_WAVES + wave : blockIdx.x;
+    if (m >= n) return; // uniform for the wave / the workgroup
+    const u64 to = off[m], lim = off[(size_t)m + 1];
+    if (to >= lim) return;
+    Row row;
+    row.open_own(h, (uint32_t)__builtin_amdgcn_readfirstlane((int)src[m]));
+    const u64 len = min(row.end - row.cur, lim - to);
+    const uint32_t t = NW == 1 ? threadIdx.x & 63 : threadIdx.x, nt = NW == 1 ? 64 : WG;
+    copy_run<u64>(counts + to, row.counts + 8 * row.cur, len, t, nt);
+    copy_run<int16_t>(keys + to, row.keys + 2 * row.cur, len, t, nt);
 }
 
 // ---- lh_kept_slide ------------------------------------------------------------------------------------------------------------
@@ -1439,7 +1566,9 @@ struct KeptCtx {
     u64 *h_totals = nullptr;   // pinned
     size_t totals_cap = 0;
     ResultBlocks res;          // host forms
-    IdBlocks ids;              // host form of lh_kept_across_ids
+    IdBlocks ids;              // host form of lh_kept_across_ids; lh_kept_gather's map, staged the same way
+    uint32_t *d_map_t = nullptr; // lh_kept_gather*: the map transposed (the measurement switch's route only)
+    size_t map_t_cap = 0;
     DoubleBlocks bounds;       // host forms of lh_kept_slo* / lh_kept_burn*: the per-entry bounds (and budgets), staged as the ids are
     CallEvent *pool = nullptr; // events no handle points to
     u64 holds = 0;
@@ -1447,6 +1576,9 @@ struct KeptCtx {
                                // turns under mu), its guard, and the host forms' landing block
 };
 std::atomic<uint32_t> g_wave_from{KEPT_WAVE_FROM_DEFAULT};
+// lh_kept_gather* of ONE handle: the direct route (profiles/kept_gather.txt has it beside the tile route)
+constexpr uint32_t GATHER_ROUTE_DEFAULT = LH_TOOL_GATHER_DIRECT;
+std::atomic<uint32_t> g_gather_route{LH_TOOL_GATHER_DEFAULT};
 
 } // namespace
 
@@ -1586,6 +1718,58 @@ int merge(KeptCtx *cx, lh_kept *const *kept, size_t nkept, uint32_t first, uint3
         [&](const u64 *off, int16_t *keys, u64 *counts) {
             return launch_rows(nrows, [&](const RowShape &sh, auto nw) {
                 hipLaunchKernelGGL((k_merge_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, nrows, first, off, keys, counts);
+            });
+        });
+}
+
+// (cx->mu held, the device current)  lh_kept_gather*: the same two passes with the row of handle i taken from the map d_src (device
+// memory, nkept * n entries, handle-major).  One handle takes the direct route -- no tile: the lengths, then the rows verbatim --
+// unless the measurement switch says otherwise; GATHER_TRANSPOSED first turns the map row-major in a block of the unit's.
+int gather(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const uint32_t *d_src, uint32_t n, uint32_t first_out, hipStream_t st,
+           lh_kept *k)
+{
+    const KeptList s = list_of(kept, nkept);
+    uint32_t route = g_gather_route.load(std::memory_order_relaxed);
+    if (route == LH_TOOL_GATHER_DEFAULT) route = GATHER_ROUTE_DEFAULT;
+    if (route == LH_TOOL_GATHER_DIRECT && nkept == 1) {
+        const KeptRec h = s.h[0];
+        return make(
+            cx, st, first_out, n, k,
+            [&](u64 *off, u64 *row_count, u64 *) {
+                hipLaunchKernelGGL(k_gather1_count, dim3((unsigned)(((u64)n + ROW_BLOCK - 1) / ROW_BLOCK)), dim3(ROW_BLOCK), 0, st, h, n, d_src, off, row_count);
+                LH_BESIDE_CHK(hipGetLastError());
+                return LH_OK;
+            },
+            [&](const u64 *off, int16_t *keys, u64 *counts) {
+                return launch_rows(n, [&](const RowShape &sh, auto nw) {
+                    hipLaunchKernelGGL((k_gather1_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, h, n, d_src, off, keys, counts);
+                });
+            });
+    }
+    const bool transposed = route == LH_TOOL_GATHER_TRANSPOSED;
+    if (transposed) {
+        const size_t entries = nkept * (size_t)n;
+        const int rc = grow_device(cx->d_map_t, cx->map_t_cap, entries, 1024);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gather_transpose, dim3((unsigned)((entries + ROW_BLOCK - 1) / ROW_BLOCK)), dim3(ROW_BLOCK), 0, st, d_src, n,
+                           (uint32_t)nkept, cx->d_map_t);
+        LH_BESIDE_CHK(hipGetLastError());
+        d_src = cx->d_map_t;
+    }
+    return make(
+        cx, st, first_out, n, k,
+        [&](u64 *off, u64 *row_count, u64 *) {
+            return launch_rows(n, [&](const RowShape &sh, auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                if (transposed) hipLaunchKernelGGL((k_gather_count<NW, true>), sh.grid, sh.block, 0, st, s, n, d_src, off, row_count);
+                else hipLaunchKernelGGL((k_gather_count<NW, false>), sh.grid, sh.block, 0, st, s, n, d_src, off, row_count);
+            });
+        },
+        [&](const u64 *off, int16_t *keys, u64 *counts) {
+            return launch_rows(n, [&](const RowShape &sh, auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                if (transposed) hipLaunchKernelGGL((k_gather_fill<NW, true>), sh.grid, sh.block, 0, st, s, n, d_src, off, keys, counts);
+                else hipLaunchKernelGGL((k_gather_fill<NW, false>), sh.grid, sh.block, 0, st, s, n, d_src, off, keys, counts);
             });
         });
 }
@@ -2899,6 +3083,44 @@ int lh_kept_merge(lh_kept *const *kept, size_t nkept, uint32_t first, size_t nme
     });
 }
 
+// lh_kept_gather*'s one front end: the checks in lh_kept_merge's style and order, then -- the host form only -- every entry of the
+// map against its handle's block, and the map staged on the call's stream as an id list is (born_of waits for it after a failure)
+static int kept_gather(lh_kept *const *kept, size_t nkept, const uint32_t *src, bool on_device, size_t n, uint32_t first_out,
+                       uint32_t flags, void *stream, lh_kept **out)
+{
+    if (bad_list(kept, nkept, LH_MAX_KEPT) || !src || misaligned(src, 4) || flags != 0 || !out || n == 0) return LH_EINVAL;
+    if (n > 0xffffffffu || (u64)first_out + n > (1ull << 32)) return LH_ERANGE;
+    // ---- from here on the handles are looked at
+    int device = -1;
+    int rc = one_device(kept, nkept, &device);
+    if (rc) return rc;
+    if (!on_device)
+        for (size_t i = 0; i < nkept; i++) {
+            const u64 lo = kept[i]->first, end = lo + kept[i]->nrows;
+            for (size_t j = 0; j < n; j++) {
+                const uint32_t r = src[i * n + j];
+                if (r != LH_KEPT_NO_ROW && (r < lo || r >= end)) return LH_ERANGE;
+            }
+        }
+    return born_of(device, stream, out, [&](KeptCtx *cx, hipStream_t st, lh_kept *k) {
+        const uint32_t *d_src = nullptr;
+        const int staged = stage_ids(cx->ids, rows_by_id(src, on_device), nkept * n, st, d_src);
+        return staged ? staged : gather(cx, kept, nkept, d_src, (uint32_t)n, first_out, st, k);
+    });
+}
+
+int lh_kept_gather(lh_kept *const *kept, size_t nkept, const uint32_t *src, size_t n, uint32_t first_out, uint32_t flags, void *stream,
+                   lh_kept **out)
+{
+    return kept_gather(kept, nkept, src, false, n, first_out, flags, stream, out);
+}
+
+int lh_kept_gather_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_src, size_t n, uint32_t first_out, uint32_t flags,
+                          void *stream, lh_kept **out)
+{
+    return kept_gather(kept, nkept, d_src, true, n, first_out, flags, stream, out);
+}
+
 int lh_kept_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics, uint32_t flags,
                   void *stream, lh_kept_under *why, lh_kept **out)
 {
@@ -3318,6 +3540,14 @@ int lh_tool_kept_compare_tile(uint32_t *bins)
 int lh_tool_kept_switch(uint32_t wave_from_rows, uint32_t *previous)
 {
     switch_exchange(g_wave_from, wave_from_rows, KEPT_WAVE_FROM_DEFAULT, previous);
+    return LH_OK;
+}
+
+int lh_tool_kept_gather_route(uint32_t route, uint32_t *previous)
+{
+    if (route > LH_TOOL_GATHER_TRANSPOSED) return LH_EINVAL;
+    const uint32_t old = g_gather_route.exchange(route, std::memory_order_relaxed);
+    if (previous) *previous = old;
     return LH_OK;
 }
 

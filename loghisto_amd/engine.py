@@ -736,7 +736,7 @@ class Snapshot:
 
 class Kept:
     """One interval's occupied cells of metrics [first, first + nrows), kept in compact form on the device (lh_kept):
-    Snapshot.keep(), Kept.merge(), Kept.slide(), or -- with no engine at all -- Kept.from_bytes / load / from_device_blob of a saved one.  It
+    Snapshot.keep(), Kept.merge(), Kept.gather(), Kept.slide(), or -- with no engine at all -- Kept.from_bytes / load / from_device_blob of a saved one.  It
     depends on neither its snapshot nor its engine, and never changes."""
 
     _OUT = (("count", 8, 0, np.uint64), ("sum", 8, 0, np.float64), ("nbuckets", 4, 0, np.uint32),
@@ -838,6 +838,35 @@ class Kept:
         h = C.c_void_p(0)
         N.check(N.lib().lh_kept_merge(C.addressof(handles), nkept, first, nmetrics, 0, _stream_handle(stream), C.byref(h)),
                 "lh_kept_merge")
+        return Kept(h, self._table)
+
+    def gather(self, src, earlier=(), first: int = 0, stream=None) -> "Kept":
+        """Rows re-mapped per handle and summed into ONE new Kept of metrics [first, first + n) (lh_kept_gather*): over
+        list(earlier) + [self], `src` is [nkept, n] and src[i, j] is the metric id (absolute, as ids are everywhere) of handle i
+        that feeds metric first + j of the result; N.KEPT_NO_ROW: handle i has nothing for it.  Per metric and bin the counts are
+        summed in 64 bits -- what merge() gives once every handle speaks of the same names: handles of other processes, of the
+        time before a restart (loghisto_amd.fleet.union_names builds src from their name lists).  A source metric may feed
+        several results and a handle may be listed several times.  A uint32 host array (a 1-D one is the map of a single handle)
+        takes the host form, where a metric outside its handle's block is LH_ERANGE; a torch device tensor of 4-byte elements the
+        device form, where such a metric counts as KEPT_NO_ROW.  The work goes on `stream` (a torch stream or a raw handle; None:
+        the null stream) and is complete on return; the new handle depends on none of the listed ones."""
+        handles, nkept = self._list(earlier)
+        if hasattr(src, "data_ptr") and getattr(src, "is_cuda", False):
+            if src.element_size() != 4 or not src.is_contiguous():
+                raise ValueError("a device map holds contiguous 4-byte elements")
+            shape, addr, fn = tuple(src.shape), int(src.data_ptr()), "lh_kept_gather_device"
+        else:
+            a = np.asarray(src.numpy() if hasattr(src, "data_ptr") else src)
+            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+                raise ValueError("the map holds unsigned 32-bit integers")
+            src = np.ascontiguousarray(a, dtype=np.uint32)
+            shape, addr, fn = src.shape, int(src.ctypes.data), "lh_kept_gather"
+        if len(shape) == 1:
+            shape = (1, shape[0])
+        if len(shape) != 2 or shape[0] != nkept:
+            raise ValueError(f"the map is [{nkept}, n]: a row per listed handle")
+        h = C.c_void_p(0)
+        N.check(getattr(N.lib(), fn)(C.addressof(handles), nkept, addr, shape[1], first, 0, _stream_handle(stream), C.byref(h)), fn)
         return Kept(h, self._table)
 
     def slide(self, add=(), sub=(), nmetrics: Optional[int] = None, first: Optional[int] = None, stream=None) -> "Kept":

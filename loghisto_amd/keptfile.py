@@ -7,7 +7,9 @@ pack() makes a blob from CSR arrays, unpack() takes one apart, and check() resta
 to -- the header's on the host, the block's on the device -- with the same verdict: of all violations the one of the lowest
 row, in it the lowest index, there the lowest cause code.  The device's check is held to check() by the tests.
 combine() states lh_kept_slide on blobs -- per row and bin the add side's sum minus the sub side's, KeptUnderflow for a cell that
-would go below zero -- and is the reference the device's slide is held to.
+would go below zero -- and is the reference the device's slide is held to.  gather() states lh_kept_gather* the same way: rows
+re-mapped per blob and summed.  pack_names() / unpack_names() are a sidecar for the names of a handle's rows (the blob itself
+carries row numbers only and its format does not change).
 """
 from __future__ import annotations
 
@@ -220,3 +222,127 @@ def combine(add_blobs, sub_blobs=(), first=None, nrows=None) -> bytes:
     off, rc, c = np.array(offsets, dtype="<u8"), np.array(row_count, dtype="<u8"), np.array(counts, dtype="<u8")
     k = np.array(keys, dtype="<u2").view("<i2")
     return header(first, nrows, len(keys), sum(row_count) & _M64) + off.tobytes() + rc.tobytes() + c.tobytes() + k.tobytes()
+
+
+NO_ROW = 0xffffffff                      # LH_KEPT_NO_ROW
+
+
+def _permuted(u, line, first_out):
+    """gather() of ONE blob, in whole-array NumPy: no cell changes, the rows' runs are copied (what a host did before
+    lh_kept_gather: a permutation of the CSR arrays)."""
+    r = np.asarray(line, dtype=np.int64)
+    has = r != NO_ROW
+    at = np.where(has, r - u["first"], 0)
+    if ((at < 0) | (at >= u["nrows"])).any():
+        raise ValueError("a row is neither NO_ROW nor inside its blob's block")
+    off = u["offsets"].astype(np.int64)
+    lo, ln = off[at], np.where(has, off[at + 1] - off[at], 0)
+    new_off = np.concatenate(([0], np.cumsum(ln)))
+    idx = np.repeat(lo - new_off[:-1], ln) + np.arange(int(new_off[-1]), dtype=np.int64)
+    rc = np.where(has, u["row_count"][at], np.uint64(0)).astype("<u8")
+    with np.errstate(over="ignore"):
+        samples = int(rc.sum(dtype=np.uint64))
+    return (header(first_out, r.size, idx.size, samples) + new_off.astype("<u8").tobytes() + rc.tobytes()
+            + u["counts"][idx].astype("<u8").tobytes() + u["keys"][idx].astype("<i2").tobytes())
+
+
+def gather(blobs, src, first_out: int = 0, *, checked: bool = True) -> bytes:
+    """The blob lh_kept_save writes for lh_kept_gather(blobs, src, first_out): src is [len(blobs), n] (a 1-D map belongs to a single
+    blob), src[i][j] the ABSOLUTE row of blob i that feeds output row first_out + j, NO_ROW: none.  Per output row and bin the sum
+    mod 2^64 of the source rows' cells, a sum of 0 not listed, bins ascending; row_count the sum mod 2^64 of the source rows'
+    row_count entries, samples the sum of those.  The same source row may feed several output rows and a blob may be listed
+    several times.  ValueError for a blob that is not sound (check(); checked=False trusts blobs of one's own), no blob, a map of
+    another shape or without a column, a row that is neither NO_ROW nor inside its blob's block, or first_out + n > 2^32.
+    One blob is a permutation of rows and is done in whole arrays; several are summed cell by cell in Python integers."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise ValueError("at least one blob")
+    for b in blobs:
+        bad = check(b) if checked else None
+        if bad:
+            raise ValueError(f"not a kept blob: {CAUSES[bad[0]]} (row {bad[1]}, index {bad[2]})")
+    U = [unpack(b) for b in blobs]
+    a = np.asarray(src)
+    if a.ndim == 1:
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[0] != len(U) or a.shape[1] < 1:
+        raise ValueError("the map is [len(blobs), n] with n >= 1")
+    n = a.shape[1]
+    if first_out < 0 or first_out + n > 1 << 32:
+        raise ValueError("rows [first_out, first_out + n) end at 2^32 at most")
+    if len(U) == 1:
+        return _permuted(U[0], a[0], first_out)
+    rows = [[int(r) for r in line] for line in a.tolist()]
+    offsets, keys, counts, row_count = [0], [], [], []
+    for j in range(n):
+        cells, rc = {}, 0
+        for u, line in zip(U, rows):
+            r = line[j]
+            if r == NO_ROW:
+                continue
+            if not u["first"] <= r < u["first"] + u["nrows"]:
+                raise ValueError(f"row {r} is neither NO_ROW nor inside its blob's block")
+            at = r - u["first"]
+            lo, hi = int(u["offsets"][at]), int(u["offsets"][at + 1])
+            bins = (u["keys"][lo:hi].view("<u2") ^ np.uint16(0x8000)).tolist()
+            for b, c in zip(bins, u["counts"][lo:hi].tolist()):
+                cells[b] = (cells.get(b, 0) + c) & _M64
+            rc = (rc + int(u["row_count"][at])) & _M64
+        for b in sorted(cells):
+            if cells[b]:
+                keys.append(b ^ 0x8000)
+                counts.append(cells[b])
+        offsets.append(len(keys))
+        row_count.append(rc)
+    off, rcs, c = np.array(offsets, dtype="<u8"), np.array(row_count, dtype="<u8"), np.array(counts, dtype="<u8")
+    k = np.array(keys, dtype="<u2").view("<i2")
+    return header(first_out, n, len(keys), sum(row_count) & _M64) + off.tobytes() + rcs.tobytes() + c.tobytes() + k.tobytes()
+
+
+# ---- the names of a handle's rows: a sidecar beside the blob, whose format does not change --------------------------------------
+NAMES_MAGIC = b"LHNAMES\n"
+NAMES_VERSION = 1
+_NAMES_HEAD = struct.Struct("<8sIIII")   # magic, version, first, count, reserved (0); then per name uint32 length + UTF-8 bytes
+
+
+def pack_names(names, first: int = 0) -> bytes:
+    """The names of rows [first, first + len(names)) of a handle -- Engine.metric_name's output, in row order -- as bytes to store
+    beside its blob: a 24-byte little-endian header (magic, version, first, count, 0), then each name as a uint32 length and its
+    UTF-8 bytes.  Pure data: nothing in the blob refers to it."""
+    names = list(names)
+    if not 0 <= first <= 0xffffffff or first + len(names) > 1 << 32:
+        raise ValueError("rows [first, first + len(names)) end at 2^32 at most")
+    out = [_NAMES_HEAD.pack(NAMES_MAGIC, NAMES_VERSION, first, len(names), 0)]
+    for name in names:
+        raw = name.encode("utf-8")
+        out.append(struct.pack("<I", len(raw)) + raw)
+    return b"".join(out)
+
+
+def unpack_names(blob, with_first: bool = False):
+    """pack_names back: the list of names (with_first: (names, first)).  ValueError for anything else: a wrong magic or version, a
+    non-zero reserved word, a truncated or over-long blob, bytes that are not UTF-8."""
+    b = bytes(blob)
+    if len(b) < _NAMES_HEAD.size:
+        raise ValueError("not a names sidecar: shorter than its header")
+    magic, version, first, count, reserved = _NAMES_HEAD.unpack_from(b)
+    if magic != NAMES_MAGIC:
+        raise ValueError("not a names sidecar: bad magic")
+    if version != NAMES_VERSION or reserved != 0 or first + count > 1 << 32:
+        raise ValueError("not a names sidecar of version 1")
+    at, names = _NAMES_HEAD.size, []
+    for _ in range(count):
+        if at + 4 > len(b):
+            raise ValueError("names sidecar truncated")
+        (ln,) = struct.unpack_from("<I", b, at)
+        at += 4
+        if at + ln > len(b):
+            raise ValueError("names sidecar truncated")
+        try:
+            names.append(b[at:at + ln].decode("utf-8"))
+        except UnicodeDecodeError as exc:
+            raise ValueError("names sidecar: a name is not UTF-8") from exc
+        at += ln
+    if at != len(b):
+        raise ValueError("names sidecar: bytes behind the last name")
+    return (names, first) if with_first else names
