@@ -748,7 +748,50 @@ int lh_spread_ids_device(lh_snapshot *s, const uint32_t *d_ids, size_t n, const 
  *                     must stay valid and unchanged until the call returns.  The two kernel shapes give identical bytes.
  *                     OUT OF SCOPE: more than LH_MAX_KEPT handles a call (gather in groups, then lh_kept_merge); many-to-one
  *                     roll-ups of names within one handle; names inside the blob (loghisto_amd.keptfile.pack_names is a sidecar);
- *                     a cross-rank collective; retuning the shape switch. */
+ *                     a cross-rank collective; retuning the shape switch.
+ *   lh_kept_group*    MANY KEPT ROWS SUMMED INTO ONE ROW, BY GROUP: the roll-up across names -- the p99 of a service over all its
+ *                     endpoints, hosts or status codes, a fleet total beside the per-endpoint rows; Prometheus' sum by (label).  It
+ *                     is where lh_kept_gather*'s out-of-scope item "many-to-one roll-ups of names within one handle" went.  The
+ *                     groups are a CSR over row numbers: group g has the members members[goff[g] .. goff[g + 1]), ABSOLUTE row
+ *                     numbers as everywhere in the family, LH_KEPT_NO_ROW: nothing.  *out is a new handle of rows [first_out,
+ *                     first_out + ngroups) that holds exactly what lh_keep would return for a snapshot whose row first_out + g has
+ *                     cells C[b] = the sum over the handles i and over the members r of group g of cell b of row r of kept[i], in
+ *                     64 bits, wrapping: bins ascending, a bin whose sum wraps to 0 not listed, row_count the wrapping sum of the
+ *                     source rows' row_count entries, samples the wrapping sum of those; the same single allocation, layout and
+ *                     bytes as every other handle, so every reader, lh_kept_merge, lh_kept_slide, lh_kept_save* and lh_lines* take
+ *                     it as they are.  A row may be a member of several groups (per service, and "everything": the normal case); a
+ *                     row that appears several times in one group counts that often, and a handle listed twice counts twice; an
+ *                     empty group gives an empty row; a call in which no cell survives gives a valid handle with cells == 0.
+ *                     1 <= nkept <= LH_MAX_KEPT; there is no limit on the sources of a group.
+ *                     THREE EQUIVALENCES ARE THE WHOLE DEFINITION:
+ *                     1. With ngroups singleton groups, goff[g] = g and members[g] = src[g]: the bytes are lh_kept_gather's for the
+ *                        list with that one map repeated for every handle.  With members[g] = first + g, they are lh_kept_merge's.
+ *                     2. A call whose largest group has G members, with nkept x G <= LH_MAX_KEPT: the bytes are lh_kept_gather's
+ *                        for the list in which every handle stands G times.  The copies are G consecutive entries per handle.  Copy
+ *                        c is mapped to member c of each group.  LH_KEPT_NO_ROW stands where the group is shorter.
+ *                     3. Any partition of every group's member list into pieces: the bytes are lh_kept_merge's over the handles
+ *                        that lh_kept_group gives for each piece.
+ *                     THE ROW RULE is lh_kept_gather's deliberate difference from the readers, not the readers' rule: a
+ *                     LH_KEPT_NO_ROW member contributes nothing, and in the device form a member outside handle i's block
+ *                     contributes nothing for handle i alone; nothing is read for it.
+ *                     Checked on the host, in lh_kept_gather's style and order, before any handle is looked at -- LH_EINVAL: a NULL
+ *                     or misaligned list, goff or members (members may be NULL only with nmembers == 0), a NULL entry, nkept == 0
+ *                     or > LH_MAX_KEPT, flags != 0, NULL out, ngroups == 0; LH_ERANGE: ngroups > 0xffffffff, first_out + ngroups >
+ *                     2^32 or nmembers > 0xffffffff -- then LH_EINVAL: handles on different devices; then, the host form only:
+ *                     LH_EINVAL if goff[0] != 0, goff decreases somewhere or goff[ngroups] != nmembers; LH_ERANGE if a member is
+ *                     neither LH_KEPT_NO_ROW nor inside EVERY handle's block.  Nothing is enqueued on a refusal and *out is
+ *                     untouched on any failure.  The host form copies goff and members to the device on the call's stream, as src
+ *                     and the id lists travel.  The device form's arrays are any bytes: entry g reads a = min(goff[g], nmembers)
+ *                     and b = min(goff[g + 1], nmembers) and is empty if b <= a; both passes apply the same clamp, and nothing is
+ *                     stored beyond a row's place whatever the arrays hold by the second pass; they must stay valid until the
+ *                     call returns.  The stream, "complete on return", the unit's mutex, LH_ENOMEM / LH_EDEVICE and "the new handle
+ *                     depends on none of the listed ones" as for lh_kept_merge.  Up to 64 sources (handles x members) of a group
+ *                     take lh_kept_gather's open and turns, one source a lane; more go through the same tile in chunks of 64.  The
+ *                     two kernel shapes give identical bytes; the switch takes the call's OUTPUT rows.
+ *                     OUT OF SCOPE: spreading ONE group over several workgroups (a single group of every name runs in one
+ *                     workgroup; profiles/kept_group.txt has it); more than LH_MAX_KEPT handles a call; readers over groups without
+ *                     materialising the handle; a different member list per handle (gather first, then group); weights; retuning
+ *                     the shape switch. */
 typedef struct lh_kept lh_kept;     /* one interval's occupied cells of rows [first, first + nrows), in device memory the handle owns */
 #define LH_MAX_KEPT 64
 typedef struct lh_kept_info {
@@ -782,6 +825,10 @@ int lh_kept_gather(lh_kept *const *kept, size_t nkept, const uint32_t *src, size
                    void *stream, lh_kept **out);
 int lh_kept_gather_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_src, size_t n, uint32_t first_out,
                           uint32_t flags, void *stream, lh_kept **out);
+int lh_kept_group(lh_kept *const *kept, size_t nkept, const uint64_t *goff, const uint32_t *members, size_t nmembers,
+                  size_t ngroups, uint32_t first_out, uint32_t flags, void *stream, lh_kept **out);
+int lh_kept_group_device(lh_kept *const *kept, size_t nkept, const uint64_t *d_goff, const uint32_t *d_members, size_t nmembers,
+                         size_t ngroups, uint32_t first_out, uint32_t flags, void *stream, lh_kept **out);
 typedef struct lh_kept_under {
     uint32_t struct_size;            /* sizeof(lh_kept_under) == 16 */
     uint32_t row;                    /* ABSOLUTE row number (metric id) of the first cell that would go below zero */

@@ -302,7 +302,9 @@ SIGNATURES = {
     "lh_kept_slide": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, C.POINTER(LhKeptUnder), C.POINTER(_vp)]),
     "lh_kept_gather": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
     "lh_kept_gather_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
-    "lh_kept_save_size": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "lh_kept_group": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_group_device": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "lh_kept_save_size":(C.c_int, [_vp, C.POINTER(_sz)]),
     "lh_kept_save": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "lh_kept_save_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "lh_kept_load": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),

@@ -56,6 +56,12 @@
 // the entry.  One handle is a permutation of rows and goes without the tile: lengths, then keys and counts verbatim (k_gather1_*).
 // The host form stages the map as an id list is staged; synchronous, under the mutex, no hold: lh_kept_merge's host side (born_of).
 //
+// THE GROUP, lh_kept_group*: the merge with MANY rows of every handle feeding one output row -- a CSR of groups over absolute rows
+// (goff, members), the roll-up of a service over its endpoints.  A third row source of the same two bodies (GroupRows): a row's
+// sources are the pairs (handle, member); at most 64 sit one a lane and take the gather's open and turns, more go through the same
+// tile in chunks of 64 (chunk_turns).  The device form clamps goff to the members in both passes; the host form holds goff to a CSR
+// and the members to every handle's block, and stages both through the id list's blocks.  Host side: lh_kept_merge's (born_of).
+//
 // THE SLIDE, lh_kept_slide: new window = old window + newest interval - oldest interval as a NEW handle, so that a rolling minute
 // emitted every second reads one merged handle and two small ones a tick where lh_kept_merge reads all sixty.  A[b] / S[b] = the
 // wrapping sums over the `add` / `sub` lists (the merge's C[b], once per side), the handle holds A[b] - S[b]: cells are unsigned
@@ -610,7 +616,7 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_kept_series(const 
 static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(KeptOut) + 5 * 8 < 4096,
               "k_kept_series' arguments inside the 4 KiB argument segment");
 
-// ---- lh_kept_merge, lh_kept_gather -------------------------------------------------------------------------------------------------
+// ---- lh_kept_merge, lh_kept_gather, lh_kept_group -------------------------------------------------------------------------------------
 // The two passes around k_keep_scan in the reader's two shapes, ONE device body each (merge_count, merge_fill) that takes the row of
 // lane i through a row-source type, as count_le_entry takes its bounds:
 //   BlockRows{first}    lh_kept_merge: row first + m of EVERY handle (the host checked that each holds the block; Row::open)
@@ -618,6 +624,10 @@ static_assert(sizeof(KeptList) + sizeof(KeptWindows) + sizeof(PctArgs) + sizeof(
 //                       outside handle i's block leaves lane i's segment empty and nothing else).  One 4-byte load a lane, from 64
 //                       lines that neighbouring rows share.  TRANSPOSED: the map as k_gather_transpose leaves it, src[m * nk + i],
 //                       one line a row (lh_tool_kept_gather_route; profiles/kept_gather.txt has both).
+//   GroupRows{goff, members, ...}  lh_kept_group: the rows members[goff[m] .. goff[m + 1]) of EVERY handle, each for that handle alone
+//                       (Row::open_own again).  Its sources are the pairs (handle, member), as many as the call likes: at most 64 of
+//                       them are seated one a lane and take the same open and turns as the two above; more go in chunks of 64
+//                       (chunk_turns).
 // count: nnz[m + 1] = the non-zero cells of the union -- a sum that wrapped to 0 is none --, row_count[m] = the wrapping sum of the
 // handles' own row_count entries (which is the wrapping sum of the cells).
 struct BlockRows {
@@ -633,6 +643,194 @@ template <bool TRANSPOSED> struct MappedRows {
     }
 };
 
+// The summed row of output row at.m, handed to `step` 256 bins a step (turns); returns the wrapping sum of its sources' row_count
+// entries.  One source a lane: lane i is handle i, its row the row source's.
+template <int NW, class Rows, class Step>
+__device__ __forceinline__ u64 summed_row(const Seat<NW> &at, const KeptList &s, const Rows &rows, Step step)
+{
+    Row row;
+    if (at.lane < s.n) rows.open(row, s.h[at.lane], at.lane, at.m);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    turns<NW>(row, s.n, at.tile, at.lane, at.w, step);
+    return total;
+}
+
+// ---- lh_kept_group's row source ---------------------------------------------------------------------------------------------------
+// What the NW waves of a workgroup-per-row kernel tell each other in a chunked row: each wave's least bin of a turn, and at the first
+// open its last bin and its sum of row_count entries.  (A wave per row shares nothing.)
+template <int NW> struct ChunkShare {
+    u64 rc[NW];
+    uint32_t least[NW], hi[NW];
+};
+__device__ __forceinline__ u64 uniform_u64(u64 v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (u64)hi << 32 | lo;
+}
+// Output row m sums the rows members[a .. a + len) of each of the nk handles, with a = min(goff[m], nmembers) and the end clamped
+// the same way (an end at or before a: none) -- the device form's arrays are any bytes, and both passes clamp alike.  SOURCE x of
+// the row, x < len * nk, is member x % len of handle x / len: handle-major, so that the 64 sources of a chunk read one or two lines
+// of `members`.
+template <int NW> struct GroupRows {
+    const u64 *__restrict__ goff;          // ngroups + 1 entries
+    const uint32_t *__restrict__ members;  // nmembers entries
+    u64 nmembers;                          // <= 0xffffffff
+    uint32_t nk;                           // handles
+    ChunkShare<NW> *share;
+    // (uniform for all that share a tile)  the first member and the number of members of row m: two 8-byte loads
+    __device__ __forceinline__ void span(uint32_t m, u64 &a, u64 &len) const
+    {
+        const u64 g0 = uniform_u64(goff[m]), g1 = uniform_u64(goff[(size_t)m + 1]);
+        a = g0 < nmembers ? g0 : nmembers;
+        const u64 b = g1 < nmembers ? g1 : nmembers;
+        len = b > a ? b - a : 0;
+    }
+    // (x < len * nk)  source x: a LH_KEPT_NO_ROW member, or one outside this handle's block, leaves the segment empty (Row::open_own)
+    __device__ __forceinline__ void open(Row &row, const KeptList &s, u64 a, u64 len, u64 x) const
+    {
+        const u64 i = x / len, j = x - i * len;
+        row.open_own(s.h[i], members[a + j]);
+    }
+};
+
+// The turns of a row of S > 64 sources, in chunks of 64: lane l of chunk c is source 64 * c + l, and wave w of the NW that share the
+// tile takes the chunks w, w + NW, ...  Per turn a FIRST SWEEP opens every chunk again -- the offsets, then (behind the first tile)
+// the binary search to `from`, one key -- for the least bin of all, which decides t0 as in turns_of; a SECOND SWEEP scatters the runs
+// of every chunk into the one tile (a wave whose only chunk is still open keeps it); then turns_of's ascending walk hands `step` its
+// cells and puts zeros back.  hi (the last bin of the union) and the sum of the row_count entries are taken at the first open.  The
+// chunk count, `from`, t0 and hi are the same in every wave: all control flow around the readlanes, ballots and barriers is
+// uniform.  The adds are integer adds: no byte depends on the chunk order, the shape or the timing.  (The tile is zero on entry and
+// again on return.)  Returns the wrapping sum of the sources' row_count entries.
+template <int NW, class Step>
+__device__ __forceinline__ u64 chunk_turns(const Seat<NW> &at, const KeptList &s, const GroupRows<NW> &g, u64 a, u64 len, u64 S, Step step)
+{
+    const uint32_t lane = at.lane, w = at.w;
+    u64 *tile = at.tile;
+    const u64 chunks = (S + 63) / 64;
+    u64 total = 0;
+    uint32_t hi = 0;
+    // source x of the row as the turn from bin `from` finds it: the cursor at the first entry at or above `from`, the bin there
+    const auto reopen = [&](Row &row, u64 x, uint32_t from) {
+        row = Row();
+        if (x < S) g.open(row, s, a, len, x);
+        if (from) {
+            u64 lo = row.cur, up = row.end;
+            while (lo < up) {
+                const u64 mid = lo + (up - lo) / 2;
+                if (bin_of(((gkeys)row.keys)[mid]) < from) lo = mid + 1;
+                else up = mid;
+            }
+            row.cur = lo;
+        }
+        if (row.cur < row.end) row.next = bin_of(((gkeys)row.keys)[row.cur]);
+    };
+    tile_sync<NW>(); // the tile is zero
+    Row row;
+    for (uint32_t from = 0;;) {
+        // ---- first sweep: the least bin at or above `from`
+        uint32_t next = NO_BIN, last = 0;
+        u64 rc = 0;
+        for (u64 c = w; c < chunks; c += NW) { // wave-uniform
+            reopen(row, 64 * c + lane, from);
+            next = min(next, row.next);
+            if (!from) { // uniform
+                rc += row.rc;
+                if (row.end > row.cur) last = max(last, bin_of(((gkeys)row.keys)[row.end - 1]));
+            }
+        }
+        uint32_t least = ~wave_max_u32(~next);
+        if (!from) {
+            hi = wave_max_u32(last);
+            total = readlane_u64(wave_scan_incl_u64(rc), 63);
+        }
+        if constexpr (NW > 1) {
+            ChunkShare<NW> &sh = *g.share;
+            if (lane == 0) {
+                sh.least[w] = least;
+                if (!from) {
+                    sh.hi[w] = hi;
+                    sh.rc[w] = total;
+                }
+            }
+            __syncthreads(); // (the next turn's stores come behind the two barriers of this one)
+            least = NO_BIN;
+            for (int k = 0; k < NW; k++) least = min(least, sh.least[k]);
+            if (!from) {
+                hi = 0;
+                total = 0;
+                for (int k = 0; k < NW; k++) {
+                    hi = max(hi, sh.hi[k]);
+                    total += sh.rc[k];
+                }
+            }
+        }
+        if (least == NO_BIN) break;
+        const uint32_t t0 = least & ~3u, tend = t0 + KEPT_TILE;
+        // ---- second sweep: every source's run inside the tile, 64 entries a turn; only the sources that have one
+        for (u64 c = w; c < chunks; c += NW) { // wave-uniform
+            if (chunks > NW) reopen(row, 64 * c + lane, from); // (else this wave's one chunk is open)
+            for (u64 live = __builtin_amdgcn_ballot_w64(row.next < tend); live; live &= live - 1) {
+                const uint32_t i = (uint32_t)__builtin_ctzll(live);
+                u64 cur = readlane_u64(row.cur, i);
+                const u64 e = readlane_u64(row.end, i);
+                const gkeys kp = (gkeys)readlane_u64(row.keys, i);
+                const gu64 cp = (gu64)readlane_u64(row.counts, i);
+                while (cur < e) {
+                    const u64 idx = cur + lane;
+                    bool in = false;
+                    if (idx < e) {
+                        const uint32_t bin = bin_of(kp[idx]) - t0;
+                        if (bin < KEPT_TILE) {
+                            in = true;
+                            atomicAdd(&tile[bin], cp[idx]);
+                        }
+                    }
+                    const uint32_t took = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
+                    cur += took;
+                    if (took < 64) break;
+                }
+            }
+        }
+        tile_sync<NW>();
+        // ---- walk, and zeros back
+        if (w == 0) {
+            const uint32_t wend = min(tend - 1, hi);
+            for (uint32_t base = t0; base <= wend; base += STEP) {
+                const uint32_t at4 = base + 4 * lane - t0;
+                u64 C[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    C[k] = tile[at4 + k];
+                    tile[at4 + k] = 0;
+                }
+                step(C, base);
+            }
+        }
+        tile_sync<NW>();
+        if (tend > hi) break; // nothing lies beyond
+        from = tend;
+    }
+    return total;
+}
+
+// lh_kept_group's summed row: S = nk * len sources.  S <= 64 is exactly the gather's open and turns, one source a lane.
+template <int NW, class Step>
+__device__ __forceinline__ u64 summed_row(const Seat<NW> &at, const KeptList &s, const GroupRows<NW> &g, Step step)
+{
+    u64 a, len;
+    g.span(at.m, a, len);
+    const u64 S = len * g.nk;
+    if (S > 64) return chunk_turns<NW>(at, s, g, a, len, S, step); // uniform for all that share a tile
+    Row row;
+    if (at.lane < S) g.open(row, s, a, len, at.lane);
+    row.settle();
+    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
+    turns<NW>(row, (uint32_t)S, at.tile, at.lane, at.w, step);
+    return total;
+}
+
 template <int NW, class Rows>
 __device__ __forceinline__ void merge_count(const KeptList &s, uint32_t nrows, const Rows rows, u64 *__restrict__ nnz,
                                             u64 *__restrict__ row_count, u64 (*s_tile)[KEPT_TILE])
@@ -641,12 +839,8 @@ __device__ __forceinline__ void merge_count(const KeptList &s, uint32_t nrows, c
     const uint32_t lane = at.lane, m = at.m;
     if (m >= nrows) return; // uniform for all that share a tile
     at.clear();
-    Row row;
-    if (lane < s.n) rows.open(row, s.h[lane], lane, m);
-    row.settle();
-    const u64 total = readlane_u64(wave_scan_incl_u64(row.rc), 63);
     uint32_t occ = 0;
-    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t) { occ += occupied4(C); });
+    const u64 total = summed_row<NW>(at, s, rows, [&](const u64 (&C)[4], uint32_t) { occ += occupied4(C); });
     if (at.w != 0) return;
     occ = wave_scan_incl_u32(occ);
     if (lane == 63) {
@@ -668,10 +862,7 @@ __device__ __forceinline__ void merge_fill(const KeptList &s, uint32_t nrows, co
     const u64 lim = off[(size_t)m + 1];
     if (to >= lim) return; // (the same)
     at.clear();
-    Row row;
-    if (lane < s.n) rows.open(row, s.h[lane], lane, m);
-    row.settle();
-    turns<NW>(row, s.n, at.tile, lane, at.w, [&](const u64 (&C)[4], uint32_t base) {
+    summed_row<NW>(at, s, rows, [&](const u64 (&C)[4], uint32_t base) {
         const uint32_t b0 = base + 4 * lane, n = occupied4(C), inc = wave_scan_incl_u32(n);
         u64 pos = to + (inc - n);
 #pragma unroll
@@ -718,6 +909,27 @@ __global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_gather_fill(const 
 {
     __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
     merge_fill<NW>(s, n, MappedRows<TRANSPOSED>{src, n, s.n}, off, keys, counts, s_tile);
+}
+// lh_kept_group*: output row m sums the rows members[goff[m] .. goff[m + 1]) of every handle (goff: ngroups + 1 entries, members:
+// nmembers; both clamped as GroupRows::span says, so any bytes will do)
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_group_count(const KeptList s, uint32_t ngroups, const u64 *__restrict__ goff,
+                                                                          const uint32_t *__restrict__ members, u64 nmembers,
+                                                                          u64 *__restrict__ nnz, u64 *__restrict__ row_count)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    __shared__ ChunkShare<NW> s_share;
+    merge_count<NW>(s, ngroups, GroupRows<NW>{goff, members, nmembers, s.n, &s_share}, nnz, row_count, s_tile);
+}
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? ROW_BLOCK : WG) void k_group_fill(const KeptList s, uint32_t ngroups, const u64 *__restrict__ goff,
+                                                                         const uint32_t *__restrict__ members, u64 nmembers,
+                                                                         const u64 *__restrict__ off, int16_t *__restrict__ keys,
+                                                                         u64 *__restrict__ counts)
+{
+    __shared__ u64 s_tile[NW == 1 ? ROW_WAVES : 1][KEPT_TILE];
+    __shared__ ChunkShare<NW> s_share;
+    merge_fill<NW>(s, ngroups, GroupRows<NW>{goff, members, nmembers, s.n, &s_share}, off, keys, counts, s_tile);
 }
 // the map of nk handles x n rows, handle-major, to row-major: to[m * nk + i] = src[i * n + m] (one thread an entry of `to`)
 __global__ __launch_bounds__(ROW_BLOCK) void k_gather_transpose(const uint32_t *__restrict__ src, uint32_t n, uint32_t nk,
@@ -1566,7 +1778,7 @@ struct KeptCtx {
     u64 *h_totals = nullptr;   // pinned
     size_t totals_cap = 0;
     ResultBlocks res;          // host forms
-    IdBlocks ids;              // host form of lh_kept_across_ids; lh_kept_gather's map, staged the same way
+    IdBlocks ids;              // host form of lh_kept_across_ids; lh_kept_gather's map and lh_kept_group's CSR, staged the same way
     uint32_t *d_map_t = nullptr; // lh_kept_gather*: the map transposed (the measurement switch's route only)
     size_t map_t_cap = 0;
     DoubleBlocks bounds;       // host forms of lh_kept_slo* / lh_kept_burn*: the per-entry bounds (and budgets), staged as the ids are
@@ -1772,6 +1984,46 @@ int gather(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const uint32_t *d_sr
                 else hipLaunchKernelGGL((k_gather_fill<NW, false>), sh.grid, sh.block, 0, st, s, n, d_src, off, keys, counts);
             });
         });
+}
+
+// (cx->mu held, the device current)  lh_kept_group*: the same two passes with the rows of output row m taken from the CSR d_goff /
+// d_members (device memory: ngroups + 1 and nmembers entries), for every handle of the list; the shape by the call's output rows.
+int group(KeptCtx *cx, lh_kept *const *kept, size_t nkept, const u64 *d_goff, const uint32_t *d_members, u64 nmembers, uint32_t ngroups,
+          uint32_t first_out, hipStream_t st, lh_kept *k)
+{
+    const KeptList s = list_of(kept, nkept);
+    return make(
+        cx, st, first_out, ngroups, k,
+        [&](u64 *off, u64 *row_count, u64 *) {
+            return launch_rows(ngroups, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_group_count<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, ngroups, d_goff, d_members, nmembers, off,
+                                   row_count);
+            });
+        },
+        [&](const u64 *off, int16_t *keys, u64 *counts) {
+            return launch_rows(ngroups, [&](const RowShape &sh, auto nw) {
+                hipLaunchKernelGGL((k_group_fill<decltype(nw)::value>), sh.grid, sh.block, 0, st, s, ngroups, d_goff, d_members, nmembers, off,
+                                   keys, counts);
+            });
+        });
+}
+
+// (cx->mu held)  The host form's CSR on its way to the kernels, through the id list's two blocks (IdBlocks, 4-byte words): goff's
+// ngroups + 1 entries first (two words each; the blocks are aligned for them), the members behind them, copied into the pinned block
+// before this returns and from there into HBM by ONE copy on `st`, ahead of the kernels.  The call waits for `st` before it returns.
+int stage_groups(IdBlocks &b, const u64 *goff, const uint32_t *members, size_t nmembers, size_t ngroups, hipStream_t st, const u64 *&d_goff,
+                 const uint32_t *&d_members)
+{
+    const size_t head = 2 * (ngroups + 1), words = head + nmembers;
+    int rc = grow_pinned(b.h_ids, b.h_cap, words, 1024);
+    if (!rc) rc = grow_device(b.d_ids, b.d_cap, words, 1024);
+    if (rc) return rc;
+    std::memcpy(b.h_ids, goff, head * sizeof(uint32_t));
+    if (nmembers) std::memcpy(b.h_ids + head, members, nmembers * sizeof(uint32_t));
+    LH_BESIDE_CHK(hipMemcpyAsync(b.d_ids, b.h_ids, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    d_goff = reinterpret_cast<const u64 *>(b.d_ids);
+    d_members = b.d_ids + head;
+    return LH_OK;
 }
 
 // (cx->mu held, the device current)  lh_kept_slide: the same with all[0 .. nadd) added and all[nadd .. n) taken away.  *verdict:
@@ -3119,6 +3371,55 @@ int lh_kept_gather_device(lh_kept *const *kept, size_t nkept, const uint32_t *d_
                           void *stream, lh_kept **out)
 {
     return kept_gather(kept, nkept, d_src, true, n, first_out, flags, stream, out);
+}
+
+// lh_kept_group*'s one front end: the checks in lh_kept_gather's style and order; the host form's CSR rules need no handle and are
+// decided before one is looked at (they and "different devices" are both LH_EINVAL, so the documented order holds), its members
+// are held to EVERY handle's block; the CSR staged on the call's stream (born_of waits for it after a failure)
+static int kept_group(lh_kept *const *kept, size_t nkept, const uint64_t *goff, const uint32_t *members, bool on_device, size_t nmembers,
+                      size_t ngroups, uint32_t first_out, uint32_t flags, void *stream, lh_kept **out)
+{
+    if (bad_list(kept, nkept, LH_MAX_KEPT) || !goff || misaligned(goff, 8) || (!members && nmembers > 0) || misaligned(members, 4) ||
+        flags != 0 || !out || ngroups == 0)
+        return LH_EINVAL;
+    if (ngroups > 0xffffffffu || (u64)first_out + ngroups > (1ull << 32) || nmembers > 0xffffffffu) return LH_ERANGE;
+    if (!on_device) {
+        if (goff[0] != 0 || goff[ngroups] != nmembers) return LH_EINVAL;
+        for (size_t g = 0; g < ngroups; g++)
+            if (goff[g + 1] < goff[g]) return LH_EINVAL;
+    }
+    // ---- from here on the handles are looked at
+    int device = -1;
+    int rc = one_device(kept, nkept, &device);
+    if (rc) return rc;
+    if (!on_device) {
+        u64 lo = 0, end = ~0ull; // the rows every handle has
+        for (size_t i = 0; i < nkept; i++) {
+            const u64 f = kept[i]->first, e = f + kept[i]->nrows;
+            lo = f > lo ? f : lo;
+            end = e < end ? e : end;
+        }
+        for (size_t j = 0; j < nmembers; j++)
+            if (members[j] != LH_KEPT_NO_ROW && (members[j] < lo || members[j] >= end)) return LH_ERANGE;
+    }
+    return born_of(device, stream, out, [&](KeptCtx *cx, hipStream_t st, lh_kept *k) {
+        const u64 *d_goff = reinterpret_cast<const u64 *>(goff);
+        const uint32_t *d_members = members;
+        const int staged = on_device ? LH_OK : stage_groups(cx->ids, d_goff, members, nmembers, ngroups, st, d_goff, d_members);
+        return staged ? staged : group(cx, kept, nkept, d_goff, d_members, nmembers, (uint32_t)ngroups, first_out, st, k);
+    });
+}
+
+int lh_kept_group(lh_kept *const *kept, size_t nkept, const uint64_t *goff, const uint32_t *members, size_t nmembers, size_t ngroups,
+                  uint32_t first_out, uint32_t flags, void *stream, lh_kept **out)
+{
+    return kept_group(kept, nkept, goff, members, false, nmembers, ngroups, first_out, flags, stream, out);
+}
+
+int lh_kept_group_device(lh_kept *const *kept, size_t nkept, const uint64_t *d_goff, const uint32_t *d_members, size_t nmembers,
+                         size_t ngroups, uint32_t first_out, uint32_t flags, void *stream, lh_kept **out)
+{
+    return kept_group(kept, nkept, d_goff, d_members, true, nmembers, ngroups, first_out, flags, stream, out);
 }
 
 int lh_kept_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t nsub, uint32_t first, size_t nmetrics, uint32_t flags,

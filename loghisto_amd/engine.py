@@ -869,6 +869,48 @@ class Kept:
         N.check(getattr(N.lib(), fn)(C.addressof(handles), nkept, addr, shape[1], first, 0, _stream_handle(stream), C.byref(h)), fn)
         return Kept(h, self._table)
 
+    def group(self, groups, earlier=(), first: int = 0, stream=None) -> "Kept":
+        """Many metrics summed into one, by group (lh_kept_group*): ONE new Kept of metrics [first, first + ngroups) whose metric
+        first + g holds, per bin, the 64-bit sum over list(earlier) + [self] and over the members of group g -- the roll-up of a
+        service over its endpoints, of "everything" beside them (loghisto_amd.fleet.group_names builds the groups from names).
+        `groups` is a sequence of sequences of metric ids (absolute, as ids are everywhere; N.KEPT_NO_ROW: nothing), or a
+        (goff, members) pair of arrays, a CSR: group g has members[goff[g]:goff[g + 1]].  A metric may stand in several groups,
+        and several times in one: it counts that often.  There is no limit on a group's size.  Host arrays take the host form,
+        where a member outside some handle's block is LH_ERANGE and a goff that is no CSR over members LH_EINVAL; a pair of torch
+        device tensors (goff of 8-byte, members of 4-byte elements) the device form, where goff is clamped to the members and a
+        member outside a handle's block counts as nothing for that handle alone.  The work goes on `stream` and is complete on
+        return; the new handle depends on none of the listed ones."""
+        handles, nkept = self._list(earlier)
+        pair = isinstance(groups, tuple) and len(groups) == 2 and all(hasattr(x, "shape") for x in groups)
+        if pair and any(hasattr(x, "data_ptr") and getattr(x, "is_cuda", False) for x in groups):
+            goff, members = groups
+            if not all(hasattr(x, "data_ptr") and x.is_cuda and x.is_contiguous() and x.dim() == 1 for x in groups):
+                raise ValueError("the device form takes two contiguous 1-D device tensors")
+            if goff.element_size() != 8 or members.element_size() != 4 or goff.numel() < 2:
+                raise ValueError("goff holds ngroups + 1 >= 2 8-byte elements, members 4-byte elements")
+            ngroups, nmembers, fn = goff.numel() - 1, members.numel(), "lh_kept_group_device"
+            addrs = (int(goff.data_ptr()), int(members.data_ptr()) if nmembers else 0)
+        else:
+            if pair:
+                goff, members = (np.asarray(x.numpy() if hasattr(x, "data_ptr") else x).ravel() for x in groups)
+            else:
+                rows = [np.asarray(g).ravel() for g in groups]
+                rows = [r if r.size else r.astype(np.uint32) for r in rows]   # (an empty group has no integers to show)
+                goff = np.cumsum([0] + [r.size for r in rows])
+                members = np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint32)
+            for a, top, what in ((goff, (1 << 64) - 1, "goff holds unsigned 64-bit integers"),
+                                 (members, 0xffffffff, "members are unsigned 32-bit integers")):
+                if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > top):
+                    raise ValueError(what)
+            if goff.size < 2:
+                raise ValueError("at least one group")
+            goff, members = np.ascontiguousarray(goff, dtype=np.uint64), np.ascontiguousarray(members, dtype=np.uint32)
+            ngroups, nmembers, fn = goff.size - 1, members.size, "lh_kept_group"
+            addrs = (int(goff.ctypes.data), int(members.ctypes.data) if nmembers else 0)
+        h = C.c_void_p(0)
+        N.check(getattr(N.lib(), fn)(C.addressof(handles), nkept, *addrs, nmembers, ngroups, first, 0, _stream_handle(stream), C.byref(h)), fn)
+        return Kept(h, self._table)
+
     def slide(self, add=(), sub=(), nmetrics: Optional[int] = None, first: Optional[int] = None, stream=None) -> "Kept":
         """A rolling window advanced exactly (lh_kept_slide): ONE new Kept of metrics [first, first+nmetrics) that holds, per
         metric and bin, the 64-bit sum over [self] + list(add) minus the sum over list(sub) -- with self the window so far,

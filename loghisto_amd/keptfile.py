@@ -8,7 +8,7 @@ to -- the header's on the host, the block's on the device -- with the same verdi
 row, in it the lowest index, there the lowest cause code.  The device's check is held to check() by the tests.
 combine() states lh_kept_slide on blobs -- per row and bin the add side's sum minus the sub side's, KeptUnderflow for a cell that
 would go below zero -- and is the reference the device's slide is held to.  gather() states lh_kept_gather* the same way: rows
-re-mapped per blob and summed.  pack_names() / unpack_names() are a sidecar for the names of a handle's rows (the blob itself
+re-mapped per blob and summed; group() states lh_kept_group*: many rows summed into one, by group.  pack_names() / unpack_names() are a sidecar for the names of a handle's rows (the blob itself
 carries row numbers only and its format does not change).
 """
 from __future__ import annotations
@@ -297,6 +297,67 @@ def gather(blobs, src, first_out: int = 0, *, checked: bool = True) -> bytes:
     off, rcs, c = np.array(offsets, dtype="<u8"), np.array(row_count, dtype="<u8"), np.array(counts, dtype="<u8")
     k = np.array(keys, dtype="<u2").view("<i2")
     return header(first_out, n, len(keys), sum(row_count) & _M64) + off.tobytes() + rcs.tobytes() + c.tobytes() + k.tobytes()
+
+
+def group(blobs, goff, members, first_out: int = 0, *, checked: bool = True) -> bytes:
+    """The blob lh_kept_save writes for lh_kept_group(blobs, goff, members, first_out): a CSR of groups over ABSOLUTE row numbers,
+    group g = members[goff[g]:goff[g + 1]], NO_ROW: nothing.  Output row first_out + g holds, per bin, the sum mod 2^64 over the
+    blobs and over the group's members of the source rows' cells, a sum of 0 not listed, bins ascending; row_count the sum mod
+    2^64 of the source rows' row_count entries, samples the sum of those.  A row may stand in several groups, and several times in
+    one (it counts that often); a blob may be listed several times; an empty group gives an empty row.  ValueError for what the
+    host form refuses: a blob that is not sound (check(); checked=False trusts blobs of one's own), no blob, no group, a goff
+    that does not start at 0, decreases or does not end at len(members), a member that is neither NO_ROW nor inside EVERY blob's
+    block, or first_out + ngroups > 2^32.  Summed cell by cell in Python integers."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise ValueError("at least one blob")
+    for b in blobs:
+        bad = check(b) if checked else None
+        if bad:
+            raise ValueError(f"not a kept blob: {CAUSES[bad[0]]} (row {bad[1]}, index {bad[2]})")
+    U = [unpack(b) for b in blobs]
+    off = [int(x) for x in np.asarray(goff).ravel().tolist()]
+    mem = [int(x) for x in np.asarray(members).ravel().tolist()]
+    ngroups = len(off) - 1
+    if ngroups < 1:
+        raise ValueError("goff has ngroups + 1 >= 2 entries")
+    if off[0] != 0 or off[-1] != len(mem) or any(b < a for a, b in zip(off[:-1], off[1:])):
+        raise ValueError("goff starts at 0, never decreases and ends at len(members)")
+    if first_out < 0 or first_out + ngroups > 1 << 32:
+        raise ValueError("rows [first_out, first_out + ngroups) end at 2^32 at most")
+    lo, end = max(u["first"] for u in U), min(u["first"] + u["nrows"] for u in U)
+    for r in mem:
+        if r != NO_ROW and not lo <= r < end:
+            raise ValueError(f"row {r} is neither NO_ROW nor inside every blob's block")
+    rows = {}                                            # (blob, row) -> (bins, counts, row_count), taken apart once
+
+    def source(i, r):
+        if (i, r) not in rows:
+            u, at = U[i], r - U[i]["first"]
+            a, b = int(u["offsets"][at]), int(u["offsets"][at + 1])
+            rows[i, r] = ((u["keys"][a:b].view("<u2") ^ np.uint16(0x8000)).tolist(), u["counts"][a:b].tolist(), int(u["row_count"][at]))
+        return rows[i, r]
+
+    offsets, keys, counts, row_count = [0], [], [], []
+    for g in range(ngroups):
+        cells, rc = {}, 0
+        for i in range(len(U)):
+            for r in mem[off[g]:off[g + 1]]:
+                if r == NO_ROW:
+                    continue
+                bins, cs, n = source(i, r)
+                for b, c in zip(bins, cs):
+                    cells[b] = (cells.get(b, 0) + c) & _M64
+                rc = (rc + n) & _M64
+        for b in sorted(cells):
+            if cells[b]:
+                keys.append(b ^ 0x8000)
+                counts.append(cells[b])
+        offsets.append(len(keys))
+        row_count.append(rc)
+    o, rcs, c = np.array(offsets, dtype="<u8"), np.array(row_count, dtype="<u8"), np.array(counts, dtype="<u8")
+    k = np.array(keys, dtype="<u2").view("<i2")
+    return header(first_out, ngroups, len(keys), sum(row_count) & _M64) + o.tobytes() + rcs.tobytes() + c.tobytes() + k.tobytes()
 
 
 # ---- the names of a handle's rows: a sidecar beside the blob, whose format does not change --------------------------------------
