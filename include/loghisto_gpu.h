@@ -842,7 +842,7 @@ int lh_kept_slide(lh_kept *const *add, size_t nadd, lh_kept *const *sub, size_t 
  * (lh_keep) or from handles of the same device (lh_kept_merge): the history dies with the process and cannot change devices.  A
  * BLOB carries one handle to a file, to another process, rank or device; a process that only QUERIES history -- a dashboard
  * backend, a fleet aggregator, a restart -- needs no engine: lh_kept_load* and the lh_kept_* readers.  The names that belong to
- * the ids are not in the blob (store lh_metric_name's output beside it); no compression, no checksum.
+ * the ids are not in the blob (store lh_metric_name's output beside it); no checksum, and verbatim: lh_kept_encode* below writes the compact form.
  *   THE BLOB (format version 1; little-endian; part of this interface) is a 64-byte header followed by the handle's single
  *   allocation VERBATIM, lh_kept_info.bytes long:
  *       offset  0  uint8[8]  magic "LHKEPT\x1a\n" (LH_KEPT_BLOB_MAGIC)
@@ -944,6 +944,96 @@ int lh_kept_load(int device, const void *buf, size_t len, uint32_t flags, void *
 int lh_kept_load_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why,
                         lh_kept **out);
 int lh_kept_values(int device, double *D /* LH_NKEYS */);
+/* KEPT INTERVALS IN A COMPACT BLOB: lh_kept_encode*, lh_kept_decode*.  The verbatim blob above costs 10 bytes a cell and 16 a row on
+ * every file, wire and PCIe copy; the ENCODED blob carries the same handle in a per-row encoding -- counts at the narrowest width
+ * that holds the row's largest, bins as byte deltas -- made and taken apart on the device, a wave per row.  A decoded handle is
+ * byte for byte the handle that was encoded, so nothing else in the family changes.  lh_kept_load* refuses an encoded blob
+ * (LH_KEPT_BAD_MAGIC) and lh_kept_decode* a verbatim one.  No checksum, no names, no entropy coding.
+ *   THE ENCODED BLOB (format version 1; little-endian; part of this interface):
+ *       offset  0  uint8[8]  magic "LHKENC\x1a\n" (LH_KEPT_ENC_MAGIC)
+ *               8  uint32    format version, 1 (LH_KEPT_ENC_VERSION)
+ *              12  uint32    header size, 64
+ *              16  uint32    LH_NKEYS, 65 536
+ *              20  uint32    first
+ *              24  uint32    nrows
+ *              28  uint32    reserved, 0
+ *              32  uint64    cells, the total over all rows
+ *              40  uint64    samples, the wrapping sum of every count
+ *              48  uint64    bytes, the length of everything behind the header
+ *              56  uint8[8]  reserved, 0
+ *              64  THE ROW DIRECTORY  uint32 desc[nrows], padded with one zero uint32 when nrows is odd: D = 8 * ceil(nrows / 2)
+ *                  bytes.  desc[m] = n | cw << 20 | km << 24: n (bits 0-16) the row's cells, 0 .. 65 536; cw (bits 20-21) the
+ *                  count width, 1 << cw bytes; km (bit 24) the key mode; every other bit 0.  A row without a cell has desc == 0
+ *                  and no record.
+ *          64 + D  THE ROW RECORDS in row order, each S(m) bytes long and 8-aligned; nothing else is stored -- no offsets, no
+ *                  row_count (the wrapping sum of the row's counts).  A record of n >= 1 cells:
+ *                    counts  n values of 1 << cw bytes, zero-padded to a multiple of 8
+ *                    keys    zero-padded to a multiple of 8; with bin = (uint16)key ^ 0x8000,
+ *                            km 0: uint16 bin[0], then n - 1 bytes d[i] = bin[i] - bin[i - 1] - 1 (gaps of 1 .. 256)
+ *                            km 1: uint16 bin[n]
+ *                  Every multi-byte value is naturally aligned.
+ *   CANONICAL: one handle has exactly one encoding.  cw is the least width that holds the row's largest count; km is 1 exactly
+ *   when some gap of the row exceeds 256; every pad byte is 0.
+ *   SIZE: for n >= 1, S(m) <= 8 n + (2 n + 6), hence bytes <= D + 10 * cells + 6 * nrows and LH_KEPT_ENC_BOUND(nrows, cells) is the
+ *   capacity that always suffices -- never above the verbatim blob's 64 + 10 * cells + 16 * nrows + 8.
+ *   lh_kept_encode_size  *bytes = the exact size of k's encoded blob: the encoder's first pass and its scan run on `stream`, the
+ *                     total alone comes to the host.  LH_EINVAL: NULL k or bytes.
+ *   lh_kept_encode    writes the encoded blob of k into HOST memory buf[0 .. cap), pageable or pinned; *written (may be NULL) = its
+ *                     size.  Encoded on the device into a block of the exact size, then ONE copy to the host.
+ *   lh_kept_encode_device  the same into DEVICE memory of the handle's device, at any alignment (an address that is not
+ *                     8-aligned is served through the unit's own block and one device copy).
+ *                     Both: three kernels on `stream` (a hipStream_t of the handle's device; NULL: its null stream) -- a wave per
+ *                     row finds desc[m] and S(m), one scan gives the records' offsets, a wave per row writes the record, every pad
+ *                     byte included: what buf held before does not show.  COMPLETE on return; under the unit's mutex; the handle
+ *                     is only read.  LH_EINVAL: NULL k or buf.  LH_ERANGE: cap below LH_KEPT_ENC_MIN (the smallest encoded blob
+ *                     there is: one row, no cell) before the handle is looked at, then cap below the exact size, known after
+ *                     the first pass: nothing written, *written untouched.
+ *   lh_kept_decode    a NEW handle on `device` from an encoded blob in HOST memory buf[0 .. len): allocation, layout and bytes
+ *                     are exactly those of the handle that was encoded.
+ *   lh_kept_decode_device  the same from an encoded blob in the memory of `device` itself, at any alignment; only its 64 header
+ *                     bytes come to the host.
+ *                     Both: an encoded blob is UNTRUSTED like a verbatim one: the kernels are safe on arbitrary bytes and the
+ *                     verdict does not depend on timing.  flags must be 0; complete on return, under the unit's mutex.  Any
+ *                     refusal is LH_EINVAL, *out untouched, nothing leaked, *why as for lh_kept_load (struct_size first).
+ *                     STAGE 0, on the HOST before any device call (lh_kept_decode_device: the arguments and len < 64 before any
+ *                     device call, the rest once the header has come over), lh_kept_load's causes in lh_kept_load's order:
+ *                       LH_KEPT_BAD_ARG, LH_KEPT_BAD_SHORT, LH_KEPT_BAD_MAGIC, LH_KEPT_BAD_VERSION, LH_KEPT_BAD_HEADER_SIZE,
+ *                       LH_KEPT_BAD_NKEYS, LH_KEPT_BAD_NROWS, LH_KEPT_BAD_FIRST, LH_KEPT_BAD_CELLS
+ *                       LH_KEPT_BAD_BYTES        bytes not a multiple of 8, below D, or above D + 10 * cells + 6 * nrows
+ *                       LH_KEPT_BAD_LENGTH       len != 64 + bytes
+ *                       LH_KEPT_BAD_RESERVED
+ *                     STAGE 1, the directory alone, a thread per descriptor:
+ *                       LH_KEPT_BAD_ENC_DESC     a reserved bit, n > 65 536, or n == 0 with desc != 0        (row m, index 0)
+ *                       LH_KEPT_BAD_ENC_TOTALS   the sum of n is not cells, or D + the sum of S(m) not bytes (row nrows, index 0)
+ *                       LH_KEPT_BAD_ENC_PAD      the pad word behind an odd nrows is not 0                 (row nrows, index 0)
+ *                     A stage-1 refusal is final: the records are read only behind a sound directory, by which every record lies
+ *                     inside the payload and every row's cells inside the handle's exact allocation, whatever the bytes say.
+ *                     STAGE 2, a wave per row, cell i of row m:
+ *                       LH_KEPT_BAD_ENC_KEY_RANGE  km 0: bin[i] above 65 535                                 (row m, index i)
+ *                       LH_KEPT_BAD_KEY_ORDER      km 1: bin[i - 1] >= bin[i]                                (row m, index i)
+ *                       LH_KEPT_BAD_ZERO_COUNT     a count of 0                                              (row m, index i)
+ *                       LH_KEPT_BAD_ENC_PAD        a pad byte of the record that is not 0                    (row m, index n)
+ *                       LH_KEPT_BAD_ENC_WIDTH      cw or km is not the canonical one                         (row m, index n)
+ *                       LH_KEPT_BAD_SAMPLES        samples is not the wrapping sum of the counts      (row = nrows, index 0)
+ *                     Of all violations of a stage the one reported is that of the LOWEST ROW, in it the LOWEST INDEX, there the
+ *                     LOWEST CAUSE CODE.  LH_ENOMEM: an allocation failed.  LH_EDEVICE: a HIP error. */
+#define LH_KEPT_ENC_MAGIC "LHKENC\x1a\n"
+#define LH_KEPT_ENC_VERSION 1
+#define LH_KEPT_ENC_MIN (LH_KEPT_BLOB_HEADER + 8) /* one row, no cell */
+#define LH_KEPT_ENC_BOUND(nrows, cells) \
+    (LH_KEPT_BLOB_HEADER + 8 * (((uint64_t)(nrows) + 1) / 2) + 10 * (uint64_t)(cells) + 6 * (uint64_t)(nrows))
+/* lh_kept_check.cause of an encoded blob: the LH_KEPT_BAD_* above, and */
+#define LH_KEPT_BAD_ENC_DESC 32
+#define LH_KEPT_BAD_ENC_TOTALS 33
+#define LH_KEPT_BAD_ENC_KEY_RANGE 34
+#define LH_KEPT_BAD_ENC_PAD 35
+#define LH_KEPT_BAD_ENC_WIDTH 36
+int lh_kept_encode_size(lh_kept *k, void *stream, size_t *bytes);
+int lh_kept_encode(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written);
+int lh_kept_encode_device(lh_kept *k, void *d_buf, size_t cap, void *stream, size_t *written);
+int lh_kept_decode(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out);
+int lh_kept_decode_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why,
+                          lh_kept **out);
 /* DISTRIBUTION SHIFT BETWEEN KEPT INTERVALS: lh_compare* over handles, so that the baseline -- the same minute an hour ago, the
  * interval before the deploy, yesterday's roll-up -- need not be alive as a dense snapshot, nor be poured back into one.  With
  *   a[j] = the sum over the `base` list of the name's cell j, b[j] = the same sum over the `cur` list, both in 64 bits

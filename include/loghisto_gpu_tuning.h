@@ -207,7 +207,15 @@ int lh_tool_kept_slide_passes_ms(lh_kept *const *add, size_t nadd, lh_kept *cons
  * over the handle's OWN block, which holds what they ask for; nothing is copied or allocated, the handle is only read.  Returns
  * when both times are known.  LH_EINVAL: NULL k or output. */
 int lh_tool_kept_check_ms(lh_kept *k, void *stream, float *check_ms, float *samples_ms);
-/* The yardstick beside it: device time of lh_keep's FIRST pass alone, k_keep_count over rows [first, first + nmetrics) of a
+/* Device time of lh_kept_encode*'s three kernels alone (HIP events on `stream` around each): k_enc_size, the scan and k_enc_fill,
+ * which writes into the unit's own block; nothing reaches the caller, the handle is only read.  LH_EINVAL: NULL k or output. */
+int lh_tool_kept_encode_ms(lh_kept *k, void *stream, float *size_ms, float *scan_ms, float *fill_ms);
+/* Device time of lh_kept_decode_device's kernels alone (HIP events around each) in ONE decode of the encoded blob at d_buf[0 .. len)
+ * in the memory of `device`: k_dec_dir, the two scans, k_dec_fill and k_kept_check_samples; the handle it makes is released.
+ * lh_kept_decode_device's checks and codes (no `why`); LH_EINVAL too for a NULL output. */
+int lh_tool_kept_decode_ms(int device, const void *d_buf, size_t len, void *stream, float *dir_ms, float *scan_ms, float *fill_ms,
+                           float *samples_ms);
+/* The yardstick beside the check: device time of lh_keep's FIRST pass alone, k_keep_count over rows [first, first + nmetrics) of a
  * live snapshot (HIP events on the snapshot's stream), into the unit's scratch block; no handle is made.  nmetrics >= 1. */
 int lh_tool_keep_count_ms(lh_snapshot *s, uint32_t first, size_t nmetrics, float *count_ms);
 

@@ -9,8 +9,9 @@ liblhgpu.so is not built.
 from ._native import (LIB_PATH, MAX_PERCENTILES, NKEYS, NTHRESH, LhError, NativeLibraryError)
 from .engine import Engine, Kept, Names, Snapshot
 from .fleet import aggregate, group_names, roll_up, union_names
+from . import keptfile
 from .keptfile import KeptUnderflow
 from .window import KeptWindow, burn_fires
 
 __all__ = ["Engine", "Kept", "KeptUnderflow", "KeptWindow", "Names", "Snapshot", "LhError", "NativeLibraryError", "LIB_PATH", "NKEYS", "NTHRESH",
-           "MAX_PERCENTILES", "burn_fires", "aggregate", "union_names", "group_names", "roll_up"]
+           "MAX_PERCENTILES", "burn_fires", "keptfile", "aggregate", "union_names", "group_names", "roll_up"]

@@ -204,6 +204,9 @@ TUNING_SIGNATURES = {
     "lh_tool_kept_compare_tile": (C.c_int, [_u32p]),
     "lh_tool_kept_check_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_keep_count_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.POINTER(C.c_float)]),
+    "lh_tool_kept_encode_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lh_tool_kept_decode_ms": (C.c_int, [C.c_int, _vp, _sz, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float)]),
     "lh_tool_kept_slide_passes_ms": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "lh_tool_top_passes_ms": (C.c_int, [_vp, C.c_uint32, _sz, C.c_uint32, C.c_double, _sz, C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
@@ -309,6 +312,11 @@ SIGNATURES = {
     "lh_kept_save_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "lh_kept_load": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
     "lh_kept_load_device": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
+    "lh_kept_encode_size": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),
+    "lh_kept_encode": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "lh_kept_encode_device": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "lh_kept_decode": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
+    "lh_kept_decode_device": (C.c_int, [C.c_int, _vp, _sz, C.c_uint32, _vp, C.POINTER(LhKeptCheck), C.POINTER(_vp)]),
     "lh_kept_values": (C.c_int, [C.c_int, _dp]),
     "lh_kept_compare": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lh_kept_compare_device": (C.c_int, [_vp, _sz, _vp, _sz, C.c_uint32, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -181,6 +181,14 @@
 // index and cause, into one uint64 with an atomic min, which comes back in one 8-byte copy.  The header's own causes are decided
 // on the host.  lh_kept_values hands out the unit's value table, for a process that has no engine to ask.
 //
+// THE COMPACT BLOB, lh_kept_encode* / lh_kept_decode*: the same handle at a few bytes a cell instead of ten, for files, wires and PCIe
+// -- per row the counts at the narrowest width that holds the largest and the bins as byte deltas (loghisto_gpu.h has the format;
+// one handle has ONE encoding).  Encode: k_enc_size (a wave per row: desc[m] and the record's length), k_keep_scan as it is,
+// the total brought back, k_enc_fill (a wave per row writes every byte of its record).  Decode proves untrusted bytes into an
+// ordinary handle in two stages: k_dec_dir reads the directory ALONE, two k_keep_scan give the cells' and the records' offsets and
+// the totals the header must state -- a refusal here is final --; then k_dec_fill, a wave per row inside ranges that are proven by
+// then, writes the handle's arrays and folds the first violation as k_kept_check does, and k_kept_check_samples closes.
+//
 // THE LIST OF HANDLES TRAVELS BY VALUE (KeptList: 64 records of 24 bytes -- address of the allocation, cells, first, nrows;
 // 1.5 KiB of the 4 KiB a kernel's arguments may take).  A block in device memory would have to be guarded across streams:
 // a device-form call returns while its kernel is still to read the block, so the next call, on whatever stream, would wait
@@ -1760,6 +1768,216 @@ __global__ __launch_bounds__(WG) void k_kept_check_samples(u64 block, uint32_t n
     }
 }
 
+// ---- lh_kept_encode* / lh_kept_decode*: the compact blob (loghisto_gpu.h has the format) ------------------------------------------
+// Behind the header a directory of uint32 desc[nrows] = n | cw << 20 | km << 24 (padded to 8 bytes), then per row of n >= 1 cells a
+// record of S(m) bytes, 8-aligned: the counts at 1 << cw bytes each, then the bins as uint16 first + n - 1 byte deltas (km 0) or as
+// uint16 bin[n] (km 1), each part zero-padded to 8.  Both directions are a wave per row in k_kept_check's shape -- a lane per cell,
+// 64 cells a step, the bin of the cell before by the same DPP shift with the carry between steps -- and need no LDS: the encoder's
+// first pass finds the row's largest count class and largest gap (desc[m] and S(m)), k_keep_scan turns S into the records'
+// offsets, the second pass writes every byte of the record, pads included.  The decoder trusts nothing: k_dec_dir reads the
+// directory ALONE and proves it (reserved bits, n <= LH_NKEYS, and with the scan's two totals on the host: the cells and the bytes
+// the header states), so that by the time k_dec_fill runs every record lies inside the payload and every output range inside the
+// handle's exact allocation, whatever the records hold; a row's walk is bounded by 1 024 steps and a delta row's bins by
+// 65 535 + 65 535 * 256 < 2^32.  Violations fold into *verdict as k_kept_check's do: row << 32 | index << 8 | cause, atomic min.
+constexpr uint32_t ENC_DESC_BITS = 0x1ffffu | 3u << 20 | 1u << 24;
+__host__ __device__ inline u64 up8(u64 x) { return (x + 7) & ~7ull; }
+__host__ __device__ inline u64 enc_directory_bytes(uint32_t nrows) { return 8 * (((u64)nrows + 1) / 2); }
+// S(m) of a row of n cells (n < 2^17, whatever a descriptor says: under 2^21 bytes)
+__host__ __device__ inline uint32_t enc_record_bytes(uint32_t n, uint32_t cw, uint32_t km)
+{
+    return n ? (uint32_t)(up8((u64)n << cw) + up8(km ? 2 * (u64)n : (u64)n + 1)) : 0u;
+}
+// cw of one count: the least of 0 .. 3 with c < 2^(8 << cw)
+__device__ __forceinline__ uint32_t width_class(u64 c) { return c > 0xffffffffull ? 3u : c > 0xffffu ? 2u : c > 0xffu ? 1u : 0u; }
+// x of lane - 1 (k_kept_check's shift: row_shr:1 inside a row of 16 lanes, the three lanes between rows by readlane), lane 0 the carry
+__device__ __forceinline__ uint32_t lane_before(uint32_t x, uint32_t lane, uint32_t carry)
+{
+    const uint32_t prev = LH_DPP32(x, 0x111, 0xf);
+    const uint32_t b15 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15), b31 = (uint32_t)__builtin_amdgcn_readlane((int)x, 31),
+                   b47 = (uint32_t)__builtin_amdgcn_readlane((int)x, 47);
+    return lane == 0 ? carry : lane == 16 ? b15 : lane == 32 ? b31 : lane == 48 ? b47 : prev;
+}
+
+// encode, pass 1: a wave per row of a HANDLE (its arrays hold what lh_keep guarantees): desc[m], and S(m) into soff[m + 1]
+__global__ __launch_bounds__(ROW_BLOCK) void k_enc_size(u64 block, uint32_t nrows, u64 cells, uint32_t *__restrict__ desc,
+                                                       u64 *__restrict__ soff)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    const gu64 off = (gu64)block, counts = off + 2 * (size_t)nrows + 1;
+    const gkeys keys = (gkeys)(block + 8 * (2 * (u64)nrows + 1) + 8 * cells);
+    const u64 a = off[m];
+    const uint32_t n = (uint32_t)(off[(size_t)m + 1] - a);
+    uint32_t cw = 0, gap = 0, carry = 0;
+    for (uint32_t base = 0; base < n; base += 64) { // wave-uniform
+        const uint32_t i = base + lane;
+        const bool in = i < n;
+        uint32_t bin = 0;
+        u64 c = 0;
+        if (in) {
+            bin = bin_of(keys[a + i]);
+            c = counts[a + i];
+        }
+        const uint32_t prev = lane_before(bin, lane, carry);
+        if (in) {
+            cw = max(cw, width_class(c));
+            if (i > 0) gap = max(gap, bin - prev);
+        }
+        carry = (uint32_t)__builtin_amdgcn_readlane((int)bin, 63);
+    }
+    cw = wave_max_u32(cw);
+    const uint32_t km = wave_max_u32(gap) > 256 ? 1u : 0u;
+    if (lane == 0) {
+        desc[m] = n ? n | cw << 20 | km << 24 : 0u;
+        soff[(size_t)m + 1] = enc_record_bytes(n, cw, km);
+    }
+}
+
+// encode, pass 2: a wave per row writes desc[m] into the directory at `payload` (8-aligned; the last row's wave the pad word) and the
+// row's record at payload + D + soff[m]: EVERY byte of it -- what the buffer held before does not show
+__global__ __launch_bounds__(ROW_BLOCK) void k_enc_fill(u64 block, uint32_t nrows, u64 cells, const uint32_t *__restrict__ desc,
+                                                       const u64 *__restrict__ soff, unsigned char *__restrict__ payload)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    const uint32_t d = desc[m];
+    if (lane == 0) {
+        uint32_t *dir = reinterpret_cast<uint32_t *>(payload);
+        dir[m] = d;
+        if (m == nrows - 1 && (nrows & 1)) dir[nrows] = 0;
+    }
+    const uint32_t n = d & 0x1ffffu, cw = d >> 20 & 3, km = d >> 24 & 1;
+    if (!n) return;
+    const gu64 off = (gu64)block, counts = off + 2 * (size_t)nrows + 1;
+    const gkeys keys = (gkeys)(block + 8 * (2 * (u64)nrows + 1) + 8 * cells);
+    const u64 a = off[m];
+    unsigned char *rec = payload + enc_directory_bytes(nrows) + soff[m];
+    const uint32_t cb = n << cw, kb = km ? 2 * n : n + 1;
+    unsigned char *kp = rec + up8(cb);
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += 64) { // wave-uniform
+        const uint32_t i = base + lane;
+        const bool in = i < n;
+        uint32_t bin = 0;
+        u64 c = 0;
+        if (in) {
+            bin = bin_of(keys[a + i]);
+            c = counts[a + i];
+        }
+        const uint32_t prev = lane_before(bin, lane, carry);
+        if (in) {
+            if (cw == 0) rec[i] = (unsigned char)c;
+            else if (cw == 1) reinterpret_cast<uint16_t *>(rec)[i] = (uint16_t)c;
+            else if (cw == 2) reinterpret_cast<uint32_t *>(rec)[i] = (uint32_t)c;
+            else reinterpret_cast<u64 *>(rec)[i] = c;
+            if (km) reinterpret_cast<uint16_t *>(kp)[i] = (uint16_t)bin;
+            else if (i == 0) *reinterpret_cast<uint16_t *>(kp) = (uint16_t)bin;
+            else kp[1 + i] = (unsigned char)(bin - prev - 1);
+        }
+        carry = (uint32_t)__builtin_amdgcn_readlane((int)bin, 63);
+    }
+    if (lane < 8) { // at most 7 pad bytes behind each part
+        if (cb + lane < up8(cb)) rec[cb + lane] = 0;
+        if (kb + lane < up8(kb)) kp[kb + lane] = 0;
+    }
+}
+
+// decode, stage 1: a thread per descriptor (and one for the pad word behind an odd number of them): n into off[m + 1], S(m) into
+// soff[m + 1] -- 0 for a descriptor that is refused, whose row then decides the verdict.  Reads dir[0 .. nrows + (nrows & 1)) only:
+// inside the payload, the host has checked bytes >= D.
+__global__ __launch_bounds__(256) void k_dec_dir(const uint32_t *__restrict__ dir, uint32_t nrows, u64 *__restrict__ off,
+                                                 u64 *__restrict__ soff, u64 *__restrict__ verdict)
+{
+    const u64 m = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (m > nrows) return;
+    if (m == nrows) {
+        if ((nrows & 1) && dir[m] != 0) atomicMin(verdict, (u64)nrows << 32 | LH_KEPT_BAD_ENC_PAD);
+        return;
+    }
+    const uint32_t d = dir[m], n = d & 0x1ffffu;
+    const bool bad = (d & ~ENC_DESC_BITS) != 0 || n > LH_NKEYS || (n == 0 && d != 0);
+    off[m + 1] = bad ? 0 : n;
+    soff[m + 1] = bad ? 0 : enc_record_bytes(n, d >> 20 & 3, d >> 24 & 1);
+    if (bad) atomicMin(verdict, m << 32 | LH_KEPT_BAD_ENC_DESC);
+}
+
+// decode, stage 2: a wave per row of a SOUND directory, from the row's record into the handle's block (offsets already there:
+// `block`'s first nrows + 1 words are the scan of n), row_count[m] too.  What stage 1 proved of the row is held once more against
+// the descriptor as it reads NOW (the device form reads the caller's memory in place): a row that no longer agrees is refused
+// and not walked, so no load or store leaves the payload's `bytes` or the block whatever happens to the source meanwhile.
+__global__ __launch_bounds__(ROW_BLOCK) void k_dec_fill(const unsigned char *__restrict__ payload, uint32_t nrows, u64 cells, u64 bytes,
+                                                       u64 block, const u64 *__restrict__ soff, u64 *__restrict__ verdict)
+{
+    const uint32_t lane = threadIdx.x & 63, m = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (m >= nrows) return; // wave-uniform
+    u64 *off = reinterpret_cast<u64 *>(block), *row_count = off + (size_t)nrows + 1, *counts = row_count + nrows;
+    int16_t *keys = reinterpret_cast<int16_t *>(counts + cells);
+    const u64 a = off[m], b = off[(size_t)m + 1], ra = soff[m], rb = soff[(size_t)m + 1], D = enc_directory_bytes(nrows);
+    const uint32_t d = reinterpret_cast<const uint32_t *>(payload)[m], n = d & 0x1ffffu, cw = d >> 20 & 3, km = d >> 24 & 1;
+    uint32_t bad = CHECK_NONE32; // index << 8 | cause
+    if ((d & ~ENC_DESC_BITS) != 0 || n > LH_NKEYS || a > b || b > cells || b - a != n || ra > rb || rb - ra != enc_record_bytes(n, cw, km) ||
+        D + rb > bytes)
+        bad = LH_KEPT_BAD_ENC_DESC;
+    u64 cnt = 0;
+    if (bad == CHECK_NONE32 && n) { // wave-uniform
+        const unsigned char *rec = payload + D + ra;
+        const uint32_t cb = n << cw, kb = km ? 2 * n : n + 1;
+        const unsigned char *kp = rec + up8(cb);
+        uint32_t carry = 0, wide = 0, gap = 0; // carry: the bin of the last cell of the step before
+        for (uint32_t base = 0; base < n; base += 64) { // wave-uniform
+            const uint32_t i = base + lane;
+            const bool in = i < n;
+            uint32_t bin = 0, step = 0;
+            u64 c = 0;
+            if (in) {
+                if (cw == 0) c = rec[i];
+                else if (cw == 1) c = reinterpret_cast<const uint16_t *>(rec)[i];
+                else if (cw == 2) c = reinterpret_cast<const uint32_t *>(rec)[i];
+                else c = reinterpret_cast<const u64 *>(rec)[i];
+                if (km) bin = reinterpret_cast<const uint16_t *>(kp)[i];
+                else step = i == 0 ? (uint32_t)*reinterpret_cast<const uint16_t *>(kp) : (uint32_t)kp[1 + i] + 1u;
+            }
+            if (!km) bin = carry + wave_scan_incl_u32(step); // (a lane behind the row: the row's last bin)
+            const uint32_t prev = lane_before(bin, lane, carry);
+            cnt += c;
+            uint32_t v = CHECK_NONE32;
+            if (in) {
+                wide = max(wide, width_class(c));
+                if (i > 0 && bin > prev) gap = max(gap, bin - prev);
+                if (bin >= LH_NKEYS) v = i << 8 | LH_KEPT_BAD_ENC_KEY_RANGE;
+                if (c == 0) v = i << 8 | LH_KEPT_BAD_ZERO_COUNT;
+                if (km && i > 0 && prev >= bin) v = i << 8 | LH_KEPT_BAD_KEY_ORDER; // (the lowest cause code last)
+                keys[a + i] = (int16_t)bin_to_key(bin & 0xffffu);
+                counts[a + i] = c;
+            }
+            const uint32_t least = ~wave_max_u32(~v);
+            if (least != CHECK_NONE32) { // wave-uniform: no later step holds a lower index
+                bad = least;
+                break;
+            }
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)bin, 63);
+        }
+        if (bad == CHECK_NONE32) { // behind the row's cells: the pads, then the canonical widths
+            uint32_t pad = 0;
+            if (lane < 8) {
+                if (cb + lane < up8(cb)) pad |= rec[cb + lane];
+                if (kb + lane < up8(kb)) pad |= kp[kb + lane];
+            }
+            if (wave_max_u32(wide) != cw || (km && wave_max_u32(gap) <= 256)) bad = n << 8 | LH_KEPT_BAD_ENC_WIDTH;
+            if (wave_max_u32(pad) != 0) bad = n << 8 | LH_KEPT_BAD_ENC_PAD; // (the lower cause code last)
+        }
+    }
+    const u64 total = readlane_u64(wave_scan_incl_u64(cnt), 63);
+    if (lane == 0) {
+        row_count[m] = total;
+        if (bad != CHECK_NONE32) atomicMin(verdict, (u64)m << 32 | bad);
+    }
+}
+static_assert(LH_KEPT_BAD_KEY_ORDER < LH_KEPT_BAD_ZERO_COUNT && LH_KEPT_BAD_ZERO_COUNT < LH_KEPT_BAD_ENC_KEY_RANGE &&
+                  LH_KEPT_BAD_ENC_KEY_RANGE < LH_KEPT_BAD_ENC_PAD && LH_KEPT_BAD_ENC_PAD < LH_KEPT_BAD_ENC_WIDTH &&
+                  LH_KEPT_BAD_ENC_TOTALS < LH_KEPT_BAD_ENC_PAD && LH_KEPT_BAD_ENC_WIDTH < 256,
+              "k_dec_fill assigns a cell's and a row's causes in descending order of their codes; a cause is the low byte");
+
 // ---- host side------------------------------------------------------------------------------------------------------------
 // behind a device-form call's kernel (or lh_kept_hold's caller's work); `users` handles point to it
 struct CallEvent {
@@ -1777,6 +1995,8 @@ struct KeptCtx {
     size_t tmp_cap = 0;
     u64 *h_totals = nullptr;   // pinned
     size_t totals_cap = 0;
+    unsigned char *d_enc = nullptr; // lh_kept_encode* / lh_kept_decode*: an encoded blob where the caller's memory cannot take the kernels
+    size_t enc_cap = 0;
     ResultBlocks res;          // host forms
     IdBlocks ids;              // host form of lh_kept_across_ids; lh_kept_gather's map and lh_kept_group's CSR, staged the same way
     uint32_t *d_map_t = nullptr; // lh_kept_gather*: the map transposed (the measurement switch's route only)
@@ -3098,6 +3318,247 @@ int kept_load(int device, const void *buf, size_t len, uint32_t flags, void *str
     return LH_OK;
 }
 
+// ---- lh_kept_encode* / lh_kept_decode*: the compact blob ------------------------------------------------------------------------
+static_assert(sizeof(LH_KEPT_ENC_MAGIC) == 9 && LH_KEPT_ENC_MIN == LH_KEPT_BLOB_HEADER + 8, "8 bytes of magic; one row, no cell");
+
+// the encoded header's causes of refusal in the documented order, `len` the blob's length; 0: none
+uint32_t enc_header_cause(const BlobHeader &h, size_t len)
+{
+    if (std::memcmp(h.magic, LH_KEPT_ENC_MAGIC, 8) != 0) return LH_KEPT_BAD_MAGIC;
+    if (h.version != LH_KEPT_ENC_VERSION) return LH_KEPT_BAD_VERSION;
+    if (h.header_size != LH_KEPT_BLOB_HEADER) return LH_KEPT_BAD_HEADER_SIZE;
+    if (h.nkeys != LH_NKEYS) return LH_KEPT_BAD_NKEYS;
+    if (h.nrows == 0) return LH_KEPT_BAD_NROWS;
+    if ((u64)h.first + h.nrows > (1ull << 32)) return LH_KEPT_BAD_FIRST;
+    if (h.cells > (u64)h.nrows * LH_NKEYS) return LH_KEPT_BAD_CELLS;
+    const u64 D = enc_directory_bytes(h.nrows);
+    if (h.bytes % 8 || h.bytes < D || h.bytes > D + 10 * h.cells + 6 * (u64)h.nrows) return LH_KEPT_BAD_BYTES; // (cells <= 2^48: no wrap)
+    if ((u64)len != LH_KEPT_BLOB_HEADER + h.bytes) return LH_KEPT_BAD_LENGTH;
+    if (h.reserved0 != 0) return LH_KEPT_BAD_RESERVED;
+    for (unsigned char c : h.reserved1)
+        if (c) return LH_KEPT_BAD_RESERVED;
+    return 0;
+}
+
+// HIP events between the stages of ONE call, for the tools that time each kernel alone (off: nothing is created or recorded)
+struct Stages {
+    static constexpr int MAX = 6;
+    hipEvent_t ev[MAX] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    bool on, ok = true;
+    hipStream_t st;
+    Stages(bool on_, hipStream_t st_) : on(on_), st(st_) {}
+    ~Stages()
+    {
+        for (int i = 0; i < n; i++)
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+    void mark()
+    {
+        if (!on || n >= MAX) return;
+        if (hipEventCreate(&ev[n]) != hipSuccess || hipEventRecord(ev[n], st) != hipSuccess) ok = false;
+        n++;
+    }
+    // (the stream waited for)  ms between marks i and j
+    int ms(int i, int j, float *out) const
+    {
+        if (!ok || j >= n || !ev[i] || !ev[j] || hipEventElapsedTime(out, ev[i], ev[j]) != hipSuccess) {
+            (void)hipGetLastError();
+            return LH_EDEVICE;
+        }
+        return LH_OK;
+    }
+};
+
+enum EncTo { ENC_SIZE, ENC_HOST, ENC_DEVICE, ENC_NOWHERE }; // ENC_NOWHERE: into the unit's own block only (the tools' timing)
+
+// (cx->mu held, the device current)  lh_kept_encode*'s work on `st`; the caller waits for `st` after a failure
+int encode_on(lh_kept *k, KeptCtx *cx, void *buf, size_t cap, hipStream_t st, size_t *written, EncTo to, Stages &clk)
+{
+    const uint32_t nrows = k->nrows;
+    const size_t head = (size_t)nrows + 1 + 2, words = ((size_t)nrows + 1) / 2; // S and its offsets, the two totals | desc[nrows]
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, head + words, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+    if (rc) return rc;
+    u64 *soff = cx->d_tmp, *totals = soff + nrows + 1;
+    uint32_t *desc = reinterpret_cast<uint32_t *>(totals + 2);
+    const u64 block = (u64)(uintptr_t)k->block;
+    clk.mark();
+    hipLaunchKernelGGL(k_enc_size, wave_per_row(nrows), dim3(ROW_BLOCK), 0, st, block, nrows, k->cells, desc, soff);
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, soff, k->row_count(), nrows, totals); // totals[0]: the records' bytes
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, totals, sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    const u64 bytes = enc_directory_bytes(nrows) + cx->h_totals[0], size = LH_KEPT_BLOB_HEADER + bytes;
+    if (to == ENC_SIZE) {
+        *written = (size_t)size;
+        return LH_OK;
+    }
+    if (to != ENC_NOWHERE && (u64)cap < size) return LH_ERANGE; // nothing written
+    // the kernel writes aligned words: into the caller's device memory where that is 8-aligned, else into the unit's block
+    const bool direct = to == ENC_DEVICE && !misaligned(buf, 8);
+    unsigned char *dst = static_cast<unsigned char *>(buf);
+    if (!direct) {
+        rc = grow_device(cx->d_enc, cx->enc_cap, (size_t)size, (size_t)1 << 20);
+        if (rc) return rc;
+        dst = cx->d_enc;
+    }
+    BlobHeader h = header_of(k);
+    std::memcpy(h.magic, LH_KEPT_ENC_MAGIC, 8);
+    h.version = LH_KEPT_ENC_VERSION;
+    h.bytes = bytes;
+    LH_BESIDE_CHK(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, st)); // (pageable: staged before the call returns)
+    clk.mark();
+    hipLaunchKernelGGL(k_enc_fill, wave_per_row(nrows), dim3(ROW_BLOCK), 0, st, block, nrows, k->cells, desc, soff, dst + sizeof h);
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    if (!direct && to != ENC_NOWHERE) // ONE copy of the exact size
+        LH_BESIDE_CHK(hipMemcpyAsync(buf, dst, (size_t)size, to == ENC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st)); // complete on return
+    if (written) *written = (size_t)size;
+    return LH_OK;
+}
+
+int kept_encode(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written, EncTo to, float *const *ms = nullptr)
+{
+    const bool writes = to == ENC_HOST || to == ENC_DEVICE;
+    if (!k || (writes && !buf) || (to == ENC_SIZE && !written)) return LH_EINVAL;
+    if (writes && cap < LH_KEPT_ENC_MIN) return LH_ERANGE; // before the handle is looked at
+    KeptCtx *cx = k->cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> g(cx->mu); // no lh_kept_release frees the block under the kernels
+    LH_BESIDE_CHK(hipSetDevice(k->device));
+    Stages clk(ms != nullptr, st);
+    int rc = encode_on(k, cx, buf, cap, st, written, to, clk);
+    if (rc && rc != LH_ERANGE) { // nothing of the call is under way afterwards
+        (void)hipGetLastError();
+        if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    }
+    if (!rc && ms) // size | scan | fill
+        for (int i = 0; i < 3 && !rc; i++) rc = clk.ms(i < 2 ? i : 3, i < 2 ? i + 1 : 4, ms[i]);
+    return rc;
+}
+
+// (cx->mu held, the device current)  The payload of an encoded blob whose header `h` passed enc_header_cause, from `src` (host or
+// this device's memory), decoded into k->block -- its exact allocation, made once the directory is proven -- and checked on the way,
+// on `st`.  LH_EINVAL with *why filled for a payload that is not what lh_kept_encode makes.  After a failure the caller waits for
+// `st` and frees k->block.
+int decode_block(KeptCtx *cx, const BlobHeader &h, const void *src, bool from_device, hipStream_t st, lh_kept_check *why, lh_kept *k,
+                 Stages &clk)
+{
+    const uint32_t nrows = h.nrows;
+    const size_t rows1 = (size_t)nrows + 1;
+    int rc = grow_device(cx->d_tmp, cx->tmp_cap, 2 * rows1 + 5, 4096);
+    if (!rc) rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+    if (rc) return rc;
+    u64 *off = cx->d_tmp, *soff = off + rows1, *back = soff + rows1, *verdict = back + 4; // back: {cells, bytes of records} | 2 unused
+    const unsigned char *payload = static_cast<const unsigned char *>(src);
+    if (!from_device || misaligned(src, 8)) { // the kernels read aligned words of this device's memory
+        rc = grow_device(cx->d_enc, cx->enc_cap, (size_t)h.bytes, (size_t)1 << 20);
+        if (rc) return rc;
+        LH_BESIDE_CHK(hipMemcpyAsync(cx->d_enc, src, (size_t)h.bytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        payload = cx->d_enc;
+    }
+    LH_BESIDE_CHK(hipMemsetAsync(verdict, 0xff, sizeof(u64), st)); // CHECK_NONE
+    // ---- stage 1: the directory alone
+    clk.mark();
+    hipLaunchKernelGGL(k_dec_dir, dim3((uint32_t)(((u64)nrows + 1 + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint32_t *>(payload), nrows, off, soff, verdict);
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, off, soff + 1, nrows, back);      // the cells' offsets; {sum n, sum S}
+    LH_BESIDE_CHK(hipGetLastError());
+    hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(WG), 0, st, soff, off + 1, nrows, back + 2);  // the records' offsets
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, back, 5 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    u64 v = cx->h_totals[4];
+    if (cx->h_totals[0] != h.cells || enc_directory_bytes(nrows) + cx->h_totals[1] != h.bytes)
+        v = std::min(v, (u64)nrows << 32 | LH_KEPT_BAD_ENC_TOTALS);
+    if (v != CHECK_NONE) return refuse(why, (uint32_t)(v & 0xff), (uint32_t)(v >> 32), (uint32_t)(v >> 8) & 0xffffffu); // final
+    // ---- stage 2: every record lies inside the payload and every row's cells inside the allocation
+    k->first = h.first;
+    k->nrows = nrows;
+    k->cells = h.cells;
+    k->samples = h.samples;
+    k->bytes = (2 * (u64)nrows + 1) * sizeof(u64) + h.cells * (sizeof(u64) + sizeof(int16_t));
+    LH_BESIDE_CHK(hipMalloc((void **)&k->block, (size_t)k->bytes));
+    LH_BESIDE_CHK(hipMemcpyAsync(k->block, off, rows1 * sizeof(u64), hipMemcpyDeviceToDevice, st));
+    const u64 block = (u64)(uintptr_t)k->block;
+    clk.mark();
+    hipLaunchKernelGGL(k_dec_fill, wave_per_row(nrows), dim3(ROW_BLOCK), 0, st, payload, nrows, h.cells, h.bytes, block, soff, verdict);
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    hipLaunchKernelGGL(k_kept_check_samples, dim3(1), dim3(WG), 0, st, block, nrows, h.samples, verdict);
+    LH_BESIDE_CHK(hipGetLastError());
+    clk.mark();
+    LH_BESIDE_CHK(hipMemcpyAsync(cx->h_totals, verdict, sizeof(u64), hipMemcpyDeviceToHost, st));
+    LH_BESIDE_CHK(hipStreamSynchronize(st));
+    v = cx->h_totals[0];
+    if (v != CHECK_NONE) return refuse(why, (uint32_t)(v & 0xff), (uint32_t)(v >> 32), (uint32_t)(v >> 8) & 0xffffffu);
+    return LH_OK;
+}
+
+int kept_decode(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out, bool from_device,
+                float *const *ms = nullptr)
+{
+    if (why && why->struct_size != sizeof(lh_kept_check)) return LH_EINVAL;
+    if (!buf || !out || flags != 0 || device < 0 || device >= MAX_DEVICES) return refuse(why, LH_KEPT_BAD_ARG);
+    if (len < LH_KEPT_BLOB_HEADER) return refuse(why, LH_KEPT_BAD_SHORT);
+    BlobHeader h;
+    if (!from_device) { // the header's causes before any device call
+        std::memcpy(&h, buf, sizeof h);
+        const uint32_t cause = enc_header_cause(h, len);
+        if (cause) return refuse(why, cause);
+    }
+    KeptCtx *cx = device_ctx<KeptCtx>(device);
+    if (!cx) return LH_EDEVICE; // (never: the range was checked)
+    lh_kept *k = new (std::nothrow) lh_kept;
+    if (!k) return LH_ENOMEM;
+    k->device = device;
+    k->cx = cx;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned char *src = static_cast<const unsigned char *>(buf);
+    int rc;
+    {
+        std::lock_guard<std::mutex> g(cx->mu);
+        rc = hipSetDevice(device) == hipSuccess ? LH_OK : LH_EDEVICE;
+        if (!rc && from_device) { // its 64 header bytes alone come to the host
+            rc = grow_pinned(cx->h_totals, cx->totals_cap, 8, 8);
+            if (!rc && (hipMemcpyAsync(cx->h_totals, src, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess))
+                rc = LH_EDEVICE;
+            if (!rc) {
+                std::memcpy(&h, cx->h_totals, sizeof h);
+                const uint32_t cause = enc_header_cause(h, len);
+                if (cause) rc = refuse(why, cause);
+            }
+        }
+        Stages clk(ms != nullptr, st);
+        if (!rc) rc = decode_block(cx, h, src + sizeof h, from_device, st, why, k, clk);
+        if (rc) {
+            (void)hipGetLastError();
+            if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+            if (k->block && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+        if (!rc && ms) { // directory | scans | fill | samples
+            static const int from[4] = {0, 1, 3, 4};
+            for (int i = 0; i < 4 && !rc; i++) rc = clk.ms(from[i], from[i] + 1, ms[i]);
+            if (rc && hipFree(k->block) != hipSuccess) (void)hipGetLastError();
+        }
+    }
+    if (rc) {
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return LH_OK;
+}
+
 // The readers' output structs from the pointers of the C ABI, host and device forms alike
 KeptOut kept_out(uint64_t *count, double *sum, uint32_t *nbuckets, uint64_t *present_bits, int16_t *pkeys, uint8_t *pvalid)
 {
@@ -3143,6 +3604,46 @@ int lh_kept_load(int device, const void *buf, size_t len, uint32_t flags, void *
 int lh_kept_load_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out)
 {
     return kept_load(device, d_buf, len, flags, stream, why, out, true);
+}
+
+int lh_kept_encode_size(lh_kept *k, void *stream, size_t *bytes) { return kept_encode(k, nullptr, 0, stream, bytes, ENC_SIZE); }
+
+int lh_kept_encode(lh_kept *k, void *buf, size_t cap, void *stream, size_t *written)
+{
+    return kept_encode(k, buf, cap, stream, written, ENC_HOST);
+}
+
+int lh_kept_encode_device(lh_kept *k, void *d_buf, size_t cap, void *stream, size_t *written)
+{
+    return kept_encode(k, d_buf, cap, stream, written, ENC_DEVICE);
+}
+
+int lh_kept_decode(int device, const void *buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out)
+{
+    return kept_decode(device, buf, len, flags, stream, why, out, false);
+}
+
+int lh_kept_decode_device(int device, const void *d_buf, size_t len, uint32_t flags, void *stream, lh_kept_check *why, lh_kept **out)
+{
+    return kept_decode(device, d_buf, len, flags, stream, why, out, true);
+}
+
+int lh_tool_kept_encode_ms(lh_kept *k, void *stream, float *size_ms, float *scan_ms, float *fill_ms)
+{
+    if (!k || !size_ms || !scan_ms || !fill_ms) return LH_EINVAL;
+    float *const ms[3] = {size_ms, scan_ms, fill_ms};
+    return kept_encode(k, nullptr, 0, stream, nullptr, ENC_NOWHERE, ms);
+}
+
+int lh_tool_kept_decode_ms(int device, const void *d_buf, size_t len, void *stream, float *dir_ms, float *scan_ms, float *fill_ms,
+                           float *samples_ms)
+{
+    if (!dir_ms || !scan_ms || !fill_ms || !samples_ms) return LH_EINVAL;
+    float *const ms[4] = {dir_ms, scan_ms, fill_ms, samples_ms};
+    lh_kept *k = nullptr;
+    const int rc = kept_decode(device, d_buf, len, 0, stream, nullptr, &k, true, ms);
+    if (rc) return rc;
+    return lh_kept_release(k);
 }
 
 int lh_tool_kept_check_ms(lh_kept *k, void *stream, float *check_ms, float *samples_ms)

@@ -1230,10 +1230,39 @@ class Kept:
         N.check(N.lib().lh_kept_save(self._h, buf.ctypes.data, n, _stream_handle(stream), C.byref(written)), "lh_kept_save")
         return buf[:int(written.value)].tobytes()
 
-    def save(self, path, stream=None):
-        """to_bytes() written to the file `path`.  The names that belong to the ids are not part of it."""
+    def save(self, path, stream=None, encoded: bool = False):
+        """to_bytes() written to the file `path` -- encoded=True: encode(), the compact blob.  The names that belong to the ids are
+        not part of it."""
         with open(path, "wb") as f:
-            f.write(self.to_bytes(stream))
+            f.write(self.encode(stream).tobytes() if encoded else self.to_bytes(stream))
+
+    # -- the compact blob (lh_kept_encode* / lh_kept_decode*; loghisto_amd.keptfile.encode is its NumPy statement) ---------------------
+    def encoded_size(self, stream=None) -> int:
+        """The exact length of encode()'s result (lh_kept_encode_size: the encoder's first pass alone)."""
+        n = C.c_size_t(0)
+        N.check(N.lib().lh_kept_encode_size(self._h, _stream_handle(stream), C.byref(n)), "lh_kept_encode_size")
+        return int(n.value)
+
+    def _encode_bound(self) -> int:
+        from . import keptfile
+        return keptfile.encoded_bound(self.info["nrows"], self.info["cells"])
+
+    def encode(self, stream=None) -> np.ndarray:
+        """The handle as an ENCODED blob (lh_kept_encode), uint8: counts at the narrowest width per row, bins as byte deltas, made on
+        the device and brought over in one copy.  Kept.decode takes it back into a handle with the same bytes as this one."""
+        buf = np.empty(self._encode_bound(), dtype=np.uint8)
+        written = C.c_size_t(0)
+        N.check(N.lib().lh_kept_encode(self._h, buf.ctypes.data, buf.size, _stream_handle(stream), C.byref(written)), "lh_kept_encode")
+        return buf[:int(written.value)].copy()
+
+    def encode_device(self, stream=None):
+        """The same blob as a torch uint8 tensor on the handle's device (lh_kept_encode_device): what a rank hands to a collective.
+        Kept.decode_device takes it back."""
+        import torch
+        n = self.encoded_size(stream)
+        t = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", self.info["device"]))
+        N.check(N.lib().lh_kept_encode_device(self._h, int(t.data_ptr()), n, _stream_handle(stream), None), "lh_kept_encode_device")
+        return t
 
     def to_device_blob(self, stream=None):
         """The same blob as a torch uint8 tensor on the handle's device (lh_kept_save_device): what a rank hands to a
@@ -1266,7 +1295,7 @@ class Kept:
         rc = getattr(N.lib(), fn)(device, addr, n, 0, _stream_handle(stream), C.byref(why), C.byref(h))
         if rc == N.EINVAL:
             from . import keptfile
-            raise ValueError(f"{fn}: not a kept blob: {keptfile.CAUSES.get(why.cause, why.cause)} (row {why.row}, index {why.index})")
+            raise ValueError(f"{fn}: not a kept blob: {keptfile.ENC_CAUSES.get(why.cause, why.cause)} (row {why.row}, index {why.index})")
         N.check(rc, fn)
         return cls(h, table)
 
@@ -1280,10 +1309,27 @@ class Kept:
         return cls._load("lh_kept_load", device, keep.ctypes.data, int(a.size), stream)
 
     @classmethod
-    def load(cls, path, device: int = 0, stream=None) -> "Kept":
-        """from_bytes() of the file `path`."""
+    def load(cls, path, device: int = 0, stream=None, encoded: bool = False) -> "Kept":
+        """from_bytes() of the file `path` -- encoded=True: decode() of it, a file save(path, encoded=True) wrote."""
         with open(path, "rb") as f:
-            return cls.from_bytes(f.read(), device, stream)
+            data = f.read()
+        return cls.decode(data, device, stream) if encoded else cls.from_bytes(data, device, stream)
+
+    @classmethod
+    def decode(cls, data, device: int = 0, stream=None) -> "Kept":
+        """A new Kept on `device` from an ENCODED blob (lh_kept_decode; bytes or a uint8 array): the handle that was encoded, byte
+        for byte.  Untrusted like from_bytes' blob: checked on the device before the handle exists, ValueError says what is wrong."""
+        a = np.frombuffer(data, dtype=np.uint8)
+        keep = a if a.size else np.zeros(1, dtype=np.uint8)
+        return cls._load("lh_kept_decode", device, keep.ctypes.data, int(a.size), stream)
+
+    @classmethod
+    def decode_device(cls, t, stream=None) -> "Kept":
+        """The same from a contiguous torch uint8 device tensor that holds an encoded blob (lh_kept_decode_device), at any
+        alignment: only its 64 header bytes come to the host."""
+        if not (getattr(t, "is_cuda", False) and t.element_size() == 1 and t.is_contiguous()):
+            raise ValueError("a contiguous torch uint8 device tensor")
+        return cls._load("lh_kept_decode_device", t.device.index, int(t.data_ptr()), int(t.numel()), stream)
 
     @classmethod
     def from_device_blob(cls, t, stream=None) -> "Kept":

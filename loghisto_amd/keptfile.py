@@ -10,6 +10,11 @@ combine() states lh_kept_slide on blobs -- per row and bin the add side's sum mi
 would go below zero -- and is the reference the device's slide is held to.  gather() states lh_kept_gather* the same way: rows
 re-mapped per blob and summed; group() states lh_kept_group*: many rows summed into one, by group.  pack_names() / unpack_names() are a sidecar for the names of a handle's rows (the blob itself
 carries row numbers only and its format does not change).
+
+encode() / decode() / check_encoded() state the COMPACT blob the same way (lh_kept_encode* / lh_kept_decode*): the same handle in
+a per-row encoding -- a directory of row descriptors, then per row the counts at the narrowest width that holds the row's largest
+and the bins as byte deltas (or raw uint16 where a gap exceeds 256).  One handle has exactly one encoding, decode(encode(b)) == b
+byte for byte, and check_encoded() gives the library's verdict on untrusted bytes.
 """
 from __future__ import annotations
 
@@ -31,6 +36,11 @@ assert _HEAD.size == HEADER
 (BAD_OFFSET_FIRST, BAD_OFFSET_ORDER, BAD_ROW_LENGTH, BAD_OFFSET_LAST, BAD_KEY_ORDER, BAD_ZERO_COUNT, BAD_ROW_COUNT,
  BAD_SAMPLES) = range(16, 24)
 CAUSES = {v: k for k, v in list(globals().items()) if k.startswith("BAD_")}
+
+# the verbatim blob's causes are CAUSES (above: the header's enum, name for name); an encoded blob reuses most of them and adds
+(BAD_ENC_DESC, BAD_ENC_TOTALS, BAD_ENC_KEY_RANGE, BAD_ENC_PAD, BAD_ENC_WIDTH) = range(32, 37)
+ENC_CAUSES = dict(CAUSES)                # every cause lh_kept_decode* can report
+ENC_CAUSES.update({v: k for k, v in list(globals().items()) if k.startswith("BAD_ENC_")})
 
 _M64 = (1 << 64) - 1
 
@@ -160,6 +170,193 @@ def check(blob):
     if sum(int(c) for c in row_count) & _M64 != h["samples"]:
         return (BAD_SAMPLES, nrows, 0)
     return None
+
+
+# ---- the compact blob (lh_kept_encode* / lh_kept_decode*; include/loghisto_gpu.h has the format) -------------------------------
+ENC_MAGIC = b"LHKENC\x1a\n"
+ENC_VERSION = 1
+ENC_MIN = HEADER + 8                     # one row, no cell: the header and a directory of one descriptor and its pad word
+_DESC_BITS = 0x1ffff | 3 << 20 | 1 << 24
+
+
+def _up8(x: int) -> int:
+    return (x + 7) & ~7
+
+
+def directory_bytes(nrows: int) -> int:
+    return 8 * ((nrows + 1) // 2)
+
+
+def record_bytes(n: int, cw: int, km: int) -> int:
+    """S(m): the length of the record of a row of n >= 1 cells with count width 1 << cw and key mode km; 0 for n == 0"""
+    return _up8(n << cw) + _up8(2 * n if km else n + 1) if n else 0
+
+
+def encoded_bound(nrows: int, cells: int) -> int:
+    """The capacity that always suffices for the encoded blob of a handle of nrows rows and `cells` cells, header included
+    (LH_KEPT_ENC_BOUND): 64 + D + 10 * cells + 6 * nrows, never above the verbatim blob's 64 + 10 * cells + 16 * nrows + 8."""
+    return HEADER + directory_bytes(nrows) + 10 * cells + 6 * nrows
+
+
+def _enc_header(first, nrows, cells, samples, nbytes) -> bytes:
+    return _HEAD.pack(ENC_MAGIC, ENC_VERSION, HEADER, NKEYS, first, nrows, 0, cells, samples, nbytes, bytes(8))
+
+
+def _width_class(c) -> int:
+    """cw: the least of 0 .. 3 with max(c) < 2^(8 << cw) (c: a non-empty uint64 array)"""
+    top = int(c.max())
+    return 0 if top <= 0xff else 1 if top <= 0xffff else 2 if top <= 0xffffffff else 3
+
+
+_COUNT_TYPES = ("u1", "<u2", "<u4", "<u8")
+
+
+def encode(blob) -> bytes:
+    """The encoded blob of a verbatim one, as lh_kept_encode writes it for the handle lh_kept_load makes of `blob`.  ValueError
+    for a blob check() refuses."""
+    blob = bytes(blob)
+    bad = check(blob)
+    if bad:
+        raise ValueError(f"not a kept blob: {CAUSES[bad[0]]} (row {bad[1]}, index {bad[2]})")
+    u = unpack(blob)
+    nrows, off = u["nrows"], u["offsets"].astype(np.int64)
+    bins_all = (u["keys"].view("<u2") ^ np.uint16(0x8000)).astype(np.int64)
+    desc = np.zeros(nrows + (nrows & 1), dtype="<u4")
+    records = []
+    for m in range(nrows):
+        a, b = int(off[m]), int(off[m + 1])
+        n = b - a
+        if not n:
+            continue
+        c, bins = u["counts"][a:b], bins_all[a:b]
+        cw = _width_class(c)
+        gaps = np.diff(bins)
+        km = int(gaps.size > 0 and int(gaps.max()) > 256)
+        desc[m] = n | cw << 20 | km << 24
+        cb = c.astype(_COUNT_TYPES[cw]).tobytes()
+        kb = bins.astype("<u2").tobytes() if km else bins[:1].astype("<u2").tobytes() + (gaps - 1).astype("u1").tobytes()
+        records.append(cb + bytes(_up8(len(cb)) - len(cb)) + kb + bytes(_up8(len(kb)) - len(kb)))
+    body = desc.tobytes() + b"".join(records)
+    return _enc_header(u["first"], nrows, u["cells"], u["samples"], len(body)) + body
+
+
+def _enc_header_cause(h: dict, length: int):
+    if h["magic"] != ENC_MAGIC:
+        return BAD_MAGIC
+    if h["version"] != ENC_VERSION:
+        return BAD_VERSION
+    if h["header_size"] != HEADER:
+        return BAD_HEADER_SIZE
+    if h["nkeys"] != NKEYS:
+        return BAD_NKEYS
+    if h["nrows"] == 0:
+        return BAD_NROWS
+    if h["first"] + h["nrows"] > 1 << 32:
+        return BAD_FIRST
+    if h["cells"] > h["nrows"] * NKEYS:
+        return BAD_CELLS
+    D = directory_bytes(h["nrows"])
+    if h["bytes"] % 8 or h["bytes"] < D or h["bytes"] > D + 10 * h["cells"] + 6 * h["nrows"]:
+        return BAD_BYTES
+    if length != HEADER + h["bytes"]:
+        return BAD_LENGTH
+    if h["reserved0"] != 0 or any(h["reserved1"]):
+        return BAD_RESERVED
+    return None
+
+
+def _walk_encoded(enc, want_arrays: bool):
+    """(verdict, arrays): check_encoded's verdict, and for a sound blob with want_arrays (first, offsets, keys, counts)"""
+    if len(enc) < HEADER:
+        return (BAD_SHORT, 0, 0), None
+    h = parse_header(enc)
+    cause = _enc_header_cause(h, len(enc))
+    if cause:
+        return (cause, 0, 0), None
+    nrows, cells = h["nrows"], h["cells"]
+    buf = np.frombuffer(enc, dtype=np.uint8)
+    D = directory_bytes(nrows)
+    desc = np.frombuffer(enc, dtype="<u4", count=D // 4, offset=HEADER).astype(np.int64)
+    # ---- stage 1: the directory alone
+    d = desc[:nrows]
+    n = d & 0x1ffff
+    bad = np.flatnonzero(((d & ~_DESC_BITS) != 0) | (n > NKEYS) | ((n == 0) & (d != 0)))
+    if bad.size:
+        return (BAD_ENC_DESC, int(bad[0]), 0), None
+    cw, km = (d >> 20) & 3, (d >> 24) & 1
+    S = np.where(n > 0, ((n << cw) + 7 & ~7) + (np.where(km == 1, 2 * n, n + 1) + 7 & ~7), 0)
+    if int(n.sum()) != cells or D + int(S.sum()) != h["bytes"]:
+        return (BAD_ENC_TOTALS, nrows, 0), None
+    if nrows & 1 and desc[nrows] != 0:
+        return (BAD_ENC_PAD, nrows, 0), None
+    # ---- stage 2: the records
+    off = np.concatenate(([0], np.cumsum(n)))
+    at = HEADER + D
+    keys = np.zeros(cells, dtype="<u2")
+    counts = np.zeros(cells, dtype="<u8")
+    samples = 0
+    for m in range(nrows):
+        nm = int(n[m])
+        if not nm:
+            continue
+        w, raw = 1 << int(cw[m]), int(km[m])
+        cb, kb = nm * w, 2 * nm if raw else nm + 1
+        c = np.frombuffer(enc, dtype=_COUNT_TYPES[int(cw[m])], count=nm, offset=at).astype(np.uint64)
+        kat = at + _up8(cb)
+        pads = np.concatenate((buf[at + cb:kat], buf[kat + kb:kat + _up8(kb)]))
+        found = []                                       # (index, cause)
+        if raw:
+            bins = np.frombuffer(enc, dtype="<u2", count=nm, offset=kat).astype(np.int64)
+            down = np.flatnonzero(bins[1:] <= bins[:-1])
+            if down.size:
+                found.append((int(down[0]) + 1, BAD_KEY_ORDER))
+        else:
+            first_bin = int(np.frombuffer(enc, dtype="<u2", count=1, offset=kat)[0])
+            bins = first_bin + np.concatenate(([0], np.cumsum(buf[kat + 2:kat + kb].astype(np.int64) + 1)))
+            over = np.flatnonzero(bins > NKEYS - 1)
+            if over.size:
+                found.append((int(over[0]), BAD_ENC_KEY_RANGE))
+        zero = np.flatnonzero(c == 0)
+        if zero.size:
+            found.append((int(zero[0]), BAD_ZERO_COUNT))
+        if not found and pads.any():
+            found.append((nm, BAD_ENC_PAD))
+        if not found and (_width_class(c) != int(cw[m]) or (raw and not (nm > 1 and int(np.diff(bins).max()) > 256))):
+            found.append((nm, BAD_ENC_WIDTH))
+        if found:
+            index, cause = min(found)
+            return (cause, m, index), None
+        a = int(off[m])
+        keys[a:a + nm] = bins.astype("<u2") ^ np.uint16(0x8000)
+        counts[a:a + nm] = c
+        with np.errstate(over="ignore"):
+            samples = (samples + int(c.sum(dtype=np.uint64))) & _M64
+        at = kat + _up8(kb)
+    if samples != h["samples"]:
+        return (BAD_SAMPLES, nrows, 0), None
+    return None, (h["first"], off, keys.view("<i2"), counts)
+
+
+def check_encoded(enc):
+    """None for an encoded blob lh_kept_decode* takes, else (cause, row, index) as lh_kept_check reports it.  The header's causes
+    in their documented order with row = index = 0.  Then the directory: a descriptor with a reserved bit, more than NKEYS
+    cells, or no cell and another bit (BAD_ENC_DESC: row m, index 0); cells or bytes that the directory does not add up to
+    (BAD_ENC_TOTALS: row nrows, index 0); a non-zero pad word behind an odd number of descriptors (BAD_ENC_PAD: row nrows,
+    index 0) -- the lowest row, there the lowest cause code, and a refusal of the directory is final.  Then the records: per
+    cell i a bin above 65 535 in delta mode (BAD_ENC_KEY_RANGE), raw bins that do not ascend (BAD_KEY_ORDER), a zero count
+    (BAD_ZERO_COUNT); behind the row's cells (index n) a non-zero pad byte (BAD_ENC_PAD), then a count width or key mode that
+    is not the canonical one (BAD_ENC_WIDTH); behind every row (row nrows) BAD_SAMPLES.  Of all violations the one of the lowest
+    row, in it the lowest index, there the lowest cause code."""
+    return _walk_encoded(bytes(enc), False)[0]
+
+
+def decode(enc) -> bytes:
+    """The verbatim blob of an encoded one: encode() back, byte for byte.  ValueError for anything check_encoded refuses."""
+    bad, arrays = _walk_encoded(bytes(enc), True)
+    if bad:
+        raise ValueError(f"not an encoded kept blob: {ENC_CAUSES[bad[0]]} (row {bad[1]}, index {bad[2]})")
+    first, off, keys, counts = arrays
+    return pack(off, keys, counts, first=first)
 
 
 class KeptUnderflow(ArithmeticError):
