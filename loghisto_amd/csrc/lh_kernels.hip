@@ -186,7 +186,8 @@ __device__ __forceinline__ void k1_add(const K1Win w, uint32_t *hc, uint64_t *ro
 #ifndef LH_K1_AGG_MIN
 #define LH_K1_AGG_MIN 24
 #endif
-__device__ __forceinline__ void k1_add_fullwave(const K1Win w, uint32_t *hc, uint64_t *row, uint32_t *s_rng, uint32_t bin)
+// Returns the size of lane 0's group (wave-uniform): the tile loop looks at it on two of a tile's samples.
+__device__ __forceinline__ uint32_t k1_add_fullwave(const K1Win w, uint32_t *hc, uint64_t *row, uint32_t *s_rng, uint32_t bin)
 {
     const uint32_t first = __builtin_amdgcn_readfirstlane(bin);
     const unsigned long long same = __builtin_amdgcn_ballot_w64(bin == first);
@@ -197,6 +198,42 @@ __device__ __forceinline__ void k1_add_fullwave(const K1Win w, uint32_t *hc, uin
     } else {
         k1_add(w, hc, row, s_rng, bin);
     }
+    return nsame;
+}
+
+// The LEAN tile body, for streams of many buckets (a lognormal stream: no group to aggregate, no window miss, one sample
+// in 4 000 inside a guard band).  The body above pays for those three cases on every sample: a readfirstlane / ballot /
+// popcount / compare / branch for the group, a branch to the Tx[j] load, a branch on the exponent field, a branch to
+// k1_miss -- nine conditional branches and some fifty scalar instructions per register pair, on a kernel whose vector
+// issue is already four fifths busy at four waves per SIMD (profiles/k1_lean_isa.txt).  Here a sample is straight-line
+// code: lh_bin_fast's index, and an LDS add under the lane mask when the index is certain and inside the main window.
+// Every other sample only sets its slot's bit in the lane's `care` word and is NOT added; after the tile's sixteen
+// samples ONE ballot tells whether any lane has such a bit, and a cold loop takes those (lane, slot) pairs through
+// lh_bin_of and k1_add, each exactly once.  Both bodies are exact, so the choice between them (k_ingest_single) never
+// changes a count.
+#ifndef LH_K1_LEAN
+#define LH_K1_LEAN 1      // 0: every tile takes the per-sample body above (A/B builds)
+#endif
+#ifndef LH_K1_CARE_MAX
+#define LH_K1_CARE_MAX 2  // passes of the cold loop (= most needs-care samples of one lane) a tile may take and stay lean
+#endif
+#ifndef LH_K1_HOLD_MAX
+#define LH_K1_HOLD_MAX 64 // tiles on the per-sample body before a stream whose lean tiles needed too much care is tried again
+#endif
+__device__ __forceinline__ uint32_t k1_lean_sample(const K1Win w, uint32_t *hc, double v, uint32_t slot, uint32_t &care)
+{
+    bool uncertain;
+    const uint32_t bin = lh_bin_fast(v, uncertain); // (an uncertain sample's bin is not used)
+    const uint32_t rel = bin - w.win_lo;
+    const bool ok = !uncertain && rel < w.win_len;
+    if (ok) atomicAdd(&hc[rel], 1u);                // exec-masked ds_add, no branch
+    care |= ok ? 0u : 1u << slot;
+    return bin;
+}
+
+__device__ __forceinline__ uint32_t k1_group_of_lane0(uint32_t bin)
+{
+    return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(bin == (uint32_t)__builtin_amdgcn_readfirstlane(bin)));
 }
 
 __global__ __launch_bounds__(K1_BLOCK) void k_ingest_single(const double *__restrict__ v, size_t n,
@@ -256,15 +293,67 @@ __global__ __launch_bounds__(K1_BLOCK) void k_ingest_single(const double *__rest
     // profiles/r04_fewvalued.jsonl.  Keeping the out-of-window handling out of the sixteen unrolled slots -- a first
     // pass that only notes misses, a second over the same registers when any lane had one -- was no faster on streams
     // without misses and up to 1.6 x slower on streams with them: profiles/r04_k1_wide_streams.txt.)
+    // Which body a tile takes is the wave's own choice (wave-uniform state, no LDS), made at the end of the tile before:
+    //   * the size of lane 0's group on two of the tile's sixteen samples (one rare value in lane 0 must not decide): a
+    //     group worth aggregating keeps the wave on the per-sample body, and it takes `calm` = two tiles in a row without
+    //     one to go lean -- a 90 / 9 / 1 stream shows a small group in both samples of one tile in a hundred;
+    //   * the passes the cold loop took: more than LH_K1_CARE_MAX and the wave holds the per-sample body for a number of
+    //     tiles that doubles every time a lean tile fails so (streams that leave the windows, streams on the thresholds).
+    // A wave starts on the per-sample body.
+    bool lean = false;
+    uint32_t calm = 1, hold = 0, backoff = 1;
     for (size_t t = blockIdx.x; t < nfull; t += gridDim.x) {
         const d2_t *p = vp + t * tile + tid;
         d2_t r[K1_UNROLL];
 #pragma unroll
         for (int u = 0; u < K1_UNROLL; u++) r[u] = __builtin_nontemporal_load(p + u * K1_BLOCK);
+        uint32_t group_a = 0, group_b = 0;
+        if (LH_K1_LEAN && lean) {
+            uint32_t care = 0, bin_a = 0, bin_b = 0;
 #pragma unroll
-        for (int u = 0; u < K1_UNROLL; u++) {
-            k1_add_fullwave(w, h, row, s_ctl, lh_bin_of(r[u].x, Tx));
-            k1_add_fullwave(w, h, row, s_ctl, lh_bin_of(r[u].y, Tx));
+            for (int u = 0; u < K1_UNROLL; u++) {
+                const uint32_t bx = k1_lean_sample(w, h, r[u].x, 2 * u, care);
+                const uint32_t by = k1_lean_sample(w, h, r[u].y, 2 * u + 1, care);
+                if (u == 0) bin_a = bx;
+                if (u == K1_UNROLL / 2) bin_b = by;
+            }
+            group_a = k1_group_of_lane0(bin_a);
+            group_b = k1_group_of_lane0(bin_b);
+            uint32_t passes = 0;
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(care != 0) != 0, 0)) {
+                // cold: every lane takes its needs-care slots one per pass, lowest first
+#pragma clang loop unroll(disable)
+                do {
+                    const uint32_t slot = (uint32_t)__builtin_ctz(care | 0x10000u); // 16: this lane has none left
+                    double x = 0.0;
+#pragma unroll
+                    for (int u = 0; u < K1_UNROLL; u++) {
+                        x = slot == 2u * u ? r[u].x : x;
+                        x = slot == 2u * u + 1u ? r[u].y : x;
+                    }
+                    if (slot < 16u) k1_add(w, h, row, s_ctl, lh_bin_of(x, Tx));
+                    care &= care - 1u;
+                    passes++;
+                } while (__builtin_amdgcn_ballot_w64(care != 0) != 0);
+            }
+            if (max(group_a, group_b) >= LH_K1_AGG_MIN) {
+                lean = false; calm = 0;
+            } else if (passes > LH_K1_CARE_MAX) {
+                lean = false; hold = backoff; backoff = min(2 * backoff, (uint32_t)LH_K1_HOLD_MAX);
+            } else {
+                backoff = 1;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < K1_UNROLL; u++) {
+                const uint32_t gx = k1_add_fullwave(w, h, row, s_ctl, lh_bin_of(r[u].x, Tx));
+                const uint32_t gy = k1_add_fullwave(w, h, row, s_ctl, lh_bin_of(r[u].y, Tx));
+                if (u == 0) group_a = gx;
+                if (u == K1_UNROLL / 2) group_b = gy;
+            }
+            calm = max(group_a, group_b) < LH_K1_AGG_MIN ? calm + 1 : 0;
+            if (hold) hold--;
+            lean = hold == 0 && calm >= 2;
         }
     }
     // remainder pairs (guarded), owned by the workgroup next in the rotation
